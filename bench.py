@@ -21,7 +21,10 @@ to rank 0 over RCCL, --gather-every (16) steps per collective, overlapped with t
 
 Timing protocol: W untimed warm-up steps, then --repeats (5) timed regions of EXACTLY K = --steps
 (1000) steps each, every region bracketed by barrier + synchronize on both sides and reduced with MAX over ranks;
-`ms_per_step` / `value` are the MEDIAN region (all regions are listed in `ms_per_step_repeats`).
+`ms_per_step` / `value` are the MEDIAN region (all regions are listed in `ms_per_step_repeats`).  The untimed clock settling
+between the two ends with the reset and the W warm-up steps again, so the regions always start from the same state.
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy: two builds run with the same arguments can be
+compared output for output.
 
 CPU leg: when the reference package is present (build container: /root/reference or $HWY_REFERENCE_ROOT) the
 UNMODIFIED reference is timed on the host cores (`cpu_baseline.kind == "reference"`, oracle/ref_bench.py); on a box
@@ -479,6 +482,32 @@ def secondary_workloads(steps: int = 200, repeats: int = 3, budget_s: float = 10
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+# what Engine.step_device returns, and the dtype each output is written as (.npy files in float32 or float64)
+DUMP_DTYPES = {"obs": np.float32, "reward": np.float64, "terminated": np.float32, "truncated": np.float32,
+               "info_speed": np.float64, "info_crashed": np.float32}
+
+
+def dump_outputs(directory: str, per_rank_views, limit_bytes: int = DUMP_LIMIT_BYTES) -> dict:
+    """--dump-outputs: one step's outputs (per-rank view dicts of PackedStepOutputs, concatenated env-major in rank order) as
+    `directory`/<name>.npy.  Past `limit_bytes` in all, a fixed sample of the environments (seed 0, ascending) is written
+    instead, with their indices as env_index.npy."""
+    import torch
+    arrays = {k: torch.cat([v[k] for v in per_rank_views], dim=0).cpu().numpy().astype(dt) for k, dt in DUMP_DTYPES.items()}
+    n_envs = arrays["reward"].shape[0]
+    per_env = sum(a[0].nbytes for a in arrays.values())
+    keep = min(n_envs, max(1, (limit_bytes - 8 * n_envs) // per_env))
+    if keep < n_envs:
+        idx = np.sort(np.random.default_rng(0).choice(n_envs, size=keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["env_index"] = idx.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
+    return {"dir": directory, "envs": int(n_envs), "envs_written": int(keep), "files": sorted(arrays),
+            "bytes": int(sum(a.nbytes for a in arrays.values()))}
+
+
 class GpuPlatform:
     """What the rank body needs from the machine: a device, a stream with an engine on it, events, the process-group backend.
     tests/test_bench_dryrun.py swaps in a CPU stand-in (gloo, a fake engine) to run the WHOLE control flow of an N-rank bench --
@@ -567,7 +596,13 @@ def main(argv=None, platform=None, emit=None):
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
                     help="hwy_config.tune_* knob (block_kernel, waves_per_eu, ix_no_helpers, ix_no_prewarm, extra_lds, prio_shift, "
                          "ix_prewarm_frames: highwayenv_amd._abi.TUNING_KEYS); selects a kernel variant, never changes a result; repeatable")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed regions, write what the last timed step returned (every rank's environments, in rank "
+                         "order) as DIR/<name>.npy in float32 / float64, at most 64 MB in all (a fixed sample of the environments "
+                         "beyond that, their indices in env_index.npy); the same arguments give the same outputs on every run")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.cpu_baseline_only:
         raise SystemExit(self_launch(sys.argv[1:] if argv is None else list(argv), args.gpus))
     tuning = {kv.split("=", 1)[0]: int(kv.split("=", 1)[1]) for kv in args.tune}
@@ -708,6 +743,14 @@ def main(argv=None, platform=None, emit=None):
             one_step(t)
         settle_steps += max(args.warmup, 1)
         platform.synchronize(dev)
+    if settle_steps:
+        # The settling advanced the environments by a number of steps that depends on the box's clocks: the timed regions start
+        # from the state they start from without it instead -- the same reset and the same --warmup steps again -- so that what
+        # they compute (--dump-outputs) depends on the arguments alone.
+        eng.reset(base_seed=1_000_003 * (rank + 1), **spawn_kw)
+        eng.set_autoreset(True, base_seed=77_000_001 * (rank + 1), **spawn_kw)
+        for t in range(args.warmup):
+            one_step(t)
     fence()
     # HIP events on every 8th launch of the timed regions: the engine hands the pair to hipExtLaunchKernelGGL, which records the
     # DISPATCH's own begin / end timestamps into them (the clock readings rocprofv3 --kernel-trace reports) on the launch stream
@@ -732,6 +775,14 @@ def main(argv=None, platform=None, emit=None):
             dist.all_reduce(el, op=dist.ReduceOp.MAX)
         region_s.append(el.item())
     elapsed = float(np.median(region_s))
+    # what the last timed step returned (fence() has completed its gather), before anything else steps the engine
+    dumped = None
+    if args.dump_outputs:
+        t_last = args.warmup + R * args.steps - 1
+        views = outs[(t_last // K) & 1].rank0_views(t_last % K)
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, views)
+            dumped["step"] = t_last
     # The dominant kernel's own duration: one more (untimed) region of the same loop in which EVERY launch carries the HIP event pair
     # hipExtLaunchKernelGGL fills with the dispatch's begin / end timestamps -- what rocprofv3 --kernel-trace reports, under the
     # same condition (every dispatch signalled).  Rounds 1-5 sampled every 8th launch of the timed regions: the sampled launches
@@ -950,6 +1001,7 @@ def main(argv=None, platform=None, emit=None):
             "terminated_in_last_step": int(term),
             "ix_spawn_counters": (lambda c: dict(c, drop_rate=c["ix_spawns_dropped"] / max(1, c["ix_spawns"] + c["ix_spawns_dropped"])))(eng.counters()) if scenario == "intersection" else None,
             "host_path_env_steps_per_s": host_rate,
+            **({"dumped_outputs": dumped} if dumped else {}),
         }
         if world == 1 and not args.no_frontend:
             line["frontend"] = frontend_view(args.workload, cfg_dict, E, local_rank)

@@ -235,6 +235,7 @@ def run_scenario(sc: dict, only_envs=None) -> dict:
 
 
 def main() -> None:
+    from tests.golden_util import record_fixture
     only = set(sys.argv[1:])
     for sc in SCENARIOS:
         if only and sc["name"] not in only:
@@ -242,6 +243,7 @@ def main() -> None:
         data = run_scenario(sc)
         path = os.path.join(HERE, sc["name"] + ".npz")
         np.savez_compressed(path, **data)
+        record_fixture(sc["name"], sc["name"] + ".npz", ["tests/golden/make_golden.py"])
         print(f"{sc['name']}: E,N,T,steps,frames_for={data['meta'].tolist()} "
               f"terminated_any={bool(data['terminated'].any())} "
               f"crashed_total={int(data['step_crashed'][-1].sum())} "

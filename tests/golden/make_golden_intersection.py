@@ -310,6 +310,7 @@ def run_scenario(sc: dict, only_envs=None) -> dict:
 
 
 def main() -> None:
+    from tests.golden_util import record_fixture
     only = set(sys.argv[1:])
     for sc in SCENARIOS:
         if only and sc["name"] not in only:
@@ -317,6 +318,7 @@ def main() -> None:
         data = run_scenario(sc)
         path = os.path.join(HERE, sc["name"] + ".npz")
         np.savez_compressed(path, **data)
+        record_fixture(sc["name"], sc["name"] + ".npz", ["tests/golden/make_golden_intersection.py"])
         print(f"{sc['name']}: E,N,T,steps,frames_for,A,R={data['meta'].tolist()} "
               f"vehicles/env at reset={data['init_present'].sum(axis=1).tolist()} "
               f"max vehicles={int(data['next_present'].sum(axis=2).max())} "

@@ -328,6 +328,7 @@ def run_scenario(sc: dict, only_envs=None) -> dict:
 
 
 def main() -> None:
+    from tests.golden_util import record_fixture
     only = set(sys.argv[1:])
     for sc in SCENARIOS:
         if only and sc["name"] not in only:
@@ -335,6 +336,7 @@ def main() -> None:
         data = run_scenario(sc)
         path = os.path.join(HERE, sc["name"] + ".npz")
         np.savez_compressed(path, **data)
+        record_fixture(sc["name"], sc["name"] + ".npz", ["tests/golden/make_golden_merge.py"])
         n_veh = data["init_present"].sum(axis=1) - data["init_obstacle"].sum(axis=1)
         print(f"{sc['name']}: E,N,T,steps,frames_for,A={data['meta'].tolist()} vehicles/env={n_veh.tolist()} "
               f"terminated_any={bool(data['terminated'].any())} "

@@ -2,6 +2,7 @@
 (tests/golden/make_golden.py) into the engine's SoA layout."""
 from __future__ import annotations
 
+import json
 import os
 
 import numpy as np
@@ -9,6 +10,64 @@ import numpy as np
 from highwayenv_amd import _abi
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# tests/golden/MANIFEST.json: for every committed fixture, a digest of its arrays and of the sources that made it, written by the
+# generator that wrote the fixture (record_fixture); tests/test_fixture_freshness.py holds the committed files to it
+MANIFEST = os.path.join(GOLDEN_DIR, "MANIFEST.json")
+SHARED_SOURCES = ["oracle/ref_stub.py"]   # (every generator imports the reference through it)
+
+
+def arrays_digest(data) -> str:
+    """sha256 over the arrays of a fixture (name, dtype, shape and bytes of each, in name order): what np.load gives back, not the
+    .npz container (whose zip entries carry timestamps)."""
+    import hashlib
+    h = hashlib.sha256()
+    for k in sorted(data.files if hasattr(data, "files") else data):
+        a = np.ascontiguousarray(np.asarray(data[k]))
+        h.update(f"{k}|{a.dtype.str}|{a.shape}|".encode())
+        h.update(a.tobytes())
+    return h.hexdigest()
+
+
+def json_fixture_arrays(obj) -> dict:
+    """A JSON fixture as the one array its manifest entry digests."""
+    return {"json": np.asarray(json.dumps(obj, sort_keys=True))}
+
+
+def sources_digest(sources) -> str:
+    """sha256 over source files (paths relative to the repository root, in the order given)."""
+    import hashlib
+    h = hashlib.sha256()
+    for rel in sources:
+        h.update(rel.encode() + b"|")
+        with open(os.path.join(ROOT, rel), "rb") as f:
+            h.update(f.read())
+    return h.hexdigest()
+
+
+def load_manifest() -> dict:
+    with open(MANIFEST) as f:
+        return json.load(f)
+
+
+def fixture_arrays(path: str):
+    """The arrays of the committed fixture `path` (relative to tests/golden) as its manifest entry digests them."""
+    full = os.path.join(GOLDEN_DIR, path)
+    if full.endswith(".json"):
+        with open(full) as f:
+            return json_fixture_arrays(json.load(f))
+    return np.load(full)
+
+
+def record_fixture(name: str, path: str, sources) -> None:
+    """Called by a generator right after it wrote fixture `name` (`path`, relative to tests/golden) from `sources`."""
+    sources = list(sources) + SHARED_SOURCES
+    manifest = load_manifest() if os.path.exists(MANIFEST) else {}
+    manifest[name] = {"path": path, "arrays_sha256": arrays_digest(fixture_arrays(path)), "sources": sources,
+                      "sources_sha256": sources_digest(sources)}
+    with open(MANIFEST, "w") as f:
+        json.dump(manifest, f, indent=1, sort_keys=True)
+        f.write("\n")
 
 GRID = ["grid_default", "grid_aligned_fine", "grid_xy_range", "grid_image"]
 ALL = ["cfg1_fast_default", "cfg2_fast_n50_l4", "v0_default", "cfg3_v0_n100", "dense_crash",
@@ -18,8 +77,8 @@ WITH_FRAMES = ["cfg1_fast_default", "cfg2_fast_n50_l4", "v0_default", "cfg3_v0_n
 
 
 class _InMemory:
-    """What np.load gives for a committed fixture, for a trace generated in this process (tests/test_oracle_live_reference.py:
-    the generators' run_scenario output, never written to disk)."""
+    """What np.load gives for a committed fixture, for a trace held in memory (tests/test_oracle_live_reference.py:
+    a recorded trace of tests/golden/live, or the generators' run_scenario output of a live run)."""
 
     def __init__(self, data: dict):
         self._d = {k: np.asarray(v) for k, v in data.items()}

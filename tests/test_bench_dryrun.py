@@ -24,9 +24,10 @@ class FakeEngine:
         self.E, self.A, self.rank = cfg.num_envs, cfg.num_agents, rank
         self.obs_len = int(np.prod(_abi.obs_shape(cfg)))
         self.steps = 0
+        self.resets_at_step = []
 
     def reset(self, **kw):
-        pass
+        self.resets_at_step.append(self.steps)
 
     def set_autoreset(self, *a, **kw):
         pass
@@ -102,7 +103,7 @@ def _rank_main(rank, world, port, argv, out_path):
     lines = []
     plat = CpuPlatform(rank)
     outs = bench.main(argv, platform=plat, emit=lines.append)
-    json.dump({"lines": lines, "steps": plat.engine.steps, "envs": plat.engine.E,
+    json.dump({"lines": lines, "steps": plat.engine.steps, "envs": plat.engine.E, "resets_at_step": plat.engine.resets_at_step,
                "gathered_rewards": ([[float(v["reward"][0, 0]) for v in o.rank0_views(0)] for o in outs] if rank == 0 else None),
                "gathered_term": ([[int(v["terminated"][0]) for v in o.rank0_views(0)] for o in outs] if rank == 0 else None)},
               open(f"{out_path}.{rank}", "w"))
@@ -156,8 +157,11 @@ def test_two_rank_bench_control_flow_on_gloo(tmp_path, scaling, envs, gather_eve
     # both ranks stepped the same number of times: warm-up + regions (+ the one-gather-per-step leg when gathers are batched)
     extra = 0 if gather_every == 1 else (20 + min(steps, 300))
     extra += 10 + min(max(steps, 300), 1000)  # the kernel-timing region after the timed ones (every launch carries an event pair there; 10 uncounted launches first)
-    # (the clock-settle rounds hold collectives: both ranks must agree on their number, whatever their own clocks say)
-    assert r0["steps"] == r1["steps"] == warmup + line["settle_steps"] + repeats * steps + extra
+    # (the clock-settle rounds hold collectives: both ranks must agree on their number, whatever their own clocks say; after
+    #  them the reset and the warm-up steps run again, so that the timed regions start from the same state as without them)
+    rewarm = warmup if line["settle_steps"] else 0
+    assert r0["steps"] == r1["steps"] == warmup + line["settle_steps"] + rewarm + repeats * steps + extra
+    assert r0["resets_at_step"] == r1["resets_at_step"] == ([0, warmup + line["settle_steps"]] if rewarm else [0])
     assert (line["settle_steps"] > 0) == (settle_ms > 0) and line["settle_steps"] % warmup == 0
     if gather_every == 1:
         assert line["gather_every_1"] is None
@@ -192,3 +196,55 @@ def test_eight_rank_bench_of_baseline_config_3_on_gloo(tmp_path, scaling, envs):
         assert terms == list(range(1, world + 1))                           # rank r's block landed in slot r of the root's buffer
     for rewards in res[0]["gathered_rewards"]:
         assert all(1000.0 * r <= rewards[r] < 1000.0 * (r + 1) for r in range(world))
+
+
+def test_dump_outputs_writes_the_last_timed_step_of_every_rank(tmp_path):
+    """--dump-outputs: after the timed regions, what the LAST timed step returned -- every rank's block, gathered to rank 0, in rank
+    order -- as .npy files in float32 / float64 (the stand-in engine stamps its rank and its running step count)."""
+    steps, warmup, repeats, envs = 6, 3, 2, 4
+    out = tmp_path / "dump"
+    argv = ["--gpus", "2", "--steps", str(steps), "--warmup", str(warmup), "--repeats", str(repeats), "--envs-per-gpu", str(envs),
+            "--gather-every", "4", "--settle-ms", "30", "--no-cpu-baseline", "--dump-outputs", str(out)]
+    r0, r1 = _run(tmp_path, argv)
+    line = r0["lines"][0]
+    settle = line["settle_steps"]
+    assert settle > 0
+    d = line["dumped_outputs"]
+    assert d["step"] == warmup + repeats * steps - 1 and d["envs"] == d["envs_written"] == 2 * envs
+    assert sorted(p.name for p in out.iterdir()) == sorted(k + ".npy" for k in d["files"])
+    arr = {k: np.load(out / (k + ".npy")) for k in d["files"]}
+    assert set(arr) == {"obs", "reward", "terminated", "truncated", "info_speed", "info_crashed"}
+    assert arr["obs"].dtype == np.float32 and arr["obs"].shape == (2 * envs, 1, 5, 5)
+    assert arr["reward"].dtype == np.float64 and arr["reward"].shape == (2 * envs, 1)
+    assert arr["terminated"].dtype == np.float32 and arr["terminated"].shape == (2 * envs,)
+    # the engine's step count at the last timed step: warm-up, settling, the repeated warm-up after it, the timed regions
+    last = warmup + settle + warmup + repeats * steps
+    np.testing.assert_array_equal(arr["reward"][:, 0], [last] * envs + [1000.0 + last] * envs)
+    np.testing.assert_array_equal(arr["obs"][:, 0, 0, 0], [0.0] * envs + [1.0] * envs)
+    np.testing.assert_array_equal(arr["terminated"], [1.0] * envs + [2.0] * envs)
+    assert d["bytes"] == sum(a.nbytes for a in arr.values())
+
+
+def test_dump_outputs_keeps_a_fixed_sample_past_the_size_limit(tmp_path):
+    sys.path.insert(0, ROOT)
+    import bench
+    E, A = 50, 2
+    rng = np.random.default_rng(3)
+
+    def views(lo):
+        return {"obs": torch.from_numpy(rng.standard_normal((E, A, 5, 5)).astype(np.float32)),
+                "reward": torch.from_numpy(np.arange(lo, lo + E * A, dtype=np.float64).reshape(E, A)),
+                "info_speed": torch.zeros((E, A), dtype=torch.float64), "terminated": torch.ones(E, dtype=torch.uint8),
+                "truncated": torch.zeros(E, dtype=torch.uint8), "info_crashed": torch.zeros((E, A), dtype=torch.uint8)}
+    per_rank = [views(0), views(E * A)]
+    full = bench.dump_outputs(str(tmp_path / "full"), per_rank)
+    assert full["envs_written"] == 2 * E and "env_index" not in full["files"]
+    limit = 40 * (A * 25 * 4 + 2 * A * 8 + 2 * 4 + A * 4)   # room for 40 environments, less their indices
+    a = bench.dump_outputs(str(tmp_path / "a"), per_rank, limit_bytes=limit)
+    b = bench.dump_outputs(str(tmp_path / "b"), per_rank, limit_bytes=limit)
+    assert 0 < a["envs_written"] < 40 and a == dict(b, dir=a["dir"]) and a["bytes"] <= limit
+    idx = np.load(tmp_path / "a" / "env_index.npy")
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0)
+    np.testing.assert_array_equal(idx, np.load(tmp_path / "b" / "env_index.npy"))
+    for k in ("obs", "reward", "terminated"):
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / (k + ".npy")), np.load(tmp_path / "full" / (k + ".npy"))[idx.astype(int)])
