@@ -13,7 +13,7 @@ import ctypes as C
 
 import numpy as np
 
-HWY_ABI_VERSION = 5
+HWY_ABI_VERSION = 6
 HWY_MAX_AGENTS = 16
 HWY_MAX_FEATURES = 16
 HWY_MAX_TARGET_SPEEDS = 8
@@ -41,6 +41,16 @@ C_OBS_VEHICLES_ONLY = 2048
 C_OBS_INTENTIONS = 4096
 C_GRID_IMAGE = 8192
 OBS_KINEMATICS, OBS_OCCUPANCY_GRID = 0, 1
+# hwy_config.traffic_model
+TRAFFIC_IDM, TRAFFIC_LINEAR = 0, 1
+HWY_BEHAVIOR_PARAMS = 5
+# config["other_vehicles_type"] -> (traffic_model, LANE_CHANGE_MIN_ACC_GAIN, TIME_WANTED) of the class (vehicle/behavior.py)
+TRAFFIC_CLASSES = {
+    "highway_env.vehicle.behavior.IDMVehicle": (TRAFFIC_IDM, 0.2, 1.5),
+    "highway_env.vehicle.behavior.LinearVehicle": (TRAFFIC_LINEAR, 0.2, 2.5),
+    "highway_env.vehicle.behavior.AggressiveVehicle": (TRAFFIC_LINEAR, 1.0, 2.5),
+    "highway_env.vehicle.behavior.DefensiveVehicle": (TRAFFIC_LINEAR, 1.0, 2.5),
+}
 HWY_MAX_GRID_CELLS = 65536
 
 FEATURE_IDS = {name: i for i, name in enumerate(
@@ -152,6 +162,11 @@ class HwyConfig(C.Structure):
         ("tune_prio_shift", C.c_int32),
         ("tune_ix_prewarm_frames", C.c_int32),
         ("tune_reserved", C.c_int32 * 1),
+        # traffic model (ABI v6)
+        ("traffic_model", C.c_int32),
+        ("reserved4", C.c_int32),
+        ("traffic_lc_min_acc_gain", C.c_double),
+        ("traffic_time_wanted", C.c_double),
     ]
 
 
@@ -332,9 +347,11 @@ def make_config(config: dict, num_envs: int, fast: bool = False, scenario: str =
     if obs["type"] not in ("Kinematics", "OccupancyGrid"):
         raise NotImplementedError(f"observation type {obs['type']} is outside the MI355X hot-path scope")
     grid = obs["type"] == "OccupancyGrid"
-    if cfg.get("other_vehicles_type", "highway_env.vehicle.behavior.IDMVehicle") != "highway_env.vehicle.behavior.IDMVehicle":
-        raise NotImplementedError("only IDMVehicle traffic is in the hot-path scope")
     merge = scenario in ("merge", "merge-generic")
+    traffic = cfg.get("other_vehicles_type", "highway_env.vehicle.behavior.IDMVehicle")
+    if traffic not in TRAFFIC_CLASSES or (traffic != "highway_env.vehicle.behavior.IDMVehicle" and scenario != "highway"):
+        raise NotImplementedError("only IDMVehicle traffic is in the hot-path scope" if scenario != "highway" else
+                                  "only IDMVehicle and the LinearVehicle family (Linear, Aggressive, Defensive) are in the hot-path scope")
     if scenario != "highway" and not merge and not ix:
         raise ValueError(f"unknown scenario {scenario!r}")
     # neighbour_vehicles_connected_lanes on the single road 0->1 of highway-v0 adds no lane to the search list
@@ -344,6 +361,7 @@ def make_config(config: dict, num_envs: int, fast: bool = False, scenario: str =
 
     c = HwyConfig()
     c.abi_version = HWY_ABI_VERSION
+    c.traffic_model, c.traffic_lc_min_acc_gain, c.traffic_time_wanted = TRAFFIC_CLASSES[traffic]
     c.num_envs = int(num_envs)
     for key, val in {**(cfg.get("tuning") or {}), **(tuning or {})}.items():
         if key not in TUNING_KEYS:

@@ -19,7 +19,7 @@ EXPORTS = [
     "hwy_destroy", "hwy_last_error", "hwy_set_state", "hwy_get_state", "hwy_reset", "hwy_step",
     "hwy_step_device", "hwy_rollout_device", "hwy_rollout", "hwy_step_frames", "hwy_observe", "hwy_set_autoreset", "hwy_sync",
     "hwy_profile_enable", "hwy_profile_read", "hwy_get_prio_turn", "hwy_debug_math", "hwy_get_counters", "hwy_set_block_order",
-    "hwy_comm_unique_id", "hwy_comm_init", "hwy_gather", "hwy_comm_destroy",
+    "hwy_comm_unique_id", "hwy_comm_init", "hwy_gather", "hwy_comm_destroy", "hwy_set_behavior", "hwy_get_behavior",
 ]
 
 

@@ -11,7 +11,8 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libhwy_engine.so")
-SOURCES = ["hwy_kernels.hip", "hwy_engine.hip", "hwy_comm.hip"]
+SOURCES = ["hwy_kernels.hip", "hwy_kernels_linear.hip", "hwy_engine.hip", "hwy_comm.hip"]
+KERNEL_SOURCES = ("hwy_kernels.hip", "hwy_kernels_linear.hip")  # the translation units that hold device code
 import glob
 
 # every header the two translation units can include: csrc/*.h (hwy_device.h, hwy_wave.h, hwy_net.h, hwy_ix.h, ...)
@@ -63,11 +64,23 @@ def kernel_source_hash() -> str:
     hwy_engine.hip, hwy_comm.hip -- is not part of it: it picks a kernel variant, whose name the summaries record too.)"""
     import hashlib
     h = hashlib.sha256(" ".join(HIPCC_FLAGS).encode())
-    for f in sorted(["hwy_kernels.hip"] + [x for x in HEADERS if not x.startswith("..")]):
+    for f in sorted(list(KERNEL_SOURCES) + [x for x in HEADERS if not x.startswith("..")]):
         h.update(os.path.basename(f).encode())
         with open(os.path.join(CSRC, f), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:16]
+
+
+def flags_for(src: str) -> list:
+    """hipcc flags of one translation unit: HIPCC_FLAGS, except that the Linear traffic family's kernels
+    (hwy_kernels_linear.hip) are scheduled by the default strategy -- ROCm 7.2's register allocator crashes on them after the
+    iterative-ilp scheduler."""
+    if src == "hwy_kernels_linear.hip":
+        out = list(HIPCC_FLAGS)
+        k = out.index("-amdgpu-sched-strategy=iterative-ilp")
+        del out[k - 1:k + 1]
+        return out
+    return list(HIPCC_FLAGS)
 
 
 def build_engine(force: bool = False, verbose: bool = False) -> str:
@@ -77,7 +90,7 @@ def build_engine(force: bool = False, verbose: bool = False) -> str:
     objs = []
     for src in SOURCES:
         obj = os.path.join(CSRC, src.replace(".hip", ".o"))
-        cmd = [hipcc, *HIPCC_FLAGS, "-c", os.path.join(CSRC, src), "-o", obj]
+        cmd = [hipcc, *flags_for(src), "-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print(" ".join(cmd))
         subprocess.run(cmd, check=True)
@@ -112,11 +125,11 @@ def build_engine_asan(force: bool = False, verbose: bool = False) -> str:
     hipcc = _hipcc()
     # the kernels' object file is the product's own (hwy_kernels.o): rebuilt if the library is stale OR the object did not travel
     # with it (*.o is git-ignored; a fresh .so without its objects would leave the link below without an input)
-    build_engine(force=not os.path.exists(os.path.join(CSRC, "hwy_kernels.o")))
+    build_engine(force=not all(os.path.exists(os.path.join(CSRC, k.replace(".hip", ".o"))) for k in KERNEL_SOURCES))
     objs = []
     for src in SOURCES:
-        if src == "hwy_kernels.hip":
-            objs.append(os.path.join(CSRC, "hwy_kernels.o"))
+        if src in KERNEL_SOURCES:
+            objs.append(os.path.join(CSRC, src.replace(".hip", ".o")))
             continue
         obj = os.path.join(CSRC, src.replace(".hip", "_asan.o"))
         flags = ["--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-fPIC", "-fsanitize=address", "-shared-libsan",

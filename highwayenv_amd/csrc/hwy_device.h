@@ -160,6 +160,30 @@ struct StepParams {
   const StepParams &q = *(const StepParams *)kernarg_##q
 #endif
 
+// ---- traffic models (hwy_config.traffic_model): compile-time policies of the workgroup kernel ------------------------------
+// IDMVehicle (behavior.py:12-347) and the LinearVehicle family (behavior.py:350-585: LinearVehicle, AggressiveVehicle,
+// DefensiveVehicle).  The family shares IDM's DISTANCE_WANTED / COMFORT_ACC_* / LANE_CHANGE_* (inherited) and has its own
+// TIME_WANTED (:387); its members differ only in LANE_CHANGE_MIN_ACC_GAIN, a kernel argument (LinearArgs::lc_gain).
+struct IdmTraffic {
+  static constexpr bool LINEAR = false;
+  static constexpr double TIME_WANTED = HWY_TIME_WANTED;
+};
+struct LinearTraffic {
+  static constexpr bool LINEAR = true;
+  static constexpr double TIME_WANTED = 2.5;
+};
+// the per-vehicle parameters of the Linear family (hwy_set_behavior): HWY_BEHAVIOR_PARAMS planes [k][E][pitch], plane = E * pitch
+struct LinearArgs {
+  double *behavior;
+  long long plane;
+  double lc_gain;  // LANE_CHANGE_MIN_ACC_GAIN of the class
+};
+// kernel argument of the Linear-family kernels: StepParams first (offset 0 of the argument segment, HWY_RELOAD_STEP_PARAMS)
+struct LinearParams {
+  StepParams s;
+  LinearArgs la;
+};
+
 // ---- utils.py ---------------------------------------------------------------------------
 // utils.py:50-56: x if |x| > eps else (eps if x >= 0 else -eps).  For every x but NaN that is max(|x|, eps) carrying the sign
 // of (x < 0) -- -0.0 counts as >= 0, like in the reference: a max, a compare and a sign flip instead of two compares and two
@@ -546,10 +570,12 @@ struct EnvBlock {
     return idm_free_from_log(idm_log_ratio(p, v, ts), delta);
   }
   // desired gap d* (behavior.py:192-217): projected speed difference, velocity = speed*(cos h, sin h)
-  __device__ static inline double desired_gap(double ve, double ce, double se, double vf, double cf, double sf) {
+  // (tw: TIME_WANTED of the vehicle class whose method runs, IdmTraffic / LinearTraffic)
+  __device__ static inline double desired_gap(double ve, double ce, double se, double vf, double cf, double sf,
+                                              double tw = HWY_TIME_WANTED) {
     const double dv = (ve * ce - vf * cf) * ce + (ve * se - vf * sf) * se;
     const double inv_2sqrt_ab = 0.12909944487358055;  // 1 / (2*sqrt(-COMFORT_ACC_MAX*COMFORT_ACC_MIN)) = 1/(2 sqrt 15)
-    return HWY_DISTANCE_WANTED + ve * HWY_TIME_WANTED + (ve * dv) * inv_2sqrt_ab;
+    return HWY_DISTANCE_WANTED + ve * tw + (ve * dv) * inv_2sqrt_ab;
   }
   // interaction term COMFORT_ACC_MAX*(d*/d)^2 of `ego` behind `front`; d = lane_distance_to
   // (objects.py:183-198): on the straight lane the longitudinal coordinate is x
@@ -580,6 +606,26 @@ struct EnvBlock {
     // |w| -> 1 sends tan(slip) to infinity: clipped to +-tan_max anyway (w2 <= 1e-12 <=> |tan| >= 1e6)
     const double tan_steer = (w2 <= 1e-12) ? copysign(tan_max, w) : clipd((2 * w) * fast_rsqrt(w2), -tan_max, tan_max);
     return 0.5 * tan_steer;
+  }
+
+  // ---- LinearVehicle.acceleration (behavior.py:417-465): dot(P, [vt, dv, dp]) summed left to right, of a vehicle with speed ve
+  //      and target speed tse (getattr(ego, "target_speed", ego.speed): not clipped to the lane's speed limit, unlike IDM) behind a
+  //      front vehicle (if `front`) at lane distance d with speed vf; the rear vehicle is ignored.  P: the CALLER's parameters.
+  __device__ static inline double linear_acc(const double P[3], double tse, double ve, bool front, double d, double vf) {
+    const double vt = tse - ve;
+    const double d_safe = HWY_DISTANCE_WANTED + fmax(ve, 0.0) * LinearTraffic::TIME_WANTED;
+    const double dv = front ? fmin(vf - ve, 0.0) : 0.0;
+    const double dp = front ? fmin(d - d_safe, 0.0) : 0.0;
+    return P[0] * vt + P[1] * dv + P[2] * dp;
+  }
+  // ---- LinearVehicle.steering_control (behavior.py:467-505) clipped to +-MAX_STEERING_ANGLE (IDMVehicle.act), returned as
+  //      tan(beta) = 1/2 tan(steering) like steer_tan_beta.  Straight lane: heading_at(s + v TAU_PURSUIT) == 0 for every s.
+  __device__ static inline double linear_tan_beta(const StepParams &p, double s0, double s1, double y, double h, double v, int tgt) {
+    const double nz = not_zero(v);
+    const double f0 = (wrap_to_pi(0.0 - h) * HWY_VEH_LENGTH) / nz;
+    const double f1 = (-(y - tgt * p.lane_width) * HWY_VEH_LENGTH) / (nz * nz);
+    const double steering = clipd(s0 * f0 + s1 * f1, -HWY_MAX_STEER, HWY_MAX_STEER);
+    return 0.5 * tan_bounded(steering);
   }
 
   // ---- AbstractLane.is_reachable_from (road/lane.py:104-118) -------------------------------------
@@ -709,6 +755,38 @@ __device__ inline void spawn_fill(const StepParams &p, const SpawnDraw &d, doubl
     o.delta = 3.5 + (4.5 - 3.5) * d.u_delta;
     o.flags = p.rp.fast ? 0 : HWY_F_CHECK_COLLISIONS;
   }
+}
+// LinearVehicle.randomize_behavior (behavior.py:406-416) on Philox draws 2 .. 4 of the vehicle (draws 0 and 1 are spawn_draw's,
+// so an IDM reset draws exactly what it drew before): ACCELERATION_RANGE[0] + u * (ACCELERATION_RANGE[1] - ACCELERATION_RANGE[0])
+// with LinearVehicle's ranges for the whole family (AggressiveVehicle / DefensiveVehicle override ACCELERATION_PARAMETERS but not
+// the range it is drawn from), the same for STEERING_RANGE.  IDMVehicle.randomize_behavior's DELTA follows (spawn_draw's u_delta).
+__host__ __device__ inline void linear_behavior_draw(uint64_t seed, int vi, uint32_t episode, double b[HWY_BEHAVIOR_PARAMS]) {
+  double u[6];
+  philox_uniform2(seed, (uint32_t)vi, episode, 2u, &u[0], &u[1]);
+  philox_uniform2(seed, (uint32_t)vi, episode, 3u, &u[2], &u[3]);
+  philox_uniform2(seed, (uint32_t)vi, episode, 4u, &u[4], &u[5]);
+  const double acc[3] = {0.3, 0.3, 2.0};                                     // LinearVehicle.ACCELERATION_PARAMETERS
+  const double steer[2] = {HWY_KP_HEADING, HWY_KP_HEADING * HWY_KP_LATERAL};  // LinearVehicle.STEERING_PARAMETERS
+  const double dsteer[2] = {0.07, 1.5};
+  // (the product and the sum as separate statements: -ffp-contract=on fuses within one expression only, numpy rounds twice)
+  for (int k = 0; k < 3; ++k) {
+    const double lo = 0.5 * acc[k], hi = 1.5 * acc[k];
+    const double span = u[k] * (hi - lo);
+    b[k] = lo + span;
+  }
+  for (int k = 0; k < 2; ++k) {
+    const double lo = steer[k] - dsteer[k], hi = steer[k] + dsteer[k];
+    const double span = u[3 + k] * (hi - lo);
+    b[3 + k] = lo + span;
+  }
+}
+// the parameters of vehicle i of environment e after a spawn (controlled vehicles: zeros, never read)
+__device__ inline void spawn_behavior(const StepParams &p, const LinearArgs &la, int e, int i, uint64_t seed, uint32_t episode,
+                                      bool controlled) {
+  double b[HWY_BEHAVIOR_PARAMS];
+  linear_behavior_draw(seed, i, episode, b);
+  const size_t k = (size_t)e * p.pitch + i;
+  for (int q = 0; q < HWY_BEHAVIOR_PARAMS; ++q) la.behavior[q * la.plane + k] = controlled ? 0.0 : b[q];
 }
 template <int NW>
 __device__ inline void spawn_env(const StepParams &p, double *scratch_step, double *scratch_base, int e, uint64_t seed,
@@ -1002,16 +1080,18 @@ __device__ inline void publish(typename EnvBlock<NW>::Shared &sh, const Veh &me,
 
 // =============================================================================================
 // Reset kernel: AbstractEnv.reset for the masked environments + first observation.
-template <int NW>
-__global__ void __launch_bounds__(NW * 64) hwy_reset_kernel(const StepParams p) {
-  typedef EnvBlock<NW> B;
-  __shared__ typename B::Shared sh;
+// (the body of both reset kernels: TM = the traffic model, whose Linear family also draws the per-vehicle parameters)
+template <int NW, typename TM>
+__device__ __forceinline__ void reset_env(const StepParams &p, typename EnvBlock<NW>::Shared &sh, const LinearArgs &la) {
   const int e = blockIdx.x, i = threadIdx.x;
   if (p.reset_mask && !p.reset_mask[e]) return;  // block-uniform
   const bool active = i < p.N;
   Veh me = Veh{};
   const uint64_t seed = p.reset_seeds ? p.reset_seeds[e] : p.rp.base_seed + (uint64_t)e;
   spawn_env<NW>(p, sh.aux0, sh.aux1, e, seed, 0u, me);
+  if constexpr (TM::LINEAR) {
+    if (active) spawn_behavior(p, la, e, i, seed, 0u, (me.flags & HWY_F_CONTROLLED) != 0);
+  }
   publish<NW>(sh, me, active);
   __syncthreads();
   observe_env<NW>(p, sh, e, me, false);
@@ -1021,6 +1101,18 @@ __global__ void __launch_bounds__(NW * 64) hwy_reset_kernel(const StepParams p) 
     p.st.done[e] = 0;
     p.st.episode[e] = 0;
   }
+}
+
+template <int NW>
+__global__ void __launch_bounds__(NW * 64) hwy_reset_kernel(const StepParams p) {
+  __shared__ typename EnvBlock<NW>::Shared sh;
+  reset_env<NW, IdmTraffic>(p, sh, LinearArgs{});
+}
+// The same for the Linear traffic family: + the per-vehicle parameters (hwy_set_behavior's planes).
+template <int NW>
+__global__ void __launch_bounds__(NW * 64) hwy_reset_linear_kernel(const LinearParams lp) {
+  __shared__ typename EnvBlock<NW>::Shared sh;
+  reset_env<NW, LinearTraffic>(lp.s, sh, lp.la);
 }
 
 // Observation-only kernel (hwy_observe).
@@ -1093,8 +1185,10 @@ __device__ inline void wave_turn(WaveTurn &w) {
 #endif
 }
 
-template <int NW>
-__device__ __forceinline__ void block_policy_step(const StepParams &p, typename EnvBlock<NW>::Shared &sh, const int e, const int eo) {
+// TM: the traffic model (IdmTraffic / LinearTraffic, compile time); la: the Linear family's parameters (unused by IdmTraffic).
+template <int NW, typename TM = IdmTraffic>
+__device__ __forceinline__ void block_policy_step(const StepParams &p, typename EnvBlock<NW>::Shared &sh, const int e, const int eo,
+                                                  const LinearArgs &la = LinearArgs{}) {
   typedef EnvBlock<NW> B;
   const int i = threadIdx.x;
   const int N = p.N;
@@ -1106,6 +1200,9 @@ __device__ __forceinline__ void block_policy_step(const StepParams &p, typename 
     Veh me = Veh{};
     const uint32_t episode = p.st.episode[e] + 1u;
     spawn_env<NW>(p, sh.aux0, sh.aux1, e, p.rp.base_seed + (uint64_t)e, episode, me);
+    if constexpr (TM::LINEAR) {
+      if (active) spawn_behavior(p, la, e, i, p.rp.base_seed + (uint64_t)e, episode, (me.flags & HWY_F_CONTROLLED) != 0);
+    }
     publish<NW>(sh, me, active);
     __syncthreads();
     observe_env<NW>(p, sh, e, me, false, eo);
@@ -1132,6 +1229,16 @@ __device__ __forceinline__ void block_policy_step(const StepParams &p, typename 
   load_vehicle<NW>(p, e, me);
   const bool controlled = active && (me.flags & HWY_F_CONTROLLED);
   const bool idm = active && !controlled;
+  // Linear family: ACCELERATION_PARAMETERS[3], STEERING_PARAMETERS[2] of my vehicle, loaded once per policy step and kept in registers
+  // for its frames (MOBIL applies
+  // the DECIDING vehicle's parameters to its followers too, so nobody reads another vehicle's)
+  double bp[HWY_BEHAVIOR_PARAMS] = {};
+  if constexpr (TM::LINEAR) {
+    if (idm) {
+      const size_t k = (size_t)e * p.pitch + i;
+      for (int q = 0; q < HWY_BEHAVIOR_PARAMS; ++q) bp[q] = la.behavior[q * la.plane + k];
+    }
+  }
   int agent = 0;
   if (controlled)
     for (int a = 0; a < p.A; ++a)
@@ -1243,9 +1350,10 @@ __device__ __forceinline__ void block_policy_step(const StepParams &p, typename 
     if (drives) {
       if (!has_tie) B::neighbours_ranked(sh, me.lane, rank, &f_own, &r_own);
       else B::neighbours_scan(p, sh, me.lane, i, me.x, &f_own, &r_own);
-      free_self = B::idm_free(p, me.v, me.ts, me.delta);
+      if constexpr (!TM::LINEAR) free_self = B::idm_free(p, me.v, me.ts, me.delta);
     }
-    if (!has_tie) {  // block-uniform
+    // (the Linear family takes the per-thread MOBIL below in every frame: its deciders carry their own parameters)
+    if (!TM::LINEAR && !has_tie) {  // block-uniform
       // MOBIL compacted per wavefront (hwy_wave.h has the one-wavefront version, round 6): a vehicle decides once per second, so in
       // a given frame ~4 of a wavefront's 64 vehicles do -- and rounds 1-5 ran both side lanes one after the other for the whole
       // wavefront whenever ONE of them decided.  Decider number d of the wavefront hands (free-road term, own-lane acceleration,
@@ -1305,8 +1413,14 @@ __device__ __forceinline__ void block_policy_step(const StepParams &p, typename 
       if (decide) {
         me.timer = 0.0;
         // self_a: my IDM acceleration behind my current leader (old_preceding)
-        const double self_a = free_self - (f_own >= 0 ? B::idm_gap(me.x, me.v, me.ch, me.sh, sh.x[f_own], sh.v[f_own],
-                                                                  sh.c[f_own], sh.s[f_own]) : 0.0);
+        double self_a;
+        if constexpr (TM::LINEAR) {
+          const int g = f_own < 0 ? 0 : f_own;
+          self_a = B::linear_acc(bp, me.ts, me.v, f_own >= 0, sh.x[g] - me.x, sh.v[g]);
+        } else {
+          self_a = free_self - (f_own >= 0 ? B::idm_gap(me.x, me.v, me.ch, me.sh, sh.x[f_own], sh.v[f_own],
+                                                        sh.c[f_own], sh.s[f_own]) : 0.0);
+        }
         for (int side = 0; side < 2; ++side) {  // side_lanes: [id-1], [id+1]  (road.py:200-211)
           const int cand = me.lane + (side == 0 ? -1 : 1);
           if (cand < 0 || cand >= p.L) continue;
@@ -1319,13 +1433,23 @@ __device__ __forceinline__ void block_policy_step(const StepParams &p, typename 
           else B::neighbours_scan(p, sh, cand, i, me.x, &nprec, &nfoll);
           // mobil() is a pure predicate: safety (new follower's braking) AND incentive (my gain) -- evaluated
           // incentive first because it needs no pow() and rejects ~98% of the candidates
-          const double self_pred_a = free_self - (nprec >= 0 ? B::idm_gap(me.x, me.v, me.ch, me.sh, sh.x[nprec], sh.v[nprec],
-                                                                          sh.c[nprec], sh.s[nprec]) : 0.0);
+          double self_pred_a;
+          if constexpr (TM::LINEAR) {
+            const int g = nprec < 0 ? 0 : nprec;
+            self_pred_a = B::linear_acc(bp, me.ts, me.v, nprec >= 0, sh.x[g] - me.x, sh.v[g]);
+          } else {
+            self_pred_a = free_self - (nprec >= 0 ? B::idm_gap(me.x, me.v, me.ch, me.sh, sh.x[nprec], sh.v[nprec],
+                                                              sh.c[nprec], sh.s[nprec]) : 0.0);
+          }
           const double jerk = self_pred_a - self_a;
-          if (jerk < HWY_LC_MIN_ACC_GAIN) continue;
+          if (jerk < (TM::LINEAR ? la.lc_gain : HWY_LC_MIN_ACC_GAIN)) continue;
           if (nfoll >= 0) {
-            const double nf_pred_a = B::idm_free(p, sh.v[nfoll], sh.ts[nfoll], me.delta) -
-                                     B::idm_gap(sh.x[nfoll], sh.v[nfoll], sh.c[nfoll], sh.s[nfoll], me.x, me.v, me.ch, me.sh);
+            double nf_pred_a;
+            if constexpr (TM::LINEAR)  // my parameters on the new follower's features, me as its leader (mobil, behavior.py:283-285)
+              nf_pred_a = B::linear_acc(bp, sh.ts[nfoll], sh.v[nfoll], true, me.x - sh.x[nfoll], me.v);
+            else
+              nf_pred_a = B::idm_free(p, sh.v[nfoll], sh.ts[nfoll], me.delta) -
+                          B::idm_gap(sh.x[nfoll], sh.v[nfoll], sh.c[nfoll], sh.s[nfoll], me.x, me.v, me.ch, me.sh);
             if (nf_pred_a < -HWY_LC_MAX_BRAKING) continue;
           }
           me.tgt = cand;
@@ -1362,10 +1486,11 @@ __device__ __forceinline__ void block_policy_step(const StepParams &p, typename 
           __hip_atomic_fetch_or(&sh.amask[me.tgt][rank >> 6], (u64)1 << (rank & 63), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         sh.acode[i] = ((me.tgt != tgt_old) ? 1 : 0) | (changer ? 2 : 0);
         const bool sane = !__syncthreads_or(active && !(me.v * me.ch >= 0.0 && fabs(me.v * me.sh) <= 5.0));
-        // d*(c, r) = 10 + 1.5 v + v dv / (2 sqrt(ab)) with dv = v (cc^2 + sc^2) - v_r (c_r cc + s_r sc) <= v + 5 + (rounding) when v_r c_r >= 0,
-        // |v_r s_r| <= 5 (sane) and cc >= 0, v >= 0; 1e-6 relative + absolute on top of the bound, far above any rounding in d*
+        // d*(c, r) = 10 + tw v + v dv / (2 sqrt(ab)) with dv = v (cc^2 + sc^2) - v_r (c_r cc + s_r sc) <= v + 5 + (rounding) when v_r c_r >= 0,
+        // |v_r s_r| <= 5 (sane) and cc >= 0, v >= 0; 1e-6 relative + absolute on top of the bound, far above any rounding in d*.
+        // tw = TIME_WANTED of the changer's class (1.5 IDM, 2.5 the Linear family: desired_gap runs as ITS method)
         const double bound = (sane && me.v >= 0.0 && me.ch >= 0.0)
-                                 ? (HWY_DISTANCE_WANTED + me.v * HWY_TIME_WANTED + me.v * (me.v + 5.0) * 0.12909944487358055) * (1.0 + 1e-6) + 1e-6
+                                 ? (HWY_DISTANCE_WANTED + me.v * TM::TIME_WANTED + me.v * (me.v + 5.0) * 0.12909944487358055) * (1.0 + 1e-6) + 1e-6
                                  : __builtin_inf();
         const u64 *prev = nullptr;  // the previous round's verdicts (index space: the ballot's own LDS slot); none in the first round
         for (;;) {  // block-uniform
@@ -1389,7 +1514,7 @@ __device__ __forceinline__ void block_policy_step(const StepParams &p, typename 
               // the target r shows to c: its current one if it comes before c in the list, else the frame-start one -- and a vehicle
               // that decided in this very frame headed nowhere with that one
               const bool valid = j < i || !(fl & 1);
-              const double d_star = B::desired_gap(me.v, me.ch, me.sh, sh.v[j], sh.c[j], sh.s[j]);
+              const double d_star = B::desired_gap(me.v, me.ch, me.sh, sh.v[j], sh.c[j], sh.s[j], TM::TIME_WANTED);
               const bool blk = valid && (0 < d) && (d < d_star);
               // an earlier changer may abort itself: it blocks only while it has not
               const bool gone = j < i && (fl & 2) != 0 && prev != nullptr && ((prev[j >> 6] >> (j & 63)) & 1) != 0;
@@ -1427,7 +1552,7 @@ __device__ __forceinline__ void block_policy_step(const StepParams &p, typename 
             bool blk = false;
             if (active && i != ci && me.lane != Tc && my_tgt_seen == Tc) {
               const double d = me.x - xc;
-              const double d_star = B::desired_gap(vc, cc, sc, me.v, me.ch, me.sh);
+              const double d_star = B::desired_gap(vc, cc, sc, me.v, me.ch, me.sh, TM::TIME_WANTED);
               blk = (0 < d) && (d < d_star);
             }
             u64 bm[NW];
@@ -1442,12 +1567,26 @@ __device__ __forceinline__ void block_policy_step(const StepParams &p, typename 
     // ---- E. Road.act: low-level control (controller.py:89-133, behavior.py:104-137) ---------------------
     // tb = tan(beta) = 1/2 tan(steering) (see steer_tan_beta); acceleration command
     double tb = 0.0, accel = 0.0;
-    if (controlled || drives) {
+    if (TM::LINEAR && drives) {
+      tb = B::linear_tan_beta(p, bp[3], bp[4], me.y, me.h, me.v, me.tgt);
+    } else if (controlled || drives) {
       const double inv_v = fast_rcp(not_zero(me.v));
       tb = B::steer_tan_beta(p, me.y, me.h, inv_v, me.tgt);
     }
     if (controlled) {
       accel = HWY_KP_A * (me.ts - me.v);  // speed_control (controller.py:189-198), not clipped
+    } else if (TM::LINEAR && drives) {
+      const int g = f_own < 0 ? 0 : f_own;
+      accel = B::linear_acc(bp, me.ts, me.v, f_own >= 0, sh.x[g] - me.x, sh.v[g]);
+      if (me.lane != me.tgt) {
+        int f2, r2;
+        if (!has_tie) B::neighbours_ranked(sh, me.tgt, rank, &f2, &r2);
+        else B::neighbours_scan(p, sh, me.tgt, i, me.x, &f2, &r2);
+        const int g2 = f2 < 0 ? 0 : f2;
+        const double a2 = B::linear_acc(bp, me.ts, me.v, f2 >= 0, sh.x[g2] - me.x, sh.v[g2]);
+        accel = (a2 < accel) ? a2 : accel;  // Python min(a, b)
+      }
+      accel = clipd(accel, -HWY_ACC_MAX, HWY_ACC_MAX);
     } else if (drives) {
       accel = free_self - (f_own >= 0 ? B::idm_gap(me.x, me.v, me.ch, me.sh, sh.x[f_own], sh.v[f_own], sh.c[f_own],
                                                    sh.s[f_own]) : 0.0);
@@ -1709,6 +1848,23 @@ __global__ void __launch_bounds__(NW * 64, WPE) hwy_rollout_kernel(const StepPar
   }
 }
 
+// The Linear traffic family (hwy_config.traffic_model == HWY_TRAFFIC_LINEAR) on the workgroup kernel: step and K-step forms.
+template <int NW, int WPE>
+__global__ void __launch_bounds__(NW * 64, WPE) hwy_step_linear_kernel(const LinearParams lp) {
+  __shared__ typename EnvBlock<NW>::Shared sh;
+  block_policy_step<NW, LinearTraffic>(lp.s, sh, blockIdx.x, blockIdx.x, lp.la);
+}
+template <int NW, int WPE>
+__global__ void __launch_bounds__(NW * 64, WPE) hwy_rollout_linear_kernel(const LinearParams lp) {
+  __shared__ typename EnvBlock<NW>::Shared sh;
+  const int e = blockIdx.x;
+  for (int k = 0; k < lp.s.k_steps; ++k) {  // block-uniform
+    HWY_RELOAD_STEP_PARAMS(pk, lp.s);  // (StepParams sits at offset 0 of LinearParams)
+    block_policy_step<NW, LinearTraffic>(pk, sh, e, k * pk.num_envs + e, lp.la);
+    __syncthreads();
+  }
+}
+
 // ---- self-test kernel for hwy_math.h (hwy_debug_math) ------------------------------------------------
 __device__ inline double math_probe(int op, double x) {
   double s, c;
@@ -1724,6 +1880,7 @@ __device__ inline double math_probe(int op, double x) {
     case 9: return atan2_bounded(x, 0.75);
     case 10: return atan2_bounded(0.5, x);
     case 11: return atan2_bounded(-0.5, x);
+    case 12: return tan_bounded(x);
     // the paired forms (hwy_math.h: two evaluations sharing every coefficient) against the scalar ones: ops 20 + 2 k / 21 + 2 k
     // return the first / second result of routine k for the arguments (x, f(x)) / (f(x), x), f = another point of the domain
     case 20: { double a, b; log_pos2(x, 0.37 * x + 0.011, a, b); return a; }

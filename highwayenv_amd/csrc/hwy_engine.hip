@@ -34,6 +34,7 @@ struct hwy_engine {
   int prio_shift = 0;    // issue-priority turns of the step kernels (hwy_config.tune_prio_shift; 0 = off)
   // device state
   double *d_f64 = nullptr;   // 9 fields x E x pitch
+  double *d_behavior = nullptr;  // HWY_TRAFFIC_LINEAR: HWY_BEHAVIOR_PARAMS planes x E x pitch (hwy_set_behavior)
   int32_t *d_packed = nullptr;
   long long *d_route = nullptr;     // intersection scenario: planned routes [E x pitch] (64-bit route words)
   int32_t *d_road_steps = nullptr;  // intersection scenario: RegulatedRoad.steps [E]
@@ -207,6 +208,12 @@ static int validate(const hwy_config *c, std::string &why) {
   if (c->num_target_speeds < 2 || c->num_target_speeds > HWY_MAX_TARGET_SPEEDS) BAD("num_target_speeds must be in [2,%d]", HWY_MAX_TARGET_SPEEDS);
   if (!(c->dt > 0) || !(c->policy_dt > 0)) BAD("dt and policy_dt must be positive");
   if (!(c->lane_width > 0) || !(c->road_length > 0)) BAD("lane_width and road_length must be positive");
+  if (c->traffic_model != HWY_TRAFFIC_IDM && c->traffic_model != HWY_TRAFFIC_LINEAR) BAD("unknown traffic_model %d", c->traffic_model);
+  if (c->traffic_model == HWY_TRAFFIC_LINEAR) {
+    if (c->scenario != HWY_SCENARIO_HIGHWAY) BAD("the Linear traffic family runs on the highway scenario only");
+    if (c->traffic_time_wanted != hwy::LinearTraffic::TIME_WANTED) BAD("traffic_time_wanted of the Linear family is 2.5");
+    if (!(c->traffic_lc_min_acc_gain >= 0.0 && c->traffic_lc_min_acc_gain < 1e3)) BAD("traffic_lc_min_acc_gain out of range");
+  }
   if (c->scenario == HWY_SCENARIO_INTERSECTION) {
     if (c->num_agents > 4) BAD("the intersection scenario holds 1..4 controlled vehicles (one per access road)");
     if (c->num_vehicles < 4 || c->num_vehicles > 64) BAD("the intersection scenario needs 4..64 slots (one wavefront per environment)");
@@ -256,6 +263,14 @@ static void fill_params(const hwy_engine *eng, StepParams &p) {
 }
 
 static bool is_ix(const hwy_engine *eng) { return eng->cfg.scenario == HWY_SCENARIO_INTERSECTION; }
+static bool is_linear(const hwy_engine *eng) { return eng->cfg.traffic_model == HWY_TRAFFIC_LINEAR; }
+static void fill_linear(const hwy_engine *eng, const StepParams &p, hwy::LinearParams &lp) {
+  std::memset(&lp, 0, sizeof lp);
+  lp.s = p;
+  lp.la.behavior = eng->d_behavior;
+  lp.la.plane = (long long)eng->cfg.num_envs * eng->pitch;
+  lp.la.lc_gain = eng->cfg.traffic_lc_min_acc_gain;
+}
 static bool is_net(const hwy_engine *eng) { return eng->cfg.scenario != HWY_SCENARIO_HIGHWAY && !is_ix(eng); }
 static void fill_ix(const hwy_engine *eng, const StepParams &p, hwy::IxParams &ip) {
   hwy::ix_params_from_config(eng->cfg, p, ip);
@@ -286,6 +301,12 @@ static hipError_t launch_step_any(const hwy_engine *eng, const StepParams &p) {
     hwy::net_params_from_config(eng->cfg, p, np);
     return hwy::launch_net_step(np, eng->cfg.num_envs, eng->stream, eng->waves_per_eu);
   }
+  if (is_linear(eng)) {
+    hwy::LinearParams lp;
+    fill_linear(eng, p, lp);
+    return hwy::launch_step_linear(lp, eng->cfg.num_envs, eng->stream, eng->waves_per_eu, eng->force_block_kernel,
+                                   eng->cfg.tune_extra_lds);
+  }
   return hwy::launch_step(p, eng->cfg.num_envs, eng->stream, eng->waves_per_eu, eng->force_block_kernel,
                           eng->cfg.tune_extra_lds);
 }
@@ -299,6 +320,11 @@ static hipError_t launch_reset_any(const hwy_engine *eng, const StepParams &p) {
     hwy::NetParams np;
     hwy::net_params_from_config(eng->cfg, p, np);
     return hwy::launch_net_reset(np, eng->cfg.num_envs, eng->stream);
+  }
+  if (is_linear(eng)) {
+    hwy::LinearParams lp;
+    fill_linear(eng, p, lp);
+    return hwy::launch_reset_linear(lp, eng->cfg.num_envs, eng->stream);
   }
   return hwy::launch_reset(p, eng->cfg.num_envs, eng->stream);
 }
@@ -341,6 +367,9 @@ extern "C" int hwy_create(const hwy_config *cfg, int device, void *stream, hwy_e
   // per thread are one 338 / 442-VGPR wavefront per SIMD and measured slower there (1024 x 201: 312 us against 240,
   // profiles/r05_history.md); 1 = the workgroup kernel wherever it exists; 2 = the wide kernel wherever it exists (N <= 256)
   eng->force_block_kernel = cfg->tune_block_kernel == 1 || (cfg->tune_block_kernel == 0 && cfg->num_vehicles > 128);
+  // the Linear traffic family: the one-wavefront kernel for N <= 64, the workgroup kernel beyond (hwy_wave2.h is IDM-only, so
+  // 64 < N <= 128 takes the workgroup kernel and tune_block_kernel == 2 is the engine's own choice)
+  if (cfg->traffic_model == HWY_TRAFFIC_LINEAR) eng->force_block_kernel = cfg->tune_block_kernel == 1 || cfg->num_vehicles > 64;
   // road-network kernel: 128 VGPRs, 4 waves/SIMD, no spills.
   // intersection kernel with helper lanes (N <= 32, hwy_ix.h): 150 VGPRs, but 20.2 KB of LDS per one-wavefront workgroup keep it
   // at 2 per SIMD.  Without them (N > 32, or tune_ix_no_helpers): 128 VGPRs / 16.7 KB (2048 x 30: 371.9 us against 285.1)
@@ -382,6 +411,10 @@ extern "C" int hwy_create(const hwy_config *cfg, int device, void *stream, hwy_e
 #define ALLOC(ptr, bytes) if ((e = hipMalloc((void **)&(ptr), (bytes))) != hipSuccess) return bail(e, "hipMalloc " #ptr)
   ALLOC(eng->d_f64, plane * 9 * sizeof(double));
   ALLOC(eng->d_packed, plane * sizeof(int32_t));
+  if (cfg->traffic_model == HWY_TRAFFIC_LINEAR) {
+    ALLOC(eng->d_behavior, plane * HWY_BEHAVIOR_PARAMS * sizeof(double));
+    if ((e = hipMemsetAsync(eng->d_behavior, 0, plane * HWY_BEHAVIOR_PARAMS * sizeof(double), eng->stream)) != hipSuccess) return bail(e, "hipMemset");
+  }
   if (cfg->scenario == HWY_SCENARIO_INTERSECTION) {
     ALLOC(eng->d_route, plane * sizeof(long long));
     ALLOC(eng->d_road_steps, E * sizeof(int32_t));
@@ -451,7 +484,8 @@ extern "C" int hwy_create(const hwy_config *cfg, int device, void *stream, hwy_e
     StepParams probe;
     hwy::params_from_config(*cfg, eng->pitch, probe);
     int resident = 0;
-    if (cfg->scenario == HWY_SCENARIO_HIGHWAY) resident = hwy::step_resident_blocks(probe, eng->waves_per_eu, eng->force_block_kernel, cfg->tune_extra_lds);
+    if (cfg->traffic_model == HWY_TRAFFIC_LINEAR) resident = hwy::step_linear_resident_blocks(probe, eng->waves_per_eu, eng->force_block_kernel, cfg->tune_extra_lds);
+    else if (cfg->scenario == HWY_SCENARIO_HIGHWAY) resident = hwy::step_resident_blocks(probe, eng->waves_per_eu, eng->force_block_kernel, cfg->tune_extra_lds);
     else if (cfg->scenario != HWY_SCENARIO_INTERSECTION) resident = hwy::net_step_resident_blocks(eng->waves_per_eu);
     // the turn that pays is about a sixth of a wavefront's lifetime, i.e. it grows with the frames of a policy step: 2^14 ticks
     // for the 5 frames of highway-fast-v0 (13: 47.0 us, 14: 44.96, 15: 47.7), 2^16 for the 15 frames of highway-v0 (14: 134.3
@@ -489,7 +523,8 @@ extern "C" int hwy_destroy(hwy_engine *eng) {
   for (auto &pr : eng->tuner.events) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
   void *ptrs[] = {eng->d_f64, eng->d_packed, eng->d_time, eng->d_done, eng->d_episode, eng->d_actions, eng->d_out, eng->d_roll,
                   eng->d_mask, eng->d_seeds, eng->d_grid_ws, eng->d_route, eng->d_road_steps, eng->d_gnet,
-                  eng->d_shadow_f64, eng->d_shadow_packed, eng->d_shadow_route, eng->d_shadow_meta, eng->d_counters, eng->d_block_env};
+                  eng->d_shadow_f64, eng->d_shadow_packed, eng->d_shadow_route, eng->d_shadow_meta, eng->d_counters, eng->d_block_env,
+                  eng->d_behavior};
   for (void *q : ptrs) if (q) (void)hipFree(q);
   if (eng->h_pinned) (void)hipHostFree(eng->h_pinned);
   if (eng->own_stream && eng->stream) (void)hipStreamDestroy(eng->stream);
@@ -628,6 +663,37 @@ extern "C" int hwy_get_state(hwy_engine *eng, hwy_state *h) {
   return HWY_OK;
 }
 
+// ---- per-vehicle behaviour parameters (HWY_TRAFFIC_LINEAR) ----------------------------------------------
+// host [E][N][HWY_BEHAVIOR_PARAMS] <-> device planes [k][E][pitch]
+extern "C" int hwy_set_behavior(hwy_engine *eng, const double *params) {
+  if (!eng || !params) return HWY_ERR_INVALID_ARG;
+  if (!is_linear(eng)) return fail(eng, HWY_ERR_INVALID_ARG, "hwy_set_behavior: the engine's traffic model has no per-vehicle parameters");
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  const int E = eng->cfg.num_envs, N = eng->cfg.num_vehicles, P = eng->pitch;
+  const size_t plane = (size_t)E * P;
+  std::vector<double> h(plane * HWY_BEHAVIOR_PARAMS, 0.0);
+  for (int e = 0; e < E; ++e)
+    for (int i = 0; i < N; ++i)
+      for (int q = 0; q < HWY_BEHAVIOR_PARAMS; ++q) h[q * plane + (size_t)e * P + i] = params[((size_t)e * N + i) * HWY_BEHAVIOR_PARAMS + q];
+  HWY_HIP(eng, hipMemcpyAsync(eng->d_behavior, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, eng->stream));
+  HWY_HIP(eng, hipStreamSynchronize(eng->stream));
+  return HWY_OK;
+}
+extern "C" int hwy_get_behavior(hwy_engine *eng, double *params) {
+  if (!eng || !params) return HWY_ERR_INVALID_ARG;
+  if (!is_linear(eng)) return fail(eng, HWY_ERR_INVALID_ARG, "hwy_get_behavior: the engine's traffic model has no per-vehicle parameters");
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  const int E = eng->cfg.num_envs, N = eng->cfg.num_vehicles, P = eng->pitch;
+  const size_t plane = (size_t)E * P;
+  std::vector<double> h(plane * HWY_BEHAVIOR_PARAMS);
+  HWY_HIP(eng, hipMemcpyAsync(h.data(), eng->d_behavior, h.size() * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+  HWY_HIP(eng, hipStreamSynchronize(eng->stream));
+  for (int e = 0; e < E; ++e)
+    for (int i = 0; i < N; ++i)
+      for (int q = 0; q < HWY_BEHAVIOR_PARAMS; ++q) params[((size_t)e * N + i) * HWY_BEHAVIOR_PARAMS + q] = h[q * plane + (size_t)e * P + i];
+  return HWY_OK;
+}
+
 // ---- kernel timing ----------------------------------------------------------------------------------
 static hipError_t launch_step_any(const hwy_engine *eng, const StepParams &p);
 static int timed_launch(hwy_engine *eng, const StepParams &p) {
@@ -738,6 +804,16 @@ extern "C" int hwy_rollout_device(hwy_engine *eng, int32_t k_steps, const int32_
   p.full_step = 1;
   p.actions = d_actions; p.obs = d_obs; p.reward = d_reward; p.terminated = d_terminated; p.truncated = d_truncated;
   p.info_speed = d_info_speed; p.info_crashed = d_info_crashed;
+  if (is_linear(eng)) {  // straight road, Linear traffic: K steps in ONE launch (one-wavefront or workgroup kernel)
+    p.k_steps = k_steps;
+    p.num_envs = eng->cfg.num_envs;
+    hwy::LinearParams lp;
+    fill_linear(eng, p, lp);
+    HWY_HIP(eng, hwy::launch_rollout_linear(lp, eng->cfg.num_envs, eng->stream,
+                                            eng->force_block_kernel ? eng->waves_per_eu : eng->rollout_waves_per_eu,
+                                            eng->force_block_kernel, eng->cfg.tune_extra_lds));
+    return HWY_OK;
+  }
   if (!is_ix(eng) && !is_net(eng)) {  // straight road: K steps in ONE launch
     p.k_steps = k_steps;
     p.num_envs = eng->cfg.num_envs;
@@ -937,7 +1013,7 @@ extern "C" int hwy_set_autoreset(hwy_engine *eng, int32_t enabled, uint64_t base
 }
 
 extern "C" int hwy_debug_math(hwy_engine *eng, int32_t op, const double *in, double *out, int64_t n) {
-  if (!eng || !in || !out || n < 0 || op < 0 || (op > 11 && (op < 20 || op > 33) && op != 40 && op != 41)) return HWY_ERR_INVALID_ARG;
+  if (!eng || !in || !out || n < 0 || op < 0 || (op > 12 && (op < 20 || op > 33) && op != 40 && op != 41)) return HWY_ERR_INVALID_ARG;
   if (n == 0) return HWY_OK;
   HWY_HIP(eng, hipSetDevice(eng->device));
   double *d_in = nullptr, *d_out = nullptr;

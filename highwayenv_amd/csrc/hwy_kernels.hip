@@ -20,6 +20,7 @@ namespace hwy {
 // Null events (the normal case): a plain launch.
 static thread_local hipEvent_t g_launch_start = nullptr, g_launch_stop = nullptr;
 void set_launch_events(hipEvent_t start, hipEvent_t stop) { g_launch_start = start; g_launch_stop = stop; }
+void get_launch_events(hipEvent_t *start, hipEvent_t *stop) { *start = g_launch_start; *stop = g_launch_stop; }
 #define HWY_LAUNCH(KERNEL, grid, block, lds, stream, ...) \
   hipExtLaunchKernelGGL(KERNEL, grid, block, lds, stream, ::hwy::g_launch_start, ::hwy::g_launch_stop, 0, __VA_ARGS__)
 

@@ -22,6 +22,15 @@ int net_step_resident_blocks(int waves_per_eu);
 hipError_t launch_reset(const StepParams &p, int num_envs, hipStream_t stream);
 hipError_t launch_math_probe(int op, const double *in, double *out, long long n, hipStream_t stream);
 hipError_t launch_observe(const StepParams &p, int num_envs, hipStream_t stream);
+// the Linear traffic family (hwy_config.traffic_model == HWY_TRAFFIC_LINEAR): the one-wavefront kernel for N <= 64 (unless
+// force_block_kernel), the workgroup kernel otherwise -- 64 < N <= 128 included (hwy_wave2.h is IDM-only)
+bool wave_linear_applies(const StepParams &p, bool force_block_kernel);
+hipError_t launch_step_linear(const LinearParams &lp, int num_envs, hipStream_t stream, int waves_per_eu, bool force_block_kernel,
+                              int extra_lds);
+hipError_t launch_rollout_linear(const LinearParams &lp, int num_envs, hipStream_t stream, int waves_per_eu, bool force_block_kernel,
+                                 int extra_lds);  // lp.s.k_steps steps per launch
+hipError_t launch_reset_linear(const LinearParams &lp, int num_envs, hipStream_t stream);
+int step_linear_resident_blocks(const StepParams &p, int waves_per_eu, bool force_block_kernel, int extra_lds);
 // road-network scenarios (hwy_net.h): one wavefront per environment
 hipError_t launch_net_step(const NetParams &np, int num_envs, hipStream_t stream, int waves_per_eu);
 hipError_t launch_net_rollout(const NetParams &np, int num_envs, hipStream_t stream, int waves_per_eu);  // np.s.k_steps steps per launch

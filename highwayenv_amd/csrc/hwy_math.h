@@ -161,6 +161,12 @@ __device__ inline void sincos_bounded(double x, double *sn, double *cs) {
   *cs = ((q + 1) & 2) ? -cc : cc;
 }
 
+// ---- tan(x), |x| <= pi/3 (the clipped steering angle of the Linear traffic family, vehicle/kinematics.py:141-142): the library
+//      routine (ocml on the device, libm in the CPU emulation).  The quotient of sincos_bounded's sine and cosine was measured at
+//      3 ulp next to +-pi/3, where the cosine's 1 ulp is a relative 2^-52; the library's tan stays within the 2 ulp the other
+//      routines of this file are held to (tests/test_traffic_parity.py: probe op 12).  Only the Linear family's kernels call it.
+__device__ inline double tan_bounded(double x) { return tan(x); }
+
 // ---- asin(x), |x| <= 1 -----------------------------------------------------------------------------------------
 __device__ inline double asin_rational(double t) {  // R(t) = t*P(t)/Q(t), asin(x) = x + x*R(x^2) on |x| <= 0.5
   constexpr double pS0 = 1.66666666666666657415e-01, pS1 = -3.25565818622400915405e-01, pS2 = 2.01212532134862925881e-01,

@@ -311,8 +311,10 @@ __device__ inline void observe_wave(const StepParams &p, int e, int eo, const Ve
 // the checker loop, which is correct for any set of checkers but O(#checkers)); the engine launches it for
 // highway-fast-v0 style configs (HWY_C_EGO_ONLY_COLLISIONS), where it keeps the frame loop at 173 VGPRs.
 // One policy step of environment e by its wavefront; eo = row of the action / output planes (see observe_wave).
-template <bool FULL_SCAN>
-__device__ __forceinline__ void wave_policy_step(const StepParams &p, WaveShared &sh, const int e, const int eo) {
+// TM: the traffic model (hwy_device.h: IdmTraffic / LinearTraffic, compile time); la: the Linear family's parameters (unused by IDM).
+template <bool FULL_SCAN, typename TM = IdmTraffic>
+__device__ __forceinline__ void wave_policy_step(const StepParams &p, WaveShared &sh, const int e, const int eo,
+                                                 const LinearArgs &la = LinearArgs{}) {
   typedef EnvBlock<1> B;
   const int i = threadIdx.x;
   const int N = p.N;
@@ -334,6 +336,9 @@ __device__ __forceinline__ void wave_policy_step(const StepParams &p, WaveShared
     me = Veh{};
     const uint32_t episode = p.st.episode[e] + 1u;
     spawn_env<1>(p, sh.x, sh.v, e, p.rp.base_seed + (uint64_t)e, episode, me);
+    if constexpr (TM::LINEAR) {
+      if (active) spawn_behavior(p, la, e, i, p.rp.base_seed + (uint64_t)e, episode, (me.flags & HWY_F_CONTROLLED) != 0);
+    }
     observe_wave<false>(p, e, eo, me, false);
     store_vehicle<1>(p, e, me);
     if (active && (me.flags & HWY_F_CONTROLLED)) {
@@ -358,6 +363,15 @@ __device__ __forceinline__ void wave_policy_step(const StepParams &p, WaveShared
   wave_turn_init(turn, p.prio_shift, p.prio_recip);
   const bool controlled = active && (me.flags & HWY_F_CONTROLLED);
   const bool idm = active && !controlled;
+  // Linear family: my ACCELERATION_PARAMETERS[3], STEERING_PARAMETERS[2], in registers for the policy step (MOBIL applies the
+  // DECIDING vehicle's parameters to its followers too, so nobody reads another vehicle's)
+  double bp[HWY_BEHAVIOR_PARAMS] = {};
+  if constexpr (TM::LINEAR) {
+    if (idm) {
+      const size_t k = (size_t)e * p.pitch + i;
+      for (int q = 0; q < HWY_BEHAVIOR_PARAMS; ++q) bp[q] = la.behavior[q * la.plane + k];
+    }
+  }
   int agent = 0, act0 = HWY_IDLE;
   for (int a = 0; a < p.A; ++a) {  // wave-uniform
     const int act_a = wave_bcast_i(act_lane, a);
@@ -408,8 +422,9 @@ __device__ __forceinline__ void wave_policy_step(const StepParams &p, WaveShared
     for (int b_ = bits; b_; b_ &= b_ - 1)
       __hip_atomic_fetch_or(&sh.lane_mask[__builtin_ctz(b_) + 1], (u64)1 << rank, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     // frame-start snapshot, stored in rank order (with each vehicle's IDM log speed ratio)
-    if (fr == 0) inv_v0 = B::idm_inv_v0(p, sh.ts[i]);  // (after the meta-action of frame 0: the target speed is fixed for the step)
-    const double log_ratio = active ? B::idm_log_ratio_inv(me.v, inv_v0) : 0.0;  // egos and wrecks can be followers too
+    if (!TM::LINEAR && fr == 0) inv_v0 = B::idm_inv_v0(p, sh.ts[i]);  // (after the meta-action of frame 0: the target speed is fixed for the step)
+    // (the Linear family keeps each vehicle's target speed in the slot instead: a MOBIL follower's vt feature)
+    const double log_ratio = TM::LINEAR ? sh.ts[i] : (active ? B::idm_log_ratio_inv(me.v, inv_v0) : 0.0);  // egos and wrecks can be followers too
     HWY_WAVE_LDS_FENCE();  // previous frame's gathers are complete
     if (active) {
       sh.x[rank] = me.x; sh.v[rank] = me.v; sh.c[rank] = me.ch; sh.s[rank] = me.sh; sh.lr[rank] = log_ratio;
@@ -433,14 +448,14 @@ __device__ __forceinline__ void wave_policy_step(const StepParams &p, WaveShared
     int fo = -1, ro = -1, fl = -1, rl = -1, frt = -1, rrt = -1, ft = -1, rt_ = -1;
     const bool left_ok = me.lane - 1 >= 0, right_ok = me.lane + 1 < p.L;
     const double delta = sh.delta[i];
-    const double free_self = B::idm_free_from_log(log_ratio, delta);
+    const double free_self = TM::LINEAR ? 0.0 : B::idm_free_from_log(log_ratio, delta);
     const bool moving = !(fabs(me.v) < 1);
     const bool cl = decide && left_ok && B::reachable(p, me.lane - 1, me.x, me.y) && moving;
     const bool cr = decide && right_ok && B::reachable(p, me.lane + 1, me.x, me.y) && moving;
     bool ok_l = false, ok_r = false;
     double gap_own = 0.0, gap_new = 0.0;  // gap_new: the IDM gap term towards the leader on the side MOBIL picks in this frame
 #ifndef HWY_WAVE_MOBIL_PER_THREAD
-    if (!has_tie) {  // wave-uniform
+    if (!TM::LINEAR && !has_tie) {  // wave-uniform (the Linear family takes the per-thread form below)
       // Every vehicle needs its leader on its own lane and -- while it changes lanes -- on its target lane in every frame.  MOBIL
       // (behavior.py:265-324: both side lanes' leaders and followers, two more gap terms, the follower's braking) is only
       // evaluated by a vehicle whose timer has run out: once per second, i.e. by a fifth (highway-fast-v0) or a fifteenth
@@ -548,14 +563,26 @@ __device__ __forceinline__ void wave_policy_step(const StepParams &p, WaveShared
       const double fo_x = sh.x[g_fo], fo_v = sh.v[g_fo], fo_c = sh.c[g_fo], fo_s = sh.s[g_fo];
       const double fl_x = sh.x[g_fl], fl_v = sh.v[g_fl], fl_c = sh.c[g_fl], fl_s = sh.s[g_fl];
       const double fr_x = sh.x[g_fr], fr_v = sh.v[g_fr], fr_c = sh.c[g_fr], fr_s = sh.s[g_fr];
+      double gap_l, gap_r;
+      if constexpr (TM::LINEAR) {
+        // LinearVehicle.acceleration (hwy_device.h: linear_acc) behind the leaders of the three lanes; gap_own / gap_new hold these
+        // ACCELERATIONS here (section E reads them as such), and jerk = self_pred_a - self_a directly
+        const double tse = sh.ts[i];
+        gap_own = B::linear_acc(bp, tse, me.v, fo >= 0, fo_x - me.x, fo_v);
+        gap_l = B::linear_acc(bp, tse, me.v, fl >= 0, fl_x - me.x, fl_v);
+        gap_r = B::linear_acc(bp, tse, me.v, frt >= 0, fr_x - me.x, fr_v);
+        ok_l = cl && !((gap_l - gap_own) < la.lc_gain);
+        ok_r = cr && !((gap_r - gap_own) < la.lc_gain);
+      } else {
       gap_own = fo >= 0 ? B::idm_gap(me.x, me.v, me.ch, me.sh, fo_x, fo_v, fo_c, fo_s) : 0.0;
       // MOBIL (behavior.py:265-324), both candidates side by side.  jerk = self_pred_a - self_a with
       // self_* = free_self - gap_*  (POLITENESS == 0: the followers' terms are multiplied by 0.0)
       const double self_a = free_self - gap_own;
-      const double gap_l = fl >= 0 ? B::idm_gap(me.x, me.v, me.ch, me.sh, fl_x, fl_v, fl_c, fl_s) : 0.0;
-      const double gap_r = frt >= 0 ? B::idm_gap(me.x, me.v, me.ch, me.sh, fr_x, fr_v, fr_c, fr_s) : 0.0;
+      gap_l = fl >= 0 ? B::idm_gap(me.x, me.v, me.ch, me.sh, fl_x, fl_v, fl_c, fl_s) : 0.0;
+      gap_r = frt >= 0 ? B::idm_gap(me.x, me.v, me.ch, me.sh, fr_x, fr_v, fr_c, fr_s) : 0.0;
       ok_l = cl && !(((free_self - gap_l) - self_a) < HWY_LC_MIN_ACC_GAIN);
       ok_r = cr && !(((free_self - gap_r) - self_a) < HWY_LC_MIN_ACC_GAIN);
+      }
       // safety: the new follower must not have to brake harder than LANE_CHANGE_MAX_BRAKING_IMPOSED.
       // Evaluated only for candidates that passed the (pow-free) incentive test, one side per pass (a
       // vehicle that needs both sides checked -- rare -- takes a second pass); the follower's log speed
@@ -567,13 +594,18 @@ __device__ __forceinline__ void wave_policy_step(const StepParams &p, WaveShared
           const bool left = pend_l;
           const int rf = pend ? (left ? rl : rrt) : 0;
           const double lr_f = sh.lr[rf];
+          bool safe;
+          if constexpr (TM::LINEAR) {  // my parameters on the new follower's features, me as its leader (mobil, behavior.py:283-285)
+            safe = !(B::linear_acc(bp, lr_f, sh.v[rf], true, me.x - sh.x[rf], me.v) < -HWY_LC_MAX_BRAKING);
+          } else {
           const double g = B::idm_gap(sh.x[rf], sh.v[rf], sh.c[rf], sh.s[rf], me.x, me.v, me.ch, me.sh);
           const bool sure_unsafe = g > HWY_COMFORT_ACC_MAX + HWY_LC_MAX_BRAKING + 1e-6;
           const bool sure_safe = lr_f < 0.0 && delta > 0.0 && g <= HWY_LC_MAX_BRAKING - 1e-6;
-          bool safe = sure_safe;
+          safe = sure_safe;
           if (__ballot(pend && !sure_unsafe && !sure_safe) != 0) {  // wave-uniform
             const double a_f = B::idm_free_from_log(lr_f, delta) - g;
             safe = !(a_f < -HWY_LC_MAX_BRAKING);
+          }
           }
           if (pend) {
             if (left) { ok_l = safe; pend_l = false; } else { ok_r = safe; pend_r = false; }
@@ -617,7 +649,7 @@ __device__ __forceinline__ void wave_policy_step(const StepParams &p, WaveShared
         // d*(c, r) = 10 + 1.5 v + v dv / (2 sqrt(ab)), dv <= v + 5 for a sane rival when v >= 0 and cos h >= 0; 1e-6 relative +
         // absolute on top, far above any rounding in d* (tests/test_wide_kernel.py::test_abort_chain_window_bound_...)
         const double bound = (sane && me.v >= 0.0 && me.ch >= 0.0)
-                                 ? (HWY_DISTANCE_WANTED + me.v * HWY_TIME_WANTED + me.v * (me.v + 5.0) * 0.12909944487358055) * (1.0 + 1e-6) + 1e-6
+                                 ? (HWY_DISTANCE_WANTED + me.v * TM::TIME_WANTED + me.v * (me.v + 5.0) * 0.12909944487358055) * (1.0 + 1e-6) + 1e-6
                                  : __builtin_inf();
         while (__ballot(rem != 0) != 0) {  // wave-uniform
           const bool go = rem != 0;
@@ -629,7 +661,7 @@ __device__ __forceinline__ void wave_policy_step(const StepParams &p, WaveShared
           const bool inside = go && d < bound;
           // a vehicle later in the list shows its frame-start target -- and one that decided in this very frame headed nowhere
           const bool valid = inside && (ir < i || !(fl_r & 1));
-          const double d_star = B::desired_gap(me.v, me.ch, me.sh, vr, cr_, sr);
+          const double d_star = B::desired_gap(me.v, me.ch, me.sh, vr, cr_, sr, TM::TIME_WANTED);  // (the changer's class)
           const bool blk = valid && (0 < d) && (d < d_star);
           const bool cond = ir < i && (fl_r & 2) != 0;  // an earlier changer: it may abort
           fixed = fixed || (blk && !cond);
@@ -653,8 +685,21 @@ __device__ __forceinline__ void wave_policy_step(const StepParams &p, WaveShared
     wave_turn(turn);
     // ---- E. Road.act: low-level control ----------------------------------------------------------------
     const double inv_v = fast_rcp(not_zero(me.v));
-    double tb = B::steer_tan_beta(p, me.y, me.h, inv_v, me.tgt);
-    double accel = free_self - gap_own;
+    double tb, accel;
+    if constexpr (TM::LINEAR) {
+      tb = drives ? B::linear_tan_beta(p, bp[3], bp[4], me.y, me.h, me.v, me.tgt) : B::steer_tan_beta(p, me.y, me.h, inv_v, me.tgt);
+      accel = gap_own;  // (the own-lane acceleration, see section D)
+      if (drives && me.lane != me.tgt) {
+        double a2 = gap_new;  // decided just now: the chosen side's acceleration of MOBIL
+        if (me.tgt == tgt_old) {
+          const int g_ft = ft < 0 ? 0 : ft;
+          a2 = B::linear_acc(bp, sh.ts[i], me.v, ft >= 0, sh.x[g_ft] - me.x, sh.v[g_ft]);
+        }
+        accel = (a2 < accel) ? a2 : accel;  // Python min(a, b)
+      }
+    } else {
+    tb = B::steer_tan_beta(p, me.y, me.h, inv_v, me.tgt);
+    accel = free_self - gap_own;
     if (drives && me.lane != me.tgt) {
       // leader on the target lane.  For a vehicle that was already changing lanes m_tgt is that lane's
       // mask; for one that decided just now the target is the left/right lane evaluated above.
@@ -666,6 +711,7 @@ __device__ __forceinline__ void wave_policy_step(const StepParams &p, WaveShared
         if (ft >= 0) a2 = free_self - B::idm_gap(me.x, me.v, me.ch, me.sh, sh.x[ft], sh.v[ft], sh.c[ft], sh.s[ft]);
       }
       accel = (a2 < accel) ? a2 : accel;  // Python min(a, b)
+    }
     }
     accel = clipd(accel, -HWY_ACC_MAX, HWY_ACC_MAX);
     accel = controlled ? HWY_KP_A * (sh.ts[i] - me.v) : accel;  // speed_control (controller.py:189-198), not clipped
@@ -879,6 +925,28 @@ __global__ void __launch_bounds__(64, WPE) hwy_rollout_wave_kernel(const StepPar
     wave_policy_step<FULL_SCAN>(pk, sh, e, k * pk.num_envs + e);
     HWY_WAVE_LDS_FENCE();
     __threadfence_block();  // the next step's loads follow this step's stores (same wavefront, same addresses)
+  }
+}
+
+// The Linear traffic family (hwy_config.traffic_model == HWY_TRAFFIC_LINEAR), N <= 64: the same step with the LinearTraffic policy
+// (instantiated in hwy_kernels_linear.hip).  StepParams sits at offset 0 of LinearParams, so HWY_RELOAD_PARAMS reads the same segment.
+template <int WPE, bool FULL_SCAN>
+__global__ void __launch_bounds__(64, WPE) hwy_step_wave_linear_kernel(const LinearParams lp) {
+  __shared__ WaveShared sh;
+  HWY_KERNARG_TOUCH(StepParams);
+  const int e = lp.s.block_env ? (int)lp.s.block_env[blockIdx.x] : (int)blockIdx.x;
+  wave_policy_step<FULL_SCAN, LinearTraffic>(lp.s, sh, e, e, lp.la);
+}
+template <int WPE, bool FULL_SCAN>
+__global__ void __launch_bounds__(64, WPE) hwy_rollout_wave_linear_kernel(const LinearParams lp) {
+  __shared__ WaveShared sh;
+  HWY_KERNARG_TOUCH(StepParams);
+  const int e = blockIdx.x;
+  for (int k = 0; k < lp.s.k_steps; ++k) {  // wave-uniform
+    HWY_RELOAD_PARAMS(pk, lp.s);
+    wave_policy_step<FULL_SCAN, LinearTraffic>(pk, sh, e, k * pk.num_envs + e, lp.la);
+    HWY_WAVE_LDS_FENCE();
+    __threadfence_block();
   }
 }
 

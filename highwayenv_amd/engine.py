@@ -84,6 +84,19 @@ class Engine:
         self._check(self._lib.hwy_get_state(self._h, C.byref(s)))
         return st
 
+    def set_behavior(self, params):
+        """hwy_set_behavior: the Linear traffic family's per-vehicle parameters [E, N, 5]
+        (ACCELERATION_PARAMETERS[0..2] | STEERING_PARAMETERS[0..2])."""
+        a = np.ascontiguousarray(params, dtype=np.float64)
+        if a.shape != (self.E, self.N, _abi.HWY_BEHAVIOR_PARAMS):
+            raise ValueError(f"set_behavior: shape {a.shape}, this engine needs {(self.E, self.N, _abi.HWY_BEHAVIOR_PARAMS)}")
+        self._check(self._lib.hwy_set_behavior(self._h, _ptr(a)))
+
+    def get_behavior(self) -> np.ndarray:
+        out = np.empty((self.E, self.N, _abi.HWY_BEHAVIOR_PARAMS), np.float64)
+        self._check(self._lib.hwy_get_behavior(self._h, _ptr(out)))
+        return out
+
     # -- stepping -----------------------------------------------------------------------------
     def step(self, actions):
         E, A = self.E, self.A

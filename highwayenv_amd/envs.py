@@ -67,7 +67,7 @@ class _Box:
 class VehicleView:
     """Read-only view of one vehicle of one env (reference: Vehicle / ControlledVehicle attributes)."""
 
-    def __init__(self, st, e, i):
+    def __init__(self, st, e, i, behavior=None):
         self.position = np.array([st["x"][e, i], st["y"][e, i]])
         self.heading = float(st["heading"][e, i])
         self.speed = float(st["speed"][e, i])
@@ -81,6 +81,9 @@ class VehicleView:
         self.speed_index = int(st["speed_index"][e, i]) if self.controlled else None
         self.timer = None if self.controlled else float(st["timer"][e, i])
         self.DELTA = None if self.controlled else float(st["delta"][e, i])
+        if behavior is not None and not self.controlled:  # LinearVehicle family (behavior.py:353-416)
+            self.ACCELERATION_PARAMETERS = np.array(behavior[e, i, :3])
+            self.STEERING_PARAMETERS = np.array(behavior[e, i, 3:])
 
     @property
     def velocity(self):
@@ -88,8 +91,8 @@ class VehicleView:
 
 
 class RoadView:
-    def __init__(self, st, e):
-        self.vehicles = [VehicleView(st, e, i) for i in range(st["x"].shape[1])]
+    def __init__(self, st, e, behavior=None):
+        self.vehicles = [VehicleView(st, e, i, behavior) for i in range(st["x"].shape[1])]
         self.objects = []
 
 
@@ -187,7 +190,10 @@ class BatchedHighwayEnv:
                 # gymnasium.utils.seeding.np_random(seed): Generator(PCG64(SeedSequence(seed)))
                 self._np_randoms[e] = np.random.Generator(np.random.PCG64(np.random.SeedSequence(s)))
         if self.spawn_mode == "reference":
-            eng.set_state(self._spawn_reference(self._np_randoms))
+            st0 = self._spawn_reference(self._np_randoms)
+            eng.set_state(st0)
+            if "behavior" in st0:  # LinearVehicle-family traffic: the parameters randomize_behavior drew
+                eng.set_behavior(st0["behavior"])
             obs = eng.observe()
         else:
             sd = np.array([np.random.SeedSequence(s).generate_state(1, np.uint64)[0] if s is None else s
@@ -299,7 +305,8 @@ class BatchedHighwayEnv:
         self._ensure_engine().set_state(st)
 
     def road(self, env_index: int = 0) -> RoadView:
-        return RoadView(self._engine.get_state(), env_index)
+        behavior = self._engine.get_behavior() if self._hcfg.traffic_model == _abi.TRAFFIC_LINEAR else None
+        return RoadView(self._engine.get_state(), env_index, behavior)
 
     def rewards(self, env_index: int = 0) -> dict:
         """HighwayEnv._rewards (highway_env.py:122-139) of one env, from the device state."""

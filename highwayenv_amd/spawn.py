@@ -10,6 +10,8 @@ Two layers:
   ``choice(lanes)`` unless ``lane_id`` is given, ``uniform(0.7*limit, 0.8*limit)`` unless ``speed``
   is given, ``uniform(0.9, 1.1)`` (``Vehicle.create_random``, vehicle/kinematics.py:50-104), then
   ``uniform(3.5, 4.5)`` for ``IDMVehicle.randomize_behavior`` (vehicle/behavior.py:66-69).
+* :func:`draw_reference_stream_linear` / :func:`behavior_from_draws`: the same for the LinearVehicle family, whose
+  ``randomize_behavior`` draws five parameters before ``DELTA`` (vehicle/behavior.py:406-416).
 * :func:`spawn_from_draws` is the spawn RULE as array arithmetic (lane ids + raw uniforms in,
   struct-of-arrays out).  The device-side reset kernel (hwy_device.h: spawn_env) implements the
   same rule on Philox uniforms, and is tested against this function.
@@ -94,7 +96,60 @@ def draw_reference_stream(cfg: _abi.HwyConfig, seeds, initial_lane_id=None):
     return lane_ids, speed_u, pos_u, delta_u
 
 
+def behavior_from_draws(cfg: _abi.HwyConfig, behavior_u) -> np.ndarray:
+    """``LinearVehicle.randomize_behavior`` (vehicle/behavior.py:406-416) as array arithmetic: raw uniforms [E, N, 5] in,
+    ``ACCELERATION_PARAMETERS[0..2] | STEERING_PARAMETERS[0..2]`` [E, N, 5] out (controlled vehicles: zeros).
+
+    ``RANGE[0] + u * (RANGE[1] - RANGE[0])`` with ``LinearVehicle``'s ranges for the whole family: ``AggressiveVehicle`` and
+    ``DefensiveVehicle`` override ``ACCELERATION_PARAMETERS`` but inherit ``ACCELERATION_RANGE``, so for one seed all three
+    classes draw the same parameters.  The device reset (hwy_device.h: linear_behavior_draw) applies the same rule."""
+    u = np.asarray(behavior_u, np.float64)
+    acc = np.array([0.3, 0.3, 2.0])                            # LinearVehicle.ACCELERATION_PARAMETERS
+    kp_heading, kp_lateral = 1 / 0.2, 1 / 0.6                  # ControlledVehicle.KP_HEADING / KP_LATERAL (controller.py:24-31)
+    steer = np.array([kp_heading, kp_heading * kp_lateral])    # LinearVehicle.STEERING_PARAMETERS
+    lo = np.concatenate([0.5 * acc, steer - np.array([0.07, 1.5])])
+    hi = np.concatenate([1.5 * acc, steer + np.array([0.07, 1.5])])
+    b = lo + u * (hi - lo)
+    b[:, controlled_mask(cfg)] = 0.0
+    return b
+
+
+def draw_reference_stream_linear(cfg: _abi.HwyConfig, seeds, initial_lane_id=None):
+    """:func:`draw_reference_stream` for the LinearVehicle family: after ``create_random``'s draws every non-controlled
+    vehicle draws ``uniform(size=3)`` (acceleration), ``uniform(size=2)`` (steering), then IDM's ``DELTA``
+    (``LinearVehicle.randomize_behavior`` calls ``IDMVehicle.randomize_behavior`` last).  Returns the four arrays of
+    :func:`draw_reference_stream` and the five behaviour uniforms [E, N, 5]."""
+    E, N, L = len(seeds), cfg.num_vehicles, cfg.lanes_count
+    ctrl = controlled_mask(cfg)
+    lane_ids = np.zeros((E, N), np.int64)
+    speed_u = np.zeros((E, N))
+    pos_u = np.zeros((E, N))
+    delta_u = np.zeros((E, N))
+    behavior_u = np.zeros((E, N, _abi.HWY_BEHAVIOR_PARAMS))
+    for e, seed in enumerate(seeds):
+        rng = seed if isinstance(seed, np.random.Generator) else np.random.default_rng(int(seed))
+        for k in range(N):
+            if ctrl[k]:
+                lane_ids[e, k] = initial_lane_id if initial_lane_id is not None else rng.choice(L)
+                pos_u[e, k] = rng.random()
+            else:
+                lane_ids[e, k] = rng.choice(L)
+                speed_u[e, k] = rng.random()
+                pos_u[e, k] = rng.random()
+                behavior_u[e, k, :3] = rng.uniform(size=3)
+                behavior_u[e, k, 3:] = rng.uniform(size=2)
+                delta_u[e, k] = rng.random()
+    return lane_ids, speed_u, pos_u, delta_u, behavior_u
+
+
 def spawn_reference_stream(cfg: _abi.HwyConfig, seeds, ego_spacing: float, vehicles_density: float,
                            initial_lane_id=None) -> dict:
+    """Stream-identical initial state; with LinearVehicle-family traffic (``cfg.traffic_model``) it also holds
+    ``"behavior"`` [E, N, 5], the per-vehicle parameters ``Engine.set_behavior`` takes."""
+    if cfg.traffic_model == _abi.TRAFFIC_LINEAR:
+        *draws, behavior_u = draw_reference_stream_linear(cfg, seeds, initial_lane_id)
+        st = spawn_from_draws(cfg, *draws, ego_spacing=ego_spacing, vehicles_density=vehicles_density)
+        st["behavior"] = behavior_from_draws(cfg, behavior_u)
+        return st
     draws = draw_reference_stream(cfg, seeds, initial_lane_id)
     return spawn_from_draws(cfg, *draws, ego_spacing=ego_spacing, vehicles_density=vehicles_density)

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define HWY_ABI_VERSION 5
+#define HWY_ABI_VERSION 6
 
 #define HWY_MAX_AGENTS 16
 #define HWY_MAX_FEATURES 16
@@ -110,6 +110,16 @@ enum {
   HWY_FEAT_ON_ROAD, /* OccupancyGrid only: the on-road layer (observation.py:454-484) */
   HWY_FEAT_COUNT
 };
+
+/* traffic models (hwy_config.traffic_model): the behaviour class of the non-controlled vehicles, config["other_vehicles_type"]
+ * (envs/common/abstract.py:105).  HWY_SCENARIO_HIGHWAY only; the other scenarios take HWY_TRAFFIC_IDM. */
+enum {
+  HWY_TRAFFIC_IDM = 0,    /* IDMVehicle (vehicle/behavior.py:12-347): IDM + MOBIL, DELTA drawn per vehicle */
+  HWY_TRAFFIC_LINEAR = 1  /* LinearVehicle / AggressiveVehicle / DefensiveVehicle (behavior.py:350-585): acceleration and steering
+                             linear in 3 + 2 parameters drawn per vehicle (hwy_set_behavior), TIME_WANTED 2.5; the three classes differ
+                             only in LANE_CHANGE_MIN_ACC_GAIN (hwy_config.traffic_lc_min_acc_gain) */
+};
+#define HWY_BEHAVIOR_PARAMS 5 /* per vehicle: ACCELERATION_PARAMETERS[3], STEERING_PARAMETERS[2] (behavior.py:406-416) */
 
 /* observation types (hwy_config.obs_type) */
 enum { HWY_OBS_KINEMATICS = 0, HWY_OBS_OCCUPANCY_GRID = 1 };
@@ -258,7 +268,9 @@ typedef struct hwy_config {
                                           hwy_wave2.h with two vehicles per thread for 64 < N <= 128 and the Kinematics observation), the
                                           generic workgroup kernel (hwy_device.h) beyond; 1: the workgroup kernel everywhere; 2: the
                                           one-wavefront kernels wherever they exist (hwy_wave2.h with three / four vehicles per thread
-                                          for N <= 192 / 256: bit-identical, measured slower than the workgroup kernel there) */
+                                          for N <= 192 / 256: bit-identical, measured slower than the workgroup kernel there).
+                                          HWY_TRAFFIC_LINEAR: hwy_wave.h for N <= 64 unless 1, the workgroup kernel beyond (hwy_wave2.h
+                                          is IDM-only: 2 is the engine's choice) */
   int32_t tune_waves_per_eu;           /* 1..4: register-allocation variant (resident wavefronts per SIMD) of the step kernel;
                                           no effect where the wide kernel runs (64 < N <= 128, Kinematics: one build, hwy_wave2.h) */
   int32_t tune_ix_no_helpers;          /* 1: HWY_SCENARIO_INTERSECTION with N <= 32 runs 32-thread workgroups (no helper lanes) */
@@ -276,6 +288,14 @@ typedef struct hwy_config {
   int32_t tune_ix_prewarm_frames;      /* HWY_SCENARIO_INTERSECTION auto-reset: warm-up frames of the NEXT episode advanced per
                                           launch by the pre-warming workgroup of an environment (0 = a third of frames_per_step) */
   int32_t tune_reserved[1];
+  /* Traffic model (ABI v6).  The Linear family runs on the one-wavefront kernel (hwy_wave.h) for N <= 64 and on the
+   * workgroup kernel (hwy_device.h) beyond; the two-vehicles-per-thread kernel (hwy_wave2.h) exists for HWY_TRAFFIC_IDM only. */
+  int32_t traffic_model;               /* HWY_TRAFFIC_* */
+  int32_t reserved4;
+  double traffic_lc_min_acc_gain;      /* LANE_CHANGE_MIN_ACC_GAIN of the traffic class: 0.2 IDM / Linear, 1.0 Aggressive /
+                                          Defensive (behavior.py:45,563,575) */
+  double traffic_time_wanted;          /* TIME_WANTED of the traffic class: 1.5 IDM, 2.5 the Linear family (behavior.py:34,387);
+                                          must be the model's own constant (the kernels compile it in) */
 } hwy_config;
 
 /*
@@ -395,6 +415,16 @@ int hwy_step_device(hwy_engine *eng, const int32_t *d_actions, float *d_obs, dou
  */
 int hwy_step_frames(hwy_engine *eng, const int32_t *actions, int32_t n_frames);
 
+/*
+ * Per-vehicle behaviour parameters of the Linear traffic family (hwy_config.traffic_model == HWY_TRAFFIC_LINEAR):
+ * LinearVehicle.ACCELERATION_PARAMETERS[0..2] and STEERING_PARAMETERS[0..2] as drawn by randomize_behavior (behavior.py:406-416),
+ * host array f64 [E][N][HWY_BEHAVIOR_PARAMS] (controlled vehicles: unused).  hwy_reset and the auto-reset draw them on the device;
+ * the stream-identical reset of the host side (highwayenv_amd/spawn.py) hands them in with hwy_set_behavior after hwy_set_state.
+ * Synchronous.  HWY_ERR_INVALID_ARG on an IDM engine (it has no such parameters).
+ */
+int hwy_set_behavior(hwy_engine *eng, const double *params);
+int hwy_get_behavior(hwy_engine *eng, double *params);
+
 /* KinematicObservation.observe for the current state (host pointer out). */
 int hwy_observe(hwy_engine *eng, float *obs);
 
@@ -435,7 +465,8 @@ int hwy_set_block_order(hwy_engine *eng, const int32_t *env_of_block);
  * Self-test hook: evaluate one of the step kernel's own math routines (csrc/hwy_math.h -- bounded-domain
  * log / exp / sincos / asin, Newton-refined v_rcp_f64 / v_rsq_f64, floor-mod angle wrap) on n doubles on
  * the device.  Host pointers.  op: 0 log_pos, 1 exp_bounded, 2 sin, 3 cos, 4 asin_bounded, 5 fast_rcp, 8 atan_fd,
- * 9 atan2_bounded(x, 0.75), 10 atan2_bounded(0.5, x), 11 atan2_bounded(-0.5, x),
+ * 9 atan2_bounded(x, 0.75), 10 atan2_bounded(0.5, x), 11 atan2_bounded(-0.5, x), 12 tan_bounded (|x| <= pi/3, the Linear
+ * traffic family's steering),
  * 6 fast_rsqrt, 7 wrap_to_pi; 20 .. 33: the paired forms (log_pos2, exp_bounded2, sincos_bounded2, asin_bounded2, fast_rcp2,
  * fast_rsqrt2: first / second result, see math_probe in csrc/hwy_device.h), which must equal the scalar ones bit for bit.
  * 40 / 41: the collision walk's reach bound (hwy_device.h: the wavefront's maximum of reach_key -- call with whole wavefronts, n a

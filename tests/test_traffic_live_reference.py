@@ -1,0 +1,90 @@
+"""The LinearVehicle family's kernels (CPU emulation, tests/emu/emu_traffic.py) against the LIVE unmodified reference on random
+configurations: about 12 per class (LinearVehicle, AggressiveVehicle, DefensiveVehicle), drawn over vehicles_count, lanes_count,
+vehicles_density, simulation / policy frequency, controlled_vehicles and highway-v0 / highway-fast-v0.  The reference is driven by
+the fixture generator (tests/golden/traffic/make_golden_traffic.py: run) and the emulation is held to the fixtures' checks: the
+initial state and parameters of the host spawn bit for bit, then every policy step's observation at 1e-6, reward at 1e-9,
+terminated / truncated / crashed and the lanes exact, each environment up to its first termination.  Build container only (the
+reference does not exist on the GPU machines).  HWY_TRAFFIC_REF_CASES: configurations per class (default 12)."""
+import importlib.util
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from highwayenv_amd import _abi, spawn
+from oracle import ref_stub
+from tests.traffic_util import TRAFFIC_DIR, TrafficGolden, make_engine
+
+pytestmark = [pytest.mark.reference,
+              pytest.mark.skipif(not ref_stub.reference_available(), reason="needs the reference package")]
+
+CLASSES = ["LinearVehicle", "AggressiveVehicle", "DefensiveVehicle"]
+CASES = range(int(os.environ.get("HWY_TRAFFIC_REF_CASES", "12")))
+_mgt = None
+
+
+def _generator():
+    global _mgt
+    if _mgt is None:
+        golden = os.path.dirname(TRAFFIC_DIR)
+        if golden not in sys.path:
+            sys.path.insert(0, golden)
+        spec = importlib.util.spec_from_file_location("make_golden_traffic", os.path.join(TRAFFIC_DIR, "make_golden_traffic.py"))
+        _mgt = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(_mgt)
+    return _mgt
+
+
+def _draw(cls: str, case: int) -> dict:
+    mgt = _generator()
+    rng = np.random.default_rng(77_000 + 1000 * CLASSES.index(cls) + case)
+    fast = bool(rng.integers(0, 2))
+    A = int(rng.choice([1, 1, 2]))
+    sim = int(rng.choice([5, 10, 15]))
+    config = {"vehicles_count": int(rng.integers(5, 46)), "lanes_count": int(rng.integers(2, 6)),
+              "vehicles_density": float(np.round(rng.uniform(0.7, 2.2), 3)), "simulation_frequency": sim,
+              "policy_frequency": int(rng.choice([1, 2])), "ego_spacing": float(np.round(rng.uniform(1.0, 2.5), 3)),
+              "duration": 20, "other_vehicles_type": "highway_env.vehicle.behavior." + cls}
+    if A > 1:
+        config.update({"controlled_vehicles": A,
+                       "observation": {"type": "MultiAgentObservation", "observation_config": {"type": "Kinematics"}},
+                       "action": {"type": "MultiAgentAction", "action_config": {"type": "DiscreteMetaAction"}}})
+    sc = dict(name=f"live_{cls}_{case}", cls=mgt.mg.HighwayEnvFast if fast else mgt.mg.HighwayEnv, config=config,
+              seeds=[int(rng.integers(0, 2**31))], steps=5, action_seed=int(rng.integers(0, 2**31)), frames_for=0)
+    if A > 1:
+        sc["multi_agent"] = A
+    return sc
+
+
+@pytest.mark.parametrize("case", CASES)
+@pytest.mark.parametrize("cls", CLASSES)
+def test_emulation_against_live_reference(cls, case):
+    sc = _draw(cls, case)
+    data = _generator().run(sc)
+    g = TrafficGolden(sc["name"], data)
+    cfg = g.hwy_config()
+    st = spawn.spawn_reference_stream(cfg, g.seeds, g.config["ego_spacing"], g.config["vehicles_density"])
+    want0 = g.state("init")
+    for k in ("x", "y", "speed", "lane", "flags"):
+        np.testing.assert_array_equal(st[k], want0[k], err_msg=f"{sc['name']}: spawn {k}")
+    np.testing.assert_array_equal(st["behavior"], g.behavior, err_msg=f"{sc['name']}: parameters")
+    eng = make_engine("emu", cfg)
+    eng.set_state(want0)
+    eng.set_behavior(g.behavior)
+    z = g.z
+    ego = cfg.agent_index[0]
+    for t in range(g.steps):
+        obs, reward, term, trunc, info = eng.step(g.actions_at(t))
+        what = f"{sc['name']} ({json.dumps(sc['config'])}) step {t}"
+        np.testing.assert_allclose(obs, z["obs"][t].reshape(obs.shape), rtol=0, atol=1e-6, err_msg=what + ": obs")
+        np.testing.assert_allclose(reward[:, 0], z["reward"][t], rtol=0, atol=1e-9, err_msg=what + ": reward")
+        np.testing.assert_array_equal(term, z["terminated"][t].astype(bool), err_msg=what + ": terminated")
+        np.testing.assert_array_equal(trunc, z["truncated"][t].astype(bool), err_msg=what + ": truncated")
+        np.testing.assert_array_equal(info["crashed"][:, 0], z["step_crashed"][t][:, ego] != 0, err_msg=what + ": crashed")
+        got = eng.get_state()
+        for k in ("lane", "target_lane"):
+            np.testing.assert_array_equal(got[k], z["step_" + k][t], err_msg=what + ": " + k)
+        if term[0]:
+            break
