@@ -1493,6 +1493,11 @@ __device__ __forceinline__ void block_policy_step(const StepParams &p, typename 
                                  ? (HWY_DISTANCE_WANTED + me.v * TM::TIME_WANTED + me.v * (me.v + 5.0) * 0.12909944487358055) * (1.0 + 1e-6) + 1e-6
                                  : __builtin_inf();
         const u64 *prev = nullptr;  // the previous round's verdicts (index space: the ballot's own LDS slot); none in the first round
+        // ... and a copy of them taken right after their barrier, for the fixed-point test: once past a round's barrier a faster
+        // wavefront may already be writing the NEXT round's verdict into the other half of the slot pair -- the half `prev` points
+        // to -- so the test must not read it there.  (The walk may: that half is rewritten only after the next barrier.)
+        u64 last[NW];
+        for (int w = 0; w < NW; ++w) last[w] = 0;
         for (;;) {  // block-uniform
           // (2) the walk: nearest member of S_T ahead first; beyond the bound everything farther is beyond it too
           bool fire = false;
@@ -1523,14 +1528,18 @@ __device__ __forceinline__ void block_policy_step(const StepParams &p, typename 
             }
           }
           // (3) the changers that abort, to the fixed point: the verdicts of a round are a workgroup ballot (its slot pair alternates,
-          // so the previous round's words are still there to compare with and to read in the next walk)
+          // so the previous round's words are still there for the next walk; the fixed-point test compares with `last`)
           const u64 b = __ballot(fire);
           u64 *slot = sh.bal1 + ph1 * NW;
           ph1 ^= 1;
           if (lane_id == 0) slot[wave] = b;
           __syncthreads();
           bool same = true;
-          for (int w = 0; w < NW; ++w) same = same && slot[w] == (prev ? prev[w] : (u64)0);
+          for (int w = 0; w < NW; ++w) {
+            const u64 v = slot[w];
+            same = same && v == last[w];
+            last[w] = v;
+          }
           prev = slot;
           if (same) break;
         }

@@ -76,7 +76,56 @@ def _p(a, t):
     return None if a is None else a.ctypes.data_as(C.POINTER(t))
 
 
-class EmuEngine:
+# schedule policies of the emulator (hip_emu.h, emu_set_schedule).  wave: "rr" (the default round-robin) or the order in which
+# the wavefronts of a workgroup run ahead to the next workgroup barrier, one at a time; lane: the order of the fibers of a
+# wavefront between two rendezvous; block: the order of the workgroups of a launch.  "seeded" orders are drawn again at every
+# barrier (wave, lane) or launch (block) from the seed.
+WAVE_ORDERS = {"rr": 0, "asc": 1, "desc": 2, "seeded": 3}
+ORDERS = {"asc": 0, "desc": 2, "seeded": 3}
+
+
+def schedule_policy(wave="rr", lane="asc", block="asc") -> int:
+    return WAVE_ORDERS[wave] | ORDERS[lane] << 4 | ORDERS[block] << 8
+
+
+class Scheduled:
+    """The schedule an emulated engine's launches run under, and the rendezvous violations they met (schedule_errors: a
+    workgroup barrier or a wave rendezvous whose fibers came from different call sites, a block whose threads passed different
+    numbers of barriers, a launch in which no fiber could run any more).  The library's schedule is set around each call and
+    put back to the default after it, so engines with different schedules can be used side by side."""
+    _policy = _seed = _calls = _errors = 0
+    _error_text = ""
+
+    def set_schedule(self, wave="rr", lane="asc", block="asc", seed=0):
+        self._policy, self._seed = schedule_policy(wave, lane, block), int(seed)
+
+    def schedule_errors(self) -> int:
+        return self._errors
+
+    def schedule_error_text(self) -> str:
+        return self._error_text
+
+    def _scheduled(self, L, call):
+        L.emu_schedule_errors.restype = C.c_longlong
+        L.emu_clear_schedule_errors()
+        # every launch of a seeded schedule draws from its own stream
+        L.emu_set_schedule(C.c_int(self._policy), C.c_uint64((self._seed * 0x9E3779B1 + self._calls) & (2 ** 64 - 1)))
+        self._calls += 1
+        try:
+            return call()
+        finally:
+            n = L.emu_schedule_errors()
+            if n:
+                if not self._errors:
+                    buf = C.create_string_buffer(4096)
+                    L.emu_schedule_error_text(buf, C.c_int(len(buf)))
+                    self._error_text = buf.value.decode()
+                self._errors += n
+            L.emu_set_schedule(C.c_int(0), C.c_uint64(0))
+            L.emu_clear_schedule_errors()
+
+
+class EmuEngine(Scheduled):
     def __init__(self, cfg: _abi.HwyConfig):
         self.cfg = cfg
         self.E, self.N, self.A = cfg.num_envs, cfg.num_vehicles, cfg.num_agents
@@ -137,11 +186,11 @@ class EmuEngine:
         self._bind_shadow()
         be = getattr(self, "_block_env", None)
         lib().emu_set_block_order(None if be is None else be.ctypes.data_as(C.c_void_p))
-        rc = lib().emu_run(C.byref(self.cfg), C.byref(s), _p(self.done, C.c_uint8), _p(self.episode, C.c_uint32),
-                           C.c_int(mode), C.c_int(n_frames), _p(acts, C.c_int32), _p(obs, C.c_float),
-                           _p(reward, C.c_double), _p(term, C.c_uint8), _p(trunc, C.c_uint8), _p(speed, C.c_double),
-                           _p(crashed, C.c_uint8), C.c_int(ar[0]), C.c_uint64(ar[1]), C.c_double(ar[2]),
-                           C.c_double(ar[3]), C.c_int(ar[4]))
+        rc = self._scheduled(lib(), lambda: lib().emu_run(
+            C.byref(self.cfg), C.byref(s), _p(self.done, C.c_uint8), _p(self.episode, C.c_uint32), C.c_int(mode), C.c_int(n_frames),
+            _p(acts, C.c_int32), _p(obs, C.c_float), _p(reward, C.c_double), _p(term, C.c_uint8), _p(trunc, C.c_uint8),
+            _p(speed, C.c_double), _p(crashed, C.c_uint8), C.c_int(ar[0]), C.c_uint64(ar[1]), C.c_double(ar[2]), C.c_double(ar[3]),
+            C.c_int(ar[4])))
         assert rc == 0
         return obs, reward, term.astype(bool), trunc.astype(bool), {"speed": speed, "crashed": (crashed & 1).astype(bool),
                                                                     "arrived": (crashed & 2).astype(bool)}
@@ -177,11 +226,11 @@ class EmuEngine:
         self._bind_shadow()
         lib().emu_set_rollout(C.c_int(K))
         try:
-            rc = lib().emu_run(C.byref(self.cfg), C.byref(s), _p(self.done, C.c_uint8), _p(self.episode, C.c_uint32),
-                               C.c_int(1), C.c_int(self.cfg.frames_per_step), _p(acts, C.c_int32), _p(obs, C.c_float),
-                               _p(reward, C.c_double), _p(term, C.c_uint8), _p(trunc, C.c_uint8), _p(speed, C.c_double),
-                               _p(crashed, C.c_uint8), C.c_int(ar[0]), C.c_uint64(ar[1]), C.c_double(ar[2]),
-                               C.c_double(ar[3]), C.c_int(ar[4]))
+            rc = self._scheduled(lib(), lambda: lib().emu_run(
+                C.byref(self.cfg), C.byref(s), _p(self.done, C.c_uint8), _p(self.episode, C.c_uint32), C.c_int(1),
+                C.c_int(self.cfg.frames_per_step), _p(acts, C.c_int32), _p(obs, C.c_float), _p(reward, C.c_double),
+                _p(term, C.c_uint8), _p(trunc, C.c_uint8), _p(speed, C.c_double), _p(crashed, C.c_uint8), C.c_int(ar[0]),
+                C.c_uint64(ar[1]), C.c_double(ar[2]), C.c_double(ar[3]), C.c_int(ar[4])))
         finally:
             lib().emu_set_rollout(C.c_int(0))
         assert rc == 0
@@ -201,9 +250,10 @@ class EmuEngine:
         mk = None if mask is None else np.ascontiguousarray(mask, np.uint8)
         s = _abi.state_struct(self.st)
         self._bind_shadow()
-        rc = lib().emu_reset(C.byref(self.cfg), C.byref(s), _p(self.done, C.c_uint8), _p(self.episode, C.c_uint32),
-                             _p(mk, C.c_uint8), _p(sd, C.c_uint64), C.c_uint64(base_seed), C.c_double(ego_spacing),
-                             C.c_double(vehicles_density), C.c_int(initial_lane_id), _p(obs, C.c_float))
+        rc = self._scheduled(lib(), lambda: lib().emu_reset(
+            C.byref(self.cfg), C.byref(s), _p(self.done, C.c_uint8), _p(self.episode, C.c_uint32), _p(mk, C.c_uint8),
+            _p(sd, C.c_uint64), C.c_uint64(base_seed), C.c_double(ego_spacing), C.c_double(vehicles_density),
+            C.c_int(initial_lane_id), _p(obs, C.c_float)))
         assert rc == 0
         return obs
 

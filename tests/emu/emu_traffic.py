@@ -48,7 +48,7 @@ def _p(a, t):
     return None if a is None else a.ctypes.data_as(C.POINTER(t))
 
 
-class EmuTrafficEngine:
+class EmuTrafficEngine(emu.Scheduled):
     def __init__(self, cfg: _abi.HwyConfig):
         assert cfg.traffic_model == _abi.TRAFFIC_LINEAR
         self.cfg = cfg
@@ -90,11 +90,11 @@ class EmuTrafficEngine:
         speed, crashed = np.zeros((K, E, A)), np.zeros((K, E, A), np.uint8)
         s = _abi.state_struct(self.st)
         ar = self.autoreset
-        rc = lib().emu_traffic_run(C.byref(self.cfg), C.byref(s), _p(self.planes, C.c_double), _p(self.done, C.c_uint8),
-                                   _p(self.episode, C.c_uint32), C.c_int(mode), C.c_int(n_frames), C.c_int(k_steps),
-                                   _p(acts, C.c_int32), _p(obs, C.c_float), _p(reward, C.c_double), _p(term, C.c_uint8),
-                                   _p(trunc, C.c_uint8), _p(speed, C.c_double), _p(crashed, C.c_uint8), C.c_int(ar[0]),
-                                   C.c_uint64(ar[1]), C.c_double(ar[2]), C.c_double(ar[3]), C.c_int(ar[4]))
+        rc = self._scheduled(lib(), lambda: lib().emu_traffic_run(
+            C.byref(self.cfg), C.byref(s), _p(self.planes, C.c_double), _p(self.done, C.c_uint8), _p(self.episode, C.c_uint32),
+            C.c_int(mode), C.c_int(n_frames), C.c_int(k_steps), _p(acts, C.c_int32), _p(obs, C.c_float), _p(reward, C.c_double),
+            _p(term, C.c_uint8), _p(trunc, C.c_uint8), _p(speed, C.c_double), _p(crashed, C.c_uint8), C.c_int(ar[0]),
+            C.c_uint64(ar[1]), C.c_double(ar[2]), C.c_double(ar[3]), C.c_int(ar[4])))
         assert rc == 0
         info = {"speed": speed, "crashed": (crashed & 1).astype(bool)}
         return obs, reward, term.astype(bool), trunc.astype(bool), info
@@ -123,10 +123,10 @@ class EmuTrafficEngine:
         sd = None if seeds is None else np.ascontiguousarray(seeds, np.uint64)
         mk = None if mask is None else np.ascontiguousarray(mask, np.uint8)
         s = _abi.state_struct(self.st)
-        rc = lib().emu_traffic_reset(C.byref(self.cfg), C.byref(s), _p(self.planes, C.c_double), _p(self.done, C.c_uint8),
-                                     _p(self.episode, C.c_uint32), _p(mk, C.c_uint8), _p(sd, C.c_uint64), C.c_uint64(base_seed),
-                                     C.c_double(ego_spacing), C.c_double(vehicles_density), C.c_int(initial_lane_id),
-                                     _p(obs, C.c_float))
+        rc = self._scheduled(lib(), lambda: lib().emu_traffic_reset(
+            C.byref(self.cfg), C.byref(s), _p(self.planes, C.c_double), _p(self.done, C.c_uint8), _p(self.episode, C.c_uint32),
+            _p(mk, C.c_uint8), _p(sd, C.c_uint64), C.c_uint64(base_seed), C.c_double(ego_spacing), C.c_double(vehicles_density),
+            C.c_int(initial_lane_id), _p(obs, C.c_float)))
         assert rc == 0
         return obs
 

@@ -4,16 +4,22 @@
 // which has no GPU.  Never compiled into, linked with or loaded by the product.
 //
 // Execution model: every GPU thread of a workgroup is a FIBER (ucontext) on one OS thread,
-// scheduled round-robin; __syncthreads / ballots / readlane / ds_permute are rendezvous points.
+// scheduled round-robin by default; __syncthreads / ballots / readlane / ds_permute are rendezvous points.
 // Workgroups run one after the other.  Restriction honoured by the kernels: every rendezvous is
-// executed in workgroup-uniform control flow.
+// executed in workgroup-uniform control flow.  emu_set_schedule picks other legal schedules (the order of
+// the wavefronts, of the lanes and of the workgroups), and every rendezvous checks that all of its fibers
+// arrive at the same call site; a violation, or a launch in which no fiber can run any more, is counted
+// (emu_schedule_errors) instead of hanging the process.
 #pragma once
 #include <math.h>
 #include <stdint.h>
 #include <ucontext.h>
 
 #include <cstdlib>
+#include <cstring>
 #include <functional>
+#include <source_location>
+#include <string>
 #include <vector>
 
 #define __global__
@@ -44,6 +50,8 @@
 struct emu_dim3 { int x = 0, y = 0, z = 0; };
 
 namespace emu {
+using Loc = std::source_location;  // the call site of a rendezvous (a default argument: the kernel source's own line)
+enum Wait { RUNNING, AT_BARRIER, AT_WAVE, FINISHED };
 struct Fiber {
   ucontext_t ctx;
   emu_dim3 tid, bid, bdim;
@@ -52,6 +60,10 @@ struct Fiber {
   unsigned bor_phase = 0;
   bool finished = false;
   char *stack = nullptr;
+  Wait wait = RUNNING;    // what the fiber waits for: the workgroup barrier / its wavefront's rendezvous of generation wait_gen
+  unsigned wait_gen = 0;
+  Loc site;               // the rendezvous it waits at (or passed last)
+  long long n_bar = 0;    // workgroup barriers passed in the current block
 };
 inline Fiber *cur = nullptr;
 inline std::vector<Fiber> *fibers = nullptr;
@@ -60,36 +72,186 @@ inline int n_fibers = 0;
 // generation barrier
 inline int bar_count = 0;
 inline unsigned bar_gen = 0;
-
-inline void yield() {
-  Fiber *me = cur;
-  const int next = (me->tid.x + 1) % n_fibers;
-  cur = &(*fibers)[next];
-  swapcontext(&me->ctx, &cur->ctx);
-}
-inline void barrier() {
-  const unsigned gen = bar_gen;
-  if (++bar_count == n_fibers) {
-    bar_count = 0;
-    ++bar_gen;
-  } else {
-    while (bar_gen == gen) yield();
-  }
-}
 // rendezvous of the (up to) 64 fibers of ONE wavefront: ballots / readlane / ds_permute are wave-level operations, and the
 // wavefronts of a multi-wave workgroup may execute different numbers of them between two workgroup barriers
 inline int wbar_count[16];
 inline unsigned wbar_gen[16];
-inline void wave_barrier() {
-  const int w = cur->tid.x >> 6;
-  const int size = n_fibers - 64 * w < 64 ? n_fibers - 64 * w : 64;
+
+// ---- schedule policies (emu_set_schedule) -------------------------------------------------------------------------------------
+// The default is the original schedule, bit for bit: fibers round-robin in thread order, a fiber gives up the CPU only while it
+// waits, the fiber that completes a rendezvous runs on.  The other policies pick among the fibers that can run:
+//  * wave order (bits 0-3): 1 ascending, 2 descending, 3 seeded -- after a workgroup barrier ONE wavefront runs until all of its
+//    fibers wait at the next workgroup barrier (or have finished), then the next one; the order is drawn again at every barrier;
+//  * lane order (bits 4-7): 2 descending, 3 seeded -- the fibers of a wavefront run in that order between two rendezvous (drawn
+//    again at every rendezvous of the wavefront);
+//  * block order (bits 8-11): 2 descending, 3 seeded -- the order of the workgroups of a launch.
+// Under any policy but the default the fiber that completes a rendezvous gives up the CPU too, so the order applies to it as well.
+enum { ORD_DEFAULT = 0, ORD_ASC = 1, ORD_DESC = 2, ORD_SEEDED = 3 };
+inline int sched_wave = 0, sched_lane = 0, sched_block = 0;
+inline uint64_t sched_rng = 0;
+inline int n_waves = 0;
+inline int wave_order[16];
+inline int lane_order[16][64];
+inline int g_order[1024], g_pos[1024];  // round-robin order over all fibers (waves ascending, lanes in lane order) and its inverse
+// rendezvous consistency: the number of violations (and the first one, described) since emu_clear_schedule_errors
+inline long long sched_errors = 0;
+inline std::string sched_first_error;
+inline long long launch_errors = 0, bars_since_error = 0;
+inline Loc bar_site, wbar_site[16];
+inline int bar_first = 0, wbar_first[16];
+inline int end_seq = -1;           // block-end check: the block sequence number and the barrier count of its first finisher
+inline long long end_nbar = 0;
+inline bool launch_aborted = false;
+
+inline uint64_t rnd() {  // splitmix64
+  uint64_t z = (sched_rng += 0x9E3779B97F4A7C15ull);
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+inline void draw_order(int *a, int n, int mode) {
+  for (int k = 0; k < n; ++k) a[k] = mode == ORD_DESC ? n - 1 - k : k;
+  if (mode == ORD_SEEDED)
+    for (int k = n - 1; k > 0; --k) { const int j = (int)(rnd() % (uint64_t)(k + 1)), t = a[k]; a[k] = a[j]; a[j] = t; }
+}
+inline int wave_size(int w) { return n_fibers - 64 * w < 64 ? n_fibers - 64 * w : 64; }
+inline void rebuild_global_order() {
+  for (int w = 0, k = 0; w < n_waves; ++w)
+    for (int l = 0; l < wave_size(w); ++l, ++k) { g_order[k] = 64 * w + lane_order[w][l]; g_pos[g_order[k]] = k; }
+}
+inline void draw_lanes(int w) {
+  draw_order(lane_order[w], wave_size(w), sched_lane);
+  if (sched_wave == ORD_DEFAULT) rebuild_global_order();
+}
+inline bool default_schedule() { return sched_wave == ORD_DEFAULT && sched_lane == ORD_DEFAULT; }
+
+inline std::string where(const Loc &l) {
+  const char *f = l.file_name(), *s = std::strrchr(f, '/');
+  return std::string(s ? s + 1 : f) + ":" + std::to_string(l.line()) + ":" + std::to_string(l.column());
+}
+inline bool same_site(const Loc &a, const Loc &b) {
+  return a.line() == b.line() && a.column() == b.column() && std::strcmp(a.file_name(), b.file_name()) == 0;
+}
+inline void violation(const std::string &what) {
+  if (sched_errors++ == 0) sched_first_error = what;
+  ++launch_errors;
+}
+
+inline bool runnable(const Fiber &f) {
+  switch (f.wait) {
+    case RUNNING: return true;
+    case AT_BARRIER: return bar_gen != f.wait_gen;
+    case AT_WAVE: return wbar_gen[f.tid.x >> 6] != f.wait_gen;
+    default: return false;
+  }
+}
+inline Fiber *pick() {
+  std::vector<Fiber> &fs = *fibers;
+  if (sched_wave == ORD_DEFAULT) {  // round-robin from the fiber after the current one
+    const int p = g_pos[cur->tid.x];
+    for (int k = 1; k <= n_fibers; ++k) {
+      Fiber &f = fs[g_order[(p + k) % n_fibers]];
+      if (runnable(f)) return &f;
+    }
+    return nullptr;
+  }
+  for (int a = 0; a < n_waves; ++a) {  // the first wavefront in wave order that has a fiber that can run
+    const int w = wave_order[a];
+    for (int l = 0; l < wave_size(w); ++l) {
+      Fiber &f = fs[64 * w + lane_order[w][l]];
+      if (runnable(f)) return &f;
+    }
+  }
+  return nullptr;
+}
+[[noreturn]] inline void end_launch() {
+  launch_aborted = true;
+  setcontext(&main_ctx);
+  std::abort();
+}
+// no fiber can run: the launch ends here with a counted error that names what every wavefront waits at
+[[noreturn]] inline void deadlock() {
+  std::string s = "deadlock: no fiber can run;";
+  const std::vector<Fiber> &fs = *fibers;
+  for (int w = 0; w < n_waves; ++w) {
+    s += " wave " + std::to_string(w) + ":";
+    for (int l = 0; l < wave_size(w); ++l) {
+      const Fiber &f = fs[64 * w + l];
+      bool seen = false;  // one entry per distinct (state, site) of the wavefront
+      for (int m = 0; m < l && !seen; ++m) {
+        const Fiber &g = fs[64 * w + m];
+        seen = g.wait == f.wait && (f.wait == FINISHED || same_site(g.site, f.site));
+      }
+      if (seen) continue;
+      s += f.wait == FINISHED ? " finished" : (f.wait == AT_BARRIER ? " barrier at " : " wave rendezvous at ") + where(f.site);
+      s += " (lane " + std::to_string(l) + ")";
+    }
+    s += ";";
+  }
+  violation(s);
+  end_launch();
+}
+inline void yield() {
+  Fiber *me = cur;
+  Fiber *next = pick();
+  if (!next) deadlock();
+  if (next == me) return;
+  cur = next;
+  swapcontext(&me->ctx, &next->ctx);
+}
+// wait (as `kind`, generation `gen`) until released; the fiber that completed the rendezvous runs on under the default schedule
+inline void wait_for(Wait kind, unsigned gen, bool released) {
+  cur->wait = kind;
+  cur->wait_gen = gen;
+  if (!released || !default_schedule()) yield();
+  cur->wait = RUNNING;
+}
+inline void barrier(Loc loc = Loc::current()) {
+  Fiber *me = cur;
+  me->site = loc;
+  ++me->n_bar;
+  if (bar_count == 0) {
+    bar_site = loc;
+    bar_first = me->tid.x;
+  } else if (!same_site(bar_site, loc)) {
+    violation("workgroup barrier: thread " + std::to_string(me->tid.x) + " at " + where(loc) + " against thread " +
+              std::to_string(bar_first) + " at " + where(bar_site));
+  }
+  // after a violation the fibers no longer pair up: bound what is left of the launch
+  if (launch_errors && ++bars_since_error > 100000) {
+    violation("launch ended: 100000 workgroup barriers after a rendezvous violation");
+    end_launch();
+  }
+  const unsigned gen = bar_gen;
+  const bool released = ++bar_count == n_fibers;
+  if (released) {
+    bar_count = 0;
+    ++bar_gen;
+    if (sched_wave == ORD_SEEDED) draw_order(wave_order, n_waves, sched_wave);
+    if (sched_lane == ORD_SEEDED)
+      for (int w = 0; w < n_waves; ++w) draw_lanes(w);
+  }
+  wait_for(AT_BARRIER, gen, released);
+}
+inline void wave_barrier(Loc loc = Loc::current()) {
+  Fiber *me = cur;
+  const int w = me->tid.x >> 6;
+  me->site = loc;
+  if (wbar_count[w] == 0) {
+    wbar_site[w] = loc;
+    wbar_first[w] = me->tid.x;
+  } else if (!same_site(wbar_site[w], loc)) {
+    violation("wave rendezvous: thread " + std::to_string(me->tid.x) + " at " + where(loc) + " against thread " +
+              std::to_string(wbar_first[w]) + " at " + where(wbar_site[w]));
+  }
   const unsigned gen = wbar_gen[w];
-  if (++wbar_count[w] == size) {
+  const bool released = ++wbar_count[w] == wave_size(w);
+  if (released) {
     wbar_count[w] = 0;
     ++wbar_gen[w];
-  } else {
-    while (wbar_gen[w] == gen) yield();
+    if (sched_lane == ORD_SEEDED) draw_lanes(w);
   }
+  wait_for(AT_WAVE, gen, released);
 }
 }  // namespace emu
 
@@ -97,7 +259,7 @@ inline void wave_barrier() {
 #define blockIdx (emu::cur->bid)
 #define blockDim (emu::cur->bdim)
 
-inline void __syncthreads() { emu::barrier(); }
+inline void __syncthreads(emu::Loc loc = emu::Loc::current()) { emu::barrier(loc); }
 inline void __threadfence() {}  // fibers of one OS thread: program order is memory order
 inline void __threadfence_block() {}
 
@@ -106,25 +268,25 @@ inline unsigned long long g_ballot[2][16];
 inline int g_xchg[2][1024];
 }  // namespace emu
 
-inline unsigned long long __ballot(int pred) {
+inline unsigned long long __ballot(int pred, emu::Loc loc = emu::Loc::current()) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   unsigned long long &acc = emu::g_ballot[emu::cur->ballot_phase & 1][wave];
   emu::cur->ballot_phase++;
   if (pred) acc |= 1ull << lane;
-  emu::wave_barrier();
+  emu::wave_barrier(loc);
   const unsigned long long v = acc;
-  emu::wave_barrier();
+  emu::wave_barrier(loc);
   if (lane == 0) acc = 0;  // reused two ballots later, with >= 1 rendezvous in between
   return v;
 }
-inline int __syncthreads_or(int pred) {  // barrier + OR of the predicate over the whole workgroup
-  unsigned long long any = __ballot(pred);  // per-wave OR (two wave rendezvous) ...
+inline int __syncthreads_or(int pred, emu::Loc loc = emu::Loc::current()) {  // barrier + OR of the predicate over the whole workgroup
+  unsigned long long any = __ballot(pred, loc);  // per-wave OR (two wave rendezvous) ...
   __shared__ unsigned long long acc[2];
   const unsigned ph = emu::cur->bor_phase++ & 1;  // (its own counter: the wavefronts' ballot counts may differ)
   if (any) acc[ph] = 1;
-  emu::barrier();
+  emu::barrier(loc);
   const int v = acc[ph] != 0;
-  emu::barrier();
+  emu::barrier(loc);
   if (threadIdx.x == 0) acc[ph] = 0;
   return v;
 }
@@ -135,29 +297,29 @@ inline int __clzll(long long v) { return v ? __builtin_clzll((unsigned long long
 // ---- wave data movement (hwy_wave.h; 64-thread workgroups, workgroup-uniform calls) --------------
 namespace emu {
 // double-buffered exchange: one rendezvous per call (a fiber can be at most one call ahead)
-inline int readlane(int v, int lane) {
+inline int readlane(int v, int lane, Loc loc = Loc::current()) {
   int *buf = g_xchg[cur->xchg_phase++ & 1];
   buf[threadIdx.x] = v;
-  wave_barrier();
+  wave_barrier(loc);
   return buf[(threadIdx.x & ~63) + (lane & 63)];
 }
-inline int ds_permute(int addr, int v) {  // my value lands in lane (addr/4)%64 (a permutation in our use)
+inline int ds_permute(int addr, int v, Loc loc = Loc::current()) {  // my value lands in lane (addr/4)%64 (a permutation in our use)
   int *buf = g_xchg[cur->xchg_phase++ & 1];
   buf[(threadIdx.x & ~63) + ((addr >> 2) & 63)] = v;
-  wave_barrier();
+  wave_barrier(loc);
   return buf[threadIdx.x];
 }
-inline int ds_bpermute(int addr, int v) {  // I read the value lane (addr/4)%64 holds
+inline int ds_bpermute(int addr, int v, Loc loc = Loc::current()) {  // I read the value lane (addr/4)%64 holds
   int *buf = g_xchg[cur->xchg_phase++ & 1];
   buf[threadIdx.x] = v;
-  wave_barrier();
+  wave_barrier(loc);
   return buf[(threadIdx.x & ~63) + ((addr >> 2) & 63)];
 }
 }  // namespace emu
 namespace emu {
-inline unsigned wave_max_u32(unsigned v) {  // butterfly over the 64 fibers of the wavefront
+inline unsigned wave_max_u32(unsigned v, Loc loc = Loc::current()) {  // butterfly over the 64 fibers of the wavefront
   for (int st = 1; st < 64; st <<= 1) {
-    const unsigned o = (unsigned)ds_bpermute((((int)threadIdx.x & 63) ^ st) << 2, (int)v);
+    const unsigned o = (unsigned)ds_bpermute((((int)threadIdx.x & 63) ^ st) << 2, (int)v, loc);
     v = o > v ? o : v;
   }
   return v;
@@ -192,13 +354,24 @@ namespace emu {
 inline std::function<void()> g_body;
 inline int g_grid = 0;
 inline int g_done = 0;
+inline std::vector<int> g_block_seq;  // the workgroups of the launch in the order they run (block order policy)
 inline void fiber_main() {
-  for (int b = 0; b < g_grid; ++b) {
-    cur->bid.x = b;
+  for (int k = 0; k < g_grid; ++k) {
+    cur->bid.x = g_block_seq[k];
     g_body();
+    // every fiber must have passed as many workgroup barriers as the first one of the workgroup to finish the block
+    if (end_seq != k) {
+      end_seq = k;
+      end_nbar = cur->n_bar;
+    } else if (cur->n_bar != end_nbar) {
+      violation("block " + std::to_string(cur->bid.x) + " ends with thread " + std::to_string(cur->tid.x) + " past " +
+                std::to_string(cur->n_bar) + " workgroup barriers, another thread past " + std::to_string(end_nbar));
+    }
     barrier();  // the whole workgroup finishes a block before the next one starts
+    cur->n_bar = 0;
   }
   cur->finished = true;
+  cur->wait = FINISHED;
   if (++g_done == n_fibers) {
     setcontext(&main_ctx);  // last fiber: back to launch()
   }
@@ -211,11 +384,20 @@ void launch(K kernel, int grid, int block, const P &params) {
   std::vector<Fiber> fs(block);
   fibers = &fs;
   n_fibers = block;
+  n_waves = (block + 63) / 64;
   bar_count = 0;
   bar_gen = 0;
   for (int w = 0; w < 16; ++w) { wbar_count[w] = 0; wbar_gen[w] = 0; }
   g_done = 0;
   g_grid = grid;
+  g_block_seq.resize(grid);
+  draw_order(g_block_seq.data(), grid, sched_block);
+  draw_order(wave_order, n_waves, sched_wave);
+  for (int w = 0; w < n_waves; ++w) draw_order(lane_order[w], wave_size(w), sched_lane);
+  rebuild_global_order();
+  launch_errors = bars_since_error = 0;
+  end_seq = -1;
+  launch_aborted = false;
   for (auto &row : g_ballot)
     for (auto &a : row) a = 0;
   g_body = [&] { kernel(params); };
@@ -230,10 +412,36 @@ void launch(K kernel, int grid, int block, const P &params) {
     f.ctx.uc_link = nullptr;
     makecontext(&f.ctx, (void (*)())fiber_main, 0);
   }
-  cur = &fs[0];
-  swapcontext(&main_ctx, &fs[0].ctx);
+  cur = &fs[sched_wave == ORD_DEFAULT ? g_order[0] : 64 * wave_order[0] + lane_order[wave_order[0]][0]];  // (fs[0] by default)
+  swapcontext(&main_ctx, &cur->ctx);
   for (auto &f : fs) std::free(f.stack);
   fibers = nullptr;
   cur = nullptr;
 }
 }  // namespace emu
+
+// the schedule and its checks, for the Python drivers (tests/emu/emu.py: EmuEngine.set_schedule / schedule_errors).  Defined here,
+// once per emulator library: each library is ONE translation unit that includes this header.
+extern "C" {
+void emu_set_schedule(int policy, uint64_t seed) {
+  emu::sched_wave = policy & 15;
+  emu::sched_lane = (policy >> 4) & 15;
+  emu::sched_block = (policy >> 8) & 15;
+  emu::sched_rng = seed;
+}
+long long emu_schedule_errors(void) { return emu::sched_errors; }
+// the first violation since the last clear, as text (truncated to n - 1 characters); returns its full length
+int emu_schedule_error_text(char *buf, int n) {
+  const std::string &s = emu::sched_first_error;
+  if (n > 0) {
+    const size_t k = s.size() < (size_t)(n - 1) ? s.size() : (size_t)(n - 1);
+    std::memcpy(buf, s.data(), k);
+    buf[k] = 0;
+  }
+  return (int)s.size();
+}
+void emu_clear_schedule_errors(void) {
+  emu::sched_errors = 0;
+  emu::sched_first_error.clear();
+}
+}

@@ -123,4 +123,30 @@ def test_wave_max_u32_on_the_device():
     got = e.debug_math(40, x.ravel()).reshape(x.shape)
     key = (np.abs(x).view(np.uint64) >> 32).astype(np.float64)
     assert (got == key.max(axis=1, keepdims=True)).all()
+    # the edges of the DPP scan: the maximum at the first and last lane of each row of 16 (row_shr within a row, row_bcast15 /
+    # row_bcast31 across rows), all-equal, all-zero and duplicated-maximum wavefronts, keys of +-inf and the largest finite double
+    big = np.finfo(np.float64).max
+    waves = []
+    for lane in (0, 15, 16, 31, 32, 47, 48, 63):
+        for top in (1.0e3, -1.0e3, np.inf, -np.inf, big, -big):
+            w = rng.uniform(-50.0, 50.0, 64)
+            w[lane] = top
+            waves.append(w)
+        w = np.full(64, 7.0)
+        w[lane] = 7.0 * (1 + 2.0 ** -20)  # (the next high word up)
+        waves.append(w)
+    waves += [np.full(64, 3.25), np.zeros(64), -np.zeros(64), np.full(64, np.inf), np.full(64, big)]
+    for pair in ((0, 63), (15, 16), (31, 32), (47, 48), (5, 40)):
+        w = rng.uniform(0.0, 1.0, 64)
+        w[list(pair)] = 9.5
+        waves.append(w)
+    x = np.stack(waves)
+    got = e.debug_math(40, x.ravel()).reshape(x.shape)
+    key = ((x.view(np.uint64) >> np.uint64(32)) & np.uint64(0x7FFFFFFF)).astype(np.float64)   # reach_key: |x|'s high word
+    np.testing.assert_array_equal(got, np.broadcast_to(key.max(axis=1, keepdims=True), x.shape))
+    # the routine needs whole wavefronts: the probe refuses any other count
+    from highwayenv_amd.engine import EngineError
+    for n in (1, 63, 65, 100):
+        with pytest.raises(EngineError, match="whole wavefronts"):
+            e.debug_math(40, np.ones(n))
     e.close()

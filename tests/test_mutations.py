@@ -11,7 +11,11 @@ FAIL on it -- while passing on the unmutated build:
 * `mobil_sides_swapped`  -- the one-wavefront kernel weighs the LEFT lane change with the right lane's gap and vice versa
   (behavior.py:265-324);
 * `reach_ignores_motion` -- the forward collision walk of the three highway kernels stops at the pre-check radius of bodies at rest,
-  forgetting what the frame moved them (road.py:477-481 tests ALL pairs): only visible with bodies that close a gap within one frame.
+  forgetting what the frame moved them (road.py:477-481 tests ALL pairs): only visible with bodies that close a gap within one frame;
+* `chain_compares_in_lds` -- an ORDERING bug: the workgroup kernel's abort-chain loop tests for its fixed point against the
+  previous round's verdicts where they lie in LDS -- the half of the slot pair a wavefront that runs ahead already rewrites with
+  the next round's.  The emulator's default round-robin schedule never lets a wavefront run ahead, so the suite's depth-two
+  chain test passes on it; the wave orders of tests/test_schedule_independence.py must catch it.
 
 Each case runs the real test functions in a subprocess with HWY_EMU_LIB pointing at the mutant."""
 import os
@@ -35,6 +39,8 @@ MUTANTS = {
         ("hwy_net.h", "const int carry = i < left ? (int)plist[count + i] : 0,", "const int carry = i < left ? (int)plist[count + i + 1] : 0,")],
     "reach_ignores_motion": [   # (round 6: the forward collision walk's reach from the frame's maxima, hwy_device.h reach_from_keys)
         ("hwy_device.h", "return ((5.5 + S * dt) + 2.0 * D) + 1e-6;", "return ((5.5 + 0.0 * S * dt) + 0.0 * D) + 1e-6;")],
+    "chain_compares_in_lds": [   # (hwy_device.h section D: the fixed-point test against the LDS half the next round rewrites)
+        ("hwy_device.h", "same = same && v == last[w];", "same = same && v == (prev ? prev[w] : (u64)0);")],
     "mobil_sides_swapped": [   # (the compacted MOBIL tasks of round 6: side 0 = left reads row lane, side 1 = right row lane + 2)
         ("hwy_wave.h", "const u64 m = sh.lane_mask[ln + (side ? 2 : 0)];", "const u64 m = sh.lane_mask[ln + (side ? 0 : 2)];")],
 }
@@ -47,6 +53,11 @@ CASES = [
     ("net_pair_list_carry", ["tests/test_pileup.py", "-m", "not gpu", "-k", "merge"], {}),
     ("mobil_sides_swapped", ["tests/test_fuzz_configs.py", "-m", "gpu", "-k", "test_random_configurations_vs_oracle"], FUZZ),
     ("reach_ignores_motion", ["tests/test_collision_steps.py", "-m", "not gpu", "-k", "fast_bodies_are_not_missed"], {}),
+    ("chain_compares_in_lds", ["tests/test_schedule_independence.py", "-m", "not gpu", "-k", "abort_chain_vs_oracle and n90_spread"], {}),
+]
+# the ordering bug survives what the default schedule runs: the depth-two chain on every kernel family against the oracle
+ROUND_ROBIN_SURVIVORS = [
+    ("chain_compares_in_lds", ["tests/test_wide_kernel.py", "-m", "not gpu", "-k", "abort_chain_of_depth_two_vs_oracle"]),
 ]
 
 
@@ -91,3 +102,14 @@ def test_seeded_bug_fails_the_comparison_that_covers_it(mutant, selection, env_e
     assert good.returncode == 0, f"the selection must pass on the unmutated kernel source:\n{good.stdout[-3000:]}"
     assert bad.returncode == 1 and "AssertionError" in bad.stdout, \
         f"mutant {mutant} SURVIVED {selection} (rc {bad.returncode}):\n{bad.stdout[-3000:]}"
+
+
+@pytest.mark.parametrize("mutant,selection", ROUND_ROBIN_SURVIVORS, ids=[c[0] for c in ROUND_ROBIN_SURVIVORS])
+def test_ordering_bug_survives_the_round_robin_schedule(mutant, selection):
+    """The other half of the ordering case above: on the default schedule the mutant PASSES a comparison that covers the mutated
+    code -- only the schedules that let one wavefront run ahead tell it apart."""
+    from tests.emu import emu
+    emu.build()
+    res = run_selection(build_mutant(mutant), selection, {})
+    assert res.returncode == 0 and " passed" in res.stdout, \
+        f"mutant {mutant} was expected to pass {selection} on the round-robin schedule (rc {res.returncode}):\n{res.stdout[-3000:]}"

@@ -1,0 +1,358 @@
+"""Every kernel's result must not depend on the order in which its wavefronts, lanes and workgroups run.
+
+The CPU emulator (tests/emu/hip_emu.h) runs one schedule by default: fibers round-robin, so after a `__syncthreads()` the
+wavefronts always resume in the same order and none runs ahead into the next barrier interval.  The GPU promises no such order.
+Here each kernel family runs under the default schedule and again under adversarial ones (hip_emu.h, emu_set_schedule):
+
+* wave order -- after each workgroup barrier ONE wavefront runs until all of its fibers wait at the next one, then the next
+  wavefront: ascending, descending or a seeded order drawn again at every barrier (the workgroup kernels only);
+* lane order -- the fibers of a wavefront run in descending or seeded order between two rendezvous: LDS handed from lane to
+  lane without HWY_WAVEFRONT_FENCE / HWY_WAVE_LDS_FENCE shows up as a different result;
+* block order -- the workgroups of a launch run in descending or seeded order (the intersection kernel's pre-warm shadow
+  blocks, blocks >= num_envs of a step launch with auto-reset, then run before the step blocks).
+
+Every output must be BIT-IDENTICAL to the default run, and no rendezvous may have been reached from two call sites, no block
+may end with its threads past different numbers of barriers, and no launch may end with no fiber able to run
+(`schedule_errors() == 0`).  HWY_SCHEDULE_SEEDS (default 2) sets how many seeded orders of each kind run.
+
+The emulator runs the workgroups of a launch one after the other, so two workgroups interleaved mid-block (a step block and its
+shadow block on two CUs) are not modelled: the `__shared__` arrays of the emulation are one instance per launch."""
+import functools
+import itertools
+import os
+
+import numpy as np
+import pytest
+
+from highwayenv_amd import _abi, spawn
+from oracle import oracle
+from tests.backends import BACKENDS, make_engine
+from tests.golden_util import assert_state_close
+
+N_SEEDS = int(os.environ.get("HWY_SCHEDULE_SEEDS", "2"))
+
+WAVE_SCHEDULES = [dict(wave="asc"), dict(wave="desc")] + [dict(wave="seeded", seed=s) for s in range(N_SEEDS)]
+LANE_SCHEDULES = [dict(lane="desc")] + [dict(lane="seeded", seed=100 + s) for s in range(N_SEEDS)]
+BLOCK_SCHEDULES = [dict(block="desc")] + [dict(block="seeded", seed=200 + s) for s in range(N_SEEDS)]
+# (everything at once: the wavefronts of a seeded order running ahead with their lanes and blocks in seeded orders)
+MIXED = [dict(wave="seeded", lane="seeded", block="seeded", seed=300 + s) for s in range(max(1, N_SEEDS // 2))]
+WORKGROUP_SCHEDULES = WAVE_SCHEDULES + LANE_SCHEDULES + BLOCK_SCHEDULES + MIXED
+ONE_WAVE_SCHEDULES = LANE_SCHEDULES + BLOCK_SCHEDULES + [dict(lane="seeded", block="seeded", seed=400 + s) for s in range(N_SEEDS)]
+
+
+def _sid(s):
+    return "-".join(f"{k}_{v}" for k, v in s.items())
+
+
+def _assert_errors_free(eng, what):
+    assert eng.schedule_errors() == 0, f"{what}: {eng.schedule_errors()} rendezvous error(s), first: {eng.schedule_error_text()}"
+
+
+def _assert_identical(a, b, what):
+    """Two recordings (lists of (label, value)) bit for bit."""
+    assert [k for k, _ in a] == [k for k, _ in b], what
+    for (k, x), (_, y) in zip(a, b):
+        if isinstance(x, dict):
+            assert sorted(x) == sorted(y), f"{what}: {k}"
+            for f in x:
+                np.testing.assert_array_equal(np.asarray(x[f]), np.asarray(y[f]), err_msg=f"{what}: {k}: {f}")
+        else:
+            np.testing.assert_array_equal(np.asarray(x), np.asarray(y), err_msg=f"{what}: {k}")
+
+
+def _record_outputs(rec, label, out):
+    obs, reward, term, trunc, info = out
+    rec += [(f"{label} obs", obs), (f"{label} reward", reward), (f"{label} terminated", term), (f"{label} truncated", trunc),
+            (f"{label} info", info)]
+
+
+# ---- the IDM workgroup kernels (hwy_device.h: hwy_step_kernel / hwy_rollout_kernel / hwy_reset_kernel / hwy_observe_kernel) ----
+def _idm_run(N, grid, schedule):
+    from tests.emu.emu import EmuEngine
+    cfg_d = _abi.highway_default_config()
+    cfg_d.update({"vehicles_count": N - 1, "lanes_count": 4, "vehicles_density": 2.0, "duration": 12,
+                  "tuning": {"block_kernel": 1}})
+    if grid:
+        cfg_d["observation"] = {"type": "OccupancyGrid", "grid_size": [[-40, 40], [-12, 12]], "grid_step": [8, 4]}
+    E = 2
+    cfg = _abi.make_config(cfg_d, E, fast=False)
+    eng = EmuEngine(cfg)
+    if schedule is not None:
+        eng.set_schedule(**schedule)
+    st = spawn.spawn_reference_stream(cfg, np.arange(E) + 51, cfg_d["ego_spacing"], cfg_d["vehicles_density"], cfg_d["initial_lane_id"])
+    eng.set_state(st)
+    eng.set_autoreset(True, base_seed=9, ego_spacing=cfg_d["ego_spacing"], vehicles_density=cfg_d["vehicles_density"])
+    rng = np.random.default_rng(6)
+    rec = []
+    for t in range(3):
+        _record_outputs(rec, f"step {t}", eng.step(rng.integers(0, 5, size=(E, 1)).astype(np.int32)))
+        rec.append((f"step {t} state", eng.get_state()))
+    _record_outputs(rec, "rollout", eng.rollout(rng.integers(0, 5, size=(3, E, 1)).astype(np.int32)))
+    rec.append(("rollout state", eng.get_state()))
+    rec.append(("observe", eng.observe()))
+    obs = eng.reset(seeds=np.array([5, 0], np.uint64), mask=np.array([1, 0], np.uint8), ego_spacing=cfg_d["ego_spacing"],
+                    vehicles_density=cfg_d["vehicles_density"])
+    rec += [("reset obs", obs), ("reset state", eng.get_state())]
+    for t in range(2):
+        _record_outputs(rec, f"after reset {t}", eng.step(rng.integers(0, 5, size=(E, 1)).astype(np.int32)))
+        rec.append((f"after reset {t} state", eng.get_state()))
+    return rec, eng
+
+
+@functools.lru_cache(maxsize=None)
+def _idm_default(N, grid):
+    rec, eng = _idm_run(N, grid, None)
+    _assert_errors_free(eng, "default schedule")
+    changing = sum(int((s["lane"] != s["target_lane"]).sum()) for k, s in rec if k.endswith("state"))
+    return rec, changing
+
+
+IDM_CASES = [pytest.param(n, False, id=f"n{n}") for n in (90, 140, 201)] + [pytest.param(140, True, id="n140_grid")]
+
+
+@pytest.mark.parametrize("schedule", WORKGROUP_SCHEDULES, ids=_sid)
+@pytest.mark.parametrize("N,grid", IDM_CASES)
+def test_idm_workgroup_kernels_are_schedule_independent(N, grid, schedule):
+    ref, changing = _idm_default(N, grid)
+    assert changing > 10, "dense traffic must hold lane changes in progress"
+    rec, eng = _idm_run(N, grid, schedule)
+    _assert_errors_free(eng, _sid(schedule))
+    _assert_identical(ref, rec, _sid(schedule))
+
+
+# ---- the Linear-family workgroup kernels (hwy_device.h: hwy_step_linear_kernel / hwy_rollout_linear_kernel / ...) --------------
+LINEAR_CLASSES = {"linear": "LinearVehicle", "aggressive": "AggressiveVehicle", "defensive": "DefensiveVehicle"}
+
+
+def _linear_run(cls, N, schedule):
+    from tests.emu.emu_traffic import EmuTrafficEngine
+    cfg_d = _abi.highway_default_config()
+    cfg_d.update({"vehicles_count": N - 1, "lanes_count": 4, "vehicles_density": 2.0, "duration": 12,
+                  "other_vehicles_type": "highway_env.vehicle.behavior." + LINEAR_CLASSES[cls]})
+    E = 2
+    cfg = _abi.make_config(cfg_d, E, fast=False)
+    eng = EmuTrafficEngine(cfg)
+    if schedule is not None:
+        eng.set_schedule(**schedule)
+    kw = dict(ego_spacing=cfg_d["ego_spacing"], vehicles_density=cfg_d["vehicles_density"])
+    rec = [("reset obs", eng.reset(seeds=np.array([3, 4], np.uint64), **kw)), ("reset state", eng.get_state()),
+           ("reset behavior", eng.get_behavior())]
+    # then the traffic of the IDM runs above (the reference's spawn stream), with drawn parameters
+    rng = np.random.default_rng(8)
+    eng.set_state(spawn.spawn_reference_stream(cfg, np.arange(E) + 51, cfg_d["ego_spacing"], cfg_d["vehicles_density"], None))
+    eng.set_behavior(spawn.behavior_from_draws(cfg, rng.uniform(size=(E, cfg.num_vehicles, _abi.HWY_BEHAVIOR_PARAMS))))
+    eng.set_autoreset(True, base_seed=21, **kw)
+    for t in range(5):
+        _record_outputs(rec, f"step {t}", eng.step(rng.integers(0, 5, size=(E, 1)).astype(np.int32)))
+        rec.append((f"step {t} state", eng.get_state()))
+    _record_outputs(rec, "rollout", eng.rollout(rng.integers(0, 5, size=(2, E, 1)).astype(np.int32)))
+    rec += [("rollout state", eng.get_state()), ("observe", eng.observe())]
+    return rec, eng
+
+
+@functools.lru_cache(maxsize=None)
+def _linear_default(cls, N):
+    rec, eng = _linear_run(cls, N, None)
+    _assert_errors_free(eng, "default schedule")
+    changing = sum(int((s["lane"] != s["target_lane"]).sum()) for k, s in rec if k.endswith("state"))
+    return rec, changing
+
+
+LINEAR_SCHEDULES = WAVE_SCHEDULES + [LANE_SCHEDULES[0], BLOCK_SCHEDULES[0]] + MIXED
+
+
+@pytest.mark.parametrize("schedule", LINEAR_SCHEDULES, ids=_sid)
+@pytest.mark.parametrize("N", [90, 140])
+@pytest.mark.parametrize("cls", sorted(LINEAR_CLASSES))
+def test_linear_workgroup_kernels_are_schedule_independent(cls, N, schedule):
+    ref, changing = _linear_default(cls, N)
+    assert changing > 3, "dense traffic must hold lane changes in progress"
+    rec, eng = _linear_run(cls, N, schedule)
+    _assert_errors_free(eng, _sid(schedule))
+    _assert_identical(ref, rec, _sid(schedule))
+
+
+# ---- the one-wavefront kernels: lane and block orders -------------------------------------------------------------------------
+def _one_wave_highway(kind, schedule):
+    """kind: "wave" (hwy_wave.h, N <= 64) or "wide" (hwy_wave2.h, 64 < N <= 256 with block_kernel 2)."""
+    from tests.emu.emu import EmuEngine
+    cfg_d = _abi.highway_default_config()
+    if kind == "wave":
+        cfg_d.update({"vehicles_count": 50, "lanes_count": 4, "vehicles_density": 2.0})
+    else:
+        cfg_d.update({"vehicles_count": 100, "lanes_count": 4, "vehicles_density": 2.0, "tuning": {"block_kernel": 2}})
+    E = 3
+    cfg = _abi.make_config(cfg_d, E, fast=False)
+    eng = EmuEngine(cfg)
+    if schedule is not None:
+        eng.set_schedule(**schedule)
+    st = spawn.spawn_reference_stream(cfg, np.arange(E) + 17, cfg_d["ego_spacing"], cfg_d["vehicles_density"], cfg_d["initial_lane_id"])
+    eng.set_state(st)
+    eng.set_autoreset(True, base_seed=4, ego_spacing=cfg_d["ego_spacing"], vehicles_density=cfg_d["vehicles_density"])
+    rng = np.random.default_rng(2)
+    rec = []
+    for t in range(3):
+        _record_outputs(rec, f"step {t}", eng.step(rng.integers(0, 5, size=(E, 1)).astype(np.int32)))
+        rec.append((f"step {t} state", eng.get_state()))
+    _record_outputs(rec, "rollout", eng.rollout(rng.integers(0, 5, size=(2, E, 1)).astype(np.int32)))
+    rec.append(("rollout state", eng.get_state()))
+    return rec, eng
+
+
+def _net(scenario, schedule):
+    """The road-network kernels (hwy_net.h: merge) and the intersection kernels (hwy_ix.h), with auto-reset and full steps, so
+    that the intersection's step launches hold the pre-warm shadow blocks."""
+    from highwayenv_amd import intersection, merge
+    from tests.emu.emu import EmuEngine
+    E = 3
+    if scenario == "merge":
+        cfg = _abi.make_config(merge.merge_default_config(), E, scenario="merge")
+    else:
+        cfg = _abi.make_config(dict(intersection.intersection_default_config(), max_vehicles=24, duration=3), E,
+                               scenario="intersection")
+    eng = EmuEngine(cfg)
+    if schedule is not None:
+        eng.set_schedule(**schedule)
+    rec = [("reset obs", eng.reset(seeds=np.arange(E, dtype=np.uint64) + 31)), ("reset state", eng.get_state())]
+    eng.set_autoreset(True, base_seed=77)
+    rng = np.random.default_rng(3)
+    n_act = 3 if scenario == "intersection" else _abi.num_actions(cfg)
+    ended = 0
+    for t in range(5 if scenario == "intersection" else 3):
+        out = eng.step(rng.integers(0, n_act, size=(E, cfg.num_agents)).astype(np.int32))
+        ended += int((out[2] | out[3]).sum())
+        _record_outputs(rec, f"step {t}", out)
+        rec.append((f"step {t} state", eng.get_state()))
+    if scenario == "intersection":
+        assert ended > 0, "the intersection run must end episodes (auto-reset from the shadow)"
+    return rec, eng
+
+
+def _one_wave(kind, schedule):
+    return _one_wave_highway(kind, schedule) if kind in ("wave", "wide") else _net(kind, schedule)
+
+
+@functools.lru_cache(maxsize=None)
+def _one_wave_default(kind):
+    rec, eng = _one_wave(kind, None)
+    _assert_errors_free(eng, "default schedule")
+    return rec
+
+
+@pytest.mark.parametrize("schedule", ONE_WAVE_SCHEDULES, ids=_sid)
+@pytest.mark.parametrize("kind", ["wave", "wide", "merge", "intersection"])
+def test_one_wavefront_kernels_are_schedule_independent(kind, schedule):
+    ref = _one_wave_default(kind)
+    rec, eng = _one_wave(kind, schedule)
+    _assert_errors_free(eng, _sid(schedule))
+    _assert_identical(ref, rec, _sid(schedule))
+
+
+# ---- the abort chain across wavefronts ----------------------------------------------------------------------------------------
+def _chain_state(cfg, placements, E):
+    st = spawn.spawn_reference_stream(cfg, np.arange(E) + 9, 2.0, 1.0)
+    N = st["x"].shape[1]
+    # everybody else: far ahead on lane 3, one behind the other, no decision due
+    st["x"][:, :] = 2000.0 + 40.0 * np.arange(N)[None, :]
+    st["y"][:, :] = 12.0
+    for k in ("heading", "timer", "impact_x", "impact_y"):
+        st[k][:, :] = 0.0
+    st["speed"][:, :] = 20.0
+    st["target_speed"][:, :] = 20.0
+    st["lane"][:, :] = 3
+    st["target_lane"][:, :] = 3
+    st["flags"][:, 1:] &= ~(_abi.F_CRASHED | _abi.F_HAS_IMPACT)
+    for e, (ir0, ic1, ic2) in enumerate(placements):
+        for idx, x, lane in ((ir0, 130.0, 2), (ic1, 100.0, 0), (ic2, 65.0, 2)):
+            st["x"][e, idx] = x
+            st["y"][e, idx] = 4.0 * lane
+            st["lane"][e, idx] = lane
+            st["target_lane"][e, idx] = 1
+    return st
+
+
+def _check_chain_outcome(got, placements):
+    for e, (ir0, ic1, ic2) in enumerate(placements):
+        t = got["target_lane"][e]
+        assert t[ir0] == 1 and t[ic1] == 0, (e, t[[ir0, ic1, ic2]])
+        # c2 goes on exactly when c1 acted (and aborted) before it
+        assert t[ic2] == (1 if ic1 < ic2 else 2), (e, t[[ir0, ic1, ic2]])
+
+
+# r0, c1, c2 on different wavefronts (and, indices 1-3, the placement of tests/test_wide_kernel.py on wavefront 0)
+CHAIN_CASES = [pytest.param(90, (3, 40, 70), id="n90_spread"), pytest.param(140, (5, 70, 130), id="n140_spread"),
+               pytest.param(90, (1, 2, 3), id="n90_wave0"), pytest.param(140, (1, 2, 3), id="n140_wave0")]
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+@pytest.mark.parametrize("N,idx", CHAIN_CASES)
+def test_cross_wavefront_abort_chain_vs_oracle(backend, N, idx):
+    """The depth-two chain of tests/test_wide_kernel.py::test_abort_chain_of_depth_two_vs_oracle (three rounds of verdicts in the
+    workgroup kernel's fixed-point loop) with its three vehicles in all six list orders, against the oracle's literal loop --
+    on the emulator under the default schedule and every wave order, where a wavefront that runs ahead into the next round must
+    not change what a slower one compares."""
+    cfg_d = _abi.highway_default_config()
+    cfg_d.update({"vehicles_count": N - 1, "lanes_count": 4, "tuning": {"block_kernel": 1}})
+    placements = [tuple(p) for p in itertools.permutations(idx)]
+    E = len(placements)
+    cfg = _abi.make_config(cfg_d, E, fast=False)
+    ref = _chain_state(cfg, placements, E)
+    oracle.frames(cfg, ref, np.full((E, 1), 1, np.int32), 1)
+    failures = []
+    for schedule in [None] + (WAVE_SCHEDULES if backend == "emu" else []):
+        eng = make_engine(backend, cfg)
+        if schedule is not None:
+            eng.set_schedule(**schedule)
+        eng.set_state(_chain_state(cfg, placements, E))
+        eng.step_frames(np.full((E, 1), 1, np.int32), 1)
+        what = "default" if schedule is None else _sid(schedule)
+        got = eng.get_state()
+        eng.close()
+        try:  # (every schedule runs: the message lists each one that fails)
+            if backend == "emu":
+                _assert_errors_free(eng, what)
+            np.testing.assert_array_equal(got["target_lane"], ref["target_lane"], err_msg=what)
+            assert_state_close(got, ref, atol=1e-9, what=f"depth-two chain, {what}")
+            _check_chain_outcome(got, placements)
+        except AssertionError as ex:
+            failures.append(str(ex).strip().splitlines()[0])
+    assert not failures, "\n".join(failures)
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+@pytest.mark.parametrize("N,idx", CHAIN_CASES[:2])
+def test_cross_wavefront_abort_chain_linear(backend, N, idx):
+    """The same chain with LinearVehicle traffic: the Linear family's workgroup kernel, whose abort rule uses TIME_WANTED 2.5
+    (d* = 60 m at 20 m/s: c1 30 m and c2 35 m behind their rivals are blocked, r0 65 m ahead of c2 is not).  The oracle has no
+    Linear traffic: the outcome is spelled out, and on the emulator every wave order must give the default run bit for bit."""
+    from tests.traffic_util import make_engine as make_traffic_engine
+    cfg_d = _abi.highway_default_config()
+    cfg_d.update({"vehicles_count": N - 1, "lanes_count": 4, "other_vehicles_type": "highway_env.vehicle.behavior.LinearVehicle"})
+    placements = [tuple(p) for p in itertools.permutations(idx)]
+    E = len(placements)
+    cfg = _abi.make_config(cfg_d, E, fast=False)
+    behavior = spawn.behavior_from_draws(cfg, np.full((E, cfg.num_vehicles, _abi.HWY_BEHAVIOR_PARAMS), 0.5))
+    first = None
+    failures = []
+    for schedule in [None] + (WAVE_SCHEDULES if backend == "emu" else []):
+        eng = make_traffic_engine(backend, cfg)
+        if schedule is not None:
+            eng.set_schedule(**schedule)
+        eng.set_state(_chain_state(cfg, placements, E))
+        eng.set_behavior(behavior)
+        eng.step_frames(np.full((E, 1), 1, np.int32), 1)
+        what = "default" if schedule is None else _sid(schedule)
+        got = eng.get_state()
+        eng.close()
+        try:
+            if backend == "emu":
+                _assert_errors_free(eng, what)
+            _check_chain_outcome(got, placements)
+            if first is None:
+                first = got
+            else:
+                for k in _abi.STATE_F64 + _abi.STATE_I32:
+                    np.testing.assert_array_equal(got[k], first[k], err_msg=f"{what}: {k}")
+        except AssertionError as ex:
+            failures.append(str(ex).strip().splitlines()[0])
+    assert not failures, "\n".join(failures)
