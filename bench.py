@@ -26,7 +26,13 @@ between the two ends with the reset and the W warm-up steps again, so the region
 `--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy: two builds run with the same arguments can be
 compared output for output.
 
-CPU leg: when the reference package is present (build container: /root/reference or $HWY_REFERENCE_ROOT) the
+A plain run does only what the headline needs: set up, warm up and settle, time the regions, write --dump-outputs, print the
+line.  `--full` adds everything else after the timed regions: the kernel-event region and the roofline / VALU / resource view
+(`roofline`), the one-gather-per-step leg (N > 1), K steps per launch (`rollout_k<K>`), `--split-batch`, the host-pointer path, the
+Python front ends (`frontend`), the CPU leg (`cpu_baseline`) and BASELINE's other workloads (`secondary_workloads`); the --no-*
+options and --rollout-k 0 leave legs out of a full run.
+
+CPU leg (--full): when the reference package is present (the build container, or wherever $HWY_REFERENCE_ROOT points) the
 UNMODIFIED reference is timed on the host cores (`cpu_baseline.kind == "reference"`, oracle/ref_bench.py); on a box
 without it (the GPU box) the C port of the oracle is timed instead and the committed build-container measurement of the
 reference (profiles/reference_cpu_baseline.json) is quoted next to it, labelled as coming from another box.
@@ -461,7 +467,7 @@ def secondary_workloads(steps: int = 200, repeats: int = 3, budget_s: float = 10
             out[argv[1]] = {"workload": name, "error": f"skipped: the {budget_s:.0f} s budget of the secondary legs was spent"}
             continue
         cmd = [sys.executable, os.path.abspath(__file__), *argv, "--steps", str(steps), "--repeats", str(repeats), "--warmup", "20",
-               "--settle-ms", "100", "--no-cpu-baseline", "--no-secondary", "--no-frontend", "--rollout-k", "0"]
+               "--settle-ms", "100", "--full", "--no-cpu-baseline", "--no-secondary", "--no-frontend", "--rollout-k", "0"]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=left)
             d = json.loads(r.stdout.strip().splitlines()[-1])
@@ -561,7 +567,11 @@ def main(argv=None, platform=None, emit=None):
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak: every GPU steps --envs-per-gpu environments; strong: that many in TOTAL, block-partitioned "
                          "over the ranks like highwayenv_amd.dist.shard_range")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed regions also measure everything that is not the headline: kernel events and the roofline "
+                         "view, the one-gather-per-step leg, --rollout-k, --split-batch, the host-pointer path, the front ends, the "
+                         "CPU leg and the secondary workloads.  Off by default: a plain run times the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU leg")
     ap.add_argument("--cpu-baseline-only", action="store_true",
                     help="run only the CPU leg (needs no GPU): the unmodified reference where it is installed, else the C port")
     ap.add_argument("--save-cpu-baseline", metavar="PATH", default=None,
@@ -578,10 +588,10 @@ def main(argv=None, platform=None, emit=None):
                          "(intersection-v0, 30 vehicle slots, OccupancyGrid 4 x 11 x 11 obs; use --envs-per-gpu 2048); intersection_kin = "
                          "the same with intersection-v0's default Kinematics 15 x 7 observation")
     ap.add_argument("--rollout-k", type=int, default=16,
-                    help="also time hwy_rollout_device with this many policy steps per launch (reported as rollout_k<K> next to the "
-                         "headline; 0 / 1 = skip)")
+                    help="--full: also time hwy_rollout_device with this many policy steps per launch (reported as rollout_k<K> next "
+                         "to the headline; 0 / 1 = skip)")
     ap.add_argument("--split-batch", type=int, default=0,
-                    help="N=1 only: also time the batch as S independent sub-batches (one engine and one HIP stream each, stepped "
+                    help="N=1 and --full only: also time the batch as S independent sub-batches (one engine and one HIP stream each, stepped "
                          "round-robin: the tail of one sub-batch's launch overlaps the body of the next one's), reported as "
                          "`split_batch_sS` next to the headline.  Off by default: its launches carry the headline kernel's name, "
                          "so they would mix into a rocprofv3 --stats average of the default command")
@@ -589,9 +599,10 @@ def main(argv=None, platform=None, emit=None):
                     help="developer knob: another traffic size / lane count for --workload fast (e.g. 20,3 = BASELINE config 1's shape "
                          "batched); the line's config.workload says so.  Never the headline.")
     ap.add_argument("--no-frontend", action="store_true",
-                    help="skip the `frontend` legs (the Python classes a user of the reference switches to, timed on the same workload)")
+                    help="--full: skip the `frontend` legs (the Python classes a user of the reference switches to, timed on the same "
+                         "workload)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="N=1, --workload fast only: skip the short legs on BASELINE's other single-GPU configurations (config 3's "
+                    help="--full, N=1, --workload fast only: skip the short legs on BASELINE's other single-GPU configurations (config 3's "
                          "per-GPU shard, config 4, config 5) that are reported NEXT TO the headline as `secondary_workloads`")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
                     help="hwy_config.tune_* knob (block_kernel, waves_per_eu, ix_no_helpers, ix_no_prewarm, extra_lds, prio_shift, "
@@ -603,6 +614,8 @@ def main(argv=None, platform=None, emit=None):
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.split_batch and not args.full:
+        ap.error("--split-batch is a leg of --full")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.cpu_baseline_only:
         raise SystemExit(self_launch(sys.argv[1:] if argv is None else list(argv), args.gpus))
     tuning = {kv.split("=", 1)[0]: int(kv.split("=", 1)[1]) for kv in args.tune}
@@ -783,13 +796,14 @@ def main(argv=None, platform=None, emit=None):
         if rank == 0:
             dumped = dump_outputs(args.dump_outputs, views)
             dumped["step"] = t_last
+    # The legs from here to the JSON line run with --full only: a plain run times the headline alone.
     # The dominant kernel's own duration: one more (untimed) region of the same loop in which EVERY launch carries the HIP event pair
     # hipExtLaunchKernelGGL fills with the dispatch's begin / end timestamps -- what rocprofv3 --kernel-trace reports, under the
     # same condition (every dispatch signalled).  Rounds 1-5 sampled every 8th launch of the timed regions: the sampled launches
     # alone were serialised against their neighbours, which made their average exceed the step they are part of (41.50 us against a
     # 40.96 us device step).
     kernel_ms, launches = 0.0, 0
-    if os.environ.get("HWY_BENCH_NO_EVENTS") != "1":
+    if args.full and os.environ.get("HWY_BENCH_NO_EVENTS") != "1":
         # (at least 300 launches whatever --steps says, over the action rows of the timed regions, behind 10 launches that are not
         #  counted: the driver's --steps 20 averaged the first 20 launches after the switch to signalled dispatches, 41.3 us where
         #  the device step of the same run was 39.6)
@@ -808,7 +822,7 @@ def main(argv=None, platform=None, emit=None):
     # N > 1: the same loop with ONE gather per step (what a policy that needs every step's outputs on rank 0 before it can
     # act would see), reported next to the batched number
     per_step_gather = None
-    if use_dist and K != 1:
+    if args.full and use_dist and K != 1:
         one_step1, fence1, _ = make_stepper(1)
         n1 = min(args.steps, 300)
         for j in range(20):   # (action rows of the timed regions, re-used: a short smoke run stages fewer than 20 of them)
@@ -826,7 +840,7 @@ def main(argv=None, platform=None, emit=None):
     # K policy steps per launch with pre-staged actions (hwy_rollout_device: open-loop rollouts / action repeat): reported NEXT TO
     # the headline, never instead of it -- `value` stays one launch per step
     rollout = None
-    if world == 1 and args.rollout_k > 1 and R * args.steps > args.rollout_k:  # (needs more staged action blocks than one call reads)
+    if args.full and world == 1 and args.rollout_k > 1 and R * args.steps > args.rollout_k:  # (needs more staged action blocks than one call reads)
         Kr = args.rollout_k
         n_calls = max(1, args.steps // Kr)
         r_obs = torch.empty((Kr, E, A, *_abi.obs_shape(cfg)), dtype=torch.float32, device=dev)
@@ -864,7 +878,7 @@ def main(argv=None, platform=None, emit=None):
     # wavefronts of a launch run alone on their SIMDs) overlaps the next sub-batch.  Reported NEXT TO the headline.
     split = None
     S = args.split_batch
-    if world == 1 and S > 1 and E % S == 0:
+    if args.full and world == 1 and S > 1 and E % S == 0:
         Es = E // S
         cfg_s = _abi.make_config(cfg_dict, Es, fast=fast, scenario=scenario, tuning=tuning)
         from highwayenv_amd.engine import Engine
@@ -904,7 +918,7 @@ def main(argv=None, platform=None, emit=None):
     # PCIe-inclusive rate of the host-pointer entry point (hwy_step: H2D actions, kernel, D2H results, sync);
     # reported for DESIGN.md, never as `value`
     host_rate = None
-    if world == 1:
+    if args.full and world == 1:
         acts_h = np.random.default_rng(5).integers(0, n_actions, size=(E, A)).astype(np.int32)
         for _ in range(5):
             eng.step(acts_h)
@@ -919,15 +933,36 @@ def main(argv=None, platform=None, emit=None):
     if rank == 0:
         env_steps = args.steps * E * world
         value = env_steps / elapsed
-        b_env = algorithmic_bytes_per_env_step(N, A, int(np.prod(_abi.obs_shape(cfg))))
-        # The dominant kernel's launch duration: the dispatch timestamps of every 8th launch (HIP events filled in by
-        # hipExtLaunchKernelGGL), reported AS MEASURED.  A kernel cannot take longer than the step that contains it: if the
-        # events say so anyway the run is flagged (`event_exceeds_wall_step`) instead of clamped.  Without events
-        # (HWY_BENCH_NO_EVENTS=1, a developer knob): the wall step.
-        wall_step_s = elapsed / args.steps
-        event_kernel_s = (kernel_ms / 1e3 / launches) if launches else None
-        avg_kernel_s = event_kernel_s if event_kernel_s and event_kernel_s > 0 else wall_step_s
-        achieved = b_env * E / avg_kernel_s / 1e9
+
+        def roofline_view():
+            b_env = algorithmic_bytes_per_env_step(N, A, int(np.prod(_abi.obs_shape(cfg))))
+            # The dominant kernel's launch duration: the dispatch timestamps of every 8th launch (HIP events filled in by
+            # hipExtLaunchKernelGGL), reported AS MEASURED.  A kernel cannot take longer than the step that contains it: if the
+            # events say so anyway the run is flagged (`event_exceeds_wall_step`) instead of clamped.  Without events
+            # (HWY_BENCH_NO_EVENTS=1, a developer knob): the wall step.
+            wall_step_s = elapsed / args.steps
+            event_kernel_s = (kernel_ms / 1e3 / launches) if launches else None
+            avg_kernel_s = event_kernel_s if event_kernel_s and event_kernel_s > 0 else wall_step_s
+            achieved = b_env * E / avg_kernel_s / 1e9
+            return {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS,
+                    "traffic": measured_traffic(args.workload, E),
+                    "kernel_source_sha16": _kernel_build_id(),
+                    "kernel": ("hwy_ix_step_kernel  (one 64-wide wavefront per env)" if scenario == "intersection" else
+                               "hwy_net_step_kernel  (one 64-wide wavefront per env)" if scenario != "highway" else
+                               f"hwy_step_wave_kernel<WPE,{str(not fast).lower()}>  (one 64-wide wavefront per env; every WPE variant is the same "
+                               "102 / 128-VGPR code)" if N <= 64 else
+                               f"hwy_step_wide_kernel<{(N + 63) // 64},{2 if N <= 128 else 1}>  (one 64-wide wavefront per env, {(N + 63) // 64} vehicles per thread)" if wide_kernel_runs(N) else
+                               f"hwy_step_kernel<{(N + 63) // 64},WPE>  ({(N + 63) // 64} wavefronts per env)"), "avg_kernel_us": avg_kernel_s * 1e6, "launches": launches, "timed_every": EVENT_EVERY,
+                    "avg_kernel_us_method": ("mean over ALL launches of a separate region after the timed ones, each carrying the HIP "
+                                             "start/stop events hipExtLaunchKernelGGL fills with the dispatch's own timestamps "
+                                             "(unclamped)" if event_kernel_s else "wall ms_per_step (no events)"),
+                    "event_kernel_us": (kernel_ms / launches * 1e3) if launches else None,
+                    "event_exceeds_wall_step": bool(event_kernel_s and event_kernel_s > wall_step_s * 1.02),
+                    "algorithmic_bytes_per_launch": b_env * E,
+                    "valu": valu_view(E, avg_kernel_s, args.workload),
+                    "kernel_resources": kernel_resources_view(scenario, fast, N)}
+
         line = {
             "metric": "env-steps/s",
             "value": value,
@@ -938,6 +973,7 @@ def main(argv=None, platform=None, emit=None):
             "settle_steps": settle_steps,
             "settle_ms": args.settle_ms,
             "repeats": R,
+            "full": args.full,
             "ms_per_step": elapsed / args.steps * 1e3,
             "ms_per_step_repeats": [x / args.steps * 1e3 for x in region_s],
             "ms_per_step_device": float(np.median(region_dev_ms)) / args.steps,
@@ -975,39 +1011,21 @@ def main(argv=None, platform=None, emit=None):
                                                "chosen_by": ("--tune prio_shift" if "prio_shift" in tuning else
                                                              {0: "scenario default (no selection: turns off or not applicable)",
                                                               1: "engine, still sampling", 2: "engine (timed its first launches)"}[prio_state])}},
-            "gather_every_1": per_step_gather,
-            f"rollout_k{args.rollout_k}": rollout,
+            **({"gather_every_1": per_step_gather, f"rollout_k{args.rollout_k}": rollout} if args.full else {}),
             **({f"split_batch_s{args.split_batch}": split} if split else {}),
             "vehicle_steps_per_s": value * N,
             "vehicle_steps_per_s_excl_ego": value * (N - A),
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": measured_traffic(args.workload, E),
-                         "kernel_source_sha16": _kernel_build_id(),
-                         "kernel": ("hwy_ix_step_kernel  (one 64-wide wavefront per env)" if scenario == "intersection" else
-                                    "hwy_net_step_kernel  (one 64-wide wavefront per env)" if scenario != "highway" else
-                                    f"hwy_step_wave_kernel<WPE,{str(not fast).lower()}>  (one 64-wide wavefront per env; every WPE variant is the same "
-                                    "102 / 128-VGPR code)" if N <= 64 else
-                                    f"hwy_step_wide_kernel<{(N + 63) // 64},{2 if N <= 128 else 1}>  (one 64-wide wavefront per env, {(N + 63) // 64} vehicles per thread)" if wide_kernel_runs(N) else
-                                    f"hwy_step_kernel<{(N + 63) // 64},WPE>  ({(N + 63) // 64} wavefronts per env)"), "avg_kernel_us": avg_kernel_s * 1e6, "launches": launches, "timed_every": EVENT_EVERY,
-                         "avg_kernel_us_method": ("mean over ALL launches of a separate region after the timed ones, each carrying the HIP "
-                                                  "start/stop events hipExtLaunchKernelGGL fills with the dispatch's own timestamps "
-                                                  "(unclamped)" if event_kernel_s else "wall ms_per_step (no events)"),
-                         "event_kernel_us": (kernel_ms / launches * 1e3) if launches else None,
-                         "event_exceeds_wall_step": bool(event_kernel_s and event_kernel_s > wall_step_s * 1.02),
-                         "algorithmic_bytes_per_launch": b_env * E,
-                         "valu": valu_view(E, avg_kernel_s, args.workload),
-                         "kernel_resources": kernel_resources_view(scenario, fast, N)},
+            **({"roofline": roofline_view()} if args.full else {}),
             "terminated_in_last_step": int(term),
             "ix_spawn_counters": (lambda c: dict(c, drop_rate=c["ix_spawns_dropped"] / max(1, c["ix_spawns"] + c["ix_spawns_dropped"])))(eng.counters()) if scenario == "intersection" else None,
-            "host_path_env_steps_per_s": host_rate,
+            **({"host_path_env_steps_per_s": host_rate} if args.full else {}),
             **({"dumped_outputs": dumped} if dumped else {}),
         }
-        if world == 1 and not args.no_frontend:
+        if args.full and world == 1 and not args.no_frontend:
             line["frontend"] = frontend_view(args.workload, cfg_dict, E, local_rank)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.workload, cfg_dict, fast, scenario)
-        if world == 1 and args.workload == "fast" and not args.no_secondary and not tuning:
+        if args.full and world == 1 and args.workload == "fast" and not args.no_secondary and not tuning:
             line["secondary_workloads"] = secondary_workloads()
         emit(line)
     eng.close()

@@ -25,6 +25,7 @@ class FakeEngine:
         self.obs_len = int(np.prod(_abi.obs_shape(cfg)))
         self.steps = 0
         self.resets_at_step = []
+        self.profiled = False
 
     def reset(self, **kw):
         self.resets_at_step.append(self.steps)
@@ -33,7 +34,7 @@ class FakeEngine:
         pass
 
     def profile_enable(self, every):
-        pass
+        self.profiled = True
 
     def profile_read(self):
         return 0.0, 0
@@ -104,6 +105,7 @@ def _rank_main(rank, world, port, argv, out_path):
     plat = CpuPlatform(rank)
     outs = bench.main(argv, platform=plat, emit=lines.append)
     json.dump({"lines": lines, "steps": plat.engine.steps, "envs": plat.engine.E, "resets_at_step": plat.engine.resets_at_step,
+               "profiled": plat.engine.profiled,
                "gathered_rewards": ([[float(v["reward"][0, 0]) for v in o.rank0_views(0)] for o in outs] if rank == 0 else None),
                "gathered_term": ([[int(v["terminated"][0]) for v in o.rank0_views(0)] for o in outs] if rank == 0 else None)},
               open(f"{out_path}.{rank}", "w"))
@@ -143,7 +145,7 @@ def test_settling_goes_on_until_the_engine_has_chosen_its_turn(tmp_path, monkeyp
 def test_two_rank_bench_control_flow_on_gloo(tmp_path, scaling, envs, gather_every, settle_ms):
     steps, warmup, repeats = 6, 3, 2   # 6 % 4 != 0: every region ends on a partly filled buffer that still has to travel
     argv = ["--gpus", "2", "--steps", str(steps), "--warmup", str(warmup), "--repeats", str(repeats), "--envs-per-gpu", str(envs),
-            "--scaling", scaling, "--gather-every", str(gather_every), "--settle-ms", str(settle_ms), "--no-cpu-baseline"]
+            "--scaling", scaling, "--gather-every", str(gather_every), "--settle-ms", str(settle_ms), "--full", "--no-cpu-baseline"]
     r0, r1 = _run(tmp_path, argv)
     assert r1["lines"] == [] and len(r0["lines"]) == 1    # ONE JSON line, from rank 0
     line = r0["lines"][0]
@@ -161,6 +163,7 @@ def test_two_rank_bench_control_flow_on_gloo(tmp_path, scaling, envs, gather_eve
     #  them the reset and the warm-up steps run again, so that the timed regions start from the same state as without them)
     rewarm = warmup if line["settle_steps"] else 0
     assert r0["steps"] == r1["steps"] == warmup + line["settle_steps"] + rewarm + repeats * steps + extra
+    assert line["full"] is True and r0["profiled"] and r1["profiled"]
     assert r0["resets_at_step"] == r1["resets_at_step"] == ([0, warmup + line["settle_steps"]] if rewarm else [0])
     assert (line["settle_steps"] > 0) == (settle_ms > 0) and line["settle_steps"] % warmup == 0
     if gather_every == 1:
@@ -182,7 +185,7 @@ def test_eight_rank_bench_of_baseline_config_3_on_gloo(tmp_path, scaling, envs):
     engine -- shard sizes, the packed gather of eight ranks' blocks into rank 0's buffer, the one JSON line (round-4 verdict item 7)."""
     steps, warmup, repeats, world = 5, 2, 2, 8
     argv = ["--gpus", str(world), "--workload", "v0_n100", "--steps", str(steps), "--warmup", str(warmup), "--repeats", str(repeats),
-            "--envs-per-gpu", str(envs), "--scaling", scaling, "--gather-every", "4", "--settle-ms", "0", "--no-cpu-baseline"]
+            "--envs-per-gpu", str(envs), "--scaling", scaling, "--gather-every", "4", "--settle-ms", "0", "--full", "--no-cpu-baseline"]
     res = _run(tmp_path, argv, world=world)
     assert all(r["lines"] == [] for r in res[1:]) and len(res[0]["lines"]) == 1
     line = res[0]["lines"][0]
@@ -196,6 +199,59 @@ def test_eight_rank_bench_of_baseline_config_3_on_gloo(tmp_path, scaling, envs):
         assert terms == list(range(1, world + 1))                           # rank r's block landed in slot r of the root's buffer
     for rewards in res[0]["gathered_rewards"]:
         assert all(1000.0 * r <= rewards[r] < 1000.0 * (r + 1) for r in range(world))
+
+
+# what only --full measures: the kernel-event region and the roofline view, the one-gather-per-step leg, K steps per launch, the
+# host-pointer path, the Python front ends, the CPU leg, BASELINE's other workloads
+FULL_ONLY = ("roofline", "gather_every_1", "rollout_k16", "host_path_env_steps_per_s", "frontend", "cpu_baseline", "secondary_workloads")
+
+
+@pytest.mark.parametrize("world,gather_every", [(1, 1), (2, 4)])
+def test_a_plain_run_times_the_headline_alone(tmp_path, world, gather_every):
+    """Without --full a run sets up, warms up, settles, times its regions and prints the line -- nothing else steps the engine
+    (the stand-in engine has no host-pointer step and no GPU behind it: any other leg would fail here)."""
+    steps, warmup, repeats = 6, 3, 2
+    argv = ["--gpus", str(world), "--steps", str(steps), "--warmup", str(warmup), "--repeats", str(repeats), "--envs-per-gpu", "4",
+            "--gather-every", str(gather_every), "--settle-ms", "30"]
+    res = _run(tmp_path, argv, world=world)
+    assert len(res[0]["lines"]) == 1 and all(r["lines"] == [] for r in res[1:])
+    line = res[0]["lines"][0]
+    assert line["metric"] == line["unit"] == "env-steps/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["value"] == pytest.approx(4 * world / (line["ms_per_step"] * 1e-3), rel=1e-9)
+    assert len(line["ms_per_step_repeats"]) == repeats and line["n_gpus"] == world
+    assert line["full"] is False and not [k for k in FULL_ONLY if k in line], sorted(line)
+    settle = line["settle_steps"]
+    assert settle > 0 and settle % warmup == 0
+    for r in res:  # warm-up, settling, the same reset and warm-up again, the timed regions
+        assert r["steps"] == warmup + settle + warmup + repeats * steps and not r["profiled"]
+        assert r["resets_at_step"] == [0, warmup + settle]
+
+
+def test_split_batch_is_a_leg_of_full():
+    sys.path.insert(0, ROOT)
+    import bench
+    with pytest.raises(SystemExit) as ex:
+        bench.main(["--split-batch", "2"], platform=CpuPlatform(0), emit=lambda line: None)
+    assert ex.value.code == 2   # (argparse's usage error, before anything touches a device)
+
+
+def test_the_secondary_legs_of_a_full_run_are_full_runs(monkeypatch):
+    """--full reports every secondary workload with its kernel duration and issue limits: each leg's own line must carry its
+    roofline, so each leg runs with --full too."""
+    import subprocess
+    sys.path.insert(0, ROOT)
+    import bench
+    leg = {"ms_per_step": 0.2, "ms_per_step_device": 0.19, "value": 5e6, "unit": "env-steps/s", "vehicle_steps_per_s": 5e8,
+           "roofline": {"avg_kernel_us": 180.0, "kernel": "k", "frac": 0.01, "algorithmic_bytes_per_launch": 7, "valu": None}}
+    cmds = []
+
+    def run(cmd, **kw):
+        cmds.append(cmd)
+        return subprocess.CompletedProcess(cmd, 0, stdout=json.dumps(leg) + "\n", stderr="")
+    monkeypatch.setattr(subprocess, "run", run)
+    out = bench.secondary_workloads()
+    assert len(cmds) == len(bench.SECONDARY) and all("--full" in c for c in cmds)
+    assert [v.get("avg_kernel_us") for v in out.values()] == [180.0] * len(bench.SECONDARY), out
 
 
 def test_dump_outputs_writes_the_last_timed_step_of_every_rank(tmp_path):

@@ -31,7 +31,7 @@ for rep in $(seq 1 $REPS); do
       name=${V%%:*}; tune=""
       if [ "$V" != "$name" ]; then for t in $(echo ${V#*:} | tr ',' ' '); do tune="$tune --tune $t"; done; fi
       if [ "$name" = "-" ]; then unset HWY_ENGINE_LIB; else export HWY_ENGINE_LIB=$B/libhwy_engine_$name.so; fi
-      timeout 300 python bench.py $(wl_args $W) --no-cpu-baseline --no-secondary --no-frontend --rollout-k 0 --steps ${STEPS:-300} --repeats 3 $tune "$@" \
+      timeout 300 python bench.py $(wl_args $W) --full --no-cpu-baseline --no-secondary --no-frontend --rollout-k 0 --steps ${STEPS:-300} --repeats 3 $tune "$@" \
         > "$O/${W}_$(echo $V | tr ':=,' '___')_$rep.json" 2>> $O/err.txt
     done
   done

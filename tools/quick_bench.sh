@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/quick; mkdir -p $O; cd $R
 for spec in "$@"; do
   w=${spec%%:*}; e=${spec##*:}
-  timeout 150 python bench.py --workload $w --envs-per-gpu $e --no-cpu-baseline --no-secondary --steps 300 --repeats 3 $QUICK_FLAGS > $O/$w_$e.json 2>> $O/err.txt
+  timeout 150 python bench.py --workload $w --envs-per-gpu $e --full --no-cpu-baseline --no-secondary --steps 300 --repeats 3 $QUICK_FLAGS > $O/$w_$e.json 2>> $O/err.txt
   python - $O/$w_$e.json $w $e <<'PY'
 import json, sys
 try:

@@ -3,8 +3,8 @@
 # plus its section clocks:   bash tools/wide_ab.sh [block]
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/wide_ab; mkdir -p $O; cd $R
 for e in 1024 2048; do
-  timeout 100 python bench.py --workload v0_n100 --envs-per-gpu $e --no-cpu-baseline --no-secondary --steps 300 --repeats 3 > $O/wide_$e.json 2>> $O/err.txt
-  [ "$1" = block ] && timeout 100 python bench.py --workload v0_n100 --envs-per-gpu $e --no-cpu-baseline --no-secondary --steps 300 --repeats 3 --tune block_kernel=1 > $O/block_$e.json 2>> $O/err.txt
+  timeout 100 python bench.py --workload v0_n100 --envs-per-gpu $e --full --no-cpu-baseline --no-secondary --steps 300 --repeats 3 > $O/wide_$e.json 2>> $O/err.txt
+  [ "$1" = block ] && timeout 100 python bench.py --workload v0_n100 --envs-per-gpu $e --full --no-cpu-baseline --no-secondary --steps 300 --repeats 3 --tune block_kernel=1 > $O/block_$e.json 2>> $O/err.txt
 done
 python - <<'PY'
 import json, glob, os
