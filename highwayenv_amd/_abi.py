@@ -13,7 +13,7 @@ import ctypes as C
 
 import numpy as np
 
-HWY_ABI_VERSION = 6
+HWY_ABI_VERSION = 7
 HWY_MAX_AGENTS = 16
 HWY_MAX_FEATURES = 16
 HWY_MAX_TARGET_SPEEDS = 8
@@ -21,6 +21,7 @@ HWY_MAX_LANES = 16
 HWY_MAX_VEHICLES = 256
 HWY_MAX_GLANES = 24
 HWY_MAX_ROUTE = 11
+HWY_MAX_ACTIONS_PER_AXIS = 16
 
 # hwy_status
 HWY_OK, HWY_ERR_INVALID_ARG, HWY_ERR_HIP, HWY_ERR_UNSUPPORTED, HWY_ERR_NO_DEVICE, HWY_ERR_ACTION = 0, -1, -2, -3, -4, -5
@@ -44,6 +45,8 @@ OBS_KINEMATICS, OBS_OCCUPANCY_GRID = 0, 1
 # hwy_config.traffic_model
 TRAFFIC_IDM, TRAFFIC_LINEAR = 0, 1
 HWY_BEHAVIOR_PARAMS = 5
+# hwy_config.ego_control: DiscreteMetaAction (the ego is an MDPVehicle) / DiscreteAction (a plain Vehicle with stored controls)
+EGO_META, EGO_DIRECT = 0, 1
 # config["other_vehicles_type"] -> (traffic_model, LANE_CHANGE_MIN_ACC_GAIN, TIME_WANTED) of the class (vehicle/behavior.py)
 TRAFFIC_CLASSES = {
     "highway_env.vehicle.behavior.IDMVehicle": (TRAFFIC_IDM, 0.2, 1.5),
@@ -65,7 +68,52 @@ ACTIONS_SET_ALL, ACTIONS_SET_LONGI, ACTIONS_SET_LAT = 0, 1, 2
 
 
 def num_actions(cfg: "HwyConfig") -> int:
+    if cfg.ego_control == EGO_DIRECT:  # actions_per_axis ** size (action.py:186-187)
+        return cfg.n_accel * cfg.n_steer
     return 5 if cfg.action_set == ACTIONS_SET_ALL else 3
+
+
+def direct_action_axes(act: dict) -> tuple:
+    """The throttle and steering values of a ``DiscreteAction`` config as the reference computes them, widened to f64:
+    ``(accel_axis, steer_axis)`` with action id ``a`` meaning ``(accel_axis[a // len(steer_axis)], steer_axis[a % len(steer_axis)])``.
+
+    Runs the reference's own expressions in NumPy: ``DiscreteAction.act`` (action.py:189-196) takes ``np.linspace`` of the
+    continuous space's ``low`` / ``high`` -- gymnasium's ``Box(-1., 1., shape=(size,), dtype=float32)`` holds them as float32
+    ARRAYS -- and ``itertools.product`` of the axes, first axis (throttle) major; ``ContinuousAction.get_action``
+    (action.py:137-157) clips and maps each coordinate with ``utils.lmap``.  Every step stays in float32 under NumPy 2 and
+    ``Vehicle.clip_actions`` applies ``float()`` (kinematics.py:159-160).  An axis that is not controlled holds the integer 0
+    of ``get_action``."""
+    longi, lat = bool(act.get("longitudinal", True)), bool(act.get("lateral", True))
+    if not (longi or lat):
+        raise ValueError("Either longitudinal and/or lateral control must be enabled")  # action.py:108-111
+    k = int(act.get("actions_per_axis", 3))
+    if k < 1:
+        raise ValueError("actions_per_axis must be positive")
+    if k > HWY_MAX_ACTIONS_PER_AXIS:
+        raise NotImplementedError(f"actions_per_axis > {HWY_MAX_ACTIONS_PER_AXIS} is outside the MI355X hot-path scope")
+    acc_range = act.get("acceleration_range") or (-5, 5.0)                  # ContinuousAction.ACCELERATION_RANGE
+    steer_range = act.get("steering_range") or (-np.pi / 4, np.pi / 4)      # ContinuousAction.STEERING_RANGE
+    size = 2 if (longi and lat) else 1
+    low, high = np.full((size,), -1.0, np.float32), np.full((size,), 1.0, np.float32)
+    axes = np.linspace(low, high, k).T
+
+    def lmap(v, x, y):  # utils.lmap (utils.py:31-33)
+        return y[0] + (v - x[0]) * (y[1] - y[0]) / (x[1] - x[0])
+
+    def axis(values, rng):
+        out = []
+        for v in values:
+            action = (v,)
+            if act.get("clip", True):
+                action = np.clip(action, -1, 1)
+            out.append(float(lmap(action[0], [-1, 1], rng)))
+        return out
+
+    accel = axis(axes[0], acc_range) if longi else [float(0)]
+    steer = axis(axes[-1], steer_range) if lat else [float(0)]
+    if max(abs(v) for v in steer) > np.pi / 3:
+        raise ValueError("steering_range must lie within +-pi/3 (the kernels' tan covers Vehicle.MAX_STEERING_ANGLE)")
+    return accel, steer
 
 
 class HwyLane(C.Structure):
@@ -167,6 +215,13 @@ class HwyConfig(C.Structure):
         ("reserved4", C.c_int32),
         ("traffic_lc_min_acc_gain", C.c_double),
         ("traffic_time_wanted", C.c_double),
+        # ego control (ABI v7)
+        ("ego_control", C.c_int32),
+        ("n_accel", C.c_int32),
+        ("n_steer", C.c_int32),
+        ("reserved5", C.c_int32),
+        ("accel_axis", C.c_double * HWY_MAX_ACTIONS_PER_AXIS),
+        ("steer_axis", C.c_double * HWY_MAX_ACTIONS_PER_AXIS),
     ]
 
 
@@ -327,10 +382,21 @@ def make_config(config: dict, num_envs: int, fast: bool = False, scenario: str =
         act = act["action_config"]
     if act["type"] not in ("DiscreteMetaAction", "ContinuousAction", "DiscreteAction", "MultiAgentAction"):
         raise ValueError("Unknown action type")
-    if act["type"] != "DiscreteMetaAction":
+    if act["type"] not in ("DiscreteMetaAction", "DiscreteAction"):
         raise NotImplementedError(f"action type {act['type']} is outside the MI355X hot-path scope")
+    direct = act["type"] == "DiscreteAction"
     ix = scenario == "intersection"
     longi, lat = bool(act.get("longitudinal", True)), bool(act.get("lateral", True))
+    direct_axes = None
+    if direct:
+        if act.get("dynamical", False):
+            raise NotImplementedError("DiscreteAction(dynamical=True) (BicycleVehicle) is outside the MI355X hot-path scope")
+        if scenario != "highway":
+            raise NotImplementedError("DiscreteAction is in the hot-path scope on the highway scenario only")
+        if config.get("other_vehicles_type", "highway_env.vehicle.behavior.IDMVehicle") != "highway_env.vehicle.behavior.IDMVehicle":
+            raise NotImplementedError("DiscreteAction is in the hot-path scope with IDMVehicle traffic only")
+        direct_axes = direct_action_axes(act)
+        longi = lat = True  # (the meta-action table is not used)
     if not (longi or lat):
         raise ValueError("At least longitudinal or lateral actions must be included")  # action.py:246-249
     if ix and (not longi or lat):
@@ -396,7 +462,14 @@ def make_config(config: dict, num_envs: int, fast: bool = False, scenario: str =
         c.road_length = 10000.0   # RoadNetwork.straight_road_network length (road/road.py:296)
         c.speed_limit = 30.0      # HighwayEnv._create_road (highway_env.py:63)
         y_lanes = c.lanes_count
-    ts = act.get("target_speeds")
+    if direct:
+        c.ego_control = EGO_DIRECT
+        c.n_accel, c.n_steer = len(direct_axes[0]), len(direct_axes[1])
+        for k, v in enumerate(direct_axes[0]):
+            c.accel_axis[k] = v
+        for k, v in enumerate(direct_axes[1]):
+            c.steer_axis[k] = v
+    ts = None if direct else act.get("target_speeds")  # (a plain Vehicle has no ladder: the class default fills the POD)
     ts = np.linspace(20, 30, 3) if ts is None else np.asarray(ts, np.float64)  # controller.py:259
     if not (2 <= ts.size <= HWY_MAX_TARGET_SPEEDS):
         raise ValueError("target_speeds must hold 2..8 values")

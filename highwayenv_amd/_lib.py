@@ -20,6 +20,7 @@ EXPORTS = [
     "hwy_step_device", "hwy_rollout_device", "hwy_rollout", "hwy_step_frames", "hwy_observe", "hwy_set_autoreset", "hwy_sync",
     "hwy_profile_enable", "hwy_profile_read", "hwy_get_prio_turn", "hwy_debug_math", "hwy_get_counters", "hwy_set_block_order",
     "hwy_comm_unique_id", "hwy_comm_init", "hwy_gather", "hwy_comm_destroy", "hwy_set_behavior", "hwy_get_behavior",
+    "hwy_set_controls", "hwy_get_controls",
 ]
 
 
@@ -85,6 +86,8 @@ def load() -> C.CDLL:
     lib.hwy_comm_init.argtypes = [vp, vp, i32, i32]
     lib.hwy_gather.argtypes = [vp, vp, vp, C.c_size_t, i32]
     lib.hwy_comm_destroy.argtypes = [vp]
+    lib.hwy_set_controls.argtypes = [vp, vp, vp]
+    lib.hwy_get_controls.argtypes = [vp, vp, vp]
     lib.hwy_profile_enable.argtypes = [vp, i32]
     lib.hwy_profile_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     lib.hwy_get_prio_turn.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]

@@ -11,8 +11,8 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libhwy_engine.so")
-SOURCES = ["hwy_kernels.hip", "hwy_kernels_linear.hip", "hwy_engine.hip", "hwy_comm.hip"]
-KERNEL_SOURCES = ("hwy_kernels.hip", "hwy_kernels_linear.hip")  # the translation units that hold device code
+SOURCES = ["hwy_kernels.hip", "hwy_kernels_linear.hip", "hwy_kernels_direct.hip", "hwy_engine.hip", "hwy_comm.hip"]
+KERNEL_SOURCES = ("hwy_kernels.hip", "hwy_kernels_linear.hip", "hwy_kernels_direct.hip")  # the translation units that hold device code
 import glob
 
 # every header the two translation units can include: csrc/*.h (hwy_device.h, hwy_wave.h, hwy_net.h, hwy_ix.h, ...)
@@ -73,9 +73,9 @@ def kernel_source_hash() -> str:
 
 def flags_for(src: str) -> list:
     """hipcc flags of one translation unit: HIPCC_FLAGS, except that the Linear traffic family's kernels
-    (hwy_kernels_linear.hip) are scheduled by the default strategy -- ROCm 7.2's register allocator crashes on them after the
-    iterative-ilp scheduler."""
-    if src == "hwy_kernels_linear.hip":
+    (hwy_kernels_linear.hip) and the direct-ego-control kernels (hwy_kernels_direct.hip) are scheduled by the default strategy --
+    ROCm 7.2's register allocator crashes on them after the iterative-ilp scheduler."""
+    if src in ("hwy_kernels_linear.hip", "hwy_kernels_direct.hip"):
         out = list(HIPCC_FLAGS)
         k = out.index("-amdgpu-sched-strategy=iterative-ilp")
         del out[k - 1:k + 1]

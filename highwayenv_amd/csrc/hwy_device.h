@@ -184,6 +184,28 @@ struct LinearParams {
   LinearArgs la;
 };
 
+// ---- ego control (hwy_config.ego_control): compile-time policies next to the traffic model ------------------------------------
+// MetaEgo: DiscreteMetaAction, the ego is an MDPVehicle (controller.py:255-315).  DirectEgo: DiscreteAction (action.py:165-196), the
+// ego is a plain Vehicle (kinematics.py:18-177) driven by a stored (acceleration, steering) pair: no target lane, no target speed,
+// no controller chain.  Instantiated in hwy_kernels_direct.hip.
+struct MetaEgo {
+  static constexpr bool DIRECT = false;
+};
+struct DirectEgo {
+  static constexpr bool DIRECT = true;
+};
+// kernel arguments of the direct-control kernels next to StepParams: the two axis tables (physical values, filled by the host)
+// and the stored controls of every agent, f64 [E][A] each (hwy_set_controls)
+struct DirectArgs {
+  double *ctl_accel, *ctl_steer;
+  int32_t n_accel, n_steer;
+  double accel_axis[HWY_MAX_ACTIONS_PER_AXIS], steer_axis[HWY_MAX_ACTIONS_PER_AXIS];
+};
+struct DirectParams {
+  StepParams s;  // (offset 0 of the argument segment: HWY_RELOAD_STEP_PARAMS / HWY_RELOAD_PARAMS read it there)
+  DirectArgs da;
+};
+
 // ---- utils.py ---------------------------------------------------------------------------
 // utils.py:50-56: x if |x| > eps else (eps if x >= 0 else -eps).  For every x but NaN that is max(|x|, eps) carrying the sign
 // of (x < 0) -- -0.0 counts as >= 0, like in the reference: a max, a compare and a sign flip instead of two compares and two
@@ -203,6 +225,60 @@ __device__ inline double lmap(double v, double x0, double x1, double y0, double 
 // the same with the host-computed reciprocal of (x1 - x0) (StepParams::inv_*)
 __device__ inline double lmap_inv(double v, double x0, double inv_dx, double y0, double y1) {
   return y0 + ((v - x0) * (y1 - y0)) * inv_dx;
+}
+
+// ---- the plain-Vehicle ego of DirectEgo (one definition for the one-wavefront and the workgroup kernel) ----------------------
+// The controls a vehicle carries through a policy step in registers: the acceleration of Vehicle.action (kinematics.py:120-127)
+// and tan(beta) of its steering angle.  The angle itself stays in its plane (DirectArgs::ctl_steer), written where it changes.
+struct EgoControls {
+  double accel, tb;
+};
+// what IDMVehicle.acceleration reads for a would-be follower that is the ego: getattr(ego_vehicle, "target_speed", 0)
+// (behavior.py:172) -- a plain Vehicle has none, so v0 = not_zero(0) = 0.01 and (v / v0)^delta is ~1e14 for a moving ego.  The
+// kernels keep it in the ego's target-speed slot, where idm_inv_v0 / idm_log_ratio find it like any vehicle's.
+__device__ inline double direct_ego_target_speed(double v) {
+  (void)v;
+  return 0.0;
+}
+// tan(beta) = 1/2 tan(steering) (Vehicle.step, kinematics.py:141-142); |steering| <= pi / 3 is validated by hwy_create
+__device__ inline double direct_tan_beta(double steering) { return 0.5 * tan_bounded(steering); }
+// DiscreteAction.act (action.py:189-196): id -> (accel_axis[id / n_steer], steer_axis[id % n_steer]); an id outside the table
+// (only hwy_step_device / hwy_rollout_device can hand one in) leaves the stored pair as it is.
+__device__ inline bool direct_id_in_table(const DirectArgs &da, int id) { return id >= 0 && id < da.n_accel * da.n_steer; }
+// The controls of a policy step from the stored pair (acceleration, steering angle) and -- if `acted` -- the table entry that
+// replaces it on the first frame (Vehicle.act(dict), kinematics.py:120-127); slot: the agent's entry of the planes.  One tan per
+// step.  Nothing reads the stored pair between the start of the step and the first frame's Vehicle.step, so the kernels call this
+// before their frame loop.
+__device__ inline EgoControls direct_begin_step(const DirectArgs &da, size_t slot, double stored_accel, double stored_steer,
+                                                bool acted, double act_accel, double act_steer) {
+  EgoControls c;
+  c.accel = acted ? act_accel : stored_accel;
+  c.tb = direct_tan_beta(acted ? act_steer : stored_steer);
+  if (acted) da.ctl_steer[slot] = act_steer;
+  return c;
+}
+// Vehicle.clip_actions (kinematics.py:155-168) WRITES INTO the stored action: once the speed is beyond +-MAX_SPEED the stored
+// acceleration becomes min / max(a, bound - speed) and stays so for the rest of the policy step, also after the speed has come
+// back inside; a crashed vehicle gets steering 0 and -1.0 * speed, every frame.
+// Returns the pair the frame integrates.
+__device__ inline EgoControls direct_clip_actions(const DirectArgs &da, size_t slot, EgoControls &stored, double v, bool crashed) {
+  EgoControls c = stored;
+  if (crashed) {
+    da.ctl_steer[slot] = 0.0;
+    c.tb = 0.0;
+    c.accel = -1.0 * v;
+  }
+  if (v > HWY_MAX_SPEED) c.accel = fmin(c.accel, 1.0 * (HWY_MAX_SPEED - v));
+  else if (v < HWY_MIN_SPEED) c.accel = fmax(c.accel, 1.0 * (HWY_MIN_SPEED - v));
+  stored = c;  // (sticky: the vehicle keeps what the clip wrote)
+  return c;
+}
+// speed += acceleration * dt (kinematics.py:152) as the reference rounds it: the product, then the sum.  The ego's speed is a
+// closed recurrence on exactly rounded operations, and next to +-MAX_SPEED its last bit picks the branch of clip_actions, so it
+// must NOT be contracted into a fused multiply-add (-ffp-contract=on fuses within one expression: two statements).
+__device__ inline double direct_speed_update(double v, double accel, double dt) {
+  const double dv = accel * dt;
+  return v + dv;
 }
 
 // ---- counter-based RNG for the device-side reset: Philox-4x32-10 --------------------------
@@ -692,6 +768,10 @@ struct Veh {
   double x, y, h, v, timer, ts, delta, impx, impy, ch, sh;
   int lane, tgt, sidx, flags, rank;
 };
+// lane_index[2] of the right-lane reward (highway_env.py:122-126): the target lane for an MDPVehicle, the lane the plain Vehicle
+// of DirectEgo is on (its target-lane slot is only brought up to date at the end of a policy step)
+template <typename EG>
+__device__ inline int ego_reward_lane(const Veh &me) { return EG::DIRECT ? me.lane : me.tgt; }
 
 // ---- device-side spawn: HighwayEnv._create_vehicles (envs/highway_env.py:72-98) with
 //      Vehicle.create_random's rule (vehicle/kinematics.py:50-104), IDMVehicle ctor timer
@@ -904,7 +984,9 @@ __device__ inline void observe_grid(const StepParams &p, int e, int a, const Veh
 // ---- KinematicObservation.observe (envs/common/observation.py:234-276) + Road.close_objects_to
 //      (road/road.py:421-450) + reward/termination (envs/highway_env.py:100-151) for every agent.
 //      Expects sh.x/y/v/c/s to hold the CURRENT state of all vehicles.  Block-uniform control flow.
-template <int NW>
+// EG: the ego control -- the right-lane term of the reward reads the ego's target lane (MDPVehicle.target_lane_index,
+// highway_env.py:122-126) or, for the plain Vehicle of DirectEgo, its lane.
+template <int NW, typename EG = MetaEgo>
 __device__ inline void observe_env(const StepParams &p, typename EnvBlock<NW>::Shared &sh, int e, const Veh &me,
                                    bool write_reward, int eo = -1) {
   eo = eo < 0 ? e : eo;  // row of the output planes (== e except in a multi-step launch, hwy_rollout_device)
@@ -977,7 +1059,7 @@ __device__ inline void observe_env(const StepParams &p, typename EnvBlock<NW>::S
       const int nl = p.L - 1 > 1 ? p.L - 1 : 1;
       double reward = 0.0;
       reward = reward + p.collision_reward * (crashed ? 1.0 : 0.0);
-      reward = reward + p.right_lane_reward * ((double)me.tgt / (double)nl);
+      reward = reward + p.right_lane_reward * ((double)ego_reward_lane<EG>(me) / (double)nl);
       reward = reward + p.high_speed_reward * clipd(scaled_speed, 0.0, 1.0);
       reward = reward + 0.0 * (on_road ? 1.0 : 0.0);
       if (p.flags & HWY_C_NORMALIZE_REWARD)
@@ -1081,8 +1163,10 @@ __device__ inline void publish(typename EnvBlock<NW>::Shared &sh, const Veh &me,
 // =============================================================================================
 // Reset kernel: AbstractEnv.reset for the masked environments + first observation.
 // (the body of both reset kernels: TM = the traffic model, whose Linear family also draws the per-vehicle parameters)
+// (da: the stored controls of a DirectEgo engine, zeroed like Vehicle.__init__ does -- the spawn itself is the one of MetaEgo)
 template <int NW, typename TM>
-__device__ __forceinline__ void reset_env(const StepParams &p, typename EnvBlock<NW>::Shared &sh, const LinearArgs &la) {
+__device__ __forceinline__ void reset_env(const StepParams &p, typename EnvBlock<NW>::Shared &sh, const LinearArgs &la,
+                                          const DirectArgs *da = nullptr) {
   const int e = blockIdx.x, i = threadIdx.x;
   if (p.reset_mask && !p.reset_mask[e]) return;  // block-uniform
   const bool active = i < p.N;
@@ -1096,6 +1180,7 @@ __device__ __forceinline__ void reset_env(const StepParams &p, typename EnvBlock
   __syncthreads();
   observe_env<NW>(p, sh, e, me, false);
   store_vehicle<NW>(p, e, me);
+  if (da && i < p.A) da->ctl_accel[(size_t)e * p.A + i] = da->ctl_steer[(size_t)e * p.A + i] = 0.0;
   if (i == 0) {
     p.st.time[e] = 0.0;
     p.st.done[e] = 0;
@@ -1113,6 +1198,13 @@ template <int NW>
 __global__ void __launch_bounds__(NW * 64) hwy_reset_linear_kernel(const LinearParams lp) {
   __shared__ typename EnvBlock<NW>::Shared sh;
   reset_env<NW, LinearTraffic>(lp.s, sh, lp.la);
+}
+
+// The same for a direct-control engine (hwy_config.ego_control == HWY_EGO_DIRECT): + the stored controls.
+template <int NW>
+__global__ void __launch_bounds__(NW * 64) hwy_reset_direct_kernel(const DirectParams dp) {
+  __shared__ typename EnvBlock<NW>::Shared sh;
+  reset_env<NW, IdmTraffic>(dp.s, sh, LinearArgs{}, &dp.da);
 }
 
 // Observation-only kernel (hwy_observe).
@@ -1186,9 +1278,10 @@ __device__ inline void wave_turn(WaveTurn &w) {
 }
 
 // TM: the traffic model (IdmTraffic / LinearTraffic, compile time); la: the Linear family's parameters (unused by IdmTraffic).
-template <int NW, typename TM = IdmTraffic>
+// EG: the ego control (MetaEgo / DirectEgo, compile time); da: the direct-control arguments (DirectEgo only).
+template <int NW, typename TM = IdmTraffic, typename EG = MetaEgo>
 __device__ __forceinline__ void block_policy_step(const StepParams &p, typename EnvBlock<NW>::Shared &sh, const int e, const int eo,
-                                                  const LinearArgs &la = LinearArgs{}) {
+                                                  const LinearArgs &la = LinearArgs{}, const DirectArgs *da = nullptr) {
   typedef EnvBlock<NW> B;
   const int i = threadIdx.x;
   const int N = p.N;
@@ -1213,6 +1306,7 @@ __device__ __forceinline__ void block_policy_step(const StepParams &p, typename 
           p.reward[(size_t)eo * p.A + a] = 0.0;
           if (p.info_speed) p.info_speed[(size_t)eo * p.A + a] = me.v;
           if (p.info_crashed) p.info_crashed[(size_t)eo * p.A + a] = 0;
+          if constexpr (EG::DIRECT) da->ctl_accel[(size_t)e * p.A + a] = da->ctl_steer[(size_t)e * p.A + a] = 0.0;  // Vehicle.__init__
         }
     }
     if (i == 0) {
@@ -1228,6 +1322,9 @@ __device__ __forceinline__ void block_policy_step(const StepParams &p, typename 
   Veh me;
   load_vehicle<NW>(p, e, me);
   const bool controlled = active && (me.flags & HWY_F_CONTROLLED);
+  if constexpr (EG::DIRECT) {
+    if (controlled) me.ts = direct_ego_target_speed(me.v);  // (the ego has no target speed: what a MOBIL caller reads for it)
+  }
   const bool idm = active && !controlled;
   // Linear family: ACCELERATION_PARAMETERS[3], STEERING_PARAMETERS[2] of my vehicle, loaded once per policy step and kept in registers
   // for its frames (MOBIL applies
@@ -1243,6 +1340,16 @@ __device__ __forceinline__ void block_policy_step(const StepParams &p, typename 
   if (controlled)
     for (int a = 0; a < p.A; ++a)
       if (p.agent_index[a] == i) agent = a;
+  EgoControls ctl = {0.0, 0.0};  // DirectEgo: Vehicle.action of my (controlled) vehicle: what the previous launch left, or this step's action
+  const size_t ctl_slot = (size_t)e * p.A + agent;
+  if constexpr (EG::DIRECT) {
+    if (controlled) {  // DiscreteAction.act -> Vehicle.act(dict) (action.py:189-196) on the first frame
+      const int id = (p.actions && p.n_frames > 0) ? p.actions[(size_t)eo * p.A + agent] : -1;
+      const bool acted = direct_id_in_table(*da, id);
+      const int ia = acted ? id / da->n_steer : 0, is = acted ? id - ia * da->n_steer : 0;
+      ctl = direct_begin_step(*da, ctl_slot, da->ctl_accel[ctl_slot], da->ctl_steer[ctl_slot], acted, da->accel_axis[ia], da->steer_axis[is]);
+    }
+  }
 
   WaveTurn turn;
   wave_turn_init_workgroup(turn, p.prio_shift, p.prio_recip);
@@ -1267,7 +1374,7 @@ __device__ __forceinline__ void block_policy_step(const StepParams &p, typename 
     wave_turn(turn);
     // ---- A. action_type.act (abstract.py:294-304) -> MDPVehicle.act(label) (controller.py:295-315):
     //         target updates only; the controllers run below with Road.act (same state => same command)
-    if (fr == 0 && p.actions && controlled) {
+    if (!EG::DIRECT && fr == 0 && p.actions && controlled) {  // (DirectEgo: direct_begin_step above)
       const int act = HWY_ACTION_TO_ALL(p.action_set, p.actions[(size_t)eo * p.A + agent]);
       if (act == HWY_FASTER || act == HWY_SLOWER) {
         const double xs = (me.v - p.target_speeds[0]) / (p.target_speeds[p.n_ts - 1] - p.target_speeds[0]);
@@ -1463,7 +1570,9 @@ __device__ __forceinline__ void block_policy_step(const StepParams &p, typename 
       // A rival is ANOTHER vehicle on its way to another lane (with the target it had at the start of the frame or the one
       // it has now): with at most one such vehicle in the environment no link can block
       u64 mv[NW], cm[NW];
-      B::block_ballot2(sh, active && (me.lane != tgt_old || me.lane != me.tgt), changer, sh.bal0, sh.bal2, ph0, ph2, mv, cm);
+      // (DirectEgo: the ego is no ControlledVehicle -- behavior.py:237 skips it -- so it is never a rival: not a mover, not in S_T)
+      const bool rival = !(EG::DIRECT && controlled);
+      B::block_ballot2(sh, active && rival && (me.lane != tgt_old || me.lane != me.tgt), changer, sh.bal0, sh.bal2, ph0, ph2, mv, cm);
       int n_movers = 0;
       for (int w = 0; w < NW; ++w) n_movers += __popcll(mv[w]);
       const bool chain = n_movers > 1 && B::any_of(cm);  // block-uniform
@@ -1482,7 +1591,7 @@ __device__ __forceinline__ void block_policy_step(const StepParams &p, typename 
         //    rounds: one workgroup ballot per round, two rounds when somebody aborts, one when nobody does.
         // (1) S_T (rank space) = the vehicles heading for lane T from another lane: every such vehicle ORs its rank bit into row T
         // (zeroed with the membership masks of section C); what a walker needs of a rival beyond the snapshot goes by index
-        if (active && me.lane != me.tgt)
+        if (active && rival && me.lane != me.tgt)
           __hip_atomic_fetch_or(&sh.amask[me.tgt][rank >> 6], (u64)1 << (rank & 63), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         sh.acode[i] = ((me.tgt != tgt_old) ? 1 : 0) | (changer ? 2 : 0);
         const bool sane = !__syncthreads_or(active && !(me.v * me.ch >= 0.0 && fabs(me.v * me.sh) <= 5.0));
@@ -1559,7 +1668,7 @@ __device__ __forceinline__ void block_policy_step(const StepParams &p, typename 
             // what vehicle ci reads from me: my target AFTER my act if I come before it in the list
             const int my_tgt_seen = (i < ci) ? me.tgt : tgt_old;
             bool blk = false;
-            if (active && i != ci && me.lane != Tc && my_tgt_seen == Tc) {
+            if (active && rival && i != ci && me.lane != Tc && my_tgt_seen == Tc) {
               const double d = me.x - xc;
               const double d_star = B::desired_gap(vc, cc, sc, me.v, me.ch, me.sh, TM::TIME_WANTED);
               blk = (0 < d) && (d < d_star);
@@ -1578,11 +1687,14 @@ __device__ __forceinline__ void block_policy_step(const StepParams &p, typename 
     double tb = 0.0, accel = 0.0;
     if (TM::LINEAR && drives) {
       tb = B::linear_tan_beta(p, bp[3], bp[4], me.y, me.h, me.v, me.tgt);
+    } else if (EG::DIRECT && controlled) {
+      // (the stored pair, clipped below: no lane keeping, no speed control)
     } else if (controlled || drives) {
       const double inv_v = fast_rcp(not_zero(me.v));
       tb = B::steer_tan_beta(p, me.y, me.h, inv_v, me.tgt);
     }
-    if (controlled) {
+    if (EG::DIRECT && controlled) {
+    } else if (controlled) {
       accel = HWY_KP_A * (me.ts - me.v);  // speed_control (controller.py:189-198), not clipped
     } else if (TM::LINEAR && drives) {
       const int g = f_own < 0 ? 0 : f_own;
@@ -1620,6 +1732,13 @@ __device__ __forceinline__ void block_policy_step(const StepParams &p, typename 
       }
       if (me.v > HWY_MAX_SPEED) accel = fmin(accel, 1.0 * (HWY_MAX_SPEED - me.v));
       else if (me.v < HWY_MIN_SPEED) accel = fmax(accel, 1.0 * (HWY_MIN_SPEED - me.v));
+      if constexpr (EG::DIRECT) {
+        if (controlled) {  // the same rule on the STORED pair, which keeps what it wrote
+          const EgoControls now = direct_clip_actions(*da, ctl_slot, ctl, me.v, crashed0);
+          tb = now.tb;
+          accel = now.accel;
+        }
+      }
       // beta = atan(tb):  cos(beta) = 1/sqrt(1+tb^2), sin(beta) = tb*cos(beta);
       // cos(h+beta), sin(h+beta) by angle addition against the cached cos(h), sin(h)
       const double cb = fast_rsqrt(1.0 + tb * tb), sb = tb * cb;
@@ -1633,7 +1752,8 @@ __device__ __forceinline__ void block_policy_step(const StepParams &p, typename 
         me.impx = me.impy = 0.0;
       }
       me.h += me.v * sb * (1.0 / (HWY_VEH_LENGTH / 2)) * p.dt;
-      me.v += accel * p.dt;
+      if (EG::DIRECT && controlled) me.v = direct_speed_update(me.v, accel, p.dt);
+      else me.v += accel * p.dt;
       me.lane = B::closest_lane(p, me.x, me.y, me.h);  // on_state_update
       sincos_bounded(me.h, &me.sh, &me.ch);
     }
@@ -1832,7 +1952,13 @@ __device__ __forceinline__ void block_policy_step(const StepParams &p, typename 
       publish<NW>(sh, me, active);
       __syncthreads();
     }
-    observe_env<NW>(p, sh, e, me, true, eo);
+    observe_env<NW, EG>(p, sh, e, me, true, eo);
+  }
+  if constexpr (EG::DIRECT) {
+    if (controlled) {
+      me.tgt = me.lane;  // (a plain Vehicle has no target lane: the slot mirrors its lane from step to step)
+      da->ctl_accel[ctl_slot] = ctl.accel;
+    }
   }
   me.rank = rank;  // the hint the next step verifies
   store_vehicle<NW>(p, e, me, false);
@@ -1870,6 +1996,23 @@ __global__ void __launch_bounds__(NW * 64, WPE) hwy_rollout_linear_kernel(const 
   for (int k = 0; k < lp.s.k_steps; ++k) {  // block-uniform
     HWY_RELOAD_STEP_PARAMS(pk, lp.s);  // (StepParams sits at offset 0 of LinearParams)
     block_policy_step<NW, LinearTraffic>(pk, sh, e, k * pk.num_envs + e, lp.la);
+    __syncthreads();
+  }
+}
+
+// Direct ego control (hwy_config.ego_control == HWY_EGO_DIRECT), IDM traffic, on the workgroup kernel: step and K-step forms.
+template <int NW, int WPE>
+__global__ void __launch_bounds__(NW * 64, WPE) hwy_step_direct_kernel(const DirectParams dp) {
+  __shared__ typename EnvBlock<NW>::Shared sh;
+  block_policy_step<NW, IdmTraffic, DirectEgo>(dp.s, sh, blockIdx.x, blockIdx.x, LinearArgs{}, &dp.da);
+}
+template <int NW, int WPE>
+__global__ void __launch_bounds__(NW * 64, WPE) hwy_rollout_direct_kernel(const DirectParams dp) {
+  __shared__ typename EnvBlock<NW>::Shared sh;
+  const int e = blockIdx.x;
+  for (int k = 0; k < dp.s.k_steps; ++k) {  // block-uniform
+    HWY_RELOAD_STEP_PARAMS(pk, dp.s);  // (StepParams sits at offset 0 of DirectParams)
+    block_policy_step<NW, IdmTraffic, DirectEgo>(pk, sh, e, k * pk.num_envs + e, LinearArgs{}, &dp.da);
     __syncthreads();
   }
 }

@@ -35,6 +35,7 @@ struct hwy_engine {
   // device state
   double *d_f64 = nullptr;   // 9 fields x E x pitch
   double *d_behavior = nullptr;  // HWY_TRAFFIC_LINEAR: HWY_BEHAVIOR_PARAMS planes x E x pitch (hwy_set_behavior)
+  double *d_controls = nullptr;  // HWY_EGO_DIRECT: stored acceleration | steering of every agent, 2 x E x A (hwy_set_controls)
   int32_t *d_packed = nullptr;
   long long *d_route = nullptr;     // intersection scenario: planned routes [E x pitch] (64-bit route words)
   int32_t *d_road_steps = nullptr;  // intersection scenario: RegulatedRoad.steps [E]
@@ -167,7 +168,7 @@ extern "C" const char *hwy_status_string(int status) {
     case HWY_ERR_HIP: return "HIP runtime error";
     case HWY_ERR_UNSUPPORTED: return "unsupported configuration";
     case HWY_ERR_NO_DEVICE: return "no MI355X / HIP device available (there is no CPU fallback)";
-    case HWY_ERR_ACTION: return "meta-action outside the configured action table";
+    case HWY_ERR_ACTION: return "action id outside the configured action table";
     default: return "unknown status";
   }
 }
@@ -213,6 +214,17 @@ static int validate(const hwy_config *c, std::string &why) {
     if (c->scenario != HWY_SCENARIO_HIGHWAY) BAD("the Linear traffic family runs on the highway scenario only");
     if (c->traffic_time_wanted != hwy::LinearTraffic::TIME_WANTED) BAD("traffic_time_wanted of the Linear family is 2.5");
     if (!(c->traffic_lc_min_acc_gain >= 0.0 && c->traffic_lc_min_acc_gain < 1e3)) BAD("traffic_lc_min_acc_gain out of range");
+  }
+  if (c->ego_control != HWY_EGO_META && c->ego_control != HWY_EGO_DIRECT) BAD("unknown ego_control %d", c->ego_control);
+  if (c->ego_control == HWY_EGO_DIRECT) {
+    if (c->scenario != HWY_SCENARIO_HIGHWAY) BAD("direct ego control runs on the highway scenario only");
+    if (c->traffic_model != HWY_TRAFFIC_IDM) BAD("direct ego control runs with IDM traffic only");
+    if (c->n_accel < 1 || c->n_accel > HWY_MAX_ACTIONS_PER_AXIS || c->n_steer < 1 || c->n_steer > HWY_MAX_ACTIONS_PER_AXIS)
+      BAD("n_accel and n_steer must be in [1,%d]", HWY_MAX_ACTIONS_PER_AXIS);
+    for (int k = 0; k < c->n_accel; ++k)
+      if (!(std::fabs(c->accel_axis[k]) < 1e6)) BAD("accel_axis[%d] must be finite", k);
+    for (int k = 0; k < c->n_steer; ++k)  // (tan_bounded covers +-pi/3, the reference's MAX_STEERING_ANGLE)
+      if (!(std::fabs(c->steer_axis[k]) <= HWY_PI / 3.0)) BAD("steer_axis[%d] must be within +-pi/3", k);
   }
   if (c->scenario == HWY_SCENARIO_INTERSECTION) {
     if (c->num_agents > 4) BAD("the intersection scenario holds 1..4 controlled vehicles (one per access road)");
@@ -271,6 +283,24 @@ static void fill_linear(const hwy_engine *eng, const StepParams &p, hwy::LinearP
   lp.la.plane = (long long)eng->cfg.num_envs * eng->pitch;
   lp.la.lc_gain = eng->cfg.traffic_lc_min_acc_gain;
 }
+static bool is_direct(const hwy_engine *eng) { return eng->cfg.ego_control == HWY_EGO_DIRECT; }
+static void fill_direct(const hwy_engine *eng, const StepParams &p, hwy::DirectParams &dp) {
+  std::memset(&dp, 0, sizeof dp);
+  dp.s = p;
+  dp.da.ctl_accel = eng->d_controls;
+  dp.da.ctl_steer = eng->d_controls + (size_t)eng->cfg.num_envs * eng->cfg.num_agents;
+  dp.da.n_accel = eng->cfg.n_accel;
+  dp.da.n_steer = eng->cfg.n_steer;
+  for (int k = 0; k < HWY_MAX_ACTIONS_PER_AXIS; ++k) {
+    dp.da.accel_axis[k] = eng->cfg.accel_axis[k];
+    dp.da.steer_axis[k] = eng->cfg.steer_axis[k];
+  }
+}
+// ids of the configured action table: [0, n)
+static int num_action_ids(const hwy_engine *eng) {
+  if (is_direct(eng)) return eng->cfg.n_accel * eng->cfg.n_steer;
+  return eng->cfg.scenario == HWY_SCENARIO_INTERSECTION ? 3 : HWY_NUM_ACTIONS(eng->cfg.action_set);
+}
 static bool is_net(const hwy_engine *eng) { return eng->cfg.scenario != HWY_SCENARIO_HIGHWAY && !is_ix(eng); }
 static void fill_ix(const hwy_engine *eng, const StepParams &p, hwy::IxParams &ip) {
   hwy::ix_params_from_config(eng->cfg, p, ip);
@@ -307,6 +337,12 @@ static hipError_t launch_step_any(const hwy_engine *eng, const StepParams &p) {
     return hwy::launch_step_linear(lp, eng->cfg.num_envs, eng->stream, eng->waves_per_eu, eng->force_block_kernel,
                                    eng->cfg.tune_extra_lds);
   }
+  if (is_direct(eng)) {
+    hwy::DirectParams dp;
+    fill_direct(eng, p, dp);
+    return hwy::launch_step_direct(dp, eng->cfg.num_envs, eng->stream, eng->waves_per_eu, eng->force_block_kernel,
+                                   eng->cfg.tune_extra_lds);
+  }
   return hwy::launch_step(p, eng->cfg.num_envs, eng->stream, eng->waves_per_eu, eng->force_block_kernel,
                           eng->cfg.tune_extra_lds);
 }
@@ -325,6 +361,11 @@ static hipError_t launch_reset_any(const hwy_engine *eng, const StepParams &p) {
     hwy::LinearParams lp;
     fill_linear(eng, p, lp);
     return hwy::launch_reset_linear(lp, eng->cfg.num_envs, eng->stream);
+  }
+  if (is_direct(eng)) {
+    hwy::DirectParams dp;
+    fill_direct(eng, p, dp);
+    return hwy::launch_reset_direct(dp, eng->cfg.num_envs, eng->stream);
   }
   return hwy::launch_reset(p, eng->cfg.num_envs, eng->stream);
 }
@@ -370,6 +411,8 @@ extern "C" int hwy_create(const hwy_config *cfg, int device, void *stream, hwy_e
   // the Linear traffic family: the one-wavefront kernel for N <= 64, the workgroup kernel beyond (hwy_wave2.h is IDM-only, so
   // 64 < N <= 128 takes the workgroup kernel and tune_block_kernel == 2 is the engine's own choice)
   if (cfg->traffic_model == HWY_TRAFFIC_LINEAR) eng->force_block_kernel = cfg->tune_block_kernel == 1 || cfg->num_vehicles > 64;
+  // direct ego control: likewise (hwy_wave2.h has no DirectEgo form)
+  if (cfg->ego_control == HWY_EGO_DIRECT) eng->force_block_kernel = cfg->tune_block_kernel == 1 || cfg->num_vehicles > 64;
   // road-network kernel: 128 VGPRs, 4 waves/SIMD, no spills.
   // intersection kernel with helper lanes (N <= 32, hwy_ix.h): 150 VGPRs, but 20.2 KB of LDS per one-wavefront workgroup keep it
   // at 2 per SIMD.  Without them (N > 32, or tune_ix_no_helpers): 128 VGPRs / 16.7 KB (2048 x 30: 371.9 us against 285.1)
@@ -414,6 +457,10 @@ extern "C" int hwy_create(const hwy_config *cfg, int device, void *stream, hwy_e
   if (cfg->traffic_model == HWY_TRAFFIC_LINEAR) {
     ALLOC(eng->d_behavior, plane * HWY_BEHAVIOR_PARAMS * sizeof(double));
     if ((e = hipMemsetAsync(eng->d_behavior, 0, plane * HWY_BEHAVIOR_PARAMS * sizeof(double), eng->stream)) != hipSuccess) return bail(e, "hipMemset");
+  }
+  if (cfg->ego_control == HWY_EGO_DIRECT) {
+    ALLOC(eng->d_controls, 2 * E * cfg->num_agents * sizeof(double));
+    if ((e = hipMemsetAsync(eng->d_controls, 0, 2 * E * cfg->num_agents * sizeof(double), eng->stream)) != hipSuccess) return bail(e, "hipMemset");
   }
   if (cfg->scenario == HWY_SCENARIO_INTERSECTION) {
     ALLOC(eng->d_route, plane * sizeof(long long));
@@ -484,7 +531,8 @@ extern "C" int hwy_create(const hwy_config *cfg, int device, void *stream, hwy_e
     StepParams probe;
     hwy::params_from_config(*cfg, eng->pitch, probe);
     int resident = 0;
-    if (cfg->traffic_model == HWY_TRAFFIC_LINEAR) resident = hwy::step_linear_resident_blocks(probe, eng->waves_per_eu, eng->force_block_kernel, cfg->tune_extra_lds);
+    if (cfg->ego_control == HWY_EGO_DIRECT) resident = hwy::step_direct_resident_blocks(probe, eng->waves_per_eu, eng->force_block_kernel, cfg->tune_extra_lds);
+    else if (cfg->traffic_model == HWY_TRAFFIC_LINEAR) resident = hwy::step_linear_resident_blocks(probe, eng->waves_per_eu, eng->force_block_kernel, cfg->tune_extra_lds);
     else if (cfg->scenario == HWY_SCENARIO_HIGHWAY) resident = hwy::step_resident_blocks(probe, eng->waves_per_eu, eng->force_block_kernel, cfg->tune_extra_lds);
     else if (cfg->scenario != HWY_SCENARIO_INTERSECTION) resident = hwy::net_step_resident_blocks(eng->waves_per_eu);
     // the turn that pays is about a sixth of a wavefront's lifetime, i.e. it grows with the frames of a policy step: 2^14 ticks
@@ -524,7 +572,7 @@ extern "C" int hwy_destroy(hwy_engine *eng) {
   void *ptrs[] = {eng->d_f64, eng->d_packed, eng->d_time, eng->d_done, eng->d_episode, eng->d_actions, eng->d_out, eng->d_roll,
                   eng->d_mask, eng->d_seeds, eng->d_grid_ws, eng->d_route, eng->d_road_steps, eng->d_gnet,
                   eng->d_shadow_f64, eng->d_shadow_packed, eng->d_shadow_route, eng->d_shadow_meta, eng->d_counters, eng->d_block_env,
-                  eng->d_behavior};
+                  eng->d_behavior, eng->d_controls};
   for (void *q : ptrs) if (q) (void)hipFree(q);
   if (eng->h_pinned) (void)hipHostFree(eng->h_pinned);
   if (eng->own_stream && eng->stream) (void)hipStreamDestroy(eng->stream);
@@ -694,6 +742,34 @@ extern "C" int hwy_get_behavior(hwy_engine *eng, double *params) {
   return HWY_OK;
 }
 
+// ---- stored controls of the agents (HWY_EGO_DIRECT) ---------------------------------------------------------
+extern "C" int hwy_set_controls(hwy_engine *eng, const double *acceleration, const double *steering) {
+  if (!eng || !acceleration || !steering) return HWY_ERR_INVALID_ARG;
+  if (!is_direct(eng)) return fail(eng, HWY_ERR_INVALID_ARG, "hwy_set_controls: the engine's controlled vehicles store no controls (ego_control is HWY_EGO_META)");
+  const size_t n = (size_t)eng->cfg.num_envs * eng->cfg.num_agents;
+  for (size_t k = 0; k < n; ++k)
+    if (!(std::fabs(steering[k]) <= HWY_PI / 3.0)) return fail(eng, HWY_ERR_INVALID_ARG, "hwy_set_controls: steering must be within +-pi/3");
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  std::vector<double> h(2 * n);
+  std::memcpy(h.data(), acceleration, n * sizeof(double));
+  std::memcpy(h.data() + n, steering, n * sizeof(double));
+  HWY_HIP(eng, hipMemcpyAsync(eng->d_controls, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, eng->stream));
+  HWY_HIP(eng, hipStreamSynchronize(eng->stream));
+  return HWY_OK;
+}
+extern "C" int hwy_get_controls(hwy_engine *eng, double *acceleration, double *steering) {
+  if (!eng || !acceleration || !steering) return HWY_ERR_INVALID_ARG;
+  if (!is_direct(eng)) return fail(eng, HWY_ERR_INVALID_ARG, "hwy_get_controls: the engine's controlled vehicles store no controls (ego_control is HWY_EGO_META)");
+  const size_t n = (size_t)eng->cfg.num_envs * eng->cfg.num_agents;
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  std::vector<double> h(2 * n);
+  HWY_HIP(eng, hipMemcpyAsync(h.data(), eng->d_controls, h.size() * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+  HWY_HIP(eng, hipStreamSynchronize(eng->stream));
+  std::memcpy(acceleration, h.data(), n * sizeof(double));
+  std::memcpy(steering, h.data() + n, n * sizeof(double));
+  return HWY_OK;
+}
+
 // ---- kernel timing ----------------------------------------------------------------------------------
 static hipError_t launch_step_any(const hwy_engine *eng, const StepParams &p);
 static int timed_launch(hwy_engine *eng, const StepParams &p) {
@@ -804,6 +880,16 @@ extern "C" int hwy_rollout_device(hwy_engine *eng, int32_t k_steps, const int32_
   p.full_step = 1;
   p.actions = d_actions; p.obs = d_obs; p.reward = d_reward; p.terminated = d_terminated; p.truncated = d_truncated;
   p.info_speed = d_info_speed; p.info_crashed = d_info_crashed;
+  if (is_direct(eng)) {  // straight road, direct ego control: K steps in ONE launch (one-wavefront or workgroup kernel)
+    p.k_steps = k_steps;
+    p.num_envs = eng->cfg.num_envs;
+    hwy::DirectParams dp;
+    fill_direct(eng, p, dp);
+    HWY_HIP(eng, hwy::launch_rollout_direct(dp, eng->cfg.num_envs, eng->stream,
+                                            eng->force_block_kernel ? eng->waves_per_eu : eng->rollout_waves_per_eu,
+                                            eng->force_block_kernel, eng->cfg.tune_extra_lds));
+    return HWY_OK;
+  }
   if (is_linear(eng)) {  // straight road, Linear traffic: K steps in ONE launch (one-wavefront or workgroup kernel)
     p.k_steps = k_steps;
     p.num_envs = eng->cfg.num_envs;
@@ -850,9 +936,9 @@ extern "C" int hwy_rollout(hwy_engine *eng, int32_t k_steps, const int32_t *acti
   size_t n_act, n_obs, n_ea;
   io_counts(eng->cfg, &n_act, &n_obs, &n_ea);
   const size_t E = eng->cfg.num_envs, K = (size_t)k_steps;
-  const int max_action = is_ix(eng) ? 2 : HWY_NUM_ACTIONS(eng->cfg.action_set) - 1;
-  for (size_t k = 0; k < K * n_act; ++k)  // the reference's KeyError, before anything is simulated (action.py:260)
-    if (actions[k] < 0 || actions[k] > max_action) return fail(eng, HWY_ERR_ACTION, "meta-action out of range");
+  const int max_action = num_action_ids(eng) - 1;
+  for (size_t k = 0; k < K * n_act; ++k)  // the reference's KeyError / IndexError, before anything is simulated (action.py:260,195)
+    if (actions[k] < 0 || actions[k] > max_action) return fail(eng, HWY_ERR_ACTION, "action id out of range");
   HWY_HIP(eng, hipSetDevice(eng->device));
   auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   const size_t o_act = 0, o_rew = up(K * n_act * 4), o_spd = o_rew + up(K * n_ea * 8), o_obs = o_spd + up(K * n_ea * 8),
@@ -890,9 +976,10 @@ extern "C" int hwy_step(hwy_engine *eng, const int32_t *actions, float *obs, dou
   io_counts(eng->cfg, &n_act, &n_obs, &n_ea);
   const size_t E = eng->cfg.num_envs;
   // the reference raises KeyError for an unknown meta-action before touching the simulation (action.py:260)
-  const int max_action = is_ix(eng) ? 2 : HWY_NUM_ACTIONS(eng->cfg.action_set) - 1;  // IntersectionEnv.ACTIONS has 3 entries (intersection_env.py:14)
+  const int max_action = num_action_ids(eng) - 1;  // IntersectionEnv.ACTIONS has 3 entries (intersection_env.py:14)
   for (size_t k = 0; k < n_act; ++k)
-    if (actions[k] < 0 || actions[k] > max_action) return fail(eng, HWY_ERR_ACTION, max_action == 2 ? "meta-action outside [0,3)" : "meta-action outside [0,5)");
+    if (actions[k] < 0 || actions[k] > max_action)
+      return fail(eng, HWY_ERR_ACTION, is_direct(eng) ? "action id outside the throttle x steering table" : max_action == 2 ? "meta-action outside [0,3)" : "meta-action outside [0,5)");
   HWY_HIP(eng, hipSetDevice(eng->device));
   // pinned layout: [mirror of the device output block][actions]
   char *h_out = (char *)eng->h_pinned;
@@ -925,7 +1012,7 @@ extern "C" int hwy_step_frames(hwy_engine *eng, const int32_t *actions, int32_t 
   p.autoreset = 0;
   if (actions) {
     for (size_t k = 0; k < n_act; ++k)
-      if (actions[k] < 0 || actions[k] > (is_ix(eng) ? 2 : HWY_NUM_ACTIONS(eng->cfg.action_set) - 1)) return fail(eng, HWY_ERR_ACTION, "meta-action out of range");
+      if (actions[k] < 0 || actions[k] >= num_action_ids(eng)) return fail(eng, HWY_ERR_ACTION, "action id out of range");
     std::memcpy(eng->h_pinned, actions, n_act * 4);
     HWY_HIP(eng, hipMemcpyAsync(eng->d_actions, eng->h_pinned, n_act * 4, hipMemcpyHostToDevice, eng->stream));
     p.actions = eng->d_actions;

@@ -31,6 +31,15 @@ hipError_t launch_rollout_linear(const LinearParams &lp, int num_envs, hipStream
                                  int extra_lds);  // lp.s.k_steps steps per launch
 hipError_t launch_reset_linear(const LinearParams &lp, int num_envs, hipStream_t stream);
 int step_linear_resident_blocks(const StepParams &p, int waves_per_eu, bool force_block_kernel, int extra_lds);
+// direct ego control (hwy_config.ego_control == HWY_EGO_DIRECT, hwy_kernels_direct.hip): the one-wavefront kernel for N <= 64 (unless
+// force_block_kernel), the workgroup kernel otherwise -- 64 < N <= 128 included (hwy_wave2.h has no DirectEgo form)
+bool wave_direct_applies(const StepParams &p, bool force_block_kernel);
+hipError_t launch_step_direct(const DirectParams &dp, int num_envs, hipStream_t stream, int waves_per_eu, bool force_block_kernel,
+                              int extra_lds);
+hipError_t launch_rollout_direct(const DirectParams &dp, int num_envs, hipStream_t stream, int waves_per_eu, bool force_block_kernel,
+                                 int extra_lds);  // dp.s.k_steps steps per launch
+hipError_t launch_reset_direct(const DirectParams &dp, int num_envs, hipStream_t stream);
+int step_direct_resident_blocks(const StepParams &p, int waves_per_eu, bool force_block_kernel, int extra_lds);
 // road-network scenarios (hwy_net.h): one wavefront per environment
 hipError_t launch_net_step(const NetParams &np, int num_envs, hipStream_t stream, int waves_per_eu);
 hipError_t launch_net_rollout(const NetParams &np, int num_envs, hipStream_t stream, int waves_per_eu);  // np.s.k_steps steps per launch

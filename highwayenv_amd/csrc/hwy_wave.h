@@ -183,7 +183,8 @@ __device__ inline void wave_update_rank(double x, bool active, int N, int &rank,
 // multi-step launch (hwy_rollout_device).
 // env_time: the environment's clock at the start of the step (requested with the state by the caller: a load here, at the end of
 // the wavefront's life, is a round trip nothing hides); only read when write_reward is set
-template <bool BY_RANK>
+// EG: the ego control (hwy_device.h: ego_reward_lane)
+template <bool BY_RANK, typename EG = MetaEgo>
 __device__ inline void observe_wave(const StepParams &p, int e, int eo, const Veh &me, bool write_reward, int rank = 0,
                                     double env_time = 0.0) {
   typedef EnvBlock<1> B;
@@ -284,7 +285,7 @@ __device__ inline void observe_wave(const StepParams &p, int e, int eo, const Ve
       const int nl = p.L - 1 > 1 ? p.L - 1 : 1;
       double reward = 0.0;
       reward = reward + p.collision_reward * (crashed ? 1.0 : 0.0);
-      reward = reward + p.right_lane_reward * ((double)me.tgt / (double)nl);
+      reward = reward + p.right_lane_reward * ((double)ego_reward_lane<EG>(me) / (double)nl);
       reward = reward + p.high_speed_reward * clipd(scaled_speed, 0.0, 1.0);
       reward = reward + 0.0 * (on_road ? 1.0 : 0.0);
       if (p.flags & HWY_C_NORMALIZE_REWARD)
@@ -312,9 +313,10 @@ __device__ inline void observe_wave(const StepParams &p, int e, int eo, const Ve
 // highway-fast-v0 style configs (HWY_C_EGO_ONLY_COLLISIONS), where it keeps the frame loop at 173 VGPRs.
 // One policy step of environment e by its wavefront; eo = row of the action / output planes (see observe_wave).
 // TM: the traffic model (hwy_device.h: IdmTraffic / LinearTraffic, compile time); la: the Linear family's parameters (unused by IDM).
-template <bool FULL_SCAN, typename TM = IdmTraffic>
+// EG: the ego control (hwy_device.h: MetaEgo / DirectEgo, compile time); da: the direct-control arguments (DirectEgo only).
+template <bool FULL_SCAN, typename TM = IdmTraffic, typename EG = MetaEgo>
 __device__ __forceinline__ void wave_policy_step(const StepParams &p, WaveShared &sh, const int e, const int eo,
-                                                 const LinearArgs &la = LinearArgs{}) {
+                                                 const LinearArgs &la = LinearArgs{}, const DirectArgs *da = nullptr) {
   typedef EnvBlock<1> B;
   const int i = threadIdx.x;
   const int N = p.N;
@@ -328,6 +330,19 @@ __device__ __forceinline__ void wave_policy_step(const StepParams &p, WaveShared
   int done_flag = p.autoreset ? (int)p.st.done[e] : 0;
   double env_time = p.st.time[e];
   int act_lane = (p.actions && i < p.A) ? p.actions[(size_t)eo * p.A + i] : HWY_IDLE;
+  // DirectEgo: the stored controls of agent a, fetched by lane a with the actions (Vehicle.action as the previous launch left it),
+  // and the two axis tables, entry j by lanes j and 16 + j -- requested with everything else, so that the action's table entry
+  // is a lane exchange away when the action arrives instead of a dependent load
+  double ctl_accel_lane = 0.0, ctl_steer_lane = 0.0, axis_lane = 0.0;
+  if constexpr (EG::DIRECT) {
+    if (i < p.A) {
+      ctl_accel_lane = da->ctl_accel[(size_t)e * p.A + i];
+      ctl_steer_lane = da->ctl_steer[(size_t)e * p.A + i];
+    }
+    static_assert(2 * HWY_MAX_ACTIONS_PER_AXIS <= 64, "one lane per table entry");
+    if (i < 2 * HWY_MAX_ACTIONS_PER_AXIS)
+      axis_lane = i < HWY_MAX_ACTIONS_PER_AXIS ? da->accel_axis[i] : da->steer_axis[i - HWY_MAX_ACTIONS_PER_AXIS];
+  }
   Veh me;
   load_vehicle<1>(p, e, me);
   HWY_ISSUED_TOGETHER(done_flag, env_time, act_lane, me.x, me.timer);  // (keeps the requests above the branch)
@@ -347,6 +362,7 @@ __device__ __forceinline__ void wave_policy_step(const StepParams &p, WaveShared
           p.reward[(size_t)eo * p.A + a] = 0.0;
           if (p.info_speed) p.info_speed[(size_t)eo * p.A + a] = me.v;
           if (p.info_crashed) p.info_crashed[(size_t)eo * p.A + a] = 0;
+          if constexpr (EG::DIRECT) da->ctl_accel[(size_t)e * p.A + a] = da->ctl_steer[(size_t)e * p.A + a] = 0.0;  // Vehicle.__init__
         }
     }
     if (i == 0) {
@@ -373,9 +389,30 @@ __device__ __forceinline__ void wave_policy_step(const StepParams &p, WaveShared
     }
   }
   int agent = 0, act0 = HWY_IDLE;
+  EgoControls ctl = {0.0, 0.0};  // DirectEgo: Vehicle.action of my (controlled) vehicle: what the previous launch left, or this step's action
+  double stored_accel = 0.0, stored_steer = 0.0;
   for (int a = 0; a < p.A; ++a) {  // wave-uniform
     const int act_a = wave_bcast_i(act_lane, a);
-    if (controlled && p.agent_index[a] == i) { agent = a; act0 = HWY_ACTION_TO_ALL(p.action_set, act_a); }
+    if constexpr (EG::DIRECT) {  // (the DiscreteAction id itself: direct_act looks it up in frame 0)
+      const double ca = wave_bcast(ctl_accel_lane, a), cs = wave_bcast(ctl_steer_lane, a);
+      if (controlled && p.agent_index[a] == i) { agent = a; act0 = act_a; stored_accel = ca; stored_steer = cs; }
+    } else {
+      if (controlled && p.agent_index[a] == i) { agent = a; act0 = HWY_ACTION_TO_ALL(p.action_set, act_a); }
+    }
+  }
+  if constexpr (EG::DIRECT) {
+    // DiscreteAction.act -> Vehicle.act(dict) (action.py:189-196) on the first frame: the table entry from the lanes that hold it
+    // (every lane takes part in the exchange)
+    const bool acted = controlled && p.actions && p.n_frames > 0 && direct_id_in_table(*da, act0);
+    const int ia = acted ? act0 / da->n_steer : 0, is = acted ? act0 - ia * da->n_steer : 0;
+    const int lo = __double2loint(axis_lane), hi = __double2hiint(axis_lane);
+    const double act_accel = __hiloint2double(__builtin_amdgcn_ds_bpermute(ia << 2, hi), __builtin_amdgcn_ds_bpermute(ia << 2, lo));
+    const int js = (HWY_MAX_ACTIONS_PER_AXIS + is) << 2;
+    const double act_steer = __hiloint2double(__builtin_amdgcn_ds_bpermute(js, hi), __builtin_amdgcn_ds_bpermute(js, lo));
+    if (controlled) {
+      ctl = direct_begin_step(*da, (size_t)e * p.A + agent, stored_accel, stored_steer, acted, act_accel, act_steer);
+      me.ts = direct_ego_target_speed(me.v);  // (the ego has no target speed: what a MOBIL caller reads for it)
+    }
   }
   sh.timer[i] = me.timer; sh.ts[i] = me.ts; sh.delta[i] = me.delta; sh.impx[i] = me.impx; sh.impy[i] = me.impy;
   const bool i_check = (me.flags & HWY_F_CHECK_COLLISIONS) != 0;
@@ -390,7 +427,7 @@ __device__ __forceinline__ void wave_policy_step(const StepParams &p, WaveShared
   for (int fr = 0; fr < p.n_frames; ++fr) {
     wave_turn(turn);
     // ---- A. meta-action (abstract.py:294-304 -> controller.py:295-315) ------------------------------
-    if (fr == 0 && p.actions && controlled) {
+    if (!EG::DIRECT && fr == 0 && p.actions && controlled) {  // (DirectEgo: direct_begin_step above)
       const int act = act0;
       if (act == HWY_FASTER || act == HWY_SLOWER) {
         const double xs = (me.v - p.target_speeds[0]) / (p.target_speeds[p.n_ts - 1] - p.target_speeds[0]);
@@ -631,14 +668,16 @@ __device__ __forceinline__ void wave_policy_step(const StepParams &p, WaveShared
     //    (unique: a link depends on earlier links only).
     {
       const u64 cm = __ballot(changer);
+      // (DirectEgo: the ego is no ControlledVehicle -- behavior.py:237 skips it -- so it is never a rival: not a mover, not in a row)
+      const bool rival = !(EG::DIRECT && controlled);
       // with a single vehicle on its way to another lane (the changer itself) no link can block
-      if (cm && __popcll(__ballot(active && (me.lane != tgt_old || me.lane != me.tgt))) > 1) {  // wave-uniform
+      if (cm && __popcll(__ballot(active && rival && (me.lane != tgt_old || me.lane != me.tgt))) > 1) {  // wave-uniform
         int *const sbits = reinterpret_cast<int *>(sh.nx);  // (the post-integration bodies only live inside section G)
         HWY_WAVE_LDS_FENCE();  // the masks' readers of this frame and section G of the previous one are done
         if (i < p.L + 2) sh.lane_mask[i] = 0;
         HWY_WAVE_LDS_FENCE();
         sbits[rank] = ((me.tgt != tgt_old) ? 1 : 0) | (changer ? 2 : 0);
-        if (active && me.lane != me.tgt)
+        if (active && rival && me.lane != me.tgt)
           __hip_atomic_fetch_or(&sh.lane_mask[me.tgt + 1], (u64)1 << rank, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         const bool sane = __ballot(active && !(me.v * me.ch >= 0.0 && fabs(me.v * me.sh) <= 5.0)) == 0;
         HWY_WAVE_LDS_FENCE();
@@ -714,7 +753,7 @@ __device__ __forceinline__ void wave_policy_step(const StepParams &p, WaveShared
     }
     }
     accel = clipd(accel, -HWY_ACC_MAX, HWY_ACC_MAX);
-    accel = controlled ? HWY_KP_A * (sh.ts[i] - me.v) : accel;  // speed_control (controller.py:189-198), not clipped
+    if constexpr (!EG::DIRECT) accel = controlled ? HWY_KP_A * (sh.ts[i] - me.v) : accel;  // speed_control (controller.py:189-198), not clipped
 
     // ---- F. Road.step: integrate -------------------------------------------------------------------------
     const double x_old = me.x;
@@ -724,6 +763,13 @@ __device__ __forceinline__ void wave_policy_step(const StepParams &p, WaveShared
       accel = crashed0 ? -1.0 * me.v : accel;
       accel = (me.v > HWY_MAX_SPEED) ? fmin(accel, 1.0 * (HWY_MAX_SPEED - me.v))
                                      : ((me.v < HWY_MIN_SPEED) ? fmax(accel, 1.0 * (HWY_MIN_SPEED - me.v)) : accel);
+      if constexpr (EG::DIRECT) {
+        if (controlled) {  // the same rule on the STORED pair, which keeps what it wrote (no lane keeping, no speed control)
+          const EgoControls now = direct_clip_actions(*da, (size_t)e * p.A + agent, ctl, me.v, crashed0);
+          tb = now.tb;
+          accel = now.accel;
+        }
+      }
       const double cb = fast_rsqrt(1.0 + tb * tb), sb = tb * cb;
       const double vx = me.v * (me.ch * cb - me.sh * sb), vy = me.v * (me.sh * cb + me.ch * sb);
       me.x += vx * p.dt;
@@ -735,7 +781,8 @@ __device__ __forceinline__ void wave_policy_step(const StepParams &p, WaveShared
         sh.impx[i] = sh.impy[i] = 0.0;
       }
       me.h += me.v * sb * (1.0 / (HWY_VEH_LENGTH / 2)) * p.dt;
-      me.v += accel * p.dt;
+      if (EG::DIRECT && controlled) me.v = direct_speed_update(me.v, accel, p.dt);
+      else me.v += accel * p.dt;
       me.lane = B::closest_lane(p, me.x, me.y, me.h);
       sincos_bounded(me.h, &me.sh, &me.ch);
     }
@@ -891,7 +938,13 @@ __device__ __forceinline__ void wave_policy_step(const StepParams &p, WaveShared
   HWY_RELOAD_PARAMS(q, p);
   if (q.full_step) wave_update_rank(me.x, active, N, rank, has_tie);  // positions moved in the last frame
   // (state stores before or after the observation: 40.8 / 40.6 us, within the noise -- profiles/r05_history.md)
-  if (q.full_step) observe_wave<true>(q, e, eo, me, true, rank, env_time);
+  if (q.full_step) observe_wave<true, EG>(q, e, eo, me, true, rank, env_time);
+  if constexpr (EG::DIRECT) {
+    if (controlled) {
+      me.tgt = me.lane;  // (a plain Vehicle has no target lane: the slot mirrors its lane from step to step)
+      da->ctl_accel[(size_t)e * q.A + agent] = ctl.accel;
+    }
+  }
   me.rank = rank;
   me.timer = sh.timer[i]; me.ts = sh.ts[i]; me.delta = sh.delta[i]; me.impx = sh.impx[i]; me.impy = sh.impy[i];
   store_vehicle<1>(q, e, me, false);
@@ -945,6 +998,28 @@ __global__ void __launch_bounds__(64, WPE) hwy_rollout_wave_linear_kernel(const 
   for (int k = 0; k < lp.s.k_steps; ++k) {  // wave-uniform
     HWY_RELOAD_PARAMS(pk, lp.s);
     wave_policy_step<FULL_SCAN, LinearTraffic>(pk, sh, e, k * pk.num_envs + e, lp.la);
+    HWY_WAVE_LDS_FENCE();
+    __threadfence_block();
+  }
+}
+
+// Direct ego control (hwy_config.ego_control == HWY_EGO_DIRECT), IDM traffic, N <= 64: the same step with the DirectEgo policy
+// (instantiated in hwy_kernels_direct.hip).  StepParams sits at offset 0 of DirectParams, so HWY_RELOAD_PARAMS reads the same segment.
+template <int WPE, bool FULL_SCAN>
+__global__ void __launch_bounds__(64, WPE) hwy_step_wave_direct_kernel(const DirectParams dp) {
+  __shared__ WaveShared sh;
+  HWY_KERNARG_TOUCH(StepParams);
+  const int e = dp.s.block_env ? (int)dp.s.block_env[blockIdx.x] : (int)blockIdx.x;
+  wave_policy_step<FULL_SCAN, IdmTraffic, DirectEgo>(dp.s, sh, e, e, LinearArgs{}, &dp.da);
+}
+template <int WPE, bool FULL_SCAN>
+__global__ void __launch_bounds__(64, WPE) hwy_rollout_wave_direct_kernel(const DirectParams dp) {
+  __shared__ WaveShared sh;
+  HWY_KERNARG_TOUCH(StepParams);
+  const int e = blockIdx.x;
+  for (int k = 0; k < dp.s.k_steps; ++k) {  // wave-uniform
+    HWY_RELOAD_PARAMS(pk, dp.s);
+    wave_policy_step<FULL_SCAN, IdmTraffic, DirectEgo>(pk, sh, e, k * pk.num_envs + e, LinearArgs{}, &dp.da);
     HWY_WAVE_LDS_FENCE();
     __threadfence_block();
   }

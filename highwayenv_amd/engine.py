@@ -47,7 +47,10 @@ class Engine:
 
     def _check(self, rc: int):
         if rc == _abi.HWY_ERR_ACTION:
-            # the reference raises KeyError from self.actions[int(action)] (envs/common/action.py:260)
+            # the reference raises KeyError from self.actions[int(action)] (envs/common/action.py:260), and IndexError from
+            # all_actions[action] of a DiscreteAction (action.py:195; a negative id, which Python would wrap, is rejected too)
+            if self.cfg.ego_control == _abi.EGO_DIRECT:
+                raise IndexError(self._lib.hwy_last_error(self._h).decode())
             raise KeyError(self._lib.hwy_last_error(self._h).decode())
         if rc != 0:
             raise EngineError(f"{self._lib.hwy_status_string(rc).decode()}: {self._lib.hwy_last_error(self._h).decode()}")
@@ -96,6 +99,21 @@ class Engine:
         out = np.empty((self.E, self.N, _abi.HWY_BEHAVIOR_PARAMS), np.float64)
         self._check(self._lib.hwy_get_behavior(self._h, _ptr(out)))
         return out
+
+    def set_controls(self, acceleration, steering):
+        """hwy_set_controls: the (acceleration, steering) pair stored on every controlled vehicle of a direct-control engine
+        (``Vehicle.action``), [E, A] each."""
+        a = np.ascontiguousarray(acceleration, dtype=np.float64)
+        s = np.ascontiguousarray(steering, dtype=np.float64)
+        if a.shape != (self.E, self.A) or s.shape != (self.E, self.A):
+            raise ValueError(f"set_controls: shapes {a.shape}, {s.shape}, this engine needs {(self.E, self.A)}")
+        self._check(self._lib.hwy_set_controls(self._h, _ptr(a), _ptr(s)))
+
+    def get_controls(self):
+        """(acceleration, steering) [E, A]: the acceleration is what ``Vehicle.clip_actions`` left in the stored action."""
+        a, s = np.empty((self.E, self.A), np.float64), np.empty((self.E, self.A), np.float64)
+        self._check(self._lib.hwy_get_controls(self._h, _ptr(a), _ptr(s)))
+        return a, s
 
     # -- stepping -----------------------------------------------------------------------------
     def step(self, actions):

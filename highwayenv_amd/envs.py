@@ -67,7 +67,7 @@ class _Box:
 class VehicleView:
     """Read-only view of one vehicle of one env (reference: Vehicle / ControlledVehicle attributes)."""
 
-    def __init__(self, st, e, i, behavior=None):
+    def __init__(self, st, e, i, behavior=None, direct=False):
         self.position = np.array([st["x"][e, i], st["y"][e, i]])
         self.heading = float(st["heading"][e, i])
         self.speed = float(st["speed"][e, i])
@@ -84,6 +84,8 @@ class VehicleView:
         if behavior is not None and not self.controlled:  # LinearVehicle family (behavior.py:353-416)
             self.ACCELERATION_PARAMETERS = np.array(behavior[e, i, :3])
             self.STEERING_PARAMETERS = np.array(behavior[e, i, 3:])
+        if direct and self.controlled:  # DiscreteAction: a plain Vehicle (action.py:132-134) has no target lane / speed / index
+            del self.target_lane_index, self.target_speed, self.speed_index
 
     @property
     def velocity(self):
@@ -91,8 +93,8 @@ class VehicleView:
 
 
 class RoadView:
-    def __init__(self, st, e, behavior=None):
-        self.vehicles = [VehicleView(st, e, i, behavior) for i in range(st["x"].shape[1])]
+    def __init__(self, st, e, behavior=None, direct=False):
+        self.vehicles = [VehicleView(st, e, i, behavior, direct) for i in range(st["x"].shape[1])]
         self.objects = []
 
 
@@ -272,7 +274,8 @@ class BatchedHighwayEnv:
             acts = acts.reshape(E, A)
         else:
             raise ValueError(f"action must be a scalar, shape ({E},) or shape ({E}, {A}); got {acts.shape}")
-        obs, reward, term, trunc, info = self._engine.step(acts.astype(np.int32))  # KeyError on bad action id
+        # a bad action id: KeyError (DiscreteMetaAction, action.py:260) / IndexError (DiscreteAction, action.py:195)
+        obs, reward, term, trunc, info = self._engine.step(acts.astype(np.int32))
         self.time += 1 / self.config["policy_frequency"]
         self.steps += self._hcfg.frames_per_step
         out_info = {"speed": info["speed"][:, 0], "crashed": info["crashed"][:, 0], "action": acts if A > 1 else acts[:, 0]}
@@ -306,7 +309,7 @@ class BatchedHighwayEnv:
 
     def road(self, env_index: int = 0) -> RoadView:
         behavior = self._engine.get_behavior() if self._hcfg.traffic_model == _abi.TRAFFIC_LINEAR else None
-        return RoadView(self._engine.get_state(), env_index, behavior)
+        return RoadView(self._engine.get_state(), env_index, behavior, self._hcfg.ego_control == _abi.EGO_DIRECT)
 
     def rewards(self, env_index: int = 0) -> dict:
         """HighwayEnv._rewards (highway_env.py:122-139) of one env, from the device state."""
@@ -314,6 +317,8 @@ class BatchedHighwayEnv:
         c, i = self._hcfg, self._hcfg.agent_index[0]
         x, y, h, v = (st[k][env_index, i] for k in ("x", "y", "heading", "speed"))
         lane, tgt = int(st["lane"][env_index, i]), int(st["target_lane"][env_index, i])
+        if c.ego_control == _abi.EGO_DIRECT:  # a plain Vehicle: lane_index[2] (highway_env.py:122-126)
+            tgt = lane
         fs = v * np.cos(h)
         r0, r1 = self.config["reward_speed_range"]
         scaled = 0 + (fs - r0) * (1 - 0) / (r1 - r0)

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define HWY_ABI_VERSION 6
+#define HWY_ABI_VERSION 7
 
 #define HWY_MAX_AGENTS 16
 #define HWY_MAX_FEATURES 16
@@ -46,6 +46,7 @@ extern "C" {
 #define HWY_MAX_VEHICLES 256
 #define HWY_MAX_GRID_CELLS 65536
 #define HWY_MAX_GLANES 24  /* lanes of a general (any direction / circular) road network: HWY_SCENARIO_INTERSECTION */
+#define HWY_MAX_ACTIONS_PER_AXIS 16 /* DiscreteAction(actions_per_axis): points per axis of the throttle x steering table */
 #define HWY_MAX_ROUTE 11   /* remaining roads of a planned route kept per vehicle (64-bit route word, 5 bits per road) */
 
 typedef enum hwy_status {
@@ -54,7 +55,8 @@ typedef enum hwy_status {
   HWY_ERR_HIP = -2,
   HWY_ERR_UNSUPPORTED = -3,
   HWY_ERR_NO_DEVICE = -4,
-  HWY_ERR_ACTION = -5 /* meta-action outside the configured table: the reference raises KeyError (action.py:260) */
+  HWY_ERR_ACTION = -5 /* action id outside the configured table: the reference raises KeyError (DiscreteMetaAction,
+                         action.py:260) or IndexError (DiscreteAction, action.py:195) */
 } hwy_status;
 
 /* per-vehicle flag bits (hwy_state.flags) */
@@ -120,6 +122,16 @@ enum {
                              only in LANE_CHANGE_MIN_ACC_GAIN (hwy_config.traffic_lc_min_acc_gain) */
 };
 #define HWY_BEHAVIOR_PARAMS 5 /* per vehicle: ACCELERATION_PARAMETERS[3], STEERING_PARAMETERS[2] (behavior.py:406-416) */
+
+/* ego control (hwy_config.ego_control): what an action id means to a controlled vehicle.  HWY_SCENARIO_HIGHWAY with
+ * HWY_TRAFFIC_IDM only takes HWY_EGO_DIRECT. */
+enum {
+  HWY_EGO_META = 0,  /* DiscreteMetaAction (action.py:199-284): the ego is an MDPVehicle, ids index hwy_config.action_set */
+  HWY_EGO_DIRECT = 1 /* DiscreteAction (action.py:165-196), the quantised ContinuousAction: the ego is a plain Vehicle
+                        (kinematics.py) -- no target lane, no target speed, no controller -- and id a means acceleration
+                        accel_axis[a / n_steer] and steering angle steer_axis[a % n_steer], stored on the vehicle and clipped
+                        there frame by frame (Vehicle.clip_actions, kinematics.py:155-168: hwy_set_controls) */
+};
 
 /* observation types (hwy_config.obs_type) */
 enum { HWY_OBS_KINEMATICS = 0, HWY_OBS_OCCUPANCY_GRID = 1 };
@@ -296,6 +308,16 @@ typedef struct hwy_config {
                                           Defensive (behavior.py:45,563,575) */
   double traffic_time_wanted;          /* TIME_WANTED of the traffic class: 1.5 IDM, 2.5 the Linear family (behavior.py:34,387);
                                           must be the model's own constant (the kernels compile it in) */
+  /* Ego control (ABI v7) */
+  int32_t ego_control;                 /* HWY_EGO_* */
+  int32_t n_accel, n_steer;            /* HWY_EGO_DIRECT: points on the throttle / steering axis, 1..HWY_MAX_ACTIONS_PER_AXIS each
+                                          (1 = the axis is not controlled: its one value is the integer 0 of action.py:147-156);
+                                          action ids run over [0, n_accel * n_steer), throttle major like
+                                          itertools.product(*axes) (action.py:193-194) */
+  int32_t reserved5;
+  double accel_axis[HWY_MAX_ACTIONS_PER_AXIS]; /* PHYSICAL values [m/s^2] / [rad]: the host evaluates the reference's own float32 */
+  double steer_axis[HWY_MAX_ACTIONS_PER_AXIS]; /* expressions (linspace of the Box bounds, clip, utils.lmap) and widens the results,
+                                                  so the kernels do no float32 arithmetic; |steer_axis| <= pi / 3 */
 } hwy_config;
 
 /*
@@ -367,7 +389,7 @@ int hwy_reset(hwy_engine *eng, const uint8_t *mask, const uint64_t *seeds, doubl
  * One batched policy step == AbstractEnv.step for every environment:
  * T x { action_type.act (first frame); road.act(); road.step(dt) } + observe +
  * reward + terminated + truncated + info{speed,crashed}.
- *   actions    int32 [E][A]   in   DiscreteMetaAction ids
+ *   actions    int32 [E][A]   in   DiscreteMetaAction ids (HWY_EGO_DIRECT: DiscreteAction ids)
  *   obs        f32   [E][A][V][F]
  *   reward     f64   [E][A]   (single-agent envs: the reference's scalar reward)
  *   terminated u8    [E]
@@ -381,7 +403,9 @@ int hwy_reset(hwy_engine *eng, const uint8_t *mask, const uint64_t *seeds, doubl
  * and does not synchronise -- the path for on-GPU policies, RCCL gathers and
  * the benchmark's HBM-resident timing.  It does NOT validate the action ids
  * (hwy_step does: HWY_ERR_ACTION): an id outside the configured table acts as
- * IDLE (HWY_ACTION_TO_ALL), where the reference raises KeyError.
+ * IDLE (HWY_ACTION_TO_ALL), where the reference raises KeyError.  HWY_EGO_DIRECT: an id outside [0, n_accel * n_steer)
+ * leaves the vehicle's stored controls as they are (hwy_step: HWY_ERR_ACTION, the reference's IndexError -- also for a
+ * negative id, which Python's list lookup would wrap).
  */
 int hwy_step(hwy_engine *eng, const int32_t *actions, float *obs, double *reward,
              uint8_t *terminated, uint8_t *truncated, double *info_speed, uint8_t *info_crashed);
@@ -424,6 +448,17 @@ int hwy_step_frames(hwy_engine *eng, const int32_t *actions, int32_t n_frames);
  */
 int hwy_set_behavior(hwy_engine *eng, const double *params);
 int hwy_get_behavior(hwy_engine *eng, double *params);
+
+/*
+ * The controls stored on the controlled vehicles of a HWY_EGO_DIRECT engine (Vehicle.action, kinematics.py:120-127): the
+ * acceleration AFTER Vehicle.clip_actions wrote into it (kinematics.py:155-168: beyond +-MAX_SPEED the stored value becomes
+ * min / max(a, bound - speed) and STAYS so for the rest of the policy step; crashed: -1.0 * speed, steering 0) and the steering
+ * angle, host arrays f64 [E][A].  They outlive a frame: hwy_step_frames(actions = NULL) continues with them, an action replaces
+ * them on the first frame of a step.  Zero after hwy_reset and after an auto-reset (Vehicle.__init__).  Synchronous.
+ * HWY_ERR_INVALID_ARG on a HWY_EGO_META engine.
+ */
+int hwy_set_controls(hwy_engine *eng, const double *acceleration, const double *steering);
+int hwy_get_controls(hwy_engine *eng, double *acceleration, double *steering);
 
 /* KinematicObservation.observe for the current state (host pointer out). */
 int hwy_observe(hwy_engine *eng, float *obs);
