@@ -146,9 +146,25 @@ def build_engine_asan(force: bool = False, verbose: bool = False) -> str:
     return ASAN_LIB_PATH
 
 
+def gfx950_code_objects(blob: bytes) -> list:
+    """Every gfx950 code object (ELF) of every offload bundle in a host object or library: one bundle per kernel translation unit."""
+    import struct
+    magic, out = b"__CLANG_OFFLOAD_BUNDLE__", []  # hipcc's fat binary: magic[24], u64 n, n x (u64 offset, u64 size, u64 len, triple)
+    o = blob.find(magic)
+    while o >= 0:
+        n, q = struct.unpack_from("<Q", blob, o + 24)[0], o + 32
+        for _ in range(n):
+            off, size, tl = struct.unpack_from("<QQQ", blob, q)
+            if b"gfx950" in blob[q + 24:q + 24 + tl] and blob[o + off:o + off + 4] == b"\x7fELF":
+                out.append(blob[o + off:o + off + size])
+            q += 24 + tl
+        o = blob.find(magic, o + 1)
+    return out
+
+
 def kernel_resources(lib_path: str = LIB_PATH) -> dict:
-    """What the compiler allocated to every kernel of the gfx950 code object inside the built library, read from the code
-    object's own metadata (NT_AMDGPU_METADATA note: the numbers the hardware dispatcher uses), keyed by demangled kernel name
+    """What the compiler allocated to every kernel of the gfx950 code objects inside the built library, read from the code
+    objects' own metadata (NT_AMDGPU_METADATA note: the numbers the hardware dispatcher uses), keyed by demangled kernel name
     without the argument list: ``{"hwy::hwy_step_wave_kernel<3, false>": {"vgpr": 102, "vgpr_spill": 0, "sgpr": 106,
     "sgpr_spill": 76, "lds": 8080, "scratch": 36, "workgroup": 64}, ...}``.  Needs no GPU.  Used by tests/test_kernel_resources.py
     (the occupancy DESIGN.md quotes for each step kernel is a property of the build, checked where the build is checked) and
@@ -157,39 +173,36 @@ def kernel_resources(lib_path: str = LIB_PATH) -> dict:
     import struct
     import msgpack  # (build / test time only)
     blob = open(lib_path, "rb").read()
-    o = blob.index(b"__CLANG_OFFLOAD_BUNDLE__")  # hipcc's fat binary: magic[24], u64 n, n x (u64 offset, u64 size, u64 len, triple)
-    n, q, co = struct.unpack_from("<Q", blob, o + 24)[0], o + 32, None
-    for _ in range(n):
-        off, size, tl = struct.unpack_from("<QQQ", blob, q)
-        if b"gfx950" in blob[q + 24:q + 24 + tl]:
-            co = blob[o + off:o + off + size]
-        q += 24 + tl
-    if co is None or co[:4] != b"\x7fELF":
+    objects = gfx950_code_objects(blob)
+    if not objects:
         raise RuntimeError(f"{lib_path}: no gfx950 code object in the offload bundle")
-    shoff = struct.unpack_from("<Q", co, 0x28)[0]
-    shentsize, shnum = struct.unpack_from("<HH", co, 0x3A)
-    meta = None
-    for i in range(shnum):
-        sh = struct.unpack_from("<IIQQQQIIQQ", co, shoff + i * shentsize)
-        if sh[1] != 7:  # SHT_NOTE
-            continue
-        d, k = co[sh[4]:sh[4] + sh[5]], 0
-        while k < len(d):
-            nsz, dsz, ty = struct.unpack_from("<III", d, k)
-            k += 12 + ((nsz + 3) & ~3)
-            if ty == 32:  # NT_AMDGPU_METADATA (msgpack)
-                meta = msgpack.unpackb(d[k:k + dsz], raw=False)
-            k += (dsz + 3) & ~3
-    if meta is None:
-        raise RuntimeError(f"{lib_path}: the gfx950 code object carries no AMDGPU metadata note")
-    kernels = meta["amdhsa.kernels"]
-    names = subprocess.run(["c++filt"] + [k[".name"] for k in kernels], capture_output=True, text=True, check=True).stdout.split("\n")
     out = {}
-    for k, name in zip(kernels, names):
-        out[re.sub(r"\(.*\)$", "", name).replace("void ", "")] = {
-            "vgpr": k[".vgpr_count"], "vgpr_spill": k[".vgpr_spill_count"], "sgpr": k[".sgpr_count"],
-            "sgpr_spill": k[".sgpr_spill_count"], "lds": k[".group_segment_fixed_size"],
-            "scratch": k[".private_segment_fixed_size"], "workgroup": k[".max_flat_workgroup_size"]}
+    for co in objects:
+        shoff = struct.unpack_from("<Q", co, 0x28)[0]
+        shentsize, shnum = struct.unpack_from("<HH", co, 0x3A)
+        meta = None
+        for i in range(shnum):
+            sh = struct.unpack_from("<IIQQQQIIQQ", co, shoff + i * shentsize)
+            if sh[1] != 7:  # SHT_NOTE
+                continue
+            d, k = co[sh[4]:sh[4] + sh[5]], 0
+            while k < len(d):
+                nsz, dsz, ty = struct.unpack_from("<III", d, k)
+                k += 12 + ((nsz + 3) & ~3)
+                if ty == 32:  # NT_AMDGPU_METADATA (msgpack)
+                    meta = msgpack.unpackb(d[k:k + dsz], raw=False)
+                k += (dsz + 3) & ~3
+        if meta is None:
+            raise RuntimeError(f"{lib_path}: a gfx950 code object carries no AMDGPU metadata note")
+        kernels = meta.get("amdhsa.kernels", [])
+        if not kernels:  # (a host-only translation unit)
+            continue
+        names = subprocess.run(["c++filt"] + [k[".name"] for k in kernels], capture_output=True, text=True, check=True).stdout.split("\n")
+        for k, name in zip(kernels, names):
+            out[re.sub(r"\(.*\)$", "", name).replace("void ", "")] = {
+                "vgpr": k[".vgpr_count"], "vgpr_spill": k[".vgpr_spill_count"], "sgpr": k[".sgpr_count"],
+                "sgpr_spill": k[".sgpr_spill_count"], "lds": k[".group_segment_fixed_size"],
+                "scratch": k[".private_segment_fixed_size"], "workgroup": k[".max_flat_workgroup_size"]}
     return out
 
 

@@ -320,67 +320,44 @@ static hipError_t invalidate_shadows(hwy_engine *eng) {
   if (!eng->d_shadow_meta) return hipSuccess;
   return hipMemsetAsync(eng->d_shadow_meta, 0xff, (size_t)eng->cfg.num_envs * 4 * sizeof(int32_t), eng->stream);
 }
-static hipError_t launch_step_any(const hwy_engine *eng, const StepParams &p) {
+// THE place that knows the kernel families: builds the parameter struct of the engine's family around p (intersection: IxParams,
+// road network: NetParams, Linear traffic: LinearParams, direct ego control: DirectParams, else p itself: IDM with meta-actions) and
+// hands it to fn, which calls the overload of hwy_launch.h it wants.
+template <typename Fn>
+static auto with_family(const hwy_engine *eng, const StepParams &p, Fn &&fn) {
   if (is_ix(eng)) {
     hwy::IxParams ip;
     fill_ix(eng, p, ip);
-    return hwy::launch_ix_step(ip, eng->cfg.num_envs, eng->stream, eng->waves_per_eu);
+    return fn(ip);
   }
   if (is_net(eng)) {
     hwy::NetParams np;
     hwy::net_params_from_config(eng->cfg, p, np);
-    return hwy::launch_net_step(np, eng->cfg.num_envs, eng->stream, eng->waves_per_eu);
+    return fn(np);
   }
   if (is_linear(eng)) {
     hwy::LinearParams lp;
     fill_linear(eng, p, lp);
-    return hwy::launch_step_linear(lp, eng->cfg.num_envs, eng->stream, eng->waves_per_eu, eng->force_block_kernel,
-                                   eng->cfg.tune_extra_lds);
+    return fn(lp);
   }
   if (is_direct(eng)) {
     hwy::DirectParams dp;
     fill_direct(eng, p, dp);
-    return hwy::launch_step_direct(dp, eng->cfg.num_envs, eng->stream, eng->waves_per_eu, eng->force_block_kernel,
-                                   eng->cfg.tune_extra_lds);
+    return fn(dp);
   }
-  return hwy::launch_step(p, eng->cfg.num_envs, eng->stream, eng->waves_per_eu, eng->force_block_kernel,
-                          eng->cfg.tune_extra_lds);
+  return fn(p);
+}
+static hwy::Launch launch_of(const hwy_engine *eng) {
+  return {eng->cfg.num_envs, eng->stream, eng->waves_per_eu, eng->rollout_waves_per_eu, eng->force_block_kernel, eng->cfg.tune_extra_lds};
+}
+static hipError_t launch_step_any(const hwy_engine *eng, const StepParams &p) {
+  return with_family(eng, p, [&](const auto &a) { return hwy::launch_step(a, launch_of(eng)); });
 }
 static hipError_t launch_reset_any(const hwy_engine *eng, const StepParams &p) {
-  if (is_ix(eng)) {
-    hwy::IxParams ip;
-    fill_ix(eng, p, ip);
-    return hwy::launch_ix_reset(ip, eng->cfg.num_envs, eng->stream);
-  }
-  if (is_net(eng)) {
-    hwy::NetParams np;
-    hwy::net_params_from_config(eng->cfg, p, np);
-    return hwy::launch_net_reset(np, eng->cfg.num_envs, eng->stream);
-  }
-  if (is_linear(eng)) {
-    hwy::LinearParams lp;
-    fill_linear(eng, p, lp);
-    return hwy::launch_reset_linear(lp, eng->cfg.num_envs, eng->stream);
-  }
-  if (is_direct(eng)) {
-    hwy::DirectParams dp;
-    fill_direct(eng, p, dp);
-    return hwy::launch_reset_direct(dp, eng->cfg.num_envs, eng->stream);
-  }
-  return hwy::launch_reset(p, eng->cfg.num_envs, eng->stream);
+  return with_family(eng, p, [&](const auto &a) { return hwy::launch_reset(a, launch_of(eng)); });
 }
 static hipError_t launch_observe_any(const hwy_engine *eng, const StepParams &p) {
-  if (is_ix(eng)) {
-    hwy::IxParams ip;
-    fill_ix(eng, p, ip);
-    return hwy::launch_ix_observe(ip, eng->cfg.num_envs, eng->stream);
-  }
-  if (is_net(eng)) {
-    hwy::NetParams np;
-    hwy::net_params_from_config(eng->cfg, p, np);
-    return hwy::launch_net_observe(np, eng->cfg.num_envs, eng->stream);
-  }
-  return hwy::launch_observe(p, eng->cfg.num_envs, eng->stream);
+  return with_family(eng, p, [&](const auto &a) { return hwy::launch_observe(a, launch_of(eng)); });
 }
 
 static size_t io_counts(const hwy_config &c, size_t *n_act, size_t *n_obs, size_t *n_ea) {
@@ -408,11 +385,10 @@ extern "C" int hwy_create(const hwy_config *cfg, int device, void *stream, hwy_e
   // per thread are one 338 / 442-VGPR wavefront per SIMD and measured slower there (1024 x 201: 312 us against 240,
   // profiles/r05_history.md); 1 = the workgroup kernel wherever it exists; 2 = the wide kernel wherever it exists (N <= 256)
   eng->force_block_kernel = cfg->tune_block_kernel == 1 || (cfg->tune_block_kernel == 0 && cfg->num_vehicles > 128);
-  // the Linear traffic family: the one-wavefront kernel for N <= 64, the workgroup kernel beyond (hwy_wave2.h is IDM-only, so
-  // 64 < N <= 128 takes the workgroup kernel and tune_block_kernel == 2 is the engine's own choice)
-  if (cfg->traffic_model == HWY_TRAFFIC_LINEAR) eng->force_block_kernel = cfg->tune_block_kernel == 1 || cfg->num_vehicles > 64;
-  // direct ego control: likewise (hwy_wave2.h has no DirectEgo form)
-  if (cfg->ego_control == HWY_EGO_DIRECT) eng->force_block_kernel = cfg->tune_block_kernel == 1 || cfg->num_vehicles > 64;
+  // the families without a wide kernel (hwy_wave2.h is IDM with meta-actions only: Linear traffic, direct ego control): the
+  // one-wavefront kernel for N <= 64, the workgroup kernel beyond, and tune_block_kernel == 2 is the engine's own choice
+  if (cfg->traffic_model == HWY_TRAFFIC_LINEAR || cfg->ego_control == HWY_EGO_DIRECT)
+    eng->force_block_kernel = cfg->tune_block_kernel == 1 || cfg->num_vehicles > 64;
   // road-network kernel: 128 VGPRs, 4 waves/SIMD, no spills.
   // intersection kernel with helper lanes (N <= 32, hwy_ix.h): 150 VGPRs, but 20.2 KB of LDS per one-wavefront workgroup keep it
   // at 2 per SIMD.  Without them (N > 32, or tune_ix_no_helpers): 128 VGPRs / 16.7 KB (2048 x 30: 371.9 us against 285.1)
@@ -530,11 +506,7 @@ extern "C" int hwy_create(const hwy_config *cfg, int device, void *stream, hwy_e
   else if (cfg->tune_prio_shift == 0) {
     StepParams probe;
     hwy::params_from_config(*cfg, eng->pitch, probe);
-    int resident = 0;
-    if (cfg->ego_control == HWY_EGO_DIRECT) resident = hwy::step_direct_resident_blocks(probe, eng->waves_per_eu, eng->force_block_kernel, cfg->tune_extra_lds);
-    else if (cfg->traffic_model == HWY_TRAFFIC_LINEAR) resident = hwy::step_linear_resident_blocks(probe, eng->waves_per_eu, eng->force_block_kernel, cfg->tune_extra_lds);
-    else if (cfg->scenario == HWY_SCENARIO_HIGHWAY) resident = hwy::step_resident_blocks(probe, eng->waves_per_eu, eng->force_block_kernel, cfg->tune_extra_lds);
-    else if (cfg->scenario != HWY_SCENARIO_INTERSECTION) resident = hwy::net_step_resident_blocks(eng->waves_per_eu);
+    const int resident = with_family(eng, probe, [&](const auto &a) { return hwy::step_resident_blocks(a, launch_of(eng)); });
     // the turn that pays is about a sixth of a wavefront's lifetime, i.e. it grows with the frames of a policy step: 2^14 ticks
     // for the 5 frames of highway-fast-v0 (13: 47.0 us, 14: 44.96, 15: 47.7), 2^16 for the 15 frames of highway-v0 (14: 134.3
     // us, 15 / 16: 133.3) and of the merge scenarios (config 5: 14: 313.8, 16 / 17: 296.0, 18: 314.8; merge-v0: 14: 178.2,
@@ -880,48 +852,11 @@ extern "C" int hwy_rollout_device(hwy_engine *eng, int32_t k_steps, const int32_
   p.full_step = 1;
   p.actions = d_actions; p.obs = d_obs; p.reward = d_reward; p.terminated = d_terminated; p.truncated = d_truncated;
   p.info_speed = d_info_speed; p.info_crashed = d_info_crashed;
-  if (is_direct(eng)) {  // straight road, direct ego control: K steps in ONE launch (one-wavefront or workgroup kernel)
-    p.k_steps = k_steps;
-    p.num_envs = eng->cfg.num_envs;
-    hwy::DirectParams dp;
-    fill_direct(eng, p, dp);
-    HWY_HIP(eng, hwy::launch_rollout_direct(dp, eng->cfg.num_envs, eng->stream,
-                                            eng->force_block_kernel ? eng->waves_per_eu : eng->rollout_waves_per_eu,
-                                            eng->force_block_kernel, eng->cfg.tune_extra_lds));
-    return HWY_OK;
-  }
-  if (is_linear(eng)) {  // straight road, Linear traffic: K steps in ONE launch (one-wavefront or workgroup kernel)
-    p.k_steps = k_steps;
-    p.num_envs = eng->cfg.num_envs;
-    hwy::LinearParams lp;
-    fill_linear(eng, p, lp);
-    HWY_HIP(eng, hwy::launch_rollout_linear(lp, eng->cfg.num_envs, eng->stream,
-                                            eng->force_block_kernel ? eng->waves_per_eu : eng->rollout_waves_per_eu,
-                                            eng->force_block_kernel, eng->cfg.tune_extra_lds));
-    return HWY_OK;
-  }
-  if (!is_ix(eng) && !is_net(eng)) {  // straight road: K steps in ONE launch
-    p.k_steps = k_steps;
-    p.num_envs = eng->cfg.num_envs;
-    HWY_HIP(eng, hwy::launch_rollout(p, eng->cfg.num_envs, eng->stream, eng->rollout_waves_per_eu, eng->cfg.tune_extra_lds,
-                                     eng->force_block_kernel, eng->waves_per_eu));
-    return HWY_OK;
-  }
-  if (is_net(eng)) {  // the merge kernel has the multi-step form too
-    p.k_steps = k_steps;
-    p.num_envs = eng->cfg.num_envs;
-    hwy::NetParams np;
-    hwy::net_params_from_config(eng->cfg, p, np);
-    HWY_HIP(eng, hwy::launch_net_rollout(np, eng->cfg.num_envs, eng->stream, eng->waves_per_eu));
-    return HWY_OK;
-  }
-  // the intersection kernel: STEP blocks only (no shadow is advanced during the launch; an environment that ends in it warms its
-  // next episode up inline -- WHEN the warm-up frames are computed cannot change a result)
+  // K steps in ONE launch, every family.  The intersection kernel: STEP blocks only (no shadow is advanced during the launch; an
+  // environment that ends in it warms its next episode up inline -- WHEN the warm-up frames are computed cannot change a result)
   p.k_steps = k_steps;
   p.num_envs = eng->cfg.num_envs;
-  hwy::IxParams ip;
-  fill_ix(eng, p, ip);
-  HWY_HIP(eng, hwy::launch_ix_rollout(ip, eng->cfg.num_envs, eng->stream, eng->waves_per_eu));
+  HWY_HIP(eng, with_family(eng, p, [&](const auto &a) { return hwy::launch_rollout(a, launch_of(eng)); }));
   return HWY_OK;
 }
 

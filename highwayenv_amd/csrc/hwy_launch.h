@@ -1,4 +1,5 @@
-// hwy_launch.h -- host-visible launch functions of the kernels in hwy_kernels.hip.
+// hwy_launch.h -- host-visible launch functions of the kernels in hwy_kernels.hip, hwy_kernels_linear.hip and
+// hwy_kernels_direct.hip: one overload per kernel family, chosen by the type of its parameter struct.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,45 +10,50 @@
 namespace hwy {
 // the events the launches of THIS THREAD record their dispatch begin / end timestamps into (nullptr, nullptr = none)
 void set_launch_events(hipEvent_t start, hipEvent_t stop);
-hipError_t launch_step(const StepParams &p, int num_envs, hipStream_t stream, int waves_per_eu, bool force_block_kernel,
-                       int extra_lds);
-// true where launch_step / launch_rollout run the two-vehicles-per-thread one-wavefront kernel of hwy_wave2.h
-bool wide_kernel_applies(const StepParams &p, bool force_block_kernel);
-// p.k_steps policy steps per launch (hwy_rollout_device): one-wavefront kernel (waves_per_eu, extra_lds) or workgroup kernel
-hipError_t launch_rollout(const StepParams &p, int num_envs, hipStream_t stream, int waves_per_eu, int extra_lds,
-                          bool force_block_kernel, int block_waves_per_eu);
+// what the engine decides about a launch, whatever the family.  waves_per_eu: the register-allocation variant of the step kernel;
+// rollout_waves_per_eu: that of the ONE-WAVEFRONT rollout kernel of the straight-road families (their workgroup rollout kernel
+// takes waves_per_eu, the wide kernel has one variant per size); force_block_kernel / extra_lds: hwy_config.tune_block_kernel /
+// tune_extra_lds as resolved by hwy_create (straight-road families only)
+struct Launch {
+  int num_envs;
+  hipStream_t stream;
+  int waves_per_eu, rollout_waves_per_eu;
+  bool force_block_kernel;
+  int extra_lds;
+};
+// Straight road, IDM traffic and meta-actions (hwy_kernels.hip): the one-wavefront kernel for N <= 64, the wide kernel of hwy_wave2.h
+// for 64 < N <= 256 with the Kinematics observation, the workgroup kernel otherwise or when forced.
+// The Linear traffic family (hwy_config.traffic_model == HWY_TRAFFIC_LINEAR, hwy_kernels_linear.hip) and direct ego control
+// (hwy_config.ego_control == HWY_EGO_DIRECT, hwy_kernels_direct.hip): the one-wavefront kernel for N <= 64 (unless
+// force_block_kernel), the workgroup kernel otherwise -- hwy_wave2.h is IDM-only and has no DirectEgo form.
+// Road-network scenarios (hwy_net.h) and the intersection scenario (hwy_ix.h): one wavefront per environment.
+hipError_t launch_step(const StepParams &p, const Launch &l);
+hipError_t launch_step(const LinearParams &lp, const Launch &l);
+hipError_t launch_step(const DirectParams &dp, const Launch &l);
+hipError_t launch_step(const NetParams &np, const Launch &l);
+hipError_t launch_step(const IxParams &ip, const Launch &l);
+// s.k_steps policy steps per launch (hwy_rollout_device)
+hipError_t launch_rollout(const StepParams &p, const Launch &l);
+hipError_t launch_rollout(const LinearParams &lp, const Launch &l);
+hipError_t launch_rollout(const DirectParams &dp, const Launch &l);
+hipError_t launch_rollout(const NetParams &np, const Launch &l);
+hipError_t launch_rollout(const IxParams &ip, const Launch &l);
+hipError_t launch_reset(const StepParams &p, const Launch &l);
+hipError_t launch_reset(const LinearParams &lp, const Launch &l);
+hipError_t launch_reset(const DirectParams &dp, const Launch &l);
+hipError_t launch_reset(const NetParams &np, const Launch &l);
+hipError_t launch_reset(const IxParams &ip, const Launch &l);
+// (the observation of a straight road does not depend on the traffic model or the ego control)
+hipError_t launch_observe(const StepParams &p, const Launch &l);
+inline hipError_t launch_observe(const LinearParams &lp, const Launch &l) { return launch_observe(lp.s, l); }
+inline hipError_t launch_observe(const DirectParams &dp, const Launch &l) { return launch_observe(dp.s, l); }
+hipError_t launch_observe(const NetParams &np, const Launch &l);
+hipError_t launch_observe(const IxParams &ip, const Launch &l);
 // workgroups of the step kernel the device holds at once (0 = unknown / not applicable)
-int step_resident_blocks(const StepParams &p, int waves_per_eu, bool force_block_kernel, int extra_lds);
-int net_step_resident_blocks(int waves_per_eu);
-hipError_t launch_reset(const StepParams &p, int num_envs, hipStream_t stream);
+int step_resident_blocks(const StepParams &p, const Launch &l);
+int step_resident_blocks(const LinearParams &lp, const Launch &l);
+int step_resident_blocks(const DirectParams &dp, const Launch &l);
+int step_resident_blocks(const NetParams &np, const Launch &l);
+inline int step_resident_blocks(const IxParams &, const Launch &) { return 0; }
 hipError_t launch_math_probe(int op, const double *in, double *out, long long n, hipStream_t stream);
-hipError_t launch_observe(const StepParams &p, int num_envs, hipStream_t stream);
-// the Linear traffic family (hwy_config.traffic_model == HWY_TRAFFIC_LINEAR): the one-wavefront kernel for N <= 64 (unless
-// force_block_kernel), the workgroup kernel otherwise -- 64 < N <= 128 included (hwy_wave2.h is IDM-only)
-bool wave_linear_applies(const StepParams &p, bool force_block_kernel);
-hipError_t launch_step_linear(const LinearParams &lp, int num_envs, hipStream_t stream, int waves_per_eu, bool force_block_kernel,
-                              int extra_lds);
-hipError_t launch_rollout_linear(const LinearParams &lp, int num_envs, hipStream_t stream, int waves_per_eu, bool force_block_kernel,
-                                 int extra_lds);  // lp.s.k_steps steps per launch
-hipError_t launch_reset_linear(const LinearParams &lp, int num_envs, hipStream_t stream);
-int step_linear_resident_blocks(const StepParams &p, int waves_per_eu, bool force_block_kernel, int extra_lds);
-// direct ego control (hwy_config.ego_control == HWY_EGO_DIRECT, hwy_kernels_direct.hip): the one-wavefront kernel for N <= 64 (unless
-// force_block_kernel), the workgroup kernel otherwise -- 64 < N <= 128 included (hwy_wave2.h has no DirectEgo form)
-bool wave_direct_applies(const StepParams &p, bool force_block_kernel);
-hipError_t launch_step_direct(const DirectParams &dp, int num_envs, hipStream_t stream, int waves_per_eu, bool force_block_kernel,
-                              int extra_lds);
-hipError_t launch_rollout_direct(const DirectParams &dp, int num_envs, hipStream_t stream, int waves_per_eu, bool force_block_kernel,
-                                 int extra_lds);  // dp.s.k_steps steps per launch
-hipError_t launch_reset_direct(const DirectParams &dp, int num_envs, hipStream_t stream);
-int step_direct_resident_blocks(const StepParams &p, int waves_per_eu, bool force_block_kernel, int extra_lds);
-// road-network scenarios (hwy_net.h): one wavefront per environment
-hipError_t launch_net_step(const NetParams &np, int num_envs, hipStream_t stream, int waves_per_eu);
-hipError_t launch_net_rollout(const NetParams &np, int num_envs, hipStream_t stream, int waves_per_eu);  // np.s.k_steps steps per launch
-hipError_t launch_net_reset(const NetParams &np, int num_envs, hipStream_t stream);
-hipError_t launch_net_observe(const NetParams &np, int num_envs, hipStream_t stream);
-// intersection scenario (hwy_ix.h): one wavefront per environment
-hipError_t launch_ix_step(const IxParams &ip, int num_envs, hipStream_t stream, int waves_per_eu);
-hipError_t launch_ix_rollout(const IxParams &ip, int num_envs, hipStream_t stream, int waves_per_eu);  // ip.s.k_steps steps per launch
-hipError_t launch_ix_reset(const IxParams &ip, int num_envs, hipStream_t stream);
-hipError_t launch_ix_observe(const IxParams &ip, int num_envs, hipStream_t stream);
 }  // namespace hwy

@@ -47,7 +47,7 @@ def compile_emulator(src_cpp: str, out_lib: str, extra=()) -> None:
 def build(force: bool = False) -> str:
     if os.environ.get("HWY_EMU_LIB"):  # a prebuilt (mutated) emulator: tests/test_mutations.py
         return os.environ["HWY_EMU_LIB"]
-    srcs = [os.path.join(_HERE, "emu_engine.cpp"), os.path.join(_HERE, "hip_emu.h"),
+    srcs = [os.path.join(_HERE, "emu_engine.cpp"), os.path.join(_HERE, "emu_straight.h"), os.path.join(_HERE, "hip_emu.h"),
             os.path.join(_ROOT, "highwayenv_amd", "csrc", "hwy_device.h"),
             os.path.join(_ROOT, "highwayenv_amd", "csrc", "hwy_wave.h"),
             os.path.join(_ROOT, "highwayenv_amd", "csrc", "hwy_wave2.h"),
@@ -123,6 +123,109 @@ class Scheduled:
                 self._errors += n
             L.emu_set_schedule(C.c_int(0), C.c_uint64(0))
             L.emu_clear_schedule_errors()
+
+
+class StraightFamilyEngine(Scheduled):
+    """What the drivers of the straight-road families beside IDM with meta-actions share (emu_traffic.py, emu_control.py: one C++
+    driver each over emu_straight.h, one extra array each).  A subclass names SOURCE (its .cpp), SYMBOL (prefix of its C symbols),
+    ENV (environment variable naming a prebuilt, mutated library; None = none), EXTRA (attribute holding its extra array, in the
+    device layout) and BAD_ACTION (exception type, message: what step raises for an action id outside the table)."""
+    SOURCE = SYMBOL = ENV = EXTRA = BAD_ACTION = None
+    _lib = None
+
+    @classmethod
+    def build(cls, force: bool = False) -> str:
+        if cls.ENV and os.environ.get(cls.ENV):
+            return os.environ[cls.ENV]
+        out = os.path.join(_HERE, "_build", f"libhwy_{cls.SYMBOL}.so")
+        csrc = os.path.join(_ROOT, "highwayenv_amd", "csrc")
+        srcs = [os.path.join(_HERE, f) for f in (cls.SOURCE, "emu_straight.h", "hip_emu.h")] + [
+            os.path.join(csrc, f) for f in ("hwy_device.h", "hwy_wave.h", "hwy_math.h", "hwy_params.h")] + [
+            os.path.join(_ROOT, "include", "hwy_engine.h")]
+        if force or not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(s) for s in srcs):
+            os.makedirs(os.path.dirname(out), exist_ok=True)
+            compile_emulator(srcs[0], out)
+        return out
+
+    @classmethod
+    def lib(cls):
+        if cls.__dict__.get("_lib") is None:
+            cls._lib = C.CDLL(cls.build())
+            size = getattr(cls._lib, cls.SYMBOL + "_config_size")
+            size.restype = C.c_size_t
+            assert size() == C.sizeof(_abi.HwyConfig)
+        return cls._lib
+
+    def __init__(self, cfg: _abi.HwyConfig):
+        self.cfg = cfg
+        self.E, self.N, self.A = cfg.num_envs, cfg.num_vehicles, cfg.num_agents
+        self.st = _abi.alloc_state(self.E, self.N)
+        self.done = np.zeros(self.E, np.uint8)
+        self.episode = np.zeros(self.E, np.uint32)
+        self.autoreset = (0, 0, 2.0, 1.0, -1)
+
+    def close(self):
+        pass
+
+    def set_state(self, st):
+        self.st = {k: np.array(st[k], copy=True) for k in _abi.STATE_F64 + _abi.STATE_I32 + ["time"]}
+        self.done[:] = 0
+
+    def get_state(self):
+        return _abi.copy_state(self.st)
+
+    def set_autoreset(self, enabled, base_seed=0, ego_spacing=2.0, vehicles_density=1.0, initial_lane_id=-1):
+        self.autoreset = (int(enabled), int(base_seed), float(ego_spacing), float(vehicles_density), int(initial_lane_id))
+
+    def _call(self, name, s, *args):
+        L = self.lib()
+        rc = self._scheduled(L, lambda: getattr(L, f"{self.SYMBOL}_{name}")(
+            C.byref(self.cfg), C.byref(s), _p(getattr(self, self.EXTRA), C.c_double), _p(self.done, C.c_uint8),
+            _p(self.episode, C.c_uint32), *args))
+        assert rc == 0
+
+    def _run(self, mode, n_frames, actions, k_steps=0):
+        E, A = self.E, self.A
+        K = max(k_steps, 1)
+        acts = None if actions is None else np.ascontiguousarray(np.asarray(actions, np.int32).reshape(K, E, A))
+        obs = np.zeros((K, E, A, *_abi.obs_shape(self.cfg)), np.float32)
+        reward = np.zeros((K, E, A))
+        term, trunc = np.zeros((K, E), np.uint8), np.zeros((K, E), np.uint8)
+        speed, crashed = np.zeros((K, E, A)), np.zeros((K, E, A), np.uint8)
+        ar = self.autoreset
+        self._call("run", _abi.state_struct(self.st),
+                   C.c_int(mode), C.c_int(n_frames), C.c_int(k_steps), _p(acts, C.c_int32), _p(obs, C.c_float), _p(reward, C.c_double),
+                   _p(term, C.c_uint8), _p(trunc, C.c_uint8), _p(speed, C.c_double), _p(crashed, C.c_uint8), C.c_int(ar[0]),
+                   C.c_uint64(ar[1]), C.c_double(ar[2]), C.c_double(ar[3]), C.c_int(ar[4]))
+        info = {"speed": speed, "crashed": (crashed & 1).astype(bool)}
+        return obs, reward, term.astype(bool), trunc.astype(bool), info
+
+    def step(self, actions):
+        a = np.asarray(actions)
+        if ((a < 0) | (a > _abi.num_actions(self.cfg) - 1)).any():
+            raise self.BAD_ACTION[0](self.BAD_ACTION[1])
+        obs, reward, term, trunc, info = self._run(1, self.cfg.frames_per_step, actions)
+        return obs[0], reward[0], term[0], trunc[0], {k: v[0] for k, v in info.items()}
+
+    def rollout(self, actions):
+        """hwy_rollout_device: actions [K, E, A] -> outputs with a leading K axis, ONE multi-step launch."""
+        K = np.asarray(actions).reshape(-1, self.E, self.A).shape[0]
+        return self._run(1, self.cfg.frames_per_step, actions, k_steps=K)
+
+    def step_frames(self, actions, n_frames):
+        self._run(0, n_frames, actions)
+
+    def observe(self):
+        return self._run(2, 0, None)[0][0]
+
+    def reset(self, seeds=None, mask=None, ego_spacing=2.0, vehicles_density=1.0, initial_lane_id=-1, base_seed=0):
+        obs = np.zeros((self.E, self.A, *_abi.obs_shape(self.cfg)), np.float32)
+        sd = None if seeds is None else np.ascontiguousarray(seeds, np.uint64)
+        mk = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        self._call("reset", _abi.state_struct(self.st),
+                   _p(mk, C.c_uint8), _p(sd, C.c_uint64), C.c_uint64(base_seed), C.c_double(ego_spacing), C.c_double(vehicles_density),
+                   C.c_int(initial_lane_id), _p(obs, C.c_float))
+        return obs
 
 
 class EmuEngine(Scheduled):

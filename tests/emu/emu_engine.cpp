@@ -30,42 +30,34 @@ inline double noisy(double v) {
 #include "../../highwayenv_amd/csrc/hwy_ix.h"
 #include "../../highwayenv_amd/csrc/hwy_params.h"
 
+#include "emu_straight.h"
+
+using emu_straight::fill_step_params;
+using emu_straight::HostImage;
+using emu_straight::ResetArgs;
+using emu_straight::Which;
+using emu_straight::OBSERVE; using emu_straight::RESET; using emu_straight::ROLLOUT; using emu_straight::STEP;
 using hwy::StepParams;
 
 namespace {
-struct HostImage {
-  int E, N;
-  bool ix;
-  std::vector<double> f64;
-  std::vector<int32_t> packed;
-  HostImage(const hwy_config &c, const hwy_state &h) : E(c.num_envs), N(c.num_vehicles), ix(c.scenario == HWY_SCENARIO_INTERSECTION) {
-    const size_t plane = (size_t)E * N;
-    f64.resize(plane * 9);
-    packed.resize(plane);
-    const double *fields[9] = {h.x, h.y, h.heading, h.speed, h.timer, h.target_speed, h.delta, h.impact_x, h.impact_y};
-    for (int f = 0; f < 9; ++f) std::memcpy(&f64[f * plane], fields[f], plane * sizeof(double));
-    for (size_t k = 0; k < plane; ++k)
-      packed[k] = ix ? hwy::ix_pack_word(h.lane[k], h.target_lane[k], h.speed_index[k], h.flags[k])
-                     : hwy::pack_word(h.lane[k], h.target_lane[k], h.speed_index[k], h.flags[k], (int)(k % N));
-  }
-  void store(hwy_state &h) const {
-    const size_t plane = (size_t)E * N;
-    double *fields[9] = {h.x, h.y, h.heading, h.speed, h.timer, h.target_speed, h.delta, h.impact_x, h.impact_y};
-    for (int f = 0; f < 9; ++f) std::memcpy(fields[f], &f64[f * plane], plane * sizeof(double));
-    for (size_t k = 0; k < plane; ++k) {
-      const int32_t w = packed[k];
-      if (ix) {
-        h.lane[k] = hwy::ix_word_lane(w); h.target_lane[k] = hwy::ix_word_target(w); h.speed_index[k] = hwy::ix_word_speed_index(w); h.flags[k] = hwy::ix_word_flags(w);
-        continue;
-      }
-      h.lane[k] = hwy::word_lane(w); h.target_lane[k] = hwy::word_target(w); h.speed_index[k] = hwy::word_speed_index(w); h.flags[k] = hwy::word_flags(w);
-      if (!(h.flags[k] & HWY_F_HAS_IMPACT)) h.impact_x[k] = h.impact_y[k] = 0.0;  // as hwy_get_state does
-    }
-  }
+// the intersection scenario's packed word (hwy_ix.h)
+int32_t pack_ix(const hwy_state &h, size_t k, int) { return hwy::ix_pack_word(h.lane[k], h.target_lane[k], h.speed_index[k], h.flags[k]); }
+void unpack_ix(int32_t w, hwy_state &h, size_t k) {
+  h.lane[k] = hwy::ix_word_lane(w); h.target_lane[k] = hwy::ix_word_target(w); h.speed_index[k] = hwy::ix_word_speed_index(w); h.flags[k] = hwy::ix_word_flags(w);
+}
+HostImage image_of(const hwy_config &c, const hwy_state &h) {
+  return c.scenario == HWY_SCENARIO_INTERSECTION ? HostImage(c, h, pack_ix, unpack_ix) : HostImage(c, h);
+}
+struct IdmEmu {
+  using Params = StepParams;
+  static const StepParams &step_params(const Params &a) { return a; }
+  template <int WPE, bool FULL_SCAN> static auto step_wave() { return hwy::hwy_step_wave_kernel<WPE, FULL_SCAN>; }
+  template <int WPE, bool FULL_SCAN> static auto rollout_wave() { return hwy::hwy_rollout_wave_kernel<WPE, FULL_SCAN>; }
+  template <int NW, int WPE> static auto step_block() { return hwy::hwy_step_kernel<NW, WPE>; }
+  template <int NW, int WPE> static auto rollout_block() { return hwy::hwy_rollout_kernel<NW, WPE>; }
+  template <int NW> static auto reset_block() { return hwy::hwy_reset_kernel<NW>; }
 };
 
-
-enum Which { STEP, RESET, OBSERVE };
 bool g_force_block = false;
 int g_k_steps = 0;  // > 0: the next STEP dispatch of the one-wavefront kernel is a multi-step launch (hwy_rollout_device)
 const hwy_config *g_cfg = nullptr;  // config of the call being dispatched (road-network scenarios need the lane table)
@@ -145,19 +137,6 @@ void dispatch(Which which, const StepParams &p, int E) {
     }
     return;
   }
-  if (which == STEP && nw == 1 && !g_force_block && g_cfg->tune_block_kernel != 1) {  // same dispatch rule as hwy_kernels.hip
-    if (g_k_steps > 0) {
-      StepParams pk = p;
-      pk.k_steps = g_k_steps;
-      pk.num_envs = E;
-      if (p.flags & HWY_C_EGO_ONLY_COLLISIONS) emu::launch([](const StepParams &q) { hwy::hwy_rollout_wave_kernel<1, false>(q); }, E, 64, pk);
-      else emu::launch([](const StepParams &q) { hwy::hwy_rollout_wave_kernel<1, true>(q); }, E, 64, pk);
-      return;
-    }
-    if (p.flags & HWY_C_EGO_ONLY_COLLISIONS) emu::launch([](const StepParams &q) { hwy::hwy_step_wave_kernel<1, false>(q); }, E, 64, p);
-    else emu::launch([](const StepParams &q) { hwy::hwy_step_wave_kernel<1, true>(q); }, E, 64, p);
-    return;
-  }
   if (which == STEP && nw >= 2 && nw <= 4 && p.obs_type == HWY_OBS_KINEMATICS && !g_force_block &&
       (g_cfg->tune_block_kernel == 2 || (g_cfg->tune_block_kernel == 0 && nw == 2))) {
     // same dispatch rule as hwy_kernels.hip (wide_kernel_applies): one wavefront per environment, nw vehicles per thread
@@ -174,21 +153,16 @@ void dispatch(Which which, const StepParams &p, int E) {
 #undef RUN_WIDE
     return;
   }
-#define RUN(NW)                                                                                         \
-  switch (which) {                                                                                      \
-    case STEP: if (g_k_steps > 0) { StepParams pk = p; pk.k_steps = g_k_steps; pk.num_envs = E;                \
-                 emu::launch([](const StepParams &q) { hwy::hwy_rollout_kernel<NW, 1>(q); }, E, NW * 64, pk); } \
-               else emu::launch([](const StepParams &q) { hwy::hwy_step_kernel<NW, 1>(q); }, E, NW * 64, p); break;     \
-    case RESET: emu::launch([](const StepParams &q) { hwy::hwy_reset_kernel<NW>(q); }, E, NW * 64, p); break;   \
-    case OBSERVE: emu::launch([](const StepParams &q) { hwy::hwy_observe_kernel<NW>(q); }, E, NW * 64, p); break; \
+  // the one-wavefront and the workgroup kernels: the straight-road family dispatch
+  const bool force_block = g_force_block || g_cfg->tune_block_kernel == 1;
+  if (which == STEP && g_k_steps > 0) {
+    StepParams pk = p;
+    pk.k_steps = g_k_steps;
+    pk.num_envs = E;
+    emu_straight::dispatch<IdmEmu>(ROLLOUT, pk, E, force_block);
+  } else {
+    emu_straight::dispatch<IdmEmu>(which, p, E, force_block);
   }
-  switch (nw) {
-    case 1: RUN(1) break;
-    case 2: RUN(2) break;
-    case 3: RUN(3) break;
-    default: RUN(4) break;
-  }
-#undef RUN
 }
 }  // namespace
 
@@ -214,23 +188,12 @@ int emu_run(const hwy_config *cfg, hwy_state *st, uint8_t *done, uint32_t *episo
             const int32_t *actions, float *obs, double *reward, uint8_t *term, uint8_t *trunc, double *speed,
             uint8_t *crashed, int autoreset, uint64_t base_seed, double ego_spacing, double vehicles_density,
             int initial_lane_id) {
-  HostImage img(*cfg, *st);
+  HostImage img = image_of(*cfg, *st);
   g_cfg = cfg;
   g_st = st;
   StepParams p;
-  hwy::params_from_config(*cfg, cfg->num_vehicles, p);
-  hwy::bind_planes(img.f64.data(), (size_t)cfg->num_envs * cfg->num_vehicles, p.st);
-  p.st.packed = img.packed.data();
-  p.st.time = st->time;
-  p.st.done = done;
-  p.st.episode = episode;
+  fill_step_params(cfg, img, st, done, episode, ResetArgs{base_seed, ego_spacing, vehicles_density, initial_lane_id}, p);
   p.autoreset = autoreset;
-  p.rp.ego_spacing = ego_spacing;
-  p.rp.other_spacing = 1 / vehicles_density;
-  p.rp.lane_factor = exp(-5.0 / 40.0 * cfg->lanes_count);
-  p.rp.initial_lane_id = initial_lane_id;
-  p.rp.fast = (cfg->flags & HWY_C_EGO_ONLY_COLLISIONS) ? 1 : 0;
-  p.rp.base_seed = base_seed;
   p.grid_ws = grid_ws_for(cfg);
   p.block_env = g_block_env;
   p.actions = actions; p.obs = obs; p.reward = reward; p.terminated = term; p.truncated = trunc;
@@ -250,22 +213,11 @@ int emu_run(const hwy_config *cfg, hwy_state *st, uint8_t *done, uint32_t *episo
 int emu_reset(const hwy_config *cfg, hwy_state *st, uint8_t *done, uint32_t *episode, const uint8_t *mask,
               const uint64_t *seeds, uint64_t base_seed, double ego_spacing, double vehicles_density,
               int initial_lane_id, float *obs) {
-  HostImage img(*cfg, *st);
+  HostImage img = image_of(*cfg, *st);
   g_cfg = cfg;
   g_st = st;
   StepParams p;
-  hwy::params_from_config(*cfg, cfg->num_vehicles, p);
-  hwy::bind_planes(img.f64.data(), (size_t)cfg->num_envs * cfg->num_vehicles, p.st);
-  p.st.packed = img.packed.data();
-  p.st.time = st->time;
-  p.st.done = done;
-  p.st.episode = episode;
-  p.rp.ego_spacing = ego_spacing;
-  p.rp.other_spacing = 1 / vehicles_density;
-  p.rp.lane_factor = exp(-5.0 / 40.0 * cfg->lanes_count);
-  p.rp.initial_lane_id = initial_lane_id;
-  p.rp.fast = (cfg->flags & HWY_C_EGO_ONLY_COLLISIONS) ? 1 : 0;
-  p.rp.base_seed = base_seed;
+  fill_step_params(cfg, img, st, done, episode, ResetArgs{base_seed, ego_spacing, vehicles_density, initial_lane_id}, p);
   p.reset_mask = mask;
   p.reset_seeds = seeds;
   p.obs = obs;

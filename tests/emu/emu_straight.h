@@ -1,0 +1,139 @@
+// emu_straight.h -- TEST INFRASTRUCTURE ONLY.  What the three CPU drivers (emu_engine.cpp: IDM with meta-actions, emu_traffic.cpp:
+// Linear traffic, emu_control.cpp: direct ego control) share on the straight road: the host image of the state, the filling of
+// StepParams, and the family dispatch.  Include it AFTER hip_emu.h and the product headers (hwy_device.h, hwy_wave.h, hwy_params.h),
+// so that a driver's own #defines (HWY_EMU_ULP_NOISE) come before the product source.
+// A family is the trait of highwayenv_amd/csrc/hwy_launch_family.h (Params, step_params, the five kernels), with WPE = 1.
+#pragma once
+#include <cstring>
+#include <type_traits>
+#include <vector>
+
+namespace emu_straight {
+using hwy::StepParams;
+
+// the packed word of one vehicle <-> the fields of hwy_state (emu_engine.cpp has the intersection scenario's pair)
+inline int32_t pack_hwy(const hwy_state &h, size_t k, int slot) {
+  return hwy::pack_word(h.lane[k], h.target_lane[k], h.speed_index[k], h.flags[k], slot);
+}
+inline void unpack_hwy(int32_t w, hwy_state &h, size_t k) {
+  h.lane[k] = hwy::word_lane(w); h.target_lane[k] = hwy::word_target(w); h.speed_index[k] = hwy::word_speed_index(w);
+  h.flags[k] = hwy::word_flags(w);
+  if (!(h.flags[k] & HWY_F_HAS_IMPACT)) h.impact_x[k] = h.impact_y[k] = 0.0;  // as hwy_get_state does
+}
+// the device image of the state: 9 f64 planes [field][E][N] + the packed words (pitch == N)
+struct HostImage {
+  int E, N;
+  void (*unpack)(int32_t, hwy_state &, size_t);
+  std::vector<double> f64;
+  std::vector<int32_t> packed;
+  HostImage(const hwy_config &c, const hwy_state &h, int32_t (*pack)(const hwy_state &, size_t, int) = pack_hwy,
+            void (*unpack_)(int32_t, hwy_state &, size_t) = unpack_hwy) : E(c.num_envs), N(c.num_vehicles), unpack(unpack_) {
+    const size_t plane = (size_t)E * N;
+    f64.resize(plane * 9);
+    packed.resize(plane);
+    const double *fields[9] = {h.x, h.y, h.heading, h.speed, h.timer, h.target_speed, h.delta, h.impact_x, h.impact_y};
+    for (int f = 0; f < 9; ++f) std::memcpy(&f64[f * plane], fields[f], plane * sizeof(double));
+    for (size_t k = 0; k < plane; ++k) packed[k] = pack(h, k, (int)(k % N));
+  }
+  void store(hwy_state &h) const {
+    const size_t plane = (size_t)E * N;
+    double *fields[9] = {h.x, h.y, h.heading, h.speed, h.timer, h.target_speed, h.delta, h.impact_x, h.impact_y};
+    for (int f = 0; f < 9; ++f) std::memcpy(fields[f], &f64[f * plane], plane * sizeof(double));
+    for (size_t k = 0; k < plane; ++k) unpack(packed[k], h, k);
+  }
+};
+
+// the reset parameters every driver call carries (hwy_set_autoreset / hwy_reset)
+struct ResetArgs {
+  uint64_t base_seed;
+  double ego_spacing, vehicles_density;
+  int initial_lane_id;
+};
+// StepParams from hwy_config, the image and the reset parameters (zeroes everything else of p)
+inline void fill_step_params(const hwy_config *cfg, HostImage &img, hwy_state *st, uint8_t *done, uint32_t *episode, const ResetArgs &ra,
+                             StepParams &p) {
+  hwy::params_from_config(*cfg, cfg->num_vehicles, p);
+  hwy::bind_planes(img.f64.data(), (size_t)cfg->num_envs * cfg->num_vehicles, p.st);
+  p.st.packed = img.packed.data();
+  p.st.time = st->time;
+  p.st.done = done;
+  p.st.episode = episode;
+  p.rp.ego_spacing = ra.ego_spacing;
+  p.rp.other_spacing = 1 / ra.vehicles_density;
+  p.rp.lane_factor = exp(-5.0 / 40.0 * cfg->lanes_count);
+  p.rp.initial_lane_id = ra.initial_lane_id;
+  p.rp.fast = (cfg->flags & HWY_C_EGO_ONLY_COLLISIONS) ? 1 : 0;
+  p.rp.base_seed = ra.base_seed;
+}
+
+enum Which { STEP, ROLLOUT, RESET, OBSERVE };
+// same dispatch rule as hwy_launch_family.h: the one-wavefront kernel for N <= 64 unless the workgroup kernel is forced
+template <typename F>
+void dispatch(Which which, const typename F::Params &a, int E, bool force_block) {
+  const StepParams &p = F::step_params(a);
+  if ((which == STEP || which == ROLLOUT) && p.N <= 64 && !force_block) {
+    const bool full = !(p.flags & HWY_C_EGO_ONLY_COLLISIONS);
+    if (which == ROLLOUT) emu::launch(full ? F::template rollout_wave<1, true>() : F::template rollout_wave<1, false>(), E, 64, a);
+    else emu::launch(full ? F::template step_wave<1, true>() : F::template step_wave<1, false>(), E, 64, a);
+    return;
+  }
+  auto run = [&](auto V) {
+    constexpr int NW = decltype(V)::value;
+    switch (which) {
+      case STEP: emu::launch(F::template step_block<NW, 1>(), E, NW * 64, a); break;
+      case ROLLOUT: emu::launch(F::template rollout_block<NW, 1>(), E, NW * 64, a); break;
+      case RESET: emu::launch(F::template reset_block<NW>(), E, NW * 64, a); break;
+      case OBSERVE: emu::launch(hwy::hwy_observe_kernel<NW>, E, NW * 64, p); break;
+    }
+  };
+  switch ((p.N + 63) / 64) {
+    case 1: run(std::integral_constant<int, 1>{}); break;
+    case 2: run(std::integral_constant<int, 2>{}); break;
+    case 3: run(std::integral_constant<int, 3>{}); break;
+    default: run(std::integral_constant<int, 4>{}); break;
+  }
+}
+
+// the body of emu_traffic_run / emu_control_run.  `a` arrives with the family's own arguments filled.
+// mode: 0 = frames only (hwy_step_frames), 1 = full policy step(s) (hwy_step; k_steps > 0: hwy_rollout_device), 2 = observe only.
+template <typename F>
+int run(const hwy_config *cfg, hwy_state *st, typename F::Params &a, uint8_t *done, uint32_t *episode, int mode, int n_frames,
+        int k_steps, const int32_t *actions, float *obs, double *reward, uint8_t *term, uint8_t *trunc, double *speed,
+        uint8_t *crashed, int autoreset, const ResetArgs &ra) {
+  HostImage img(*cfg, *st);
+  StepParams &p = F::step_params(a);
+  fill_step_params(cfg, img, st, done, episode, ra, p);
+  p.autoreset = autoreset;
+  p.actions = actions; p.obs = obs; p.reward = reward; p.terminated = term; p.truncated = trunc;
+  p.info_speed = speed; p.info_crashed = crashed;
+  Which which = OBSERVE;
+  if (mode != 2) {
+    p.n_frames = n_frames;
+    p.full_step = mode == 1;
+    if (mode == 0) p.autoreset = 0;
+    which = STEP;
+    if (mode == 1 && k_steps > 0) {
+      p.k_steps = k_steps;
+      p.num_envs = cfg->num_envs;
+      which = ROLLOUT;
+    }
+  }
+  dispatch<F>(which, a, cfg->num_envs, cfg->tune_block_kernel == 1);
+  img.store(*st);
+  return 0;
+}
+// the body of emu_traffic_reset / emu_control_reset
+template <typename F>
+int reset(const hwy_config *cfg, hwy_state *st, typename F::Params &a, uint8_t *done, uint32_t *episode, const uint8_t *mask,
+          const uint64_t *seeds, const ResetArgs &ra, float *obs) {
+  HostImage img(*cfg, *st);
+  StepParams &p = F::step_params(a);
+  fill_step_params(cfg, img, st, done, episode, ra, p);
+  p.reset_mask = mask;
+  p.reset_seeds = seeds;
+  p.obs = obs;
+  dispatch<F>(RESET, a, cfg->num_envs, cfg->tune_block_kernel == 1);
+  img.store(*st);
+  return 0;
+}
+}  // namespace emu_straight

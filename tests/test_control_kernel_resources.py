@@ -1,11 +1,7 @@
 """Register / LDS allocation of the direct-ego-control kernels (hwy_kernels_direct.hip), read from the code object's own metadata
-like tests/test_traffic_kernel_resources.py (no GPU needed): every gfx950 bundle of the library is handed to
-build.kernel_resources as a file of its own.
+like tests/test_traffic_kernel_resources.py (no GPU needed).
 
 gfx950: 512 VGPRs per SIMD lane (allocation granule 8), 160 KB of LDS per CU, 4 SIMDs per CU."""
-import os
-import tempfile
-
 import pytest
 
 from highwayenv_amd import build
@@ -18,19 +14,7 @@ def res():
     pytest.importorskip("msgpack")
     if build.is_stale():
         build.build_engine()
-    blob = open(build.LIB_PATH, "rb").read()
-    magic = b"__CLANG_OFFLOAD_BUNDLE__"
-    out, i = {}, blob.find(magic)
-    while i >= 0:
-        fd, path = tempfile.mkstemp(suffix=".bin")
-        try:
-            with os.fdopen(fd, "wb") as fh:
-                fh.write(blob[i:])
-            out.update(build.kernel_resources(path))
-        finally:
-            os.unlink(path)
-        i = blob.find(magic, i + 1)
-    return out
+    return build.kernel_resources()
 
 
 def waves_per_simd(vgpr: int) -> int:

@@ -14,15 +14,9 @@ source:
 * `reward_from_target_lane` -- the right-lane reward reads the ego's target-lane slot (last step's lane) instead of its lane.
 
 Each case runs the real test functions in a subprocess with HWY_EMU_CONTROL_LIB pointing at the mutant."""
-import os
-import shutil
-import subprocess
-import sys
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "tests", "emu", "_build")
+from tests import mutation_util
 
 RIVAL = ("const bool rival = !(EG::DIRECT && controlled);", "const bool rival = true;")
 MUTANTS = {
@@ -43,32 +37,11 @@ CASES = [
 
 
 def build_mutant(name: str) -> str:
-    from tests.emu import emu
-    src = os.path.join(BUILD, f"mutc_{name}_{os.getpid()}")
-    shutil.rmtree(src, ignore_errors=True)
-    for d in ("tests/emu", "highwayenv_amd/csrc", "include"):
-        os.makedirs(os.path.join(src, d))
-        for f in os.listdir(os.path.join(ROOT, d)):
-            if f.endswith((".h", ".cpp")):
-                shutil.copy(os.path.join(ROOT, d, f), os.path.join(src, d, f))
-    for fname, old, new in MUTANTS[name]:
-        path = os.path.join(src, "highwayenv_amd", "csrc", fname)
-        text = open(path).read()
-        assert text.count(old) == 1, f"mutation site of {name} not found exactly once in {fname}: {old}"
-        open(path, "w").write(text.replace(old, new))
-    lib = os.path.join(BUILD, f"libhwy_emu_control_mut_{name}.so")
-    emu.compile_emulator(os.path.join(src, "tests", "emu", "emu_control.cpp"), lib)
-    shutil.rmtree(src)
-    return lib
+    return mutation_util.build_mutant(MUTANTS[name], "emu_control.cpp", f"libhwy_emu_control_mut_{name}.so")
 
 
-def run_selection(lib, selection) -> subprocess.CompletedProcess:
-    env = dict(os.environ)
-    env.pop("HWY_EMU_CONTROL_LIB", None)
-    if lib:
-        env["HWY_EMU_CONTROL_LIB"] = lib
-    return subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider", *selection], cwd=ROOT, env=env,
-                          capture_output=True, text=True, timeout=1500)
+def run_selection(lib, selection):
+    return mutation_util.run_selection(lib, selection, "HWY_EMU_CONTROL_LIB")
 
 
 @pytest.mark.parametrize("mutant,selection", CASES, ids=[c[0] for c in CASES])

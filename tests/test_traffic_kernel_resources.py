@@ -1,11 +1,8 @@
 """Register / LDS allocation of the Linear traffic family's kernels (hwy_kernels_linear.hip), read from the code object's own
 metadata like tests/test_kernel_resources.py (no GPU needed).  That translation unit is the library's SECOND gfx950 code object
-(hwy_kernels.hip's is the first, which build.kernel_resources reads): every bundle is handed over as a file of its own.
+(hwy_kernels.hip's is the first): build.kernel_resources reads every one.
 
 gfx950: 512 VGPRs per SIMD lane (allocation granule 8), 160 KB of LDS per CU, 4 SIMDs per CU."""
-import os
-import tempfile
-
 import pytest
 
 from highwayenv_amd import build
@@ -82,19 +79,7 @@ def res():
     pytest.importorskip("msgpack")
     if build.is_stale():
         build.build_engine()
-    blob = open(build.LIB_PATH, "rb").read()
-    magic = b"__CLANG_OFFLOAD_BUNDLE__"
-    out, i = {}, blob.find(magic)
-    while i >= 0:
-        fd, path = tempfile.mkstemp(suffix=".bin")
-        try:
-            with os.fdopen(fd, "wb") as fh:
-                fh.write(blob[i:])
-            out.update(build.kernel_resources(path))
-        finally:
-            os.unlink(path)
-        i = blob.find(magic, i + 1)
-    return out
+    return build.kernel_resources()
 
 
 def waves_per_simd(vgpr: int) -> int:

@@ -11,7 +11,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from highwayenv_amd.build import HIPCC_FLAGS, SOURCES  # noqa: E402
+from highwayenv_amd.build import SOURCES, flags_for  # noqa: E402
 
 rev = sys.argv[1]
 name = sys.argv[2] if len(sys.argv) > 2 else rev
@@ -25,7 +25,7 @@ with tempfile.TemporaryDirectory() as tmp:
     procs = []
     for src in SOURCES:
         obj = os.path.join(csrc, src.replace(".hip", ".o"))
-        procs.append(subprocess.Popen(["hipcc", *HIPCC_FLAGS, "-c", os.path.join(csrc, src), "-o", obj], stderr=subprocess.DEVNULL))
+        procs.append(subprocess.Popen(["hipcc", *flags_for(src), "-c", os.path.join(csrc, src), "-o", obj]))
         objs.append(obj)
     for p in procs:
         if p.wait() != 0:

@@ -11,11 +11,12 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from highwayenv_amd.build import CSRC, HIPCC_FLAGS, build_engine  # noqa: E402
+from highwayenv_amd.build import CSRC, SOURCES, build_engine, flags_for  # noqa: E402
 
 OUT = os.path.join(ROOT, "tools", "ablate", "_build")
 os.makedirs(OUT, exist_ok=True)
-build_engine()  # hwy_engine.o / hwy_comm.o of the tree (the host side does not depend on the kernels' tuning macros)
+build_engine()  # every other object of the tree (the host side and the other kernel units do not take the tuning macros)
+OTHERS = [os.path.join(CSRC, s.replace(".hip", ".o")) for s in SOURCES if s != "hwy_kernels.hip"]
 groups, cur = [], []
 for a in sys.argv[1:]:
     if a == "--":
@@ -29,13 +30,12 @@ procs = []
 for g in groups:
     name, flags = g[0], g[1:]
     obj = os.path.join(OUT, f"hwy_kernels_{name}.o")
-    procs.append((name, obj, subprocess.Popen(["hipcc", *HIPCC_FLAGS, *flags, "-c", os.path.join(CSRC, "hwy_kernels.hip"), "-o", obj],
-                                              stderr=subprocess.DEVNULL)))
+    procs.append((name, obj, subprocess.Popen(["hipcc", *flags_for("hwy_kernels.hip"), *flags, "-c", os.path.join(CSRC, "hwy_kernels.hip"),
+                                               "-o", obj])))
 for name, obj, pr in procs:
     if pr.wait() != 0:
         raise SystemExit(f"{name}: compile failed")
     lib = os.path.join(OUT, f"libhwy_engine_{name}.so")
-    subprocess.run(["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, obj, os.path.join(CSRC, "hwy_engine.o"),
-                    os.path.join(CSRC, "hwy_comm.o"), "-ldl"], check=True)
+    subprocess.run(["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, obj, *OTHERS, "-ldl"], check=True)
     os.remove(obj)
     print(lib)
