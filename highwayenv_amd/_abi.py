@@ -13,7 +13,7 @@ import ctypes as C
 
 import numpy as np
 
-HWY_ABI_VERSION = 7
+HWY_ABI_VERSION = 8
 HWY_MAX_AGENTS = 16
 HWY_MAX_FEATURES = 16
 HWY_MAX_TARGET_SPEEDS = 8
@@ -22,6 +22,7 @@ HWY_MAX_VEHICLES = 256
 HWY_MAX_GLANES = 24
 HWY_MAX_ROUTE = 11
 HWY_MAX_ACTIONS_PER_AXIS = 16
+HWY_MAX_LIDAR_CELLS = 64
 
 # hwy_status
 HWY_OK, HWY_ERR_INVALID_ARG, HWY_ERR_HIP, HWY_ERR_UNSUPPORTED, HWY_ERR_NO_DEVICE, HWY_ERR_ACTION = 0, -1, -2, -3, -4, -5
@@ -41,7 +42,7 @@ C_OBS_UNSORTED = 1024
 C_OBS_VEHICLES_ONLY = 2048
 C_OBS_INTENTIONS = 4096
 C_GRID_IMAGE = 8192
-OBS_KINEMATICS, OBS_OCCUPANCY_GRID = 0, 1
+OBS_KINEMATICS, OBS_OCCUPANCY_GRID, OBS_LIDAR = 0, 1, 2
 # hwy_config.traffic_model
 TRAFFIC_IDM, TRAFFIC_LINEAR = 0, 1
 HWY_BEHAVIOR_PARAMS = 5
@@ -222,11 +223,17 @@ class HwyConfig(C.Structure):
         ("reserved5", C.c_int32),
         ("accel_axis", C.c_double * HWY_MAX_ACTIONS_PER_AXIS),
         ("steer_axis", C.c_double * HWY_MAX_ACTIONS_PER_AXIS),
+        # LidarObservation (ABI v8)
+        ("lidar_cells", C.c_int32),
+        ("lidar_normalize", C.c_int32),
+        ("lidar_max_range", C.c_double),
     ]
 
 
 def obs_shape(cfg: "HwyConfig") -> tuple:
-    """Per-agent observation shape: (V, F) Kinematics, (F, W, H) OccupancyGrid."""
+    """Per-agent observation shape: (V, F) Kinematics, (F, W, H) OccupancyGrid, (cells, 2) Lidar."""
+    if cfg.obs_type == OBS_LIDAR:
+        return (cfg.lidar_cells, 2)
     if cfg.obs_type == OBS_OCCUPANCY_GRID:
         return (cfg.obs_features, cfg.grid_shape[0], cfg.grid_shape[1])
     return (cfg.obs_vehicles, cfg.obs_features)
@@ -410,9 +417,19 @@ def make_config(config: dict, num_envs: int, fast: bool = False, scenario: str =
              "ExitObservation")
     if obs["type"] not in known:
         raise ValueError("Unknown observation type")
-    if obs["type"] not in ("Kinematics", "OccupancyGrid"):
+    if obs["type"] not in ("Kinematics", "OccupancyGrid", "LidarObservation"):
         raise NotImplementedError(f"observation type {obs['type']} is outside the MI355X hot-path scope")
     grid = obs["type"] == "OccupancyGrid"
+    lidar = obs["type"] == "LidarObservation"
+    if lidar:
+        # LidarObservation.__init__ (observation.py:682-696)
+        if scenario != "highway":
+            raise NotImplementedError("LidarObservation is in the hot-path scope on the highway scenario only")
+        lidar_cells, lidar_range = int(obs.get("cells", 16)), float(obs.get("maximum_range", 60))
+        if lidar_cells < 1 or not (0 < lidar_range < float("inf")):
+            raise ValueError("LidarObservation needs cells >= 1 and a positive, finite maximum_range")
+        if lidar_cells > HWY_MAX_LIDAR_CELLS:
+            raise NotImplementedError(f"LidarObservation(cells > {HWY_MAX_LIDAR_CELLS}) is outside the MI355X hot-path scope")
     merge = scenario in ("merge", "merge-generic")
     traffic = cfg.get("other_vehicles_type", "highway_env.vehicle.behavior.IDMVehicle")
     if traffic not in TRAFFIC_CLASSES or (traffic != "highway_env.vehicle.behavior.IDMVehicle" and scenario != "highway"):
@@ -422,7 +439,7 @@ def make_config(config: dict, num_envs: int, fast: bool = False, scenario: str =
         raise ValueError(f"unknown scenario {scenario!r}")
     # neighbour_vehicles_connected_lanes on the single road 0->1 of highway-v0 adds no lane to the search list
     # (road.py:513-529: nothing leaves "1", nothing arrives at "0"), so the flag is accepted there and changes nothing
-    if not grid and obs.get("order", "sorted") not in ("sorted", "shuffled"):
+    if not grid and not lidar and obs.get("order", "sorted") not in ("sorted", "shuffled"):
         raise ValueError("KinematicObservation order must be 'sorted' or 'shuffled'")
 
     c = HwyConfig()
@@ -483,7 +500,15 @@ def make_config(config: dict, num_envs: int, fast: bool = False, scenario: str =
     c.reward_speed_range[0], c.reward_speed_range[1] = map(float, cfg["reward_speed_range"])
     c.perception_distance = 5.0 * 40.0  # AbstractEnv.PERCEPTION_DISTANCE (abstract.py:58)
 
-    if grid:
+    if lidar:
+        # the kernels of csrc/hwy_lidar.h read these three; the step kernels run without an observation (one presence column
+        # keeps the Kinematics fields they would read valid)
+        c.obs_type = OBS_LIDAR
+        c.lidar_cells, c.lidar_max_range, c.lidar_normalize = lidar_cells, lidar_range, int(bool(obs.get("normalize", True)))
+        c.obs_vehicles = 1
+        feats, default_range = ["presence"], {}
+        obs = {"normalize": False, "clip": False}  # (none of the Kinematics flags below applies)
+    elif grid:
         # OccupancyGridObservation.__init__ (observation.py:286-327)
         feats = obs["features"] if obs.get("features") is not None else ["presence", "vx", "vy", "on_road"]
         if obs.get("absolute", False):

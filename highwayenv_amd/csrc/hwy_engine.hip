@@ -196,7 +196,13 @@ static int validate(const hwy_config *c, std::string &why) {
   if (c->tune_prio_shift < -1 || (c->tune_prio_shift > 30 && c->tune_prio_shift < 64) || c->tune_prio_shift > (1 << 20))
     BAD("tune_prio_shift must be -1 (off), 0 (engine's choice), 1..30 (a turn of 2^k clock ticks) or 64..2^20 (a turn of k x 64 ticks)");
   if (c->obs_vehicles < 1 || c->obs_vehicles > c->num_vehicles + 64) BAD("obs_vehicles out of range");
-  if (c->obs_type != HWY_OBS_KINEMATICS && c->obs_type != HWY_OBS_OCCUPANCY_GRID) BAD("unknown obs_type");
+  if (c->obs_type != HWY_OBS_KINEMATICS && c->obs_type != HWY_OBS_OCCUPANCY_GRID && c->obs_type != HWY_OBS_LIDAR) BAD("unknown obs_type");
+  if (c->obs_type == HWY_OBS_LIDAR) {
+    if (c->scenario != HWY_SCENARIO_HIGHWAY) BAD("the Lidar observation runs on the highway scenario only");
+    if (c->lidar_cells < 1 || c->lidar_cells > HWY_MAX_LIDAR_CELLS) BAD("lidar_cells must be in [1,%d]", HWY_MAX_LIDAR_CELLS);
+    if (!(c->lidar_max_range > 0) || !(c->lidar_max_range < 1e30)) BAD("lidar_max_range must be positive and finite");
+    if (c->lidar_normalize != 0 && c->lidar_normalize != 1) BAD("lidar_normalize must be 0 or 1");
+  }
   if (c->obs_type == HWY_OBS_OCCUPANCY_GRID) {
     if (c->grid_shape[0] < 1 || c->grid_shape[1] < 1 || (int64_t)c->grid_shape[0] * c->grid_shape[1] > HWY_MAX_GRID_CELLS)
       BAD("grid_shape must hold 1..%d cells", HWY_MAX_GRID_CELLS);
@@ -284,6 +290,20 @@ static void fill_linear(const hwy_engine *eng, const StepParams &p, hwy::LinearP
   lp.la.lc_gain = eng->cfg.traffic_lc_min_acc_gain;
 }
 static bool is_direct(const hwy_engine *eng) { return eng->cfg.ego_control == HWY_EGO_DIRECT; }
+static bool is_lidar(const hwy_engine *eng) { return eng->cfg.obs_type == HWY_OBS_LIDAR; }
+// LidarObservation of the CURRENT state of every environment into d_obs ([E][A][cells][2]), enqueued behind whatever wrote that state
+static hipError_t launch_lidar_obs(const hwy_engine *eng, float *d_obs) {
+  hwy::LidarParams lp;
+  std::memset(&lp, 0, sizeof lp);
+  const size_t plane = (size_t)eng->cfg.num_envs * eng->pitch;
+  lp.x = eng->d_f64 + 0 * plane; lp.y = eng->d_f64 + 1 * plane; lp.heading = eng->d_f64 + 2 * plane; lp.speed = eng->d_f64 + 3 * plane;
+  lp.packed = eng->d_packed;
+  lp.obs = d_obs;
+  lp.N = eng->cfg.num_vehicles; lp.A = eng->cfg.num_agents; lp.pitch = eng->pitch; lp.cells = eng->cfg.lidar_cells;
+  for (int a = 0; a < HWY_MAX_AGENTS; ++a) lp.agent_index[a] = a < eng->cfg.num_agents ? eng->cfg.agent_index[a] : 0;
+  lp.max_range = eng->cfg.lidar_max_range;
+  return hwy::launch_lidar(lp, eng->cfg.lidar_normalize != 0, eng->cfg.num_envs * eng->cfg.num_agents, eng->stream);
+}
 static void fill_direct(const hwy_engine *eng, const StepParams &p, hwy::DirectParams &dp) {
   std::memset(&dp, 0, sizeof dp);
   dp.s = p;
@@ -833,6 +853,12 @@ extern "C" int hwy_step_device(hwy_engine *eng, const int32_t *d_actions, float 
   p.info_speed = d_info_speed; p.info_crashed = d_info_crashed;
   if (eng->profiling && eng->events_used >= 65536)
     if (int rc = drain_events(eng)) return rc;
+  if (is_lidar(eng)) {  // the family's step kernel without an observation, then the lidar kernel on the state it left
+    p.obs = nullptr;
+    if (int rc = timed_launch(eng, p)) return rc;
+    HWY_HIP(eng, launch_lidar_obs(eng, d_obs));
+    return HWY_OK;
+  }
   return timed_launch(eng, p);
 }
 
@@ -852,6 +878,21 @@ extern "C" int hwy_rollout_device(hwy_engine *eng, int32_t k_steps, const int32_
   p.full_step = 1;
   p.actions = d_actions; p.obs = d_obs; p.reward = d_reward; p.terminated = d_terminated; p.truncated = d_truncated;
   p.info_speed = d_info_speed; p.info_crashed = d_info_crashed;
+  if (is_lidar(eng)) {
+    // k_steps x (step launch + lidar launch): step k's observation is of the state after step k, so the steps cannot share a launch.
+    // The launches are those of k_steps hwy_step_device calls on block k of every plane: the same results by construction.
+    const size_t E = eng->cfg.num_envs, EA = E * eng->cfg.num_agents, n_obs = EA * hwy::obs_len(eng->cfg);
+    for (int k = 0; k < k_steps; ++k) {
+      StepParams q = p;
+      q.actions = d_actions + k * EA; q.obs = nullptr; q.reward = d_reward + k * EA;
+      q.terminated = d_terminated + k * E; q.truncated = d_truncated + k * E;
+      q.info_speed = d_info_speed ? d_info_speed + k * EA : nullptr;
+      q.info_crashed = d_info_crashed ? d_info_crashed + k * EA : nullptr;
+      HWY_HIP(eng, launch_step_any(eng, q));
+      HWY_HIP(eng, launch_lidar_obs(eng, d_obs + k * n_obs));
+    }
+    return HWY_OK;
+  }
   // K steps in ONE launch, every family.  The intersection kernel: STEP blocks only (no shadow is advanced during the launch; an
   // environment that ends in it warms its next episode up inline -- WHEN the warm-up frames are computed cannot change a result)
   p.k_steps = k_steps;
@@ -967,7 +1008,8 @@ extern "C" int hwy_observe(hwy_engine *eng, float *obs) {
   fill_params(eng, p);
   p.obs = eng->d_obs;
   p.reward = eng->d_reward; p.terminated = eng->d_term; p.truncated = eng->d_trunc;
-  HWY_HIP(eng, launch_observe_any(eng, p));
+  if (is_lidar(eng)) HWY_HIP(eng, launch_lidar_obs(eng, eng->d_obs));  // (the observe kernel has nothing else to do)
+  else HWY_HIP(eng, launch_observe_any(eng, p));
   HWY_HIP(eng, hipMemcpyAsync(eng->h_pinned, eng->d_obs, n_obs * 4, hipMemcpyDeviceToHost, eng->stream));
   HWY_HIP(eng, hipStreamSynchronize(eng->stream));
   std::memcpy(obs, eng->h_pinned, n_obs * 4);
@@ -1006,9 +1048,10 @@ extern "C" int hwy_reset(hwy_engine *eng, const uint8_t *mask, const uint64_t *s
     HWY_HIP(eng, hipMemcpyAsync(eng->d_mask, base + E * 8, E, hipMemcpyHostToDevice, eng->stream));
     p.reset_mask = eng->d_mask;
   }
-  p.obs = eng->d_obs;
+  p.obs = is_lidar(eng) ? nullptr : eng->d_obs;
   p.reward = eng->d_reward; p.terminated = eng->d_term; p.truncated = eng->d_trunc;
   HWY_HIP(eng, launch_reset_any(eng, p));
+  if (is_lidar(eng)) HWY_HIP(eng, launch_lidar_obs(eng, eng->d_obs));  // (every row; only the masked ones are copied out below)
   HWY_HIP(eng, hipStreamSynchronize(eng->stream));
   if (obs) {
     HWY_HIP(eng, hipMemcpyAsync(eng->h_pinned, eng->d_obs, n_obs * 4, hipMemcpyDeviceToHost, eng->stream));

@@ -1,11 +1,13 @@
 // hwy_launch.h -- host-visible launch functions of the kernels in hwy_kernels.hip, hwy_kernels_linear.hip and
-// hwy_kernels_direct.hip: one overload per kernel family, chosen by the type of its parameter struct.
+// hwy_kernels_direct.hip: one overload per kernel family, chosen by the type of its parameter struct; and of the
+// LidarObservation kernel in hwy_kernels_lidar.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "hwy_device.h"
 #include "hwy_net.h"
 #include "hwy_ix.h"
+#include "hwy_lidar.h"
 
 namespace hwy {
 // the events the launches of THIS THREAD record their dispatch begin / end timestamps into (nullptr, nullptr = none)
@@ -55,5 +57,7 @@ int step_resident_blocks(const LinearParams &lp, const Launch &l);
 int step_resident_blocks(const DirectParams &dp, const Launch &l);
 int step_resident_blocks(const NetParams &np, const Launch &l);
 inline int step_resident_blocks(const IxParams &, const Launch &) { return 0; }
+// LidarObservation of the current state (hwy_lidar.h): `rows` = environments x agents wavefronts, row r -> lp.obs + r * cells * 2
+hipError_t launch_lidar(const LidarParams &lp, bool normalize, int rows, hipStream_t stream);
 hipError_t launch_math_probe(int op, const double *in, double *out, long long n, hipStream_t stream);
 }  // namespace hwy

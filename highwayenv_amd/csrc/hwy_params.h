@@ -41,7 +41,9 @@ inline void params_from_config(const hwy_config &c, int pitch, StepParams &p) {
   p.inv_rx = 1.0 / (p.rx1 - p.rx0); p.inv_ry = 1.0 / (p.ry1 - p.ry0);
   p.inv_rvx = 1.0 / (p.rvx1 - p.rvx0); p.inv_rvy = 1.0 / (p.rvy1 - p.rvy0);
   set_prio_turn(p, c.tune_prio_shift > 0 ? c.tune_prio_shift : 0);  // the engine turns the default on where it pays (hwy_create)
-  p.obs_type = c.obs_type;
+  // a Lidar engine's step / reset kernels run with a null `obs` and are chosen like a Kinematics engine's (the wide kernel for
+  // 64 < N <= 128): the observation is hwy_lidar.h's own launch
+  p.obs_type = c.obs_type == HWY_OBS_LIDAR ? HWY_OBS_KINEMATICS : c.obs_type;
   p.obs_std5 = c.obs_type == HWY_OBS_KINEMATICS && c.obs_features == 5;
   for (int f = 0; f < 5; ++f) p.obs_std5 = p.obs_std5 && c.obs_feature_ids[f] == f;  // presence, x, y, vx, vy
   if (c.obs_type == HWY_OBS_OCCUPANCY_GRID) {
@@ -91,8 +93,9 @@ inline void ix_params_from_config(const hwy_config &c, const StepParams &p, IP &
   ip.d0 = c.idm_distance_wanted; ip.tau = c.idm_time_wanted; ip.a_max = c.idm_comfort_acc_max; ip.b_min = c.idm_comfort_acc_min;
 }
 
-// observation length per agent: V*F (Kinematics) or F*W*H (OccupancyGrid)
+// observation length per agent: V*F (Kinematics), F*W*H (OccupancyGrid) or cells*2 (Lidar)
 inline size_t obs_len(const hwy_config &c) {
+  if (c.obs_type == HWY_OBS_LIDAR) return (size_t)c.lidar_cells * 2;
   return c.obs_type == HWY_OBS_OCCUPANCY_GRID ? (size_t)c.obs_features * c.grid_shape[0] * c.grid_shape[1]
                                               : (size_t)c.obs_vehicles * c.obs_features;
 }

@@ -161,6 +161,14 @@ class BatchedHighwayEnv:
         else:
             self.single_action_space = _Discrete(_abi.num_actions(hc))
             self.single_observation_space = _Box(self.single_observation_shape, np.uint8 if hc.flags & _abi.C_GRID_IMAGE else np.float32)
+        if hc.obs_type == _abi.OBS_LIDAR:
+            # LidarObservation.space (observation.py:698-700): Box(-high, high, (cells, 2), float32), high = 1 if normalize else
+            # maximum_range (MultiAgentObservation: one such space per agent, stacked here like the observation)
+            high = 1.0 if hc.lidar_normalize else float(hc.lidar_max_range)
+            if _gym is not None:
+                self.single_observation_space = _gym.spaces.Box(-high, high, self.single_observation_shape, np.float32)
+            else:
+                self.single_observation_space.low, self.single_observation_space.high = -high, high
         self.action_space, self.observation_space = self.single_action_space, self.single_observation_space
 
     def _ensure_engine(self):

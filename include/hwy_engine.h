@@ -24,8 +24,8 @@
  * HighwayEnv._create_vehicles puts them, index 0 for a single agent).  All
  * floating-point state is f64 like the reference (vehicle/objects.py:43);
  * observations are f32 (observation.py:276).  Host-side arrays are row-major
- * [E][N] (state), [E][A][V][F] (Kinematics obs) or [E][A][F][W][H] (OccupancyGrid obs),
- * [E][A] (actions) unless stated otherwise.
+ * [E][N] (state), [E][A][V][F] (Kinematics obs), [E][A][F][W][H] (OccupancyGrid obs) or
+ * [E][A][cells][2] (Lidar obs), [E][A] (actions) unless stated otherwise.
  */
 #ifndef HWY_ENGINE_H
 #define HWY_ENGINE_H
@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define HWY_ABI_VERSION 7
+#define HWY_ABI_VERSION 8
 
 #define HWY_MAX_AGENTS 16
 #define HWY_MAX_FEATURES 16
@@ -47,6 +47,7 @@ extern "C" {
 #define HWY_MAX_GRID_CELLS 65536
 #define HWY_MAX_GLANES 24  /* lanes of a general (any direction / circular) road network: HWY_SCENARIO_INTERSECTION */
 #define HWY_MAX_ACTIONS_PER_AXIS 16 /* DiscreteAction(actions_per_axis): points per axis of the throttle x steering table */
+#define HWY_MAX_LIDAR_CELLS 64 /* LidarObservation(cells): one lane of a wavefront per cell */
 #define HWY_MAX_ROUTE 11   /* remaining roads of a planned route kept per vehicle (64-bit route word, 5 bits per road) */
 
 typedef enum hwy_status {
@@ -134,7 +135,23 @@ enum {
 };
 
 /* observation types (hwy_config.obs_type) */
-enum { HWY_OBS_KINEMATICS = 0, HWY_OBS_OCCUPANCY_GRID = 1 };
+enum {
+  HWY_OBS_KINEMATICS = 0,
+  HWY_OBS_OCCUPANCY_GRID = 1,
+  HWY_OBS_LIDAR = 2 /* LidarObservation (observation.py:678-769), HWY_SCENARIO_HIGHWAY only (every traffic model and ego control
+                       of it): obs is f32 [E][A][cells][2] = (distance, relative radial speed) per angular cell.  Traced by a
+                       kernel of its own (csrc/hwy_lidar.h) launched on the engine's stream AFTER the step / reset kernel, which
+                       runs with a null observation pointer and is otherwise the Kinematics engine's, unchanged:
+                         hwy_step / hwy_step_device   the family's step kernel, then the lidar kernel;
+                         hwy_reset, hwy_observe       their own work, then the lidar kernel (hwy_observe: the lidar kernel alone);
+                         hwy_rollout / _device        k_steps x (step launch + lidar launch), NOT one multi-step launch: step k's
+                                                      observation is of the state after step k, which a K-step launch has
+                                                      overwritten by its end.  Results equal k_steps calls of hwy_step_device, bit
+                                                      for bit, like everywhere else.
+                       Auto-reset is next-step (hwy_set_autoreset): the state a step leaves behind is the one its observation is
+                       of, also when that step re-spawned the environment.  obs_vehicles / obs_features / obs_feature_ids /
+                       obs_range_* are not read (obs_vehicles and obs_features must still be >= 1) */
+};
 
 /* scenarios (hwy_config.scenario) */
 enum {
@@ -318,6 +335,11 @@ typedef struct hwy_config {
   double accel_axis[HWY_MAX_ACTIONS_PER_AXIS]; /* PHYSICAL values [m/s^2] / [rad]: the host evaluates the reference's own float32 */
   double steer_axis[HWY_MAX_ACTIONS_PER_AXIS]; /* expressions (linspace of the Box bounds, clip, utils.lmap) and widens the results,
                                                   so the kernels do no float32 arithmetic; |steer_axis| <= pi / 3 */
+  /* LidarObservation (ABI v8; read when obs_type == HWY_OBS_LIDAR, otherwise ignored) */
+  int32_t lidar_cells;                 /* cells, 1..HWY_MAX_LIDAR_CELLS: cell k looks along k * 2 pi / cells */
+  int32_t lidar_normalize;             /* normalize: the float32 grid is divided by float32(maximum_range) (observation.py:706-707) */
+  double lidar_max_range;              /* maximum_range [m], > 0 and finite: an obstacle whose CENTRE is farther is not traced;
+                                          a cell nothing was traced into holds (maximum_range, maximum_range) */
 } hwy_config;
 
 /*
@@ -380,7 +402,7 @@ int hwy_get_state(hwy_engine *eng, hwy_state *host);
  * stream-identical reset is host-side (highwayenv_amd/spawn.py) + hwy_set_state.
  * `ego_spacing`/`vehicles_density`/`initial_lane_id` (-1 = random) are the
  * config entries of the same names.  Writes the first observation if obs != NULL
- * (host pointer, [E][A][V][F]; rows of unmasked envs untouched).
+ * (host pointer, [E][A][V][F] -- the observation's own shape; rows of unmasked envs untouched).
  */
 int hwy_reset(hwy_engine *eng, const uint8_t *mask, const uint64_t *seeds, double ego_spacing,
               double vehicles_density, int32_t initial_lane_id, float *obs);
@@ -390,7 +412,7 @@ int hwy_reset(hwy_engine *eng, const uint8_t *mask, const uint64_t *seeds, doubl
  * T x { action_type.act (first frame); road.act(); road.step(dt) } + observe +
  * reward + terminated + truncated + info{speed,crashed}.
  *   actions    int32 [E][A]   in   DiscreteMetaAction ids (HWY_EGO_DIRECT: DiscreteAction ids)
- *   obs        f32   [E][A][V][F]
+ *   obs        f32   [E][A][V][F]   (OccupancyGrid: [E][A][F][W][H]; Lidar: [E][A][cells][2])
  *   reward     f64   [E][A]   (single-agent envs: the reference's scalar reward)
  *   terminated u8    [E]
  *   truncated  u8    [E]
@@ -460,7 +482,7 @@ int hwy_get_behavior(hwy_engine *eng, double *params);
 int hwy_set_controls(hwy_engine *eng, const double *acceleration, const double *steering);
 int hwy_get_controls(hwy_engine *eng, double *acceleration, double *steering);
 
-/* KinematicObservation.observe for the current state (host pointer out). */
+/* KinematicObservation / OccupancyGridObservation / LidarObservation.observe for the current state (host pointer out). */
 int hwy_observe(hwy_engine *eng, float *obs);
 
 /*

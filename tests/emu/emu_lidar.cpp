@@ -1,0 +1,33 @@
+// emu_lidar.cpp -- TEST INFRASTRUCTURE ONLY.  Runs the LidarObservation kernel of the product source
+// (highwayenv_amd/csrc/hwy_lidar.h: hwy_lidar_kernel) on the CPU through hip_emu.h, on the host SoA arrays of a state.  The
+// simulation itself is the family's own driver's (emu_engine.cpp / emu_traffic.cpp / emu_control.cpp): tests/emu/emu_lidar.py runs
+// it and then this, the way hwy_engine.hip launches the lidar kernel after the step kernel.
+#include "hip_emu.h"
+
+#include <vector>
+
+#include "../../highwayenv_amd/csrc/hwy_lidar.h"
+
+extern "C" {
+
+size_t emu_lidar_config_size(void) { return sizeof(hwy_config); }
+
+// LidarObservation of the state `st` ([E][N] planes, pitch == N) -> obs f32 [E][A][cells][2]
+int emu_lidar_observe(const hwy_config *cfg, const hwy_state *st, float *obs) {
+  const int E = cfg->num_envs, N = cfg->num_vehicles;
+  std::vector<int32_t> packed((size_t)E * N);
+  for (size_t k = 0; k < packed.size(); ++k)
+    packed[k] = hwy::pack_word(st->lane[k], st->target_lane[k], st->speed_index[k], st->flags[k], (int)(k % N));
+  hwy::LidarParams lp;
+  std::memset(&lp, 0, sizeof lp);
+  lp.x = st->x; lp.y = st->y; lp.heading = st->heading; lp.speed = st->speed;
+  lp.packed = packed.data();
+  lp.obs = obs;
+  lp.N = N; lp.A = cfg->num_agents; lp.pitch = N; lp.cells = cfg->lidar_cells;
+  for (int a = 0; a < HWY_MAX_AGENTS; ++a) lp.agent_index[a] = a < cfg->num_agents ? cfg->agent_index[a] : 0;
+  lp.max_range = cfg->lidar_max_range;
+  if (cfg->lidar_normalize) emu::launch([](const hwy::LidarParams &q) { hwy::hwy_lidar_kernel<true>(q); }, E * cfg->num_agents, 64, lp);
+  else emu::launch([](const hwy::LidarParams &q) { hwy::hwy_lidar_kernel<false>(q); }, E * cfg->num_agents, 64, lp);
+  return 0;
+}
+}

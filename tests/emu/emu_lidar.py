@@ -1,0 +1,103 @@
+"""TEST INFRASTRUCTURE ONLY: the LidarObservation kernel of the product source on the CPU (tests/emu/emu_lidar.cpp).
+
+``EmuLidarEngine`` has the Python surface of ``highwayenv_amd.engine.Engine`` that the lidar tests use.  It is built the way
+``hwy_engine.hip`` builds a Lidar engine: the simulation is the family's own emulated engine (``EmuEngine`` for IDM traffic with
+meta-actions, ``EmuTrafficEngine`` for the Linear family, ``EmuControlEngine`` for direct ego control) stepping WITHOUT the
+observation that matters -- a one-column Kinematics observation stands in for the null pointer, nothing of the state depends on
+it --, and after every step / reset / observe the lidar kernel (``hwy_lidar.h``) traces the state that call left behind.  A
+K-step rollout is K x (step + lidar), like ``hwy_rollout_device`` on a Lidar engine.  ``HWY_EMU_LIDAR_LIB`` names a prebuilt
+(mutated) emulator instead (tests/test_lidar_mutations.py).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+
+import numpy as np
+
+from highwayenv_amd import _abi
+
+from . import emu
+from .emu import _p
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_ROOT = os.path.dirname(os.path.dirname(_HERE))
+_lib = None
+
+
+def build(force: bool = False) -> str:
+    if os.environ.get("HWY_EMU_LIDAR_LIB"):
+        return os.environ["HWY_EMU_LIDAR_LIB"]
+    out = os.path.join(_HERE, "_build", "libhwy_emu_lidar.so")
+    csrc = os.path.join(_ROOT, "highwayenv_amd", "csrc")
+    srcs = [os.path.join(_HERE, f) for f in ("emu_lidar.cpp", "hip_emu.h")] + [
+        os.path.join(csrc, f) for f in ("hwy_lidar.h", "hwy_device.h", "hwy_math.h")] + [os.path.join(_ROOT, "include", "hwy_engine.h")]
+    if force or not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(s) for s in srcs):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        emu.compile_emulator(srcs[0], out)
+    return out
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        _lib = C.CDLL(build())
+        _lib.emu_lidar_config_size.restype = C.c_size_t
+        assert _lib.emu_lidar_config_size() == C.sizeof(_abi.HwyConfig)
+    return _lib
+
+
+def trace(cfg: _abi.HwyConfig, st: dict) -> np.ndarray:
+    """The lidar kernel on a host state: obs f32 [E, A, cells, 2]."""
+    assert cfg.obs_type == _abi.OBS_LIDAR
+    st = {k: np.ascontiguousarray(st[k]) for k in _abi.STATE_F64 + _abi.STATE_I32 + ["time"]}
+    obs = np.full((cfg.num_envs, cfg.num_agents, cfg.lidar_cells, 2), np.nan, np.float32)
+    s = _abi.state_struct(st)
+    assert lib().emu_lidar_observe(C.byref(cfg), C.byref(s), _p(obs, C.c_float)) == 0
+    return obs
+
+
+def _simulation_config(cfg: _abi.HwyConfig) -> _abi.HwyConfig:
+    """`cfg` as the step kernels of a Lidar engine see it (hwy_params.h: params_from_config)."""
+    sim = _abi.HwyConfig.from_buffer_copy(bytes(cfg))
+    sim.obs_type = _abi.OBS_KINEMATICS
+    return sim
+
+
+class EmuLidarEngine:
+    def __init__(self, cfg: _abi.HwyConfig):
+        assert cfg.obs_type == _abi.OBS_LIDAR and cfg.scenario == _abi.SCENARIO_HIGHWAY
+        self.cfg = cfg
+        self.E, self.N, self.A = cfg.num_envs, cfg.num_vehicles, cfg.num_agents
+        sim = _simulation_config(cfg)
+        if cfg.traffic_model == _abi.TRAFFIC_LINEAR:
+            from .emu_traffic import EmuTrafficEngine
+            self.sim = EmuTrafficEngine(sim)
+        elif cfg.ego_control == _abi.EGO_DIRECT:
+            from .emu_control import EmuControlEngine
+            self.sim = EmuControlEngine(sim)
+        else:
+            self.sim = emu.EmuEngine(sim)
+
+    def __getattr__(self, name):  # state, behaviour parameters, stored controls, auto-reset, frames: the simulation's own
+        return getattr(self.sim, name)
+
+    def observe(self):
+        return trace(self.cfg, self.sim.st)
+
+    def step(self, actions):
+        _, reward, term, trunc, info = self.sim.step(actions)
+        return self.observe(), reward, term, trunc, info
+
+    def rollout(self, actions):
+        acts = np.asarray(actions, np.int32).reshape(-1, self.E, self.A)
+        outs = [self.step(a) for a in acts]
+        info = {key: np.stack([o[4][key] for o in outs]) for key in outs[0][4]}
+        return tuple(np.stack([o[j] for o in outs]) for j in range(4)) + (info,)
+
+    def reset(self, seeds=None, mask=None, **kw):
+        self.sim.reset(seeds=seeds, mask=mask, **kw)
+        obs = self.observe()
+        if mask is not None:  # hwy_reset: rows of unmasked environments are left untouched (zeros from Engine.reset)
+            obs[np.asarray(mask) == 0] = 0
+        return obs
