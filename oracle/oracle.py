@@ -48,11 +48,53 @@ def _p(a, ctype):
     return None if a is None else a.ctypes.data_as(C.POINTER(ctype))
 
 
+class _extras:
+    """What an engine keeps beside its state planes, handed to the oracle for one call: ``st["behavior"]`` [E, N, 5], the
+    Linear family's per-vehicle parameters (``Engine.set_behavior``; ``spawn.spawn_reference_stream`` puts them there), and
+    ``st["ctl_accel"]`` / ``st["ctl_steer"]`` [E, A], the stored action of every direct-control ego (``Engine.set_controls``),
+    which ``frames`` / ``step`` update in place."""
+
+    def __init__(self, cfg, st: dict):
+        self.keep = []
+        if getattr(cfg, "traffic_model", 0) == _abi.TRAFFIC_LINEAR and "behavior" in st:
+            b = st["behavior"]
+            assert b.dtype == np.float64 and b.flags.c_contiguous and b.shape == (cfg.num_envs, cfg.num_vehicles, _abi.HWY_BEHAVIOR_PARAMS)
+            self.keep.append(b)
+        if getattr(cfg, "ego_control", 0) == _abi.EGO_DIRECT and "ctl_accel" in st:
+            for k in ("ctl_accel", "ctl_steer"):
+                a = st[k]
+                assert a.dtype == np.float64 and a.flags.c_contiguous and a.shape == (cfg.num_envs, cfg.num_agents), k
+            self.keep += [st["ctl_accel"], st["ctl_steer"]]
+        self.cfg, self.st = cfg, st
+
+    def __enter__(self):
+        if getattr(self.cfg, "traffic_model", 0) == _abi.TRAFFIC_LINEAR and "behavior" in self.st:
+            lib().orc_set_behavior(_p(self.st["behavior"], C.c_double))
+        if getattr(self.cfg, "ego_control", 0) == _abi.EGO_DIRECT and "ctl_accel" in self.st:
+            lib().orc_set_controls(_p(self.st["ctl_accel"], C.c_double), _p(self.st["ctl_steer"], C.c_double))
+        return self
+
+    def __exit__(self, *exc):
+        lib().orc_set_behavior(None)
+        lib().orc_set_controls(None, None)
+        return False
+
+
+def zero_controls(cfg: _abi.HwyConfig, st: dict) -> dict:
+    """``st`` with the stored action of ``Vehicle.__init__`` (kinematics.py:44) for every direct-control ego."""
+    st["ctl_accel"] = np.zeros((cfg.num_envs, cfg.num_agents))
+    st["ctl_steer"] = np.zeros((cfg.num_envs, cfg.num_agents))
+    return st
+
+
 def frames(cfg: _abi.HwyConfig, st: dict, actions, n_frames: int) -> None:
     """n_frames x {[meta-action]; Road.act(); Road.step(dt)} in place on the SoA dict."""
     acts = None if actions is None else np.ascontiguousarray(actions, np.int32)
     s = _abi.state_struct(st)
-    rc = lib().orc_frames(C.byref(cfg), C.byref(s), _p(acts, C.c_int32), C.c_int32(n_frames))
+    with _extras(cfg, st):
+        rc = lib().orc_frames(C.byref(cfg), C.byref(s), _p(acts, C.c_int32), C.c_int32(n_frames))
+    if rc == _abi.HWY_ERR_ACTION:
+        raise IndexError("action id outside the throttle x steering table")
     assert rc == 0, rc
 
 
@@ -71,7 +113,8 @@ def net_neighbours(cfg: _abi.HwyConfig, st: dict, e: int, slot: int, lane) -> tu
 def observe(cfg: _abi.HwyConfig, st: dict) -> np.ndarray:
     obs = np.zeros((cfg.num_envs, cfg.num_agents, *_abi.obs_shape(cfg)), np.float32)
     s = _abi.state_struct(st)
-    rc = lib().orc_observe(C.byref(cfg), C.byref(s), _p(obs, C.c_float))
+    with _extras(cfg, st):
+        rc = lib().orc_observe(C.byref(cfg), C.byref(s), _p(obs, C.c_float))
     assert rc == 0, rc
     return obs
 
@@ -87,10 +130,13 @@ def step(cfg: _abi.HwyConfig, st: dict, actions) -> tuple:
     speed = np.zeros((E, A), np.float64)
     crashed = np.zeros((E, A), np.uint8)
     s = _abi.state_struct(st)
-    rc = lib().orc_step(C.byref(cfg), C.byref(s), _p(acts, C.c_int32), _p(obs, C.c_float),
-                        _p(reward, C.c_double), _p(term, C.c_uint8), _p(trunc, C.c_uint8),
-                        _p(speed, C.c_double), _p(crashed, C.c_uint8))
+    with _extras(cfg, st):
+        rc = lib().orc_step(C.byref(cfg), C.byref(s), _p(acts, C.c_int32), _p(obs, C.c_float),
+                            _p(reward, C.c_double), _p(term, C.c_uint8), _p(trunc, C.c_uint8),
+                            _p(speed, C.c_double), _p(crashed, C.c_uint8))
     if rc == _abi.HWY_ERR_ACTION:
+        if cfg.ego_control == _abi.EGO_DIRECT:  # the reference's IndexError (action.py:195-196), as the engine reports it
+            raise IndexError("action id outside the throttle x steering table")
         raise KeyError("invalid meta-action")
     assert rc == 0, rc
     return obs, reward, term.astype(bool), trunc.astype(bool), {"speed": speed, "crashed": crashed.astype(bool)}

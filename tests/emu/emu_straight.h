@@ -49,6 +49,13 @@ struct ResetArgs {
   double ego_spacing, vehicles_density;
   int initial_lane_id;
 };
+// the OccupancyGrid workspace [E][A][2][W*H] hwy_engine.hip allocates for every family (null for the other observations)
+inline int32_t *grid_ws_for(const hwy_config *cfg) {
+  static std::vector<int32_t> ws;
+  if (cfg->obs_type != HWY_OBS_OCCUPANCY_GRID) return nullptr;
+  ws.assign((size_t)cfg->num_envs * cfg->num_agents * 2 * cfg->grid_shape[0] * cfg->grid_shape[1], 0);
+  return ws.data();
+}
 // StepParams from hwy_config, the image and the reset parameters (zeroes everything else of p)
 inline void fill_step_params(const hwy_config *cfg, HostImage &img, hwy_state *st, uint8_t *done, uint32_t *episode, const ResetArgs &ra,
                              StepParams &p) {
@@ -64,6 +71,7 @@ inline void fill_step_params(const hwy_config *cfg, HostImage &img, hwy_state *s
   p.rp.initial_lane_id = ra.initial_lane_id;
   p.rp.fast = (cfg->flags & HWY_C_EGO_ONLY_COLLISIONS) ? 1 : 0;
   p.rp.base_seed = ra.base_seed;
+  p.grid_ws = grid_ws_for(cfg);
 }
 
 enum Which { STEP, ROLLOUT, RESET, OBSERVE };

@@ -2,7 +2,8 @@
 
 ``EmuTrafficEngine`` has the Python surface of ``highwayenv_amd.engine.Engine`` that the traffic tests use (state, behaviour
 parameters, step, frames, K-step rollout, device reset, auto-reset, math probes), so that tests/test_traffic_parity.py runs
-the same checks against this emulation and against the HIP engine on the MI355X.
+the same checks against this emulation and against the HIP engine on the MI355X.  ``HWY_EMU_TRAFFIC_LIB`` names a prebuilt
+(mutated) emulator instead (tests/test_families_mutations.py).
 """
 from __future__ import annotations
 
@@ -17,7 +18,8 @@ from .emu import _p
 
 
 class EmuTrafficEngine(emu.StraightFamilyEngine):
-    SOURCE, SYMBOL, EXTRA, BAD_ACTION = "emu_traffic.cpp", "emu_traffic", "planes", (KeyError, "invalid meta-action")
+    SOURCE, SYMBOL, ENV, EXTRA = "emu_traffic.cpp", "emu_traffic", "HWY_EMU_TRAFFIC_LIB", "planes"
+    BAD_ACTION = (KeyError, "invalid meta-action")
 
     def __init__(self, cfg: _abi.HwyConfig):
         assert cfg.traffic_model == _abi.TRAFFIC_LINEAR

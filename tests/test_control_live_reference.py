@@ -16,6 +16,7 @@ import pytest
 
 from highwayenv_amd import spawn
 from oracle import ref_stub
+from tests.families_util import check_free_running_steps
 from tests.control_util import CONTROL_DIR, ControlGolden, make_engine
 
 pytestmark = [pytest.mark.reference,
@@ -87,3 +88,4 @@ def test_emulation_against_live_reference(case):
         np.testing.assert_array_equal(eng.get_controls()[0], z["step_act_accel"][t][:, agents], err_msg=what + ": stored acceleration")
         if term[0]:
             break
+    check_free_running_steps(g)  # the same run through the oracle: state 1e-8, the egos' speed and stored action bit for bit

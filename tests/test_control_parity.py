@@ -3,7 +3,8 @@ hwy_step_wave_direct_kernel / hwy_rollout_wave_direct_kernel for N <= 64, and of
 hwy_step_direct_kernel / hwy_rollout_direct_kernel / hwy_reset_direct_kernel) against the unmodified reference's fixtures
 (tests/golden/control), on the CPU emulation of the kernel source (``emu``) and on the MI355X (``hip``).
 
-The C oracle has no plain-Vehicle ego: the reference's own traces are the yardstick.  The ego's speed is a closed recurrence on
+Here the reference's own traces are the yardstick; the C oracle restates the plain-Vehicle ego too (pinned to these fixtures by
+tests/test_oracle_golden_families.py) and is the yardstick beyond their shapes (tests/test_fuzz_configs.py, tests/test_families_edge_cases.py).  The ego's speed is a closed recurrence on
 exactly rounded operations (speed += a * dt as a product and a sum, MAX_SPEED - speed, -1.0 * speed), so it and the stored
 acceleration are compared BIT FOR BIT; a teacher-forced frame whose discrete outcome differs from the reference's would be a knife
 edge, and the budget for those is 0 on every fixture."""

@@ -6,50 +6,7 @@ import pytest
 from highwayenv_amd import _abi, spawn
 from oracle import oracle
 from tests.backends import BACKENDS, make_engine
-from tests.golden_util import assert_obs_close, assert_state_close
-
-
-def rollout(backend, cfg_d, fast, E, steps, seed, mutate=None, actions=None, compare_wrecks=False):
-    cfg = _abi.make_config(cfg_d, E, fast=fast)
-    st = spawn.spawn_reference_stream(cfg, np.arange(E) + 100 * seed, cfg_d["ego_spacing"], cfg_d["vehicles_density"],
-                                      cfg_d["initial_lane_id"])
-    if mutate:
-        mutate(st)
-    ref = _abi.copy_state(st)
-    eng = make_engine(backend, cfg)
-    eng.set_state(st)
-    rng = np.random.default_rng(seed)
-    live = np.ones(E, bool)
-    for t in range(steps):
-        acts = (rng.integers(0, _abi.num_actions(cfg), size=(E, cfg.num_agents)) if actions is None else np.full((E, cfg.num_agents), actions[t % len(actions)])).astype(np.int32)
-        obs, reward, term, trunc, info = eng.step(acts)
-        with oracle.impact_margins(cfg) as m:
-            o2, r2, te2, tr2, i2 = oracle.step(cfg, ref, acts)
-        wreck = ((ref["flags"] & (_abi.F_CRASHED | _abi.F_HAS_IMPACT)) != 0).any(1)
-        # the step of an env's first collision is compared like any other (terminal observation, reward, positions) unless a
-        # push direction sits on the knife edge (|d.normal| < 1e-9, utils.py:232-236); assert_state_close compares |impact|
-        # (free-running: the engine's state may differ from the oracle's by the 1e-7 the previous steps are held to, so a push
-        #  direction decided by |d.normal| below 1e-6 can flip -- two cars tracking one lane centre are that close laterally)
-        ok = live & (~wreck | compare_wrecks | (m.margin.min(1) >= 1e-6))
-        what = f"step {t}"
-        np.testing.assert_array_equal(term[live], te2[live], err_msg=what)
-        np.testing.assert_array_equal(trunc, tr2, err_msg=what)
-        np.testing.assert_allclose(reward[ok], r2[ok], rtol=0, atol=1e-9, err_msg=what)
-        got = eng.get_state()
-        # free-running (no re-synchronisation of live environments): every step without a collision at 1e-7; the step of a
-        # collision at 2.5e-6 -- the minimum-translation vector is a difference of projected corner coordinates, i.e. it carries
-        # the two bodies' heading differences times a 2.7 m lever arm on top of their position differences (largest seen in 20 000
-        # random configurations: 1.2e-6 m); un-normalised relative features are differences of two such positions
-        for rows, atol, atol_obs in ((ok & ~wreck, 1e-7, 1e-6), (ok & wreck, 2.5e-6, 5e-6)):
-            assert_obs_close(obs[rows], o2[rows], bool(cfg.flags & _abi.C_GRID_IMAGE), what, atol=atol_obs)
-            assert_state_close({k: v[rows] for k, v in got.items()}, {k: v[rows] for k, v in ref.items()}, atol=atol, what=what)
-        live &= ~wreck
-        if not live.all():  # keep dead envs in lock-step with the oracle so that live ones stay comparable
-            for k in got:
-                got[k][~live] = ref[k][~live]
-            eng.set_state(got)
-    eng.close()
-    return ref
+from tests.families_util import rollout  # noqa: F401  (the shared free-running comparison; tests/test_fuzz_configs.py imports it from here)
 
 
 @pytest.mark.parametrize("backend", BACKENDS)

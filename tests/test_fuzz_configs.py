@@ -98,6 +98,104 @@ def test_random_wide_configurations_vs_oracle(chunk):
             raise AssertionError(f"chunk {chunk} config {k}: {cfg}\n{ex}") from ex
 
 
+# ---- the Linear traffic family, direct ego control and the Lidar observation -------------------------------------------------
+FAMILY_SEEDS = {"linear": 31000, "direct": 37000, "lidar": 41000}
+LINEAR_CLASSES = ["LinearVehicle", "AggressiveVehicle", "DefensiveVehicle"]
+LIDAR_CELLS = [1, 2, 3, 7, 16, 24, 63, 64]
+# at least this share of the live env-steps of a chunk must be compared in full; the rest fall under rollout()'s one exclusion (a
+# collision whose push direction the oracle itself reports within 1e-6 of the knife edge).  A condition on the oracle's own margins:
+# tests/test_families_fuzz_coverage.py checks it on the oracle alone for the draws below, chunks 0..99.
+FULL_FLOOR = 0.9
+
+
+def random_discrete_action(rng):
+    """A DiscreteAction over every field _abi.make_config takes (tests/test_control_host.py): 1 .. 16 points per axis, either axis
+    off, acceleration range, steering range up to (just inside) +-pi/3, clip."""
+    act = {"type": "DiscreteAction", "actions_per_axis": int(rng.choice([1, 2, 3, 3, 4, 5, 7, 16])), "clip": bool(rng.integers(2))}
+    if rng.integers(2):
+        act["acceleration_range"] = [-float(rng.uniform(1, 6)), float(rng.uniform(1, 6))]
+    if rng.integers(4):  # (else the class default, +-pi/4)
+        hi = float(rng.choice([0.02, 0.05, 0.1, 0.3, np.pi / 4, 1.047]))
+        act["steering_range"] = [-hi if rng.integers(3) else -float(rng.uniform(0, hi)), hi]
+    axis = int(rng.integers(4))
+    if axis == 0:
+        act["longitudinal"] = False
+    elif axis == 1:
+        act["lateral"] = False
+    return act
+
+
+def family_cases(family, chunk):
+    """The configurations of one chunk of a family's fuzz: (config, fast, E, steps, seed).  Eight with N <= 64 vehicles -- the
+    one-wavefront kernels and, every other one (tune_block_kernel = 1), the workgroup kernel at those sizes -- , one with 65 .. 128
+    and one with 129 .. 256, the workgroup kernel's own sizes, at a smaller E x steps (like test_random_wide_configurations_vs_oracle)
+    so that a chunk costs no more than an IDM chunk."""
+    rng = np.random.default_rng(FAMILY_SEEDS[family] + chunk)
+    for k in range(10):
+        cfg, fast = random_config(rng)
+        agents = cfg["controlled_vehicles"]
+        multi = (lambda kind, inner: inner if agents == 1 else {"type": "MultiAgent" + kind, kind.lower() + "_config": inner})
+        mode = family if family != "lidar" else ["idm", "linear", "direct"][int(rng.integers(3))]
+        if mode == "linear":
+            cfg["other_vehicles_type"] = "highway_env.vehicle.behavior." + LINEAR_CLASSES[int(rng.integers(3))]
+        if mode == "direct":
+            cfg["action"] = multi("Action", random_discrete_action(rng))
+        if family == "lidar":
+            cfg["observation"] = multi("Observation", {"type": "LidarObservation", "cells": int(rng.choice(LIDAR_CELLS)),
+                                                       "maximum_range": float(rng.uniform(15, 150)), "normalize": bool(rng.integers(2))})
+        E, steps = 8, 8
+        if k < 8:
+            cfg["vehicles_count"] = int(rng.integers(0, 65 - agents))
+            cfg["tuning"] = {"block_kernel": (chunk + k) % 2}
+        elif k == 8:
+            cfg["vehicles_count"] = int(rng.integers(65 - agents, 129 - agents))
+            E, steps = 4, 6
+        else:
+            cfg["vehicles_count"] = int(rng.integers(129 - agents, 257 - agents))
+            E, steps = 2, 4
+        yield cfg, fast, E, steps, chunk * 100 + k
+
+
+def run_family_chunk(family, chunk, backend):
+    """One chunk of a family through rollout(); returns the env-step counts (`backend` None: the oracle alone, counts only)."""
+    stats = {"live": 0, "full": 0, "excluded": 0}
+    for k, (cfg, fast, E, steps, seed) in enumerate(family_cases(family, chunk)):
+        try:
+            rollout(backend, cfg, fast, E=E, steps=steps, seed=seed, stats=stats)
+        except AssertionError as ex:  # name the configuration in the failure
+            raise AssertionError(f"chunk {chunk} config {k}: {cfg}\n{ex}") from ex
+    return stats
+
+
+def _family_chunk(family, chunk):
+    stats = run_family_chunk(family, chunk, BACKEND)
+    print(f"\n{family} fuzz chunk {chunk}: {stats['live']} live env-steps, {stats['full']} compared in full, {stats['excluded']} "
+          f"under the push-direction exclusion ({100.0 * stats['full'] / max(stats['live'], 1):.1f} % in full)")
+    assert stats["full"] >= FULL_FLOOR * stats["live"], stats
+
+
+@pytest.mark.parametrize("chunk", CHUNKS)  # 10 configurations each
+def test_random_linear_configurations_vs_oracle(chunk):
+    """random_config() with LinearVehicle / AggressiveVehicle / DefensiveVehicle traffic (1 .. 3 agents, every observation variant
+    of the family): the spawn's parameters on the engine and on the oracle, rollout()'s comparison."""
+    _family_chunk("linear", chunk)
+
+
+@pytest.mark.parametrize("chunk", CHUNKS)
+def test_random_direct_configurations_vs_oracle(chunk):
+    """random_config() with IDM traffic and a drawn DiscreteAction (random_discrete_action), single- and multi-agent: ids drawn
+    over the whole table, stored controls compared with the state."""
+    _family_chunk("direct", chunk)
+
+
+@pytest.mark.parametrize("chunk", CHUNKS)
+def test_random_lidar_configurations_vs_oracle(chunk):
+    """The Lidar observation (cells 1 .. 64, maximum_range 15 .. 150 m, normalize on / off) over IDM, Linear and direct-control
+    engines, single- and multi-agent: every observation against the oracle's trace of the engine's own state with no exclusion
+    (tests/families_util.py: assert_lidar_of_own_state), the dynamics of the same run like everywhere else."""
+    _family_chunk("lidar", chunk)
+
+
 def random_merge_config(rng):
     from highwayenv_amd import merge
     cfg = merge.merge_generic_default_config()

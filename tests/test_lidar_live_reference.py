@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 
 from oracle import ref_stub
+from oracle import oracle
+from tests.families_util import check_free_running_steps, golden_state
 from tests.lidar_util import LIDAR_DIR, OBS_ATOL, LidarGolden, cells_off, make_engine
 
 pytestmark = [pytest.mark.reference,
@@ -76,3 +78,9 @@ def test_emulation_against_live_reference(case):
         np.testing.assert_array_equal(term[rows], g.z["terminated"][t][rows].astype(bool), err_msg=f"{what} step {t}: terminated")
         alive &= ~np.asarray(term, bool)
     eng.close()
+    # the same case through the oracle: every recorded state traced, then the free run (no cell beyond 1e-6 in either)
+    cfg = g.hwy_config()
+    for index in [None] + list(range(g.steps)):
+        st = golden_state(g, "init" if index is None else "step", index)
+        assert cells_off(oracle.observe(cfg, st), g.reference_obs(index)) == 0, f"{what}: the oracle on recorded state {index}"
+    check_free_running_steps(g)

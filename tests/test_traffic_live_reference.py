@@ -4,7 +4,8 @@ vehicles_density, simulation / policy frequency, controlled_vehicles and highway
 the fixture generator (tests/golden/traffic/make_golden_traffic.py: run) and the emulation is held to the fixtures' checks: the
 initial state and parameters of the host spawn bit for bit, then every policy step's observation at 1e-6, reward at 1e-9,
 terminated / truncated / crashed and the lanes exact, each environment up to its first termination.  Build container only (the
-reference does not exist on the GPU machines).  HWY_TRAFFIC_REF_CASES: configurations per class (default 12)."""
+reference does not exist on the GPU machines).  Every case is also run through the C oracle (oracle/hwy_oracle.c), which is held to the
+same run: observations 1e-6, reward and speed 1e-9, the state after every step 1e-8, flags and lanes exact.  HWY_TRAFFIC_REF_CASES: configurations per class (default 12)."""
 import importlib.util
 import json
 import os
@@ -15,6 +16,7 @@ import pytest
 
 from highwayenv_amd import _abi, spawn
 from oracle import ref_stub
+from tests.families_util import check_free_running_steps
 from tests.traffic_util import TRAFFIC_DIR, TrafficGolden, make_engine
 
 pytestmark = [pytest.mark.reference,
@@ -88,3 +90,4 @@ def test_emulation_against_live_reference(cls, case):
             np.testing.assert_array_equal(got[k], z["step_" + k][t], err_msg=what + ": " + k)
         if term[0]:
             break
+    check_free_running_steps(g)  # the same run through the oracle (tests/test_oracle_golden_families.py's assertions)

@@ -3,7 +3,8 @@
 hwy_rollout_linear_kernel / hwy_reset_linear_kernel) against the unmodified reference's fixtures
 (tests/golden/traffic), on the CPU emulation of the kernel source (``emu``) and on the MI355X (``hip``).
 
-The C oracle has no Linear model: the reference's own traces are the yardstick.  Knife edges: a discrete
+Here the reference's own traces are the yardstick; the C oracle restates the Linear model too (pinned to these fixtures by
+tests/test_oracle_golden_families.py) and is the yardstick beyond their shapes (tests/test_fuzz_configs.py, tests/test_families_edge_cases.py).  Knife edges: a discrete
 decision that sits within rounding of its threshold may go the other way under another libm or BLAS (np.dot's summation order
 is not specified); such frames are COUNTED per fixture and capped at the counts measured on both backends, never dropped."""
 import numpy as np
