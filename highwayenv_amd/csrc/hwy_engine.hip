@@ -282,40 +282,8 @@ static void fill_params(const hwy_engine *eng, StepParams &p) {
 
 static bool is_ix(const hwy_engine *eng) { return eng->cfg.scenario == HWY_SCENARIO_INTERSECTION; }
 static bool is_linear(const hwy_engine *eng) { return eng->cfg.traffic_model == HWY_TRAFFIC_LINEAR; }
-static void fill_linear(const hwy_engine *eng, const StepParams &p, hwy::LinearParams &lp) {
-  std::memset(&lp, 0, sizeof lp);
-  lp.s = p;
-  lp.la.behavior = eng->d_behavior;
-  lp.la.plane = (long long)eng->cfg.num_envs * eng->pitch;
-  lp.la.lc_gain = eng->cfg.traffic_lc_min_acc_gain;
-}
 static bool is_direct(const hwy_engine *eng) { return eng->cfg.ego_control == HWY_EGO_DIRECT; }
 static bool is_lidar(const hwy_engine *eng) { return eng->cfg.obs_type == HWY_OBS_LIDAR; }
-// LidarObservation of the CURRENT state of every environment into d_obs ([E][A][cells][2]), enqueued behind whatever wrote that state
-static hipError_t launch_lidar_obs(const hwy_engine *eng, float *d_obs) {
-  hwy::LidarParams lp;
-  std::memset(&lp, 0, sizeof lp);
-  const size_t plane = (size_t)eng->cfg.num_envs * eng->pitch;
-  lp.x = eng->d_f64 + 0 * plane; lp.y = eng->d_f64 + 1 * plane; lp.heading = eng->d_f64 + 2 * plane; lp.speed = eng->d_f64 + 3 * plane;
-  lp.packed = eng->d_packed;
-  lp.obs = d_obs;
-  lp.N = eng->cfg.num_vehicles; lp.A = eng->cfg.num_agents; lp.pitch = eng->pitch; lp.cells = eng->cfg.lidar_cells;
-  for (int a = 0; a < HWY_MAX_AGENTS; ++a) lp.agent_index[a] = a < eng->cfg.num_agents ? eng->cfg.agent_index[a] : 0;
-  lp.max_range = eng->cfg.lidar_max_range;
-  return hwy::launch_lidar(lp, eng->cfg.lidar_normalize != 0, eng->cfg.num_envs * eng->cfg.num_agents, eng->stream);
-}
-static void fill_direct(const hwy_engine *eng, const StepParams &p, hwy::DirectParams &dp) {
-  std::memset(&dp, 0, sizeof dp);
-  dp.s = p;
-  dp.da.ctl_accel = eng->d_controls;
-  dp.da.ctl_steer = eng->d_controls + (size_t)eng->cfg.num_envs * eng->cfg.num_agents;
-  dp.da.n_accel = eng->cfg.n_accel;
-  dp.da.n_steer = eng->cfg.n_steer;
-  for (int k = 0; k < HWY_MAX_ACTIONS_PER_AXIS; ++k) {
-    dp.da.accel_axis[k] = eng->cfg.accel_axis[k];
-    dp.da.steer_axis[k] = eng->cfg.steer_axis[k];
-  }
-}
 // ids of the configured action table: [0, n)
 static int num_action_ids(const hwy_engine *eng) {
   if (is_direct(eng)) return eng->cfg.n_accel * eng->cfg.n_steer;
@@ -355,36 +323,42 @@ static auto with_family(const hwy_engine *eng, const StepParams &p, Fn &&fn) {
     hwy::net_params_from_config(eng->cfg, p, np);
     return fn(np);
   }
-  if (is_linear(eng)) {
-    hwy::LinearParams lp;
-    fill_linear(eng, p, lp);
-    return fn(lp);
-  }
-  if (is_direct(eng)) {
-    hwy::DirectParams dp;
-    fill_direct(eng, p, dp);
-    return fn(dp);
-  }
+  if (is_linear(eng)) return fn(hwy::LinearParams{p, hwy::linear_args(eng->cfg, eng->d_behavior, eng->pitch)});
+  if (is_direct(eng)) return fn(hwy::DirectParams{p, hwy::direct_args(eng->cfg, eng->d_controls)});
   return fn(p);
 }
-static hwy::Launch launch_of(const hwy_engine *eng) {
-  return {eng->cfg.num_envs, eng->stream, eng->waves_per_eu, eng->rollout_waves_per_eu, eng->force_block_kernel, eng->cfg.tune_extra_lds};
+// start / stop: the events the launch records its dispatch's begin / end timestamps into (timed_launch)
+static hwy::Launch launch_of(const hwy_engine *eng, hipEvent_t start = nullptr, hipEvent_t stop = nullptr) {
+  return {eng->cfg.num_envs, eng->stream, eng->waves_per_eu, eng->rollout_waves_per_eu, eng->force_block_kernel, eng->cfg.tune_extra_lds,
+          start, stop};
 }
-static hipError_t launch_step_any(const hwy_engine *eng, const StepParams &p) {
-  return with_family(eng, p, [&](const auto &a) { return hwy::launch_step(a, launch_of(eng)); });
-}
-static hipError_t launch_reset_any(const hwy_engine *eng, const StepParams &p) {
-  return with_family(eng, p, [&](const auto &a) { return hwy::launch_reset(a, launch_of(eng)); });
-}
-static hipError_t launch_observe_any(const hwy_engine *eng, const StepParams &p) {
-  return with_family(eng, p, [&](const auto &a) { return hwy::launch_observe(a, launch_of(eng)); });
+// One launch of the engine's family -- its step kernel (p.full_step / p.n_frames as bound by the caller), its reset or its observe
+// kernel, with the observation going to p.obs -- and, on a Lidar engine, the trace behind it: the family's kernel runs with a null
+// `obs` (the observe kernel has nothing else to do and is not launched), then hwy_lidar.h's kernel observes the state it left.
+enum Stage { STEP, RESET, OBSERVE };
+static hipError_t launch_stage(const hwy_engine *eng, Stage stage, StepParams p, hipEvent_t start = nullptr, hipEvent_t stop = nullptr) {
+  float *obs = p.obs;
+  if (is_lidar(eng)) p.obs = nullptr;
+  const hwy::Launch l = launch_of(eng, start, stop);
+  hipError_t e = hipSuccess;
+  if (stage == STEP) e = with_family(eng, p, [&](const auto &a) { return hwy::launch_step(a, l); });
+  else if (stage == RESET) e = with_family(eng, p, [&](const auto &a) { return hwy::launch_reset(a, l); });
+  else if (!is_lidar(eng)) e = with_family(eng, p, [&](const auto &a) { return hwy::launch_observe(a, l); });
+  if (e != hipSuccess || !is_lidar(eng) || !obs) return e;
+  const size_t plane = (size_t)eng->cfg.num_envs * eng->pitch;
+  const double *f = eng->d_f64;
+  const hwy::LidarParams lp = hwy::lidar_params(eng->cfg, f, f + plane, f + 2 * plane, f + 3 * plane, eng->d_packed, eng->pitch, obs);
+  return hwy::launch_lidar(lp, eng->cfg.lidar_normalize != 0, eng->cfg.num_envs * eng->cfg.num_agents, eng->stream);
 }
 
-static size_t io_counts(const hwy_config &c, size_t *n_act, size_t *n_obs, size_t *n_ea) {
-  *n_act = (size_t)c.num_envs * c.num_agents;
-  *n_obs = *n_act * hwy::obs_len(c);
-  *n_ea = *n_act;
-  return 0;
+// rows of the per-agent planes (actions, reward, info) of one policy step, and floats of its observation
+static size_t num_agent_rows(const hwy_config &c) { return (size_t)c.num_envs * c.num_agents; }
+static size_t num_obs_floats(const hwy_config &c) { return num_agent_rows(c) * hwy::obs_len(c); }
+
+template <typename T>
+static hipError_t alloc_zeroed(T *&ptr, size_t bytes, hipStream_t stream) {
+  const hipError_t e = hipMalloc((void **)&ptr, bytes);
+  return e != hipSuccess ? e : hipMemsetAsync(ptr, 0, bytes, stream);
 }
 
 extern "C" int hwy_create(const hwy_config *cfg, int device, void *stream, hwy_engine **out) {
@@ -401,14 +375,7 @@ extern "C" int hwy_create(const hwy_config *cfg, int device, void *stream, hwy_e
   eng->cfg = *cfg;
   eng->device = device;
   eng->pitch = (cfg->num_vehicles + 7) & ~7;  // 64-byte aligned rows of f64
-  // 0 = the engine's choice: the wide kernel (hwy_wave2.h) for 64 < N <= 128, the workgroup kernel beyond -- three / four vehicles
-  // per thread are one 338 / 442-VGPR wavefront per SIMD and measured slower there (1024 x 201: 312 us against 240,
-  // profiles/r05_history.md); 1 = the workgroup kernel wherever it exists; 2 = the wide kernel wherever it exists (N <= 256)
-  eng->force_block_kernel = cfg->tune_block_kernel == 1 || (cfg->tune_block_kernel == 0 && cfg->num_vehicles > 128);
-  // the families without a wide kernel (hwy_wave2.h is IDM with meta-actions only: Linear traffic, direct ego control): the
-  // one-wavefront kernel for N <= 64, the workgroup kernel beyond, and tune_block_kernel == 2 is the engine's own choice
-  if (cfg->traffic_model == HWY_TRAFFIC_LINEAR || cfg->ego_control == HWY_EGO_DIRECT)
-    eng->force_block_kernel = cfg->tune_block_kernel == 1 || cfg->num_vehicles > 64;
+  eng->force_block_kernel = hwy::force_block_kernel(*cfg);  // hwy_config.tune_block_kernel resolved (hwy_params.h)
   // road-network kernel: 128 VGPRs, 4 waves/SIMD, no spills.
   // intersection kernel with helper lanes (N <= 32, hwy_ix.h): 150 VGPRs, but 20.2 KB of LDS per one-wavefront workgroup keep it
   // at 2 per SIMD.  Without them (N > 32, or tune_ix_no_helpers): 128 VGPRs / 16.7 KB (2048 x 30: 371.9 us against 285.1)
@@ -445,50 +412,41 @@ extern "C" int hwy_create(const hwy_config *cfg, int device, void *stream, hwy_e
     eng->own_stream = true;
   }
   const size_t E = cfg->num_envs, plane = E * eng->pitch;
-  size_t n_act, n_obs, n_ea;
-  io_counts(*cfg, &n_act, &n_obs, &n_ea);
+  const size_t n_act = num_agent_rows(*cfg), n_obs = num_obs_floats(*cfg);
+  // ALLOC: device memory; ALLOC0: ... zeroed (on the engine's stream: synchronised below)
 #define ALLOC(ptr, bytes) if ((e = hipMalloc((void **)&(ptr), (bytes))) != hipSuccess) return bail(e, "hipMalloc " #ptr)
-  ALLOC(eng->d_f64, plane * 9 * sizeof(double));
-  ALLOC(eng->d_packed, plane * sizeof(int32_t));
-  if (cfg->traffic_model == HWY_TRAFFIC_LINEAR) {
-    ALLOC(eng->d_behavior, plane * HWY_BEHAVIOR_PARAMS * sizeof(double));
-    if ((e = hipMemsetAsync(eng->d_behavior, 0, plane * HWY_BEHAVIOR_PARAMS * sizeof(double), eng->stream)) != hipSuccess) return bail(e, "hipMemset");
-  }
-  if (cfg->ego_control == HWY_EGO_DIRECT) {
-    ALLOC(eng->d_controls, 2 * E * cfg->num_agents * sizeof(double));
-    if ((e = hipMemsetAsync(eng->d_controls, 0, 2 * E * cfg->num_agents * sizeof(double), eng->stream)) != hipSuccess) return bail(e, "hipMemset");
-  }
+#define ALLOC0(ptr, bytes) if ((e = alloc_zeroed((ptr), (bytes), eng->stream)) != hipSuccess) return bail(e, "hipMalloc / hipMemset " #ptr)
+  if (cfg->traffic_model == HWY_TRAFFIC_LINEAR) ALLOC0(eng->d_behavior, plane * HWY_BEHAVIOR_PARAMS * sizeof(double));
+  if (cfg->ego_control == HWY_EGO_DIRECT) ALLOC0(eng->d_controls, 2 * n_act * sizeof(double));
   if (cfg->scenario == HWY_SCENARIO_INTERSECTION) {
-    ALLOC(eng->d_route, plane * sizeof(long long));
-    ALLOC(eng->d_road_steps, E * sizeof(int32_t));
+    ALLOC0(eng->d_route, plane * sizeof(long long));
+    ALLOC0(eng->d_road_steps, E * sizeof(int32_t));
     ALLOC(eng->d_gnet, sizeof(hwy_glane) * HWY_MAX_GLANES);
-    if ((e = hipMemsetAsync(eng->d_route, 0, plane * sizeof(long long), eng->stream)) != hipSuccess) return bail(e, "hipMemset");
-    if ((e = hipMemsetAsync(eng->d_road_steps, 0, E * sizeof(int32_t), eng->stream)) != hipSuccess) return bail(e, "hipMemset");
     if ((e = hipMemcpy(eng->d_gnet, cfg->gnet, sizeof(hwy_glane) * HWY_MAX_GLANES, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
     if (!(cfg->flags & HWY_C_HOST_TRAFFIC) && !cfg->tune_ix_no_prewarm) {  // (tuning: every auto-reset runs its warm-up inline)
-      ALLOC(eng->d_shadow_f64, plane * 9 * sizeof(double));
+      ALLOC0(eng->d_shadow_f64, plane * 9 * sizeof(double));
       ALLOC(eng->d_shadow_packed, plane * sizeof(int32_t));
       ALLOC(eng->d_shadow_route, plane * sizeof(long long));
       ALLOC(eng->d_shadow_meta, E * 4 * sizeof(int32_t));
-      if ((e = hipMemsetAsync(eng->d_shadow_f64, 0, plane * 9 * sizeof(double), eng->stream)) != hipSuccess) return bail(e, "hipMemset");
-      if ((e = hipMemsetAsync(eng->d_shadow_meta, 0xff, E * 4 * sizeof(int32_t), eng->stream)) != hipSuccess) return bail(e, "hipMemset");
+      if ((e = invalidate_shadows(eng)) != hipSuccess) return bail(e, "hipMemset");
     }
   }
-  ALLOC(eng->d_counters, HWY_CTR_COUNT * sizeof(unsigned long long));
-  if ((e = hipMemsetAsync(eng->d_counters, 0, HWY_CTR_COUNT * sizeof(unsigned long long), eng->stream)) != hipSuccess) return bail(e, "hipMemset");
-  ALLOC(eng->d_time, E * sizeof(double));
-  ALLOC(eng->d_done, E);
-  ALLOC(eng->d_episode, E * sizeof(uint32_t));
+  ALLOC0(eng->d_counters, HWY_CTR_COUNT * sizeof(unsigned long long));
+  ALLOC0(eng->d_f64, plane * 9 * sizeof(double));
+  ALLOC0(eng->d_packed, plane * sizeof(int32_t));
+  ALLOC0(eng->d_time, E * sizeof(double));
+  ALLOC0(eng->d_done, E);
+  ALLOC0(eng->d_episode, E * sizeof(uint32_t));
   ALLOC(eng->d_actions, n_act * sizeof(int32_t));
   {
     auto up = [](size_t v) { return (v + 63) & ~(size_t)63; };
     size_t off = 0;
-    eng->off_reward = off;  off = up(off + n_ea * sizeof(double));
-    eng->off_speed = off;   off = up(off + n_ea * sizeof(double));
+    eng->off_reward = off;  off = up(off + n_act * sizeof(double));
+    eng->off_speed = off;   off = up(off + n_act * sizeof(double));
     eng->off_obs = off;     off = up(off + n_obs * sizeof(float));
     eng->off_term = off;    off = up(off + E);
     eng->off_trunc = off;   off = up(off + E);
-    eng->off_crashed = off; off = up(off + n_ea);
+    eng->off_crashed = off; off = up(off + n_act);
     eng->out_bytes = off;
   }
   ALLOC(eng->d_out, eng->out_bytes);
@@ -500,27 +458,16 @@ extern "C" int hwy_create(const hwy_config *cfg, int device, void *stream, hwy_e
   eng->d_info_crashed = (uint8_t *)(eng->d_out + eng->off_crashed);
   ALLOC(eng->d_mask, E);
   ALLOC(eng->d_seeds, E * sizeof(uint64_t));
-  if (cfg->obs_type == HWY_OBS_OCCUPANCY_GRID)
-    ALLOC(eng->d_grid_ws, n_act * 2 * (size_t)cfg->grid_shape[0] * cfg->grid_shape[1] * sizeof(int32_t));
+  if (cfg->obs_type == HWY_OBS_OCCUPANCY_GRID) ALLOC(eng->d_grid_ws, hwy::grid_ws_len(*cfg) * sizeof(int32_t));
+#undef ALLOC0
 #undef ALLOC
-  if ((e = hipMemsetAsync(eng->d_f64, 0, plane * 9 * sizeof(double), eng->stream)) != hipSuccess) return bail(e, "hipMemset");
-  if ((e = hipMemsetAsync(eng->d_packed, 0, plane * sizeof(int32_t), eng->stream)) != hipSuccess) return bail(e, "hipMemset");
-  if ((e = hipMemsetAsync(eng->d_time, 0, E * sizeof(double), eng->stream)) != hipSuccess) return bail(e, "hipMemset");
-  if ((e = hipMemsetAsync(eng->d_done, 0, E, eng->stream)) != hipSuccess) return bail(e, "hipMemset");
-  if ((e = hipMemsetAsync(eng->d_episode, 0, E * sizeof(uint32_t), eng->stream)) != hipSuccess) return bail(e, "hipMemset");
   // pinned staging: the largest of {state SoA, step I/O}
   const size_t state_bytes = plane * (9 * sizeof(double) + sizeof(int32_t) + sizeof(long long)) + E * (sizeof(double) + sizeof(int32_t));
   const size_t io_bytes = eng->out_bytes + n_act * 4 + E * 9 + 64;
   eng->h_pinned_bytes = state_bytes > io_bytes ? state_bytes : io_bytes;
   if ((e = hipHostMalloc(&eng->h_pinned, eng->h_pinned_bytes, hipHostMallocDefault)) != hipSuccess) return bail(e, "hipHostMalloc");
   if ((e = hipStreamSynchronize(eng->stream)) != hipSuccess) return bail(e, "hipStreamSynchronize");
-  // default reset parameters: highway-v0 semantics (every vehicle checks collisions)
-  eng->rp.ego_spacing = 2.0;
-  eng->rp.other_spacing = 1.0;
-  eng->rp.lane_factor = std::exp(-5.0 / 40.0 * cfg->lanes_count);
-  eng->rp.initial_lane_id = -1;
-  eng->rp.fast = (cfg->flags & HWY_C_EGO_ONLY_COLLISIONS) ? 1 : 0;  // HighwayEnvFast (highway_env.py:177-182)
-  eng->rp.base_seed = 0;
+  eng->rp = hwy::default_reset_params(*cfg);
   // issue-priority turns: on by default only where the whole grid of the step kernel is resident at once
   if (cfg->tune_prio_shift > 0) eng->prio_shift = cfg->tune_prio_shift;
   else if (cfg->tune_prio_shift == 0) {
@@ -649,27 +596,24 @@ extern "C" int hwy_get_state(hwy_engine *eng, hwy_state *h) {
     HWY_HIP(eng, hipMemcpyAsync(rs, eng->d_road_steps, E * sizeof(int32_t), hipMemcpyDeviceToHost, eng->stream));
   }
   HWY_HIP(eng, hipStreamSynchronize(eng->stream));
-  if (is_ix(eng)) {
+  double *fields[9] = {h->x, h->y, h->heading, h->speed, h->timer, h->target_speed, h->delta, h->impact_x, h->impact_y};
+  for (int f = 0; f < 9; ++f) if (fields[f]) unpack_rows(eng, stage + f * plane, fields[f]);
+  // one path for both packed-word layouts (hwy_device.h, hwy_ix.h)
+  auto unpack = [&](auto lane_of, auto target_of, auto speed_index_of, auto flags_of) {
     for (int e = 0; e < E; ++e)
       for (int i = 0; i < N; ++i) {
         const int32_t w = pk[(size_t)e * P + i];
         const size_t k = (size_t)e * N + i;
-        if (h->lane) h->lane[k] = hwy::ix_word_lane(w);
-        if (h->target_lane) h->target_lane[k] = hwy::ix_word_target(w);
-        if (h->speed_index) h->speed_index[k] = hwy::ix_word_speed_index(w);
-        if (h->flags) h->flags[k] = hwy::ix_word_flags(w);
-        if (h->route) h->route[k] = (int64_t)rt[(size_t)e * P + i];
-      }
-    if (h->road_steps) std::memcpy(h->road_steps, rs, sizeof(int32_t) * E);
-    double *flds[9] = {h->x, h->y, h->heading, h->speed, h->timer, h->target_speed, h->delta, h->impact_x, h->impact_y};
-    for (int f = 0; f < 9; ++f) if (flds[f]) unpack_rows(eng, stage + f * plane, flds[f]);
-    // the step kernel maintains the impact pair only while its flag is set, and nothing but the flag word of an empty slot
-    for (int e = 0; e < E; ++e)
-      for (int i = 0; i < N; ++i) {
-        const int fl = hwy::ix_word_flags(pk[(size_t)e * P + i]);
-        const size_t k = (size_t)e * N + i;
-        if (fl & HWY_F_ABSENT) {
-          for (int f = 0; f < 9; ++f) if (flds[f]) flds[f][k] = 0.0;
+        const int fl = flags_of(w);
+        if (h->lane) h->lane[k] = lane_of(w);
+        if (h->target_lane) h->target_lane[k] = target_of(w);
+        if (h->speed_index) h->speed_index[k] = speed_index_of(w);
+        if (h->flags) h->flags[k] = fl;
+        if (is_ix(eng) && h->route) h->route[k] = (int64_t)rt[(size_t)e * P + i];
+        // the step kernel maintains nothing but the flag word of an empty slot (intersection scenario), and the impact pair only
+        // while its flag is set (Vehicle.impact is None otherwise)
+        if (is_ix(eng) && (fl & HWY_F_ABSENT)) {
+          for (int f = 0; f < 9; ++f) if (fields[f]) fields[f][k] = 0.0;
           if (h->lane) h->lane[k] = 0;
           if (h->target_lane) h->target_lane[k] = 0;
           if (h->speed_index) h->speed_index[k] = 0;
@@ -680,25 +624,13 @@ extern "C" int hwy_get_state(hwy_engine *eng, hwy_state *h) {
           if (h->impact_y) h->impact_y[k] = 0.0;
         }
       }
-    if (h->time) std::memcpy(h->time, tm, sizeof(double) * E);
-    return HWY_OK;
+  };
+  if (is_ix(eng)) {
+    unpack(hwy::ix_word_lane, hwy::ix_word_target, hwy::ix_word_speed_index, hwy::ix_word_flags);
+    if (h->road_steps) std::memcpy(h->road_steps, rs, sizeof(int32_t) * E);
+  } else {
+    unpack(hwy::word_lane, hwy::word_target, hwy::word_speed_index, hwy::word_flags);
   }
-  double *fields[9] = {h->x, h->y, h->heading, h->speed, h->timer, h->target_speed, h->delta, h->impact_x, h->impact_y};
-  for (int f = 0; f < 9; ++f) if (fields[f]) unpack_rows(eng, stage + f * plane, fields[f]);
-  for (int e = 0; e < E; ++e)
-    for (int i = 0; i < N; ++i) {
-      const int32_t w = pk[(size_t)e * P + i];
-      const size_t k = (size_t)e * N + i;
-      if (h->lane) h->lane[k] = hwy::word_lane(w);
-      if (h->target_lane) h->target_lane[k] = hwy::word_target(w);
-      if (h->speed_index) h->speed_index[k] = hwy::word_speed_index(w);
-      if (h->flags) h->flags[k] = hwy::word_flags(w);
-      // the impact pair is only maintained while the flag is set (Vehicle.impact is None otherwise)
-      if (!(hwy::word_flags(w) & HWY_F_HAS_IMPACT)) {
-        if (h->impact_x) h->impact_x[k] = 0.0;
-        if (h->impact_y) h->impact_y[k] = 0.0;
-      }
-    }
   if (h->time) std::memcpy(h->time, tm, sizeof(double) * E);
   return HWY_OK;
 }
@@ -763,43 +695,38 @@ extern "C" int hwy_get_controls(hwy_engine *eng, double *acceleration, double *s
 }
 
 // ---- kernel timing ----------------------------------------------------------------------------------
-static hipError_t launch_step_any(const hwy_engine *eng, const StepParams &p);
+// pair k of a pool of launch events, created on first use
+static int event_pair(hwy_engine *eng, std::vector<std::pair<hipEvent_t, hipEvent_t>> &pool, size_t k, std::pair<hipEvent_t, hipEvent_t> &out) {
+  while (pool.size() <= k) {
+    hipEvent_t a, b;
+    HWY_HIP(eng, hipEventCreate(&a));
+    HWY_HIP(eng, hipEventCreate(&b));
+    pool.emplace_back(a, b);
+  }
+  out = pool[k];
+  return HWY_OK;
+}
+// the step launch of the engine's family (launch_stage), timed by the turn tuner or by hwy_profile_* when either wants it
 static int timed_launch(hwy_engine *eng, const StepParams &p) {
   auto &tn = eng->tuner;
+  std::pair<hipEvent_t, hipEvent_t> ev;
   if (tn.state == hwy_engine::TurnTuner::SAMPLING && !eng->profiling && p.full_step) {
     const int c = tn.launches % 5;
-    if (tn.events.size() <= (size_t)tn.launches) {
-      hipEvent_t a, b;
-      HWY_HIP(eng, hipEventCreate(&a));
-      HWY_HIP(eng, hipEventCreate(&b));
-      tn.events.emplace_back(a, b);
-    }
+    if (int rc = event_pair(eng, tn.events, (size_t)tn.launches, ev)) return rc;
     StepParams q = p;
     hwy::set_prio_turn(q, tn.cand[c]);
-    auto &pr = tn.events[tn.launches];
-    hwy::set_launch_events(pr.first, pr.second);
-    const hipError_t err = launch_step_any(eng, q);
-    hwy::set_launch_events(nullptr, nullptr);
-    HWY_HIP(eng, err);
+    HWY_HIP(eng, launch_stage(eng, STEP, q, ev.first, ev.second));
     tn.which.push_back(c);
     if (++tn.launches == 5 * (HWY_TUNE_ROUNDS + 1)) return tuner_finish_stage(eng);
     return HWY_OK;
   }
   if (!eng->profiling || (eng->launch_counter++ % eng->profiling) != 0) {
-    HWY_HIP(eng, launch_step_any(eng, p));
+    HWY_HIP(eng, launch_stage(eng, STEP, p));
     return HWY_OK;
   }
-  if (eng->events_used == eng->events.size()) {
-    hipEvent_t a, b;
-    HWY_HIP(eng, hipEventCreate(&a));
-    HWY_HIP(eng, hipEventCreate(&b));
-    eng->events.emplace_back(a, b);
-  }
-  auto &pr = eng->events[eng->events_used++];
-  hwy::set_launch_events(pr.first, pr.second);  // the dispatch's own begin / end timestamps (hwy_kernels.hip)
-  const hipError_t err = launch_step_any(eng, p);
-  hwy::set_launch_events(nullptr, nullptr);
-  HWY_HIP(eng, err);
+  if (int rc = event_pair(eng, eng->events, eng->events_used, ev)) return rc;
+  eng->events_used++;
+  HWY_HIP(eng, launch_stage(eng, STEP, p, ev.first, ev.second));  // the dispatch's own begin / end timestamps (hwy_launch.h)
   return HWY_OK;
 }
 static int drain_events(hwy_engine *eng) {
@@ -838,6 +765,16 @@ extern "C" int hwy_profile_read(hwy_engine *eng, double *total_ms, int64_t *laun
 }
 
 // ---- stepping ------------------------------------------------------------------------------------------
+// the arguments of a full policy step around the caller's I/O planes
+static void bind_full_step(const hwy_engine *eng, StepParams &p, const int32_t *d_actions, float *d_obs, double *d_reward,
+                           uint8_t *d_terminated, uint8_t *d_truncated, double *d_info_speed, uint8_t *d_info_crashed) {
+  fill_params(eng, p);
+  p.n_frames = eng->cfg.frames_per_step;
+  p.full_step = 1;
+  p.actions = d_actions; p.obs = d_obs; p.reward = d_reward; p.terminated = d_terminated; p.truncated = d_truncated;
+  p.info_speed = d_info_speed; p.info_crashed = d_info_crashed;
+}
+
 extern "C" int hwy_step_device(hwy_engine *eng, const int32_t *d_actions, float *d_obs, double *d_reward,
                                uint8_t *d_terminated, uint8_t *d_truncated, double *d_info_speed,
                                uint8_t *d_info_crashed) {
@@ -846,19 +783,9 @@ extern "C" int hwy_step_device(hwy_engine *eng, const int32_t *d_actions, float 
     return fail(eng, HWY_ERR_INVALID_ARG, "hwy_step_device: actions/obs/reward/terminated/truncated must be non-NULL");
   HWY_HIP(eng, hipSetDevice(eng->device));
   StepParams p;
-  fill_params(eng, p);
-  p.n_frames = eng->cfg.frames_per_step;
-  p.full_step = 1;
-  p.actions = d_actions; p.obs = d_obs; p.reward = d_reward; p.terminated = d_terminated; p.truncated = d_truncated;
-  p.info_speed = d_info_speed; p.info_crashed = d_info_crashed;
+  bind_full_step(eng, p, d_actions, d_obs, d_reward, d_terminated, d_truncated, d_info_speed, d_info_crashed);
   if (eng->profiling && eng->events_used >= 65536)
     if (int rc = drain_events(eng)) return rc;
-  if (is_lidar(eng)) {  // the family's step kernel without an observation, then the lidar kernel on the state it left
-    p.obs = nullptr;
-    if (int rc = timed_launch(eng, p)) return rc;
-    HWY_HIP(eng, launch_lidar_obs(eng, d_obs));
-    return HWY_OK;
-  }
   return timed_launch(eng, p);
 }
 
@@ -873,28 +800,20 @@ extern "C" int hwy_rollout_device(hwy_engine *eng, int32_t k_steps, const int32_
                                           "_clear_vehicles / _spawn_vehicle run on the host between steps)");
   HWY_HIP(eng, hipSetDevice(eng->device));
   StepParams p;
-  fill_params(eng, p);
-  p.n_frames = eng->cfg.frames_per_step;
-  p.full_step = 1;
-  p.actions = d_actions; p.obs = d_obs; p.reward = d_reward; p.terminated = d_terminated; p.truncated = d_truncated;
-  p.info_speed = d_info_speed; p.info_crashed = d_info_crashed;
   if (is_lidar(eng)) {
     // k_steps x (step launch + lidar launch): step k's observation is of the state after step k, so the steps cannot share a launch.
-    // The launches are those of k_steps hwy_step_device calls on block k of every plane: the same results by construction.
-    const size_t E = eng->cfg.num_envs, EA = E * eng->cfg.num_agents, n_obs = EA * hwy::obs_len(eng->cfg);
+    // The launches are those of k_steps hwy_step_device calls on block k of every plane (untimed): the same results by construction.
+    const size_t E = eng->cfg.num_envs, EA = num_agent_rows(eng->cfg), n_obs = num_obs_floats(eng->cfg);
     for (int k = 0; k < k_steps; ++k) {
-      StepParams q = p;
-      q.actions = d_actions + k * EA; q.obs = nullptr; q.reward = d_reward + k * EA;
-      q.terminated = d_terminated + k * E; q.truncated = d_truncated + k * E;
-      q.info_speed = d_info_speed ? d_info_speed + k * EA : nullptr;
-      q.info_crashed = d_info_crashed ? d_info_crashed + k * EA : nullptr;
-      HWY_HIP(eng, launch_step_any(eng, q));
-      HWY_HIP(eng, launch_lidar_obs(eng, d_obs + k * n_obs));
+      bind_full_step(eng, p, d_actions + k * EA, d_obs + k * n_obs, d_reward + k * EA, d_terminated + k * E, d_truncated + k * E,
+                     d_info_speed ? d_info_speed + k * EA : nullptr, d_info_crashed ? d_info_crashed + k * EA : nullptr);
+      HWY_HIP(eng, launch_stage(eng, STEP, p));
     }
     return HWY_OK;
   }
   // K steps in ONE launch, every family.  The intersection kernel: STEP blocks only (no shadow is advanced during the launch; an
   // environment that ends in it warms its next episode up inline -- WHEN the warm-up frames are computed cannot change a result)
+  bind_full_step(eng, p, d_actions, d_obs, d_reward, d_terminated, d_truncated, d_info_speed, d_info_crashed);
   p.k_steps = k_steps;
   p.num_envs = eng->cfg.num_envs;
   HWY_HIP(eng, with_family(eng, p, [&](const auto &a) { return hwy::launch_rollout(a, launch_of(eng)); }));
@@ -909,17 +828,16 @@ extern "C" int hwy_rollout(hwy_engine *eng, int32_t k_steps, const int32_t *acti
     return fail(eng, HWY_ERR_INVALID_ARG, "hwy_rollout: actions/obs/reward/terminated/truncated must be non-NULL");
   if (k_steps > 1 && is_ix(eng) && (eng->cfg.flags & HWY_C_HOST_TRAFFIC))
     return fail(eng, HWY_ERR_INVALID_ARG, "hwy_rollout: k_steps > 1 needs device traffic (HWY_C_HOST_TRAFFIC is set)");
-  size_t n_act, n_obs, n_ea;
-  io_counts(eng->cfg, &n_act, &n_obs, &n_ea);
+  const size_t n_act = num_agent_rows(eng->cfg), n_obs = num_obs_floats(eng->cfg);
   const size_t E = eng->cfg.num_envs, K = (size_t)k_steps;
   const int max_action = num_action_ids(eng) - 1;
   for (size_t k = 0; k < K * n_act; ++k)  // the reference's KeyError / IndexError, before anything is simulated (action.py:260,195)
     if (actions[k] < 0 || actions[k] > max_action) return fail(eng, HWY_ERR_ACTION, "action id out of range");
   HWY_HIP(eng, hipSetDevice(eng->device));
   auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_act = 0, o_rew = up(K * n_act * 4), o_spd = o_rew + up(K * n_ea * 8), o_obs = o_spd + up(K * n_ea * 8),
+  const size_t o_act = 0, o_rew = up(K * n_act * 4), o_spd = o_rew + up(K * n_act * 8), o_obs = o_spd + up(K * n_act * 8),
                o_term = o_obs + up(K * n_obs * 4), o_trunc = o_term + up(K * E), o_crash = o_trunc + up(K * E),
-               total = o_crash + up(K * n_ea);
+               total = o_crash + up(K * n_act);
   if (total > eng->roll_bytes) {
     HWY_HIP(eng, hipStreamSynchronize(eng->stream));
     if (eng->d_roll) (void)hipFree(eng->d_roll);
@@ -934,11 +852,11 @@ extern "C" int hwy_rollout(hwy_engine *eng, int32_t k_steps, const int32_t *acti
                                   (uint8_t *)(d + o_term), (uint8_t *)(d + o_trunc), (double *)(d + o_spd), (uint8_t *)(d + o_crash)))
     return rc;
   HWY_HIP(eng, hipMemcpyAsync(obs, d + o_obs, K * n_obs * 4, hipMemcpyDeviceToHost, eng->stream));
-  HWY_HIP(eng, hipMemcpyAsync(reward, d + o_rew, K * n_ea * 8, hipMemcpyDeviceToHost, eng->stream));
+  HWY_HIP(eng, hipMemcpyAsync(reward, d + o_rew, K * n_act * 8, hipMemcpyDeviceToHost, eng->stream));
   HWY_HIP(eng, hipMemcpyAsync(terminated, d + o_term, K * E, hipMemcpyDeviceToHost, eng->stream));
   HWY_HIP(eng, hipMemcpyAsync(truncated, d + o_trunc, K * E, hipMemcpyDeviceToHost, eng->stream));
-  if (info_speed) HWY_HIP(eng, hipMemcpyAsync(info_speed, d + o_spd, K * n_ea * 8, hipMemcpyDeviceToHost, eng->stream));
-  if (info_crashed) HWY_HIP(eng, hipMemcpyAsync(info_crashed, d + o_crash, K * n_ea, hipMemcpyDeviceToHost, eng->stream));
+  if (info_speed) HWY_HIP(eng, hipMemcpyAsync(info_speed, d + o_spd, K * n_act * 8, hipMemcpyDeviceToHost, eng->stream));
+  if (info_crashed) HWY_HIP(eng, hipMemcpyAsync(info_crashed, d + o_crash, K * n_act, hipMemcpyDeviceToHost, eng->stream));
   HWY_HIP(eng, hipStreamSynchronize(eng->stream));
   return HWY_OK;
 }
@@ -948,8 +866,7 @@ extern "C" int hwy_step(hwy_engine *eng, const int32_t *actions, float *obs, dou
   if (!eng) return HWY_ERR_INVALID_ARG;
   if (!actions || !obs || !reward || !terminated || !truncated)
     return fail(eng, HWY_ERR_INVALID_ARG, "hwy_step: actions/obs/reward/terminated/truncated must be non-NULL");
-  size_t n_act, n_obs, n_ea;
-  io_counts(eng->cfg, &n_act, &n_obs, &n_ea);
+  const size_t n_act = num_agent_rows(eng->cfg), n_obs = num_obs_floats(eng->cfg);
   const size_t E = eng->cfg.num_envs;
   // the reference raises KeyError for an unknown meta-action before touching the simulation (action.py:260)
   const int max_action = num_action_ids(eng) - 1;  // IntersectionEnv.ACTIONS has 3 entries (intersection_env.py:14)
@@ -968,19 +885,18 @@ extern "C" int hwy_step(hwy_engine *eng, const int32_t *actions, float *obs, dou
   HWY_HIP(eng, hipMemcpyAsync(h_out, eng->d_out, eng->out_bytes, hipMemcpyDeviceToHost, eng->stream));
   HWY_HIP(eng, hipStreamSynchronize(eng->stream));
   std::memcpy(obs, h_out + eng->off_obs, n_obs * 4);
-  std::memcpy(reward, h_out + eng->off_reward, n_ea * 8);
+  std::memcpy(reward, h_out + eng->off_reward, n_act * 8);
   std::memcpy(terminated, h_out + eng->off_term, E);
   std::memcpy(truncated, h_out + eng->off_trunc, E);
-  if (info_speed) std::memcpy(info_speed, h_out + eng->off_speed, n_ea * 8);
-  if (info_crashed) std::memcpy(info_crashed, h_out + eng->off_crashed, n_ea);
+  if (info_speed) std::memcpy(info_speed, h_out + eng->off_speed, n_act * 8);
+  if (info_crashed) std::memcpy(info_crashed, h_out + eng->off_crashed, n_act);
   return HWY_OK;
 }
 
 extern "C" int hwy_step_frames(hwy_engine *eng, const int32_t *actions, int32_t n_frames) {
   if (!eng || n_frames < 0) return HWY_ERR_INVALID_ARG;
   HWY_HIP(eng, hipSetDevice(eng->device));
-  size_t n_act, n_obs, n_ea;
-  io_counts(eng->cfg, &n_act, &n_obs, &n_ea);
+  const size_t n_act = num_agent_rows(eng->cfg);
   StepParams p;
   fill_params(eng, p);
   p.n_frames = n_frames;
@@ -1002,14 +918,12 @@ extern "C" int hwy_step_frames(hwy_engine *eng, const int32_t *actions, int32_t 
 extern "C" int hwy_observe(hwy_engine *eng, float *obs) {
   if (!eng || !obs) return HWY_ERR_INVALID_ARG;
   HWY_HIP(eng, hipSetDevice(eng->device));
-  size_t n_act, n_obs, n_ea;
-  io_counts(eng->cfg, &n_act, &n_obs, &n_ea);
+  const size_t n_obs = num_obs_floats(eng->cfg);
   StepParams p;
   fill_params(eng, p);
   p.obs = eng->d_obs;
   p.reward = eng->d_reward; p.terminated = eng->d_term; p.truncated = eng->d_trunc;
-  if (is_lidar(eng)) HWY_HIP(eng, launch_lidar_obs(eng, eng->d_obs));  // (the observe kernel has nothing else to do)
-  else HWY_HIP(eng, launch_observe_any(eng, p));
+  HWY_HIP(eng, launch_stage(eng, OBSERVE, p));
   HWY_HIP(eng, hipMemcpyAsync(eng->h_pinned, eng->d_obs, n_obs * 4, hipMemcpyDeviceToHost, eng->stream));
   HWY_HIP(eng, hipStreamSynchronize(eng->stream));
   std::memcpy(obs, eng->h_pinned, n_obs * 4);
@@ -1020,10 +934,7 @@ extern "C" int hwy_observe(hwy_engine *eng, float *obs) {
 static int set_reset_params(hwy_engine *eng, double ego_spacing, double vehicles_density, int32_t initial_lane_id) {
   if (!(ego_spacing > 0) || !(vehicles_density > 0)) return fail(eng, HWY_ERR_INVALID_ARG, "spacing/density must be positive");
   if (initial_lane_id >= eng->cfg.lanes_count) return fail(eng, HWY_ERR_INVALID_ARG, "initial_lane_id out of range");
-  // (road-network scenarios: the spawn rule of MergeEnv / MergeGenericEnv has no spacing / density / lane parameters)
-  eng->rp.ego_spacing = ego_spacing;
-  eng->rp.other_spacing = 1 / vehicles_density;  // highway_env.py:94
-  eng->rp.initial_lane_id = initial_lane_id < 0 ? -1 : initial_lane_id;
+  hwy::set_reset_args(eng->rp, ego_spacing, vehicles_density, initial_lane_id);
   return HWY_OK;
 }
 
@@ -1033,8 +944,7 @@ extern "C" int hwy_reset(hwy_engine *eng, const uint8_t *mask, const uint64_t *s
   if (int rc = set_reset_params(eng, ego_spacing, vehicles_density, initial_lane_id)) return rc;
   HWY_HIP(eng, hipSetDevice(eng->device));
   const size_t E = eng->cfg.num_envs;
-  size_t n_act, n_obs, n_ea;
-  io_counts(eng->cfg, &n_act, &n_obs, &n_ea);
+  const size_t n_obs = num_obs_floats(eng->cfg);
   StepParams p;
   fill_params(eng, p);
   char *base = (char *)eng->h_pinned;
@@ -1048,10 +958,9 @@ extern "C" int hwy_reset(hwy_engine *eng, const uint8_t *mask, const uint64_t *s
     HWY_HIP(eng, hipMemcpyAsync(eng->d_mask, base + E * 8, E, hipMemcpyHostToDevice, eng->stream));
     p.reset_mask = eng->d_mask;
   }
-  p.obs = is_lidar(eng) ? nullptr : eng->d_obs;
+  p.obs = eng->d_obs;  // (a Lidar engine traces every row; only the masked ones are copied out below)
   p.reward = eng->d_reward; p.terminated = eng->d_term; p.truncated = eng->d_trunc;
-  HWY_HIP(eng, launch_reset_any(eng, p));
-  if (is_lidar(eng)) HWY_HIP(eng, launch_lidar_obs(eng, eng->d_obs));  // (every row; only the masked ones are copied out below)
+  HWY_HIP(eng, launch_stage(eng, RESET, p));
   HWY_HIP(eng, hipStreamSynchronize(eng->stream));
   if (obs) {
     HWY_HIP(eng, hipMemcpyAsync(eng->h_pinned, eng->d_obs, n_obs * 4, hipMemcpyDeviceToHost, eng->stream));

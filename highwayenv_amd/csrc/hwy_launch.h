@@ -1,28 +1,42 @@
 // hwy_launch.h -- host-visible launch functions of the kernels in hwy_kernels.hip, hwy_kernels_linear.hip and
 // hwy_kernels_direct.hip: one overload per kernel family, chosen by the type of its parameter struct; and of the
-// LidarObservation kernel in hwy_kernels_lidar.hip.
+// LidarObservation kernel in hwy_kernels_lidar.hip.  Each is the shared selection layer (hwy_launch_family.h, hwy_launch_rules.h)
+// with the HIP backend below.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 
-#include "hwy_device.h"
+#include "hwy_launch_family.h"
 #include "hwy_net.h"
 #include "hwy_ix.h"
 #include "hwy_lidar.h"
 
 namespace hwy {
-// the events the launches of THIS THREAD record their dispatch begin / end timestamps into (nullptr, nullptr = none)
-void set_launch_events(hipEvent_t start, hipEvent_t stop);
-// what the engine decides about a launch, whatever the family.  waves_per_eu: the register-allocation variant of the step kernel;
-// rollout_waves_per_eu: that of the ONE-WAVEFRONT rollout kernel of the straight-road families (their workgroup rollout kernel
-// takes waves_per_eu, the wide kernel has one variant per size); force_block_kernel / extra_lds: hwy_config.tune_block_kernel /
-// tune_extra_lds as resolved by hwy_create (straight-road families only)
-struct Launch {
-  int num_envs;
-  hipStream_t stream;
-  int waves_per_eu, rollout_waves_per_eu;
-  bool force_block_kernel;
-  int extra_lds;
+// The HIP backend of the selection layer (hwy_launch_family.h, hwy_launch_rules.h), for the kernel translation units.
+struct HipBackend {
+  // Kernel timing (hwy_profile_enable, the turn tuner): every launch goes through hipExtLaunchKernelGGL, which records the DISPATCH's
+  // own begin and end timestamps into the two events of the Launch -- the same clock readings rocprofv3 --kernel-trace reports, with
+  // no stream overhead between them (events recorded around a launch with hipEventRecord also measure ~3 us of command processing).
+  // Null events (the normal case): a plain launch.
+  template <typename K, typename... A>
+  static hipError_t launch(K kernel, unsigned grid, int block, int lds, const Launch &l, const A &...a) {
+    hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, l.stream, l.start, l.stop, 0, a...);
+    return hipGetLastError();
+  }
+  // How many workgroups of a kernel the device holds at once (occupancy x compute units): the issue-priority turns (hwy_wave.h:
+  // WaveTurn) only pay when the whole grid is resident.
+  template <typename K>
+  static int resident(K kernel, int block, int lds) {
+    int per_cu = 0, dev = 0;
+    hipDeviceProp_t prop;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, lds) != hipSuccess) return 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
+    return per_cu * prop.multiProcessorCount;
+  }
+  template <typename Fn>
+  static auto pick_wpe(int v, Fn &&fn) { return dispatch_1_4(v, fn); }
 };
+// One overload per kernel family, chosen by the type of its parameter struct; `l`: hwy_launch_family.h.
 // Straight road, IDM traffic and meta-actions (hwy_kernels.hip): the one-wavefront kernel for N <= 64, the wide kernel of hwy_wave2.h
 // for 64 < N <= 256 with the Kinematics observation, the workgroup kernel otherwise or when forced.
 // The Linear traffic family (hwy_config.traffic_model == HWY_TRAFFIC_LINEAR, hwy_kernels_linear.hip) and direct ego control

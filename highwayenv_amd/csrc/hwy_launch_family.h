@@ -1,25 +1,47 @@
-// hwy_launch_family.h -- the host launch functions of ONE straight-road kernel family (IDM: hwy_kernels.hip, Linear traffic:
-// hwy_kernels_linear.hip, direct ego control: hwy_kernels_direct.hip), written once.  A family is a trait:
+// hwy_launch_family.h -- (kernel arguments, Launch) -> (kernel instantiation, grid, block, LDS) of the straight-road kernel
+// families, written ONCE for the product and for the CPU emulation of tests/emu.  hwy_launch_rules.h has the rest of the rules (the
+// wide kernel, the road-network and the intersection scenarios).  Host code only, generic over the thing that launches -- a backend B
+// with three members:
+//   B::launch(kernel, grid, block, lds, const Launch &, args...)   enqueue / run the kernel
+//   B::resident(kernel, block, lds)                                workgroups of it the device holds at once (0 = unknown)
+//   B::pick_wpe(v, fn)                                             fn(std::integral_constant<int, W>{}) for the waves-per-EU variant
+//                                                                  W of a run-time v: the register-allocation builds of one kernel
+// hwy_launch.h: HipBackend (hipExtLaunchKernelGGL, the occupancy query, W = v); tests/emu/emu_straight.h: EmuBackend (emu::launch, 0,
+// W = 1 -- the variants are the same source, the emulation compiles one).
+// A family is a trait:
 //   using Params = ...;                                      the kernel argument (StepParams / LinearParams / DirectParams)
-//   static const StepParams &step_params(const Params &);    the StepParams inside it
+//   step_params(Params &)                                    the StepParams inside it
 //   step_wave<WPE, FULL_SCAN>() / rollout_wave<WPE, FULL_SCAN>()   the one-wavefront kernels (hwy_wave.h, N <= 64)
 //   step_block<NW, WPE>() / rollout_block<NW, WPE>() / reset_block<NW>()   the workgroup kernels (hwy_device.h, NW wavefronts)
-// each returning the address of the kernel.  Host code only: it is included by the kernel translation units after the kernel headers.
+// each returning the address of the kernel (taking it is what instantiates the kernel: a translation unit holds the kernels of the
+// families it launches and no others).
+// hipError_t / hipStream_t / hipEvent_t come from the HIP runtime (the emulation: from hip_emu.h).
 #pragma once
-#include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
 #include <type_traits>
 
-#include "hwy_launch.h"
+#include "hwy_device.h"
+#include "hwy_wave.h"
+#include "hwy_params.h"
 
 namespace hwy {
 
-void get_launch_events(hipEvent_t *start, hipEvent_t *stop);  // hwy_kernels.hip: the events of this thread's launches (hwy_profile_*)
+// What the engine decides about a launch, whatever the family.  waves_per_eu: the register-allocation variant of the step kernel;
+// rollout_waves_per_eu: that of the ONE-WAVEFRONT rollout kernel of the straight-road families (their workgroup rollout kernel
+// takes waves_per_eu, the wide kernel has one variant per size); force_block_kernel / extra_lds: hwy_config.tune_block_kernel /
+// tune_extra_lds as resolved by hwy_create (straight-road families only); start / stop: the events the launch records its
+// dispatch's begin / end timestamps into (hwy_profile_*, the turn tuner), null = a plain launch
+struct Launch {
+  int num_envs;
+  hipStream_t stream;
+  int waves_per_eu, rollout_waves_per_eu;
+  bool force_block_kernel;
+  int extra_lds;
+  hipEvent_t start, stop;
+};
 
 static inline int waves_for(int n_vehicles) { return (n_vehicles + 63) / 64; }
 
-// fn(std::integral_constant<int, v>{}) for a run-time v in 1 .. 4 (anything else: 4, the register-allocation variants' default):
-// every choice of a kernel instantiation by waves_per_eu or by wavefronts per environment goes through here
+// fn(std::integral_constant<int, v>{}) for a run-time v in 1 .. 4 (anything else: 4, the register-allocation variants' default)
 template <typename Fn>
 static auto dispatch_1_4(int v, Fn &&fn) {
   switch (v) {
@@ -30,30 +52,38 @@ static auto dispatch_1_4(int v, Fn &&fn) {
   }
 }
 
-// Kernel timing (hwy_profile_enable): every launch goes through hipExtLaunchKernelGGL, which records the DISPATCH's own begin and
-// end timestamps into the two events it is given -- the same clock readings rocprofv3 --kernel-trace reports, with no stream
-// overhead between them (events recorded around a launch with hipEventRecord also measure ~3 us of command processing).
-// Null events (the normal case): a plain launch.
-template <typename K, typename... A>
-static hipError_t launch_kernel(K kernel, unsigned grid, int block, int lds, hipStream_t stream, const A &...a) {
-  hipEvent_t start, stop;
-  get_launch_events(&start, &stop);
-  hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, stream, start, stop, 0, a...);
-  return hipGetLastError();
-}
+struct IdmFamily {  // IDM traffic, meta-actions (hwy_kernels.hip)
+  using Params = StepParams;
+  static StepParams &step_params(Params &a) { return a; }
+  static const StepParams &step_params(const Params &a) { return a; }
+  template <int WPE, bool FULL_SCAN> static auto step_wave() { return hwy_step_wave_kernel<WPE, FULL_SCAN>; }
+  template <int WPE, bool FULL_SCAN> static auto rollout_wave() { return hwy_rollout_wave_kernel<WPE, FULL_SCAN>; }
+  template <int NW, int WPE> static auto step_block() { return hwy_step_kernel<NW, WPE>; }
+  template <int NW, int WPE> static auto rollout_block() { return hwy_rollout_kernel<NW, WPE>; }
+  template <int NW> static auto reset_block() { return hwy_reset_kernel<NW>; }
+};
+struct LinearFamily {  // hwy_config.traffic_model == HWY_TRAFFIC_LINEAR (hwy_kernels_linear.hip)
+  using Params = LinearParams;
+  static StepParams &step_params(Params &a) { return a.s; }
+  static const StepParams &step_params(const Params &a) { return a.s; }
+  template <int WPE, bool FULL_SCAN> static auto step_wave() { return hwy_step_wave_linear_kernel<WPE, FULL_SCAN>; }
+  template <int WPE, bool FULL_SCAN> static auto rollout_wave() { return hwy_rollout_wave_linear_kernel<WPE, FULL_SCAN>; }
+  template <int NW, int WPE> static auto step_block() { return hwy_step_linear_kernel<NW, WPE>; }
+  template <int NW, int WPE> static auto rollout_block() { return hwy_rollout_linear_kernel<NW, WPE>; }
+  template <int NW> static auto reset_block() { return hwy_reset_linear_kernel<NW>; }
+};
+struct DirectFamily {  // hwy_config.ego_control == HWY_EGO_DIRECT (hwy_kernels_direct.hip)
+  using Params = DirectParams;
+  static StepParams &step_params(Params &a) { return a.s; }
+  static const StepParams &step_params(const Params &a) { return a.s; }
+  template <int WPE, bool FULL_SCAN> static auto step_wave() { return hwy_step_wave_direct_kernel<WPE, FULL_SCAN>; }
+  template <int WPE, bool FULL_SCAN> static auto rollout_wave() { return hwy_rollout_wave_direct_kernel<WPE, FULL_SCAN>; }
+  template <int NW, int WPE> static auto step_block() { return hwy_step_direct_kernel<NW, WPE>; }
+  template <int NW, int WPE> static auto rollout_block() { return hwy_rollout_direct_kernel<NW, WPE>; }
+  template <int NW> static auto reset_block() { return hwy_reset_direct_kernel<NW>; }
+};
 
-// How many workgroups of a kernel the device holds at once (occupancy x compute units): the issue-priority turns (hwy_wave.h:
-// WaveTurn) only pay when the whole grid is resident.
-template <typename K>
-static int resident(K kernel, int block, int lds = 0) {
-  int per_cu = 0, dev = 0;
-  hipDeviceProp_t prop;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, lds) != hipSuccess) return 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
-  return per_cu * prop.multiProcessorCount;
-}
-
-template <typename F>
+template <typename F, typename B>
 struct FamilyLaunch {
   using P = typename F::Params;
   // N <= 64: one wavefront per environment (hwy_wave.h); otherwise ceil(N / 64) wavefronts per workgroup (hwy_device.h)
@@ -67,20 +97,20 @@ struct FamilyLaunch {
       // workgroup, i.e. fewer resident wavefronts per SIMD, so that part of the grid is dispatched as wavefronts retire (the
       // hardware then balances unevenly loaded SIMDs)
       const bool fast = (p.flags & HWY_C_EGO_ONLY_COLLISIONS) != 0;
-      return dispatch_1_4(rollout ? l.rollout_waves_per_eu : l.waves_per_eu, [&](auto W) {
+      return B::pick_wpe(rollout ? l.rollout_waves_per_eu : l.waves_per_eu, [&](auto W) {
         constexpr int WPE = decltype(W)::value;
-        if (rollout) return fast ? launch_kernel(F::template rollout_wave<WPE, false>(), l.num_envs, 64, l.extra_lds, l.stream, a)
-                                 : launch_kernel(F::template rollout_wave<WPE, true>(), l.num_envs, 64, l.extra_lds, l.stream, a);
-        return fast ? launch_kernel(F::template step_wave<WPE, false>(), l.num_envs, 64, l.extra_lds, l.stream, a)
-                    : launch_kernel(F::template step_wave<WPE, true>(), l.num_envs, 64, l.extra_lds, l.stream, a);
+        if (rollout) return fast ? B::launch(F::template rollout_wave<WPE, false>(), l.num_envs, 64, l.extra_lds, l, a)
+                                 : B::launch(F::template rollout_wave<WPE, true>(), l.num_envs, 64, l.extra_lds, l, a);
+        return fast ? B::launch(F::template step_wave<WPE, false>(), l.num_envs, 64, l.extra_lds, l, a)
+                    : B::launch(F::template step_wave<WPE, true>(), l.num_envs, 64, l.extra_lds, l, a);
       });
     }
     if (nw < 1 || nw > 4) return hipErrorInvalidValue;
-    return dispatch_1_4(l.waves_per_eu, [&](auto W) {  // WPE = the register-allocation variant (hwy_engine.hip: waves_per_eu)
+    return B::pick_wpe(l.waves_per_eu, [&](auto W) {  // WPE = the register-allocation variant (hwy_engine.hip: waves_per_eu)
       return dispatch_1_4(nw, [&](auto V) {
         constexpr int WPE = decltype(W)::value, NW = decltype(V)::value;
-        return rollout ? launch_kernel(F::template rollout_block<NW, WPE>(), l.num_envs, NW * 64, 0, l.stream, a)
-                       : launch_kernel(F::template step_block<NW, WPE>(), l.num_envs, NW * 64, 0, l.stream, a);
+        return rollout ? B::launch(F::template rollout_block<NW, WPE>(), l.num_envs, NW * 64, 0, l, a)
+                       : B::launch(F::template step_block<NW, WPE>(), l.num_envs, NW * 64, 0, l, a);
       });
     });
   }
@@ -89,7 +119,7 @@ struct FamilyLaunch {
     if (nw < 1 || nw > 4) return hipErrorInvalidValue;
     return dispatch_1_4(nw, [&](auto V) {
       constexpr int NW = decltype(V)::value;
-      return launch_kernel(F::template reset_block<NW>(), l.num_envs, NW * 64, 0, l.stream, a);
+      return B::launch(F::template reset_block<NW>(), l.num_envs, NW * 64, 0, l, a);
     });
   }
   // workgroups of the step kernel this launch would run that the device holds at once (0 = unknown)
@@ -97,15 +127,36 @@ struct FamilyLaunch {
     const StepParams &p = F::step_params(a);
     const int nw = waves_for(p.N);
     if (!wave_applies(p, l) && (nw < 1 || nw > 4)) return 0;
-    return dispatch_1_4(l.waves_per_eu, [&](auto W) {
+    return B::pick_wpe(l.waves_per_eu, [&](auto W) {
       constexpr int WPE = decltype(W)::value;
       if (wave_applies(p, l))
-        return (p.flags & HWY_C_EGO_ONLY_COLLISIONS) ? resident(F::template step_wave<WPE, false>(), 64, l.extra_lds)
-                                                     : resident(F::template step_wave<WPE, true>(), 64, l.extra_lds);
+        return (p.flags & HWY_C_EGO_ONLY_COLLISIONS) ? B::resident(F::template step_wave<WPE, false>(), 64, l.extra_lds)
+                                                     : B::resident(F::template step_wave<WPE, true>(), 64, l.extra_lds);
       // workgroup kernel: turns by workgroup (hwy_device.h: wave_turn_init_workgroup)
-      return dispatch_1_4(nw, [&](auto V) { return resident(F::template step_block<decltype(V)::value, WPE>(), decltype(V)::value * 64); });
+      return dispatch_1_4(nw, [&](auto V) { return B::resident(F::template step_block<decltype(V)::value, WPE>(), decltype(V)::value * 64, 0); });
     });
   }
 };
+
+// The selection of every family is the overload set select_step / select_reset / select_observe / select_resident_blocks<B>, chosen
+// by the type of the kernel argument (StepParams, NetParams and IxParams: hwy_launch_rules.h).  Linear traffic and direct ego control:
+// the one-wavefront kernel for N <= 64 (unless force_block_kernel), the workgroup kernel otherwise -- hwy_wave2.h is IDM-only.
+template <typename B> hipError_t select_step(const LinearParams &a, const Launch &l, bool rollout) { return FamilyLaunch<LinearFamily, B>::step(a, l, rollout); }
+template <typename B> hipError_t select_reset(const LinearParams &a, const Launch &l) { return FamilyLaunch<LinearFamily, B>::reset(a, l); }
+template <typename B> int select_resident_blocks(const LinearParams &a, const Launch &l) { return FamilyLaunch<LinearFamily, B>::resident_blocks(a, l); }
+template <typename B> hipError_t select_step(const DirectParams &a, const Launch &l, bool rollout) { return FamilyLaunch<DirectFamily, B>::step(a, l, rollout); }
+template <typename B> hipError_t select_reset(const DirectParams &a, const Launch &l) { return FamilyLaunch<DirectFamily, B>::reset(a, l); }
+template <typename B> int select_resident_blocks(const DirectParams &a, const Launch &l) { return FamilyLaunch<DirectFamily, B>::resident_blocks(a, l); }
+// (the observation of a straight road does not depend on the traffic model or the ego control)
+template <typename B> hipError_t select_observe(const StepParams &p, const Launch &l) {
+  const int nw = waves_for(p.N);
+  if (nw < 1 || nw > 4) return hipErrorInvalidValue;
+  return dispatch_1_4(nw, [&](auto V) {
+    constexpr int NW = decltype(V)::value;
+    return B::launch(hwy_observe_kernel<NW>, l.num_envs, NW * 64, 0, l, p);
+  });
+}
+template <typename B> hipError_t select_observe(const LinearParams &a, const Launch &l) { return select_observe<B>(a.s, l); }
+template <typename B> hipError_t select_observe(const DirectParams &a, const Launch &l) { return select_observe<B>(a.s, l); }
 
 }  // namespace hwy

@@ -28,6 +28,7 @@
 #pragma once
 
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/hwy_engine.h"
 #include "hwy_device.h"
@@ -42,6 +43,19 @@ struct LidarParams {
   int32_t agent_index[HWY_MAX_AGENTS];
   double max_range;
 };
+// host side: the arguments of a config over the four planes it reads ([E][pitch] each), the packed words and the output
+inline LidarParams lidar_params(const hwy_config &c, const double *x, const double *y, const double *heading, const double *speed,
+                                const int32_t *packed, int pitch, float *obs) {
+  LidarParams lp;
+  memset(&lp, 0, sizeof lp);
+  lp.x = x; lp.y = y; lp.heading = heading; lp.speed = speed;
+  lp.packed = packed;
+  lp.obs = obs;
+  lp.N = c.num_vehicles; lp.A = c.num_agents; lp.pitch = pitch; lp.cells = c.lidar_cells;
+  for (int a = 0; a < HWY_MAX_AGENTS; ++a) lp.agent_index[a] = a < c.num_agents ? c.agent_index[a] : 0;
+  lp.max_range = c.lidar_max_range;
+  return lp;
+}
 
 // the type of a grid cell: np.ones((cells, 2), dtype=np.float32) (observation.py:712)
 typedef float lidar_cell_t;

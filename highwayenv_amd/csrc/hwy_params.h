@@ -1,4 +1,6 @@
-// hwy_params.h -- host helper: flatten hwy_config into the kernel-argument block.
+// hwy_params.h -- host helpers: hwy_config -> the kernel-argument blocks, and hwy_config -> what the engine decides about a launch
+// without asking the device.  Written ONCE: hwy_engine.hip calls them on device pointers with a pitch, the CPU emulation
+// (tests/emu) on its host arrays with pitch == N.  Host code only, and plain C++: nothing of the HIP runtime is named here.
 #pragma once
 #include <cstdlib>
 #include <cmath>
@@ -53,6 +55,67 @@ inline void params_from_config(const hwy_config &c, int pitch, StepParams &p) {
     // len(np.arange(origin - 100, origin + 100, spacing)) == ceil(200 / spacing)
     p.g_nwp = (int32_t)std::ceil(200.0 / p.g_spacing);
   }
+}
+
+// the reset parameters of a fresh engine: highway-v0 semantics (every vehicle checks collisions), HighwayEnvFast with
+// HWY_C_EGO_ONLY_COLLISIONS (highway_env.py:177-182)
+inline ResetParams default_reset_params(const hwy_config &c) {
+  ResetParams rp;
+  std::memset(&rp, 0, sizeof rp);
+  rp.ego_spacing = 2.0;
+  rp.other_spacing = 1.0;
+  rp.lane_factor = std::exp(-5.0 / 40.0 * c.lanes_count);
+  rp.initial_lane_id = -1;
+  rp.fast = (c.flags & HWY_C_EGO_ONLY_COLLISIONS) ? 1 : 0;
+  return rp;
+}
+// (ego_spacing, vehicles_density, initial_lane_id) of hwy_reset / hwy_set_autoreset.  (Road-network scenarios: the spawn rule of
+// MergeEnv / MergeGenericEnv has no spacing / density / lane parameters.)
+inline void set_reset_args(ResetParams &rp, double ego_spacing, double vehicles_density, int initial_lane_id) {
+  rp.ego_spacing = ego_spacing;
+  rp.other_spacing = 1 / vehicles_density;  // highway_env.py:94
+  rp.initial_lane_id = initial_lane_id < 0 ? -1 : initial_lane_id;
+}
+
+// the Linear traffic family's arguments next to StepParams: `behavior` = HWY_BEHAVIOR_PARAMS planes [k][E][pitch]
+inline LinearArgs linear_args(const hwy_config &c, double *behavior, int pitch) {
+  LinearArgs la;
+  std::memset(&la, 0, sizeof la);
+  la.behavior = behavior;
+  la.plane = (long long)c.num_envs * pitch;
+  la.lc_gain = c.traffic_lc_min_acc_gain;
+  return la;
+}
+// direct ego control's: `controls` = the stored acceleration | steering of every agent, 2 x [E][A]
+inline DirectArgs direct_args(const hwy_config &c, double *controls) {
+  DirectArgs da;
+  std::memset(&da, 0, sizeof da);
+  da.ctl_accel = controls;
+  da.ctl_steer = controls + (size_t)c.num_envs * c.num_agents;
+  da.n_accel = c.n_accel;
+  da.n_steer = c.n_steer;
+  for (int k = 0; k < HWY_MAX_ACTIONS_PER_AXIS; ++k) {
+    da.accel_axis[k] = c.accel_axis[k];
+    da.steer_axis[k] = c.steer_axis[k];
+  }
+  return da;
+}
+
+// length (int32 words) of the OccupancyGrid workspace StepParams::grid_ws, [E][A][2][W*H]; 0 for the other observations
+inline size_t grid_ws_len(const hwy_config &c) {
+  if (c.obs_type != HWY_OBS_OCCUPANCY_GRID) return 0;
+  return (size_t)c.num_envs * c.num_agents * 2 * c.grid_shape[0] * c.grid_shape[1];
+}
+
+// hwy_config.tune_block_kernel resolved.  IDM with meta-actions: 0 = the engine's choice: the wide kernel (hwy_wave2.h) for
+// 64 < N <= 128, the workgroup kernel beyond -- three / four vehicles per thread are one 338 / 442-VGPR wavefront per SIMD and
+// measured slower there (1024 x 201: 312 us against 240, profiles/r05_history.md); 1 = the workgroup kernel wherever it exists;
+// 2 = the wide kernel wherever it exists (N <= 256).  The families without a wide kernel (hwy_wave2.h is IDM with meta-actions
+// only: Linear traffic, direct ego control): the one-wavefront kernel for N <= 64, the workgroup kernel beyond, and 2 is the
+// engine's own choice.
+inline bool force_block_kernel(const hwy_config &c) {
+  if (c.traffic_model == HWY_TRAFFIC_LINEAR || c.ego_control == HWY_EGO_DIRECT) return c.tune_block_kernel == 1 || c.num_vehicles > 64;
+  return c.tune_block_kernel == 1 || (c.tune_block_kernel == 0 && c.num_vehicles > 128);
 }
 
 // road-network scenarios: the lane table and merge reward / termination constants next to the StepParams

@@ -55,6 +55,8 @@ def build(force: bool = False) -> str:
             os.path.join(_ROOT, "highwayenv_amd", "csrc", "hwy_ix.h"),
             os.path.join(_ROOT, "highwayenv_amd", "csrc", "hwy_math.h"),
             os.path.join(_ROOT, "highwayenv_amd", "csrc", "hwy_params.h"),
+            os.path.join(_ROOT, "highwayenv_amd", "csrc", "hwy_launch_family.h"),
+            os.path.join(_ROOT, "highwayenv_amd", "csrc", "hwy_launch_rules.h"),
             os.path.join(_ROOT, "include", "hwy_engine.h")]
     stale = not os.path.exists(_LIB) or os.path.getmtime(_LIB) < max(os.path.getmtime(s) for s in srcs)
     if force or stale:
@@ -140,7 +142,7 @@ class StraightFamilyEngine(Scheduled):
         out = os.path.join(_HERE, "_build", f"libhwy_{cls.SYMBOL}.so")
         csrc = os.path.join(_ROOT, "highwayenv_amd", "csrc")
         srcs = [os.path.join(_HERE, f) for f in (cls.SOURCE, "emu_straight.h", "hip_emu.h")] + [
-            os.path.join(csrc, f) for f in ("hwy_device.h", "hwy_wave.h", "hwy_math.h", "hwy_params.h")] + [
+            os.path.join(csrc, f) for f in ("hwy_device.h", "hwy_wave.h", "hwy_math.h", "hwy_params.h", "hwy_launch_family.h")] + [
             os.path.join(_ROOT, "include", "hwy_engine.h")]
         if force or not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(s) for s in srcs):
             os.makedirs(os.path.dirname(out), exist_ok=True)

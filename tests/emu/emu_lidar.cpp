@@ -18,14 +18,7 @@ int emu_lidar_observe(const hwy_config *cfg, const hwy_state *st, float *obs) {
   std::vector<int32_t> packed((size_t)E * N);
   for (size_t k = 0; k < packed.size(); ++k)
     packed[k] = hwy::pack_word(st->lane[k], st->target_lane[k], st->speed_index[k], st->flags[k], (int)(k % N));
-  hwy::LidarParams lp;
-  std::memset(&lp, 0, sizeof lp);
-  lp.x = st->x; lp.y = st->y; lp.heading = st->heading; lp.speed = st->speed;
-  lp.packed = packed.data();
-  lp.obs = obs;
-  lp.N = N; lp.A = cfg->num_agents; lp.pitch = N; lp.cells = cfg->lidar_cells;
-  for (int a = 0; a < HWY_MAX_AGENTS; ++a) lp.agent_index[a] = a < cfg->num_agents ? cfg->agent_index[a] : 0;
-  lp.max_range = cfg->lidar_max_range;
+  const hwy::LidarParams lp = hwy::lidar_params(*cfg, st->x, st->y, st->heading, st->speed, packed.data(), N, obs);
   if (cfg->lidar_normalize) emu::launch([](const hwy::LidarParams &q) { hwy::hwy_lidar_kernel<true>(q); }, E * cfg->num_agents, 64, lp);
   else emu::launch([](const hwy::LidarParams &q) { hwy::hwy_lidar_kernel<false>(q); }, E * cfg->num_agents, 64, lp);
   return 0;

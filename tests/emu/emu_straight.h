@@ -1,8 +1,9 @@
-// emu_straight.h -- TEST INFRASTRUCTURE ONLY.  What the three CPU drivers (emu_engine.cpp: IDM with meta-actions, emu_traffic.cpp:
-// Linear traffic, emu_control.cpp: direct ego control) share on the straight road: the host image of the state, the filling of
-// StepParams, and the family dispatch.  Include it AFTER hip_emu.h and the product headers (hwy_device.h, hwy_wave.h, hwy_params.h),
-// so that a driver's own #defines (HWY_EMU_ULP_NOISE) come before the product source.
-// A family is the trait of highwayenv_amd/csrc/hwy_launch_family.h (Params, step_params, the five kernels), with WPE = 1.
+// emu_straight.h -- TEST INFRASTRUCTURE ONLY.  The ONE driver of the CPU emulation (emu_engine.cpp: IDM with meta-actions on every
+// scenario, emu_traffic.cpp: Linear traffic, emu_control.cpp: direct ego control): the host image of the state, the binding of
+// StepParams to it, and the emulation's backend of the product's launch layer.  Nothing here builds a family's arguments or picks a
+// kernel: hwy_config -> arguments is highwayenv_amd/csrc/hwy_params.h, (arguments, Launch) -> (kernel, grid, block) is
+// hwy_launch_family.h / hwy_launch_rules.h -- the code hwy_engine.hip and the hwy_kernels*.hip units run, here with EmuBackend.
+// Include it AFTER hip_emu.h and the product headers, so that a driver's own #defines (HWY_EMU_ULP_NOISE) come before the product source.
 #pragma once
 #include <cstring>
 #include <type_traits>
@@ -49,99 +50,81 @@ struct ResetArgs {
   double ego_spacing, vehicles_density;
   int initial_lane_id;
 };
-// the OccupancyGrid workspace [E][A][2][W*H] hwy_engine.hip allocates for every family (null for the other observations)
-inline int32_t *grid_ws_for(const hwy_config *cfg) {
-  static std::vector<int32_t> ws;
-  if (cfg->obs_type != HWY_OBS_OCCUPANCY_GRID) return nullptr;
-  ws.assign((size_t)cfg->num_envs * cfg->num_agents * 2 * cfg->grid_shape[0] * cfg->grid_shape[1], 0);
-  return ws.data();
-}
 // StepParams from hwy_config, the image and the reset parameters (zeroes everything else of p)
 inline void fill_step_params(const hwy_config *cfg, HostImage &img, hwy_state *st, uint8_t *done, uint32_t *episode, const ResetArgs &ra,
                              StepParams &p) {
+  static std::vector<int32_t> grid_ws;  // the OccupancyGrid workspace hwy_engine.hip allocates for every family
   hwy::params_from_config(*cfg, cfg->num_vehicles, p);
   hwy::bind_planes(img.f64.data(), (size_t)cfg->num_envs * cfg->num_vehicles, p.st);
   p.st.packed = img.packed.data();
   p.st.time = st->time;
   p.st.done = done;
   p.st.episode = episode;
-  p.rp.ego_spacing = ra.ego_spacing;
-  p.rp.other_spacing = 1 / ra.vehicles_density;
-  p.rp.lane_factor = exp(-5.0 / 40.0 * cfg->lanes_count);
-  p.rp.initial_lane_id = ra.initial_lane_id;
-  p.rp.fast = (cfg->flags & HWY_C_EGO_ONLY_COLLISIONS) ? 1 : 0;
+  p.rp = hwy::default_reset_params(*cfg);
+  hwy::set_reset_args(p.rp, ra.ego_spacing, ra.vehicles_density, ra.initial_lane_id);
   p.rp.base_seed = ra.base_seed;
-  p.grid_ws = grid_ws_for(cfg);
+  grid_ws.assign(hwy::grid_ws_len(*cfg), 0);
+  p.grid_ws = grid_ws.empty() ? nullptr : grid_ws.data();
 }
 
-enum Which { STEP, ROLLOUT, RESET, OBSERVE };
-// same dispatch rule as hwy_launch_family.h: the one-wavefront kernel for N <= 64 unless the workgroup kernel is forced
-template <typename F>
-void dispatch(Which which, const typename F::Params &a, int E, bool force_block) {
-  const StepParams &p = F::step_params(a);
-  if ((which == STEP || which == ROLLOUT) && p.N <= 64 && !force_block) {
-    const bool full = !(p.flags & HWY_C_EGO_ONLY_COLLISIONS);
-    if (which == ROLLOUT) emu::launch(full ? F::template rollout_wave<1, true>() : F::template rollout_wave<1, false>(), E, 64, a);
-    else emu::launch(full ? F::template step_wave<1, true>() : F::template step_wave<1, false>(), E, 64, a);
-    return;
+// the emulation's backend of the launch layer (hwy_launch_family.h): workgroups run one after the other on the CPU, nothing is
+// resident, and the waves-per-EU builds of a kernel are one source -- one of them is compiled
+struct EmuBackend {
+  template <typename K, typename... A>
+  static hipError_t launch(K kernel, int grid, int block, int, const hwy::Launch &, const A &...a) {
+    emu::launch(kernel, grid, block, a...);
+    return hipSuccess;
   }
-  auto run = [&](auto V) {
-    constexpr int NW = decltype(V)::value;
-    switch (which) {
-      case STEP: emu::launch(F::template step_block<NW, 1>(), E, NW * 64, a); break;
-      case ROLLOUT: emu::launch(F::template rollout_block<NW, 1>(), E, NW * 64, a); break;
-      case RESET: emu::launch(F::template reset_block<NW>(), E, NW * 64, a); break;
-      case OBSERVE: emu::launch(hwy::hwy_observe_kernel<NW>, E, NW * 64, p); break;
-    }
-  };
-  switch ((p.N + 63) / 64) {
-    case 1: run(std::integral_constant<int, 1>{}); break;
-    case 2: run(std::integral_constant<int, 2>{}); break;
-    case 3: run(std::integral_constant<int, 3>{}); break;
-    default: run(std::integral_constant<int, 4>{}); break;
-  }
+  template <typename K> static int resident(K, int, int) { return 0; }
+  template <typename Fn> static auto pick_wpe(int, Fn &&fn) { return fn(std::integral_constant<int, 1>{}); }
+};
+// the Launch hwy_create would resolve from the config; force_block: emu_force_block_kernel
+inline hwy::Launch launch_of(const hwy_config &c, bool force_block = false) {
+  return {c.num_envs, nullptr, 1, 1, force_block || hwy::force_block_kernel(c), 0, nullptr, nullptr};
 }
 
-// the body of emu_traffic_run / emu_control_run.  `a` arrives with the family's own arguments filled.
-// mode: 0 = frames only (hwy_step_frames), 1 = full policy step(s) (hwy_step; k_steps > 0: hwy_rollout_device), 2 = observe only.
-template <typename F>
-int run(const hwy_config *cfg, hwy_state *st, typename F::Params &a, uint8_t *done, uint32_t *episode, int mode, int n_frames,
-        int k_steps, const int32_t *actions, float *obs, double *reward, uint8_t *term, uint8_t *trunc, double *speed,
-        uint8_t *crashed, int autoreset, const ResetArgs &ra) {
-  HostImage img(*cfg, *st);
-  StepParams &p = F::step_params(a);
+// The body of every driver's run entry point.  with_family(p, fn): builds the family's kernel argument around p and calls fn on it
+// (hwy_engine.hip: with_family).
+// mode: 0 = frames only (hwy_step_frames), 1 = full policy step(s) (hwy_step; k_steps > 0: hwy_rollout_device, the action / output
+// arrays hold k_steps blocks), 2 = observe only.
+template <typename WithFamily>
+int run(const hwy_config *cfg, hwy_state *st, HostImage &img, const hwy::Launch &l, WithFamily &&with_family, uint8_t *done,
+        uint32_t *episode, int mode, int n_frames, int k_steps, const int32_t *actions, float *obs, double *reward, uint8_t *term,
+        uint8_t *trunc, double *speed, uint8_t *crashed, int autoreset, const ResetArgs &ra, const uint16_t *block_env = nullptr) {
+  StepParams p;
   fill_step_params(cfg, img, st, done, episode, ra, p);
-  p.autoreset = autoreset;
+  p.autoreset = mode == 0 ? 0 : autoreset;
+  p.block_env = block_env;
   p.actions = actions; p.obs = obs; p.reward = reward; p.terminated = term; p.truncated = trunc;
   p.info_speed = speed; p.info_crashed = crashed;
-  Which which = OBSERVE;
+  const bool rollout = mode != 2 && k_steps > 0;
   if (mode != 2) {
     p.n_frames = n_frames;
     p.full_step = mode == 1;
-    if (mode == 0) p.autoreset = 0;
-    which = STEP;
-    if (mode == 1 && k_steps > 0) {
-      p.k_steps = k_steps;
-      p.num_envs = cfg->num_envs;
-      which = ROLLOUT;
-    }
   }
-  dispatch<F>(which, a, cfg->num_envs, cfg->tune_block_kernel == 1);
+  if (rollout) {
+    p.k_steps = k_steps;
+    p.num_envs = cfg->num_envs;
+  }
+  hipError_t e = hipSuccess;
+  with_family(p, [&](const auto &a) {
+    e = mode == 2 ? hwy::select_observe<EmuBackend>(a, l) : hwy::select_step<EmuBackend>(a, l, rollout);
+  });
   img.store(*st);
-  return 0;
+  return e == hipSuccess ? 0 : 1;
 }
-// the body of emu_traffic_reset / emu_control_reset
-template <typename F>
-int reset(const hwy_config *cfg, hwy_state *st, typename F::Params &a, uint8_t *done, uint32_t *episode, const uint8_t *mask,
-          const uint64_t *seeds, const ResetArgs &ra, float *obs) {
-  HostImage img(*cfg, *st);
-  StepParams &p = F::step_params(a);
+// the body of every driver's reset entry point
+template <typename WithFamily>
+int reset(const hwy_config *cfg, hwy_state *st, HostImage &img, const hwy::Launch &l, WithFamily &&with_family, uint8_t *done,
+          uint32_t *episode, const uint8_t *mask, const uint64_t *seeds, const ResetArgs &ra, float *obs) {
+  StepParams p;
   fill_step_params(cfg, img, st, done, episode, ra, p);
   p.reset_mask = mask;
   p.reset_seeds = seeds;
   p.obs = obs;
-  dispatch<F>(RESET, a, cfg->num_envs, cfg->tune_block_kernel == 1);
+  hipError_t e = hipSuccess;
+  with_family(p, [&](const auto &a) { e = hwy::select_reset<EmuBackend>(a, l); });
   img.store(*st);
-  return 0;
+  return e == hipSuccess ? 0 : 1;
 }
 }  // namespace emu_straight

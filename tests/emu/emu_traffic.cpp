@@ -1,37 +1,22 @@
 // emu_traffic.cpp -- TEST INFRASTRUCTURE ONLY.  Runs the Linear traffic family's kernels of the product source
 // (highwayenv_amd/csrc/hwy_wave.h: hwy_step_wave_linear_kernel, hwy_rollout_wave_linear_kernel; hwy_device.h: hwy_step_linear_kernel,
-// hwy_rollout_linear_kernel, hwy_reset_linear_kernel) on the CPU
-// through hip_emu.h, on host SoA arrays plus the per-vehicle parameter planes.  (emu_engine.cpp is the IDM driver; it has
-// no slot for the planes.)  The driver itself is emu_straight.h's.
+// hwy_rollout_linear_kernel, hwy_reset_linear_kernel) on the CPU through hip_emu.h, on host SoA arrays plus the per-vehicle
+// parameter planes.  (emu_engine.cpp is the IDM driver; it has no slot for the planes.)  The driver is emu_straight.h's, the
+// arguments and the choice of a kernel the product's own (hwy_params.h: linear_args; hwy_launch_family.h: LinearFamily).
 #include "hip_emu.h"
 
-#include "../../highwayenv_amd/csrc/hwy_device.h"
-#include "../../highwayenv_amd/csrc/hwy_wave.h"
-#include "../../highwayenv_amd/csrc/hwy_params.h"
+#include "../../highwayenv_amd/csrc/hwy_launch_family.h"
 #include "emu_straight.h"
 
+using emu_straight::HostImage;
 using emu_straight::ResetArgs;
 using hwy::LinearParams;
 using hwy::StepParams;
 
 namespace {
-struct LinearEmu {
-  using Params = LinearParams;
-  static StepParams &step_params(Params &a) { return a.s; }
-  static const StepParams &step_params(const Params &a) { return a.s; }
-  template <int WPE, bool FULL_SCAN> static auto step_wave() { return hwy::hwy_step_wave_linear_kernel<WPE, FULL_SCAN>; }
-  template <int WPE, bool FULL_SCAN> static auto rollout_wave() { return hwy::hwy_rollout_wave_linear_kernel<WPE, FULL_SCAN>; }
-  template <int NW, int WPE> static auto step_block() { return hwy::hwy_step_linear_kernel<NW, WPE>; }
-  template <int NW, int WPE> static auto rollout_block() { return hwy::hwy_rollout_linear_kernel<NW, WPE>; }
-  template <int NW> static auto reset_block() { return hwy::hwy_reset_linear_kernel<NW>; }
-};
-LinearParams extra_args(const hwy_config *cfg, double *behavior) {
-  LinearParams lp;
-  std::memset(&lp, 0, sizeof lp);
-  lp.la.behavior = behavior;
-  lp.la.plane = (long long)cfg->num_envs * cfg->num_vehicles;
-  lp.la.lc_gain = cfg->traffic_lc_min_acc_gain;
-  return lp;
+// behavior: HWY_BEHAVIOR_PARAMS planes [k][E][N] (pitch == N)
+auto linear_family(const hwy_config *cfg, double *behavior) {
+  return [=](const StepParams &p, auto &&fn) { fn(LinearParams{p, hwy::linear_args(*cfg, behavior, cfg->num_vehicles)}); };
 }
 }  // namespace
 
@@ -39,22 +24,23 @@ extern "C" {
 
 size_t emu_traffic_config_size(void) { return sizeof(hwy_config); }
 
-// mode, k_steps: emu_straight::run.  behavior: HWY_BEHAVIOR_PARAMS planes [k][E][N].
+// mode, k_steps: emu_straight::run
 int emu_traffic_run(const hwy_config *cfg, hwy_state *st, double *behavior, uint8_t *done, uint32_t *episode, int mode, int n_frames,
                     int k_steps, const int32_t *actions, float *obs, double *reward, uint8_t *term, uint8_t *trunc, double *speed,
                     uint8_t *crashed, int autoreset, uint64_t base_seed, double ego_spacing, double vehicles_density,
                     int initial_lane_id) {
-  LinearParams a = extra_args(cfg, behavior);
-  return emu_straight::run<LinearEmu>(cfg, st, a, done, episode, mode, n_frames, k_steps, actions, obs, reward, term, trunc, speed, crashed,
-                                  autoreset, ResetArgs{base_seed, ego_spacing, vehicles_density, initial_lane_id});
+  HostImage img(*cfg, *st);
+  return emu_straight::run(cfg, st, img, emu_straight::launch_of(*cfg), linear_family(cfg, behavior), done, episode, mode, n_frames, k_steps,
+                           actions, obs, reward, term, trunc, speed, crashed, autoreset,
+                           ResetArgs{base_seed, ego_spacing, vehicles_density, initial_lane_id});
 }
 
 int emu_traffic_reset(const hwy_config *cfg, hwy_state *st, double *behavior, uint8_t *done, uint32_t *episode, const uint8_t *mask,
                       const uint64_t *seeds, uint64_t base_seed, double ego_spacing, double vehicles_density, int initial_lane_id,
                       float *obs) {
-  LinearParams a = extra_args(cfg, behavior);
-  return emu_straight::reset<LinearEmu>(cfg, st, a, done, episode, mask, seeds,
-                                    ResetArgs{base_seed, ego_spacing, vehicles_density, initial_lane_id}, obs);
+  HostImage img(*cfg, *st);
+  return emu_straight::reset(cfg, st, img, emu_straight::launch_of(*cfg), linear_family(cfg, behavior), done, episode, mask, seeds,
+                             ResetArgs{base_seed, ego_spacing, vehicles_density, initial_lane_id}, obs);
 }
 
 void emu_traffic_debug_math(int op, const double *in, double *out, long long n) {

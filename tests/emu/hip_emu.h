@@ -48,6 +48,10 @@
 #define HWY_KC(c) (c)  // hwy_math.h: SGPR-pinned constant (an AMDGPU inline-asm constraint on the device)
 
 struct emu_dim3 { int x = 0, y = 0, z = 0; };
+// the host-side names the product's launch layer uses (hwy_launch_family.h: Launch and the selection layer)
+using hipStream_t = void *;
+using hipEvent_t = void *;
+enum hipError_t { hipSuccess = 0, hipErrorInvalidValue = 1 };
 
 namespace emu {
 using Loc = std::source_location;  // the call site of a rendezvous (a default argument: the kernel source's own line)

@@ -24,7 +24,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 CSRC = os.path.join(ROOT, "highwayenv_amd", "csrc")
 OUT = os.path.join(HERE, "_build")
-FILES = ("hwy_kernels.hip", "hwy_engine.hip", "hwy_comm.hip", "hwy_comm.h", "hwy_launch.h", "hwy_launch_family.h", "hwy_params.h",
+FILES = ("hwy_kernels.hip", "hwy_engine.hip", "hwy_comm.hip", "hwy_comm.h", "hwy_launch.h", "hwy_launch_family.h", "hwy_launch_rules.h", "hwy_params.h",
          "hwy_wave.h", "hwy_wave2.h", "hwy_device.h", "hwy_math.h", "hwy_net.h", "hwy_ix.h")
 W, D, NET, IX = "hwy_wave.h", "hwy_device.h", "hwy_net.h", "hwy_ix.h"
 W2 = "hwy_wave2.h"

@@ -1,0 +1,111 @@
+#!/usr/bin/env python3
+"""Developer tool: does a refactor of the host launch layer still launch the same kernels?  Needs an MI355X.
+
+    rocprofv3 --kernel-trace --stats -d OUT_A -- python tools/launch_table.py        (HWY_ENGINE_LIB = library A)
+    rocprofv3 --kernel-trace --stats -d OUT_B -- python tools/launch_table.py        (HWY_ENGINE_LIB = library B)
+    python tools/launch_table.py --compare OUT_A OUT_B                               exit status 0 = the same launches
+
+Without arguments: resets, steps, observes and runs a 2-step rollout once each on a table of tiny engines (4 environments) that
+covers every branch of the kernel selection (csrc/hwy_launch_family.h, hwy_launch_rules.h): the one-wavefront kernel with and
+without FULL_SCAN, the wide kernel, the workgroup kernel (OccupancyGrid, forced, N > 128), the Linear and direct families on both
+sides of N = 64, the Lidar trace, the road-network kernels with both observations, the intersection kernel with and without helper
+lanes, its 64-slot build and the doubled grid of next-episode pre-warming.  --compare reads the two kernel traces in dispatch
+order and requires equal sequences of (kernel name, grid size, workgroup size, LDS)."""
+from __future__ import annotations
+
+import csv
+import glob
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+LINEAR = "highway_env.vehicle.behavior.LinearVehicle"
+
+
+def table():
+    """(label, config dict, make_config keywords, auto-reset)"""
+    from highwayenv_amd import _abi, intersection, merge
+
+    def hwy(n, **over):
+        d = _abi.highway_default_config()
+        d.update({"vehicles_count": n - 1, **over})
+        return d
+
+    def ix(slots, **over):
+        d = intersection.intersection_default_config()
+        d.update({"max_vehicles": slots, "host_traffic": False, **over})
+        return d
+
+    grid = {"observation": {"type": "OccupancyGrid"}}
+    return [
+        ("N=50 ego-only collisions", hwy(50), {"fast": True}, False),
+        ("N=50 full scan", hwy(50), {}, False),
+        ("N=101 Kinematics", hwy(101), {}, False),
+        ("N=101 OccupancyGrid", hwy(101, **grid), {}, False),
+        ("N=101 block_kernel=1", hwy(101), {"tuning": {"block_kernel": 1}}, False),
+        ("N=150 block_kernel=0", hwy(150), {}, False),
+        ("N=150 block_kernel=2", hwy(150), {"tuning": {"block_kernel": 2}}, False),
+        ("Linear N=50", hwy(50, other_vehicles_type=LINEAR), {}, False),
+        ("Linear N=101", hwy(101, other_vehicles_type=LINEAR), {}, False),
+        ("Direct N=50", hwy(50, action={"type": "DiscreteAction"}), {}, False),
+        ("Lidar N=50", hwy(50, observation={"type": "LidarObservation"}), {}, False),
+        ("merge Kinematics", merge.merge_default_config(), {"scenario": "merge"}, False),
+        ("merge OccupancyGrid", dict(merge.merge_default_config(), **grid), {"scenario": "merge"}, False),
+        ("intersection N=30 helpers", ix(30), {"scenario": "intersection"}, False),
+        ("intersection N=30 no helpers", ix(30), {"scenario": "intersection", "tuning": {"ix_no_helpers": 1}}, False),
+        ("intersection N=40", ix(40), {"scenario": "intersection"}, False),
+        ("intersection N=30 pre-warming", ix(30), {"scenario": "intersection"}, True),
+    ]
+
+
+def run() -> None:
+    import numpy as np
+
+    from highwayenv_amd import _abi
+    from highwayenv_amd.engine import Engine
+
+    E = 4
+    for label, d, kw, autoreset in table():
+        cfg = _abi.make_config(d, E, **kw)
+        eng = Engine(cfg)
+        eng.reset(base_seed=11)
+        if autoreset:
+            eng.set_autoreset(True, base_seed=12)
+        acts = np.ones((2, E, cfg.num_agents), np.int32)
+        eng.step(acts[0])
+        obs = eng.observe()
+        out = eng.rollout(acts)
+        eng.close()
+        print(f"{label}: N={cfg.num_vehicles} obs {obs.shape} rollout {out[0].shape}", flush=True)
+
+
+def launches(out_dir: str) -> list:
+    files = sorted(glob.glob(os.path.join(out_dir, "**", "*kernel_trace.csv"), recursive=True))
+    if not files:
+        raise SystemExit(f"no *kernel_trace.csv under {out_dir}")
+    rows = [r for f in files for r in csv.DictReader(open(f))]
+    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+
+    def cols(r, prefix):
+        return tuple(int(r[k]) for k in sorted(r) if k.startswith(prefix))
+
+    return [(r["Kernel_Name"], cols(r, "Grid_Size"), cols(r, "Workgroup_Size"), int(r["LDS_Block_Size"])) for r in rows]
+
+
+def compare(a_dir: str, b_dir: str) -> int:
+    a, b = launches(a_dir), launches(b_dir)
+    print(f"{len(a)} launches in {a_dir}, {len(b)} in {b_dir}")
+    diff = [(k, x, y) for k, (x, y) in enumerate(zip(a, b)) if x != y]
+    for k, x, y in diff[:10]:
+        print(f"launch {k}: {x} != {y}")
+    same = len(a) == len(b) and not diff
+    print(f"{len(set(x[0] for x in a))} distinct kernels;", "the two sequences are equal line for line" if same else "DIFFERENT")
+    return 0 if same else 1
+
+
+if __name__ == "__main__":
+    if len(sys.argv) == 4 and sys.argv[1] == "--compare":
+        sys.exit(compare(sys.argv[2], sys.argv[3]))
+    run()
