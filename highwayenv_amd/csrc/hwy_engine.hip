@@ -385,10 +385,12 @@ extern "C" int hwy_create(const hwy_config *cfg, int device, void *stream, hwy_e
   }
   else if (cfg->scenario != HWY_SCENARIO_HIGHWAY) eng->waves_per_eu = 4;
   else {
-    // highway scenario.  One-wavefront kernels (N <= 64; 102 VGPRs ego-only, 128 full-pairwise: every allocation variant is the
-    // same code since the build stopped hoisting literals, build.py).  Workgroup kernel (N > 64, ceil(N / 64) wavefronts per
-    // environment): 146 .. 154 VGPRs at 3 waves/SIMD, 128 with 18 .. 30 spilled at 4 -- the 4-wave build pays as soon as the grid
-    // no longer fits 3 resident wavefronts per SIMD (1024 x 101: 159.2 / 164.4 us; 2048 x 101: 273.2 / 209.6 us)
+    // highway scenario.  One-wavefront kernels (N <= 64; 99 VGPRs ego-only, 113 full-pairwise: every allocation variant gets the
+    // same registers since the build stopped hoisting literals, build.py; that every variant of every kernel COMPUTES the same,
+    // the spilling 4-wave workgroup builds included, is tests/test_kernel_variants.py, bit for bit on the device).
+    // Workgroup kernel (N > 64, ceil(N / 64) wavefronts per environment): 146 .. 154 VGPRs at 3 waves/SIMD, 128 with 18 .. 30
+    // spilled at 4 -- the 4-wave build pays as soon as the grid no longer fits 3 resident wavefronts per SIMD (1024 x 101:
+    // 159.2 / 164.4 us; 2048 x 101: 273.2 / 209.6 us)
     hipDeviceProp_t prop;
     const int simds = (hipGetDeviceProperties(&prop, device) == hipSuccess ? prop.multiProcessorCount : 256) * 4;
     const long long waves = (long long)cfg->num_envs * ((cfg->num_vehicles + 63) / 64);

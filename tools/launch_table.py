@@ -1,16 +1,20 @@
 #!/usr/bin/env python3
 """Developer tool: does a refactor of the host launch layer still launch the same kernels?  Needs an MI355X.
 
-    rocprofv3 --kernel-trace --stats -d OUT_A -- python tools/launch_table.py        (HWY_ENGINE_LIB = library A)
-    rocprofv3 --kernel-trace --stats -d OUT_B -- python tools/launch_table.py        (HWY_ENGINE_LIB = library B)
+    rocprofv3 --kernel-trace --stats --output-format csv -d OUT_A -- python tools/launch_table.py     (HWY_ENGINE_LIB = library A)
+    rocprofv3 --kernel-trace --stats --output-format csv -d OUT_B -- python tools/launch_table.py     (HWY_ENGINE_LIB = library B)
     python tools/launch_table.py --compare OUT_A OUT_B                               exit status 0 = the same launches
+    python tools/launch_table.py --covers OUT_A                                      exit status 0 = every step / rollout build ran
 
 Without arguments: resets, steps, observes and runs a 2-step rollout once each on a table of tiny engines (4 environments) that
 covers every branch of the kernel selection (csrc/hwy_launch_family.h, hwy_launch_rules.h): the one-wavefront kernel with and
 without FULL_SCAN, the wide kernel, the workgroup kernel (OccupancyGrid, forced, N > 128), the Linear and direct families on both
 sides of N = 64, the Lidar trace, the road-network kernels with both observations, the intersection kernel with and without helper
-lanes, its 64-slot build and the doubled grid of next-episode pre-warming.  --compare reads the two kernel traces in dispatch
-order and requires equal sequences of (kernel name, grid size, workgroup size, LDS)."""
+lanes, its 64-slot build and the doubled grid of next-episode pre-warming -- and then every row of tests/variants_util.py (the
+branches in which hwy_config.tune_waves_per_eu picks a register-allocation build) at every value of the knob.  --compare reads the
+two kernel traces in dispatch order and requires equal sequences of (kernel name, grid size, workgroup size, LDS).  --covers reads
+one trace and lists which step and rollout kernels of the built code object (highwayenv_amd.build.kernel_resources) were and were
+not launched: the evidence that the selection rules as tests/variants_util.py restates them are what the engine really launches."""
 from __future__ import annotations
 
 import csv
@@ -38,7 +42,11 @@ def table():
         d.update({"max_vehicles": slots, "host_traffic": False, **over})
         return d
 
+    from tests import variants_util
+
     grid = {"observation": {"type": "OccupancyGrid"}}
+    variants = [(f"{label} waves_per_eu={v}", d, variants_util.with_tuning(kw, waves_per_eu=v), False)
+                for label, d, kw in variants_util.rows() for v in variants_util.values(kw)]
     return [
         ("N=50 ego-only collisions", hwy(50), {"fast": True}, False),
         ("N=50 full scan", hwy(50), {}, False),
@@ -47,6 +55,7 @@ def table():
         ("N=101 block_kernel=1", hwy(101), {"tuning": {"block_kernel": 1}}, False),
         ("N=150 block_kernel=0", hwy(150), {}, False),
         ("N=150 block_kernel=2", hwy(150), {"tuning": {"block_kernel": 2}}, False),
+        ("N=200 block_kernel=2", hwy(200), {"tuning": {"block_kernel": 2}}, False),
         ("Linear N=50", hwy(50, other_vehicles_type=LINEAR), {}, False),
         ("Linear N=101", hwy(101, other_vehicles_type=LINEAR), {}, False),
         ("Direct N=50", hwy(50, action={"type": "DiscreteAction"}), {}, False),
@@ -57,7 +66,7 @@ def table():
         ("intersection N=30 no helpers", ix(30), {"scenario": "intersection", "tuning": {"ix_no_helpers": 1}}, False),
         ("intersection N=40", ix(40), {"scenario": "intersection"}, False),
         ("intersection N=30 pre-warming", ix(30), {"scenario": "intersection"}, True),
-    ]
+    ] + variants
 
 
 def run() -> None:
@@ -105,7 +114,26 @@ def compare(a_dir: str, b_dir: str) -> int:
     return 0 if same else 1
 
 
+def covers(out_dir: str) -> int:
+    import re
+
+    from highwayenv_amd import build
+    from tests.variants_util import STEP_OR_ROLLOUT
+
+    # the trace names a kernel with its argument list ("void hwy::hwy_step_kernel<2, 4>(hwy::StepParams)"), kernel_resources() without
+    ran = {re.sub(r"\(.*\)$", "", x[0]).replace("void ", "").strip() for x in launches(out_dir)}
+    want = sorted(k for k in build.kernel_resources() if STEP_OR_ROLLOUT.match(k))
+    missing = [k for k in want if k not in ran]
+    print(f"{len(ran)} distinct kernels launched; {len(want) - len(missing)} of the {len(want)} step and rollout kernels of the code object among them")
+    for k in want:
+        print(("launched      " if k in ran else "NOT LAUNCHED  ") + k)
+    print("not launched:", ", ".join(missing) if missing else "none")
+    return 1 if missing else 0
+
+
 if __name__ == "__main__":
     if len(sys.argv) == 4 and sys.argv[1] == "--compare":
         sys.exit(compare(sys.argv[2], sys.argv[3]))
+    if len(sys.argv) == 3 and sys.argv[1] == "--covers":
+        sys.exit(covers(sys.argv[2]))
     run()
