@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from highwayenv_amd import _abi
+from tests import spawn_util
 from tests.control_util import BACKENDS, FIXTURES, WITH_FRAMES, ControlGolden, make_engine
 from tests.golden_util import assert_state_close
 
@@ -160,21 +161,24 @@ def _direct_cfg(E, fast=True, **over):
 @pytest.mark.parametrize("backend", BACKENDS)
 @pytest.mark.parametrize("n", [50, 100])
 def test_device_reset_is_the_meta_action_reset_with_zero_controls(backend, n):
-    """hwy_reset of a direct-control engine: every state plane is the one the meta-action engine's reset writes for the same seeds
-    (same Philox draws; the emulation of the meta-action kernels is the yardstick), the stored controls are zero."""
+    """hwy_reset of a direct-control engine against the yardstick of tests/spawn_util.py (the Python Philox and the reference's rule,
+    nothing compiled from the kernel source): every state plane, the first observation and zero stored controls.  Beside it: every
+    plane is bit for bit the one the emulated meta-action engine's reset writes for the same seeds (same Philox draws)."""
     from tests.emu.emu import EmuEngine
     E = 8
     d, cfg = _direct_cfg(E, vehicles_count=n)
     eng = make_engine(backend, cfg)
     eng.set_controls(np.full((E, 1), 3.0), np.full((E, 1), 0.25))
     seeds = np.arange(E, dtype=np.uint64) * 7919 + 3
-    obs = eng.reset(seeds=seeds, ego_spacing=d["ego_spacing"], vehicles_density=d["vehicles_density"])
+    kw = dict(ego_spacing=d["ego_spacing"], vehicles_density=d["vehicles_density"])
+    obs = eng.reset(seeds=seeds, **kw)
     st = eng.get_state()
     accel, steer = eng.get_controls()
+    spawn_util.assert_spawned(d, cfg, eng, np.arange(E), seeds, 0, obs, kw, "direct-control reset")
     eng.close()
     assert not accel.any() and not steer.any()
     meta = EmuEngine(_abi.make_config(dict(d, action={"type": "DiscreteMetaAction"}), E, fast=True))
-    obs_meta = meta.reset(seeds=seeds, ego_spacing=d["ego_spacing"], vehicles_density=d["vehicles_density"])
+    obs_meta = meta.reset(seeds=seeds, **kw)
     ref = meta.get_state()
     for k in _abi.STATE_F64 + _abi.STATE_I32:
         np.testing.assert_array_equal(st[k], ref[k], err_msg=k)
@@ -198,9 +202,13 @@ def test_autoreset_clears_the_controls(backend, block_kernel):
     assert (accel == 5.0).all() and (steer == cfg.steer_axis[2]).all()
     _, _, te, tr, _ = eng.step(gas)
     assert (te | tr).all()  # duration 2 at policy frequency 1: every environment ends in its second step ...
-    _, reward, te, tr, _ = eng.step(gas)  # ... and is re-spawned in the third (next-step auto-reset: reward 0, not done)
+    out = eng.step(gas)  # ... and is re-spawned in the third (next-step auto-reset: reward 0, not done)
+    _, reward, te, tr, _ = out
     assert not (te | tr).any() and not reward.any()
     accel, steer = eng.get_controls()
+    # (the whole re-spawn against the rule on the Python Philox: state, observation, outputs, zero controls)
+    kw = dict(ego_spacing=d["ego_spacing"], vehicles_density=d["vehicles_density"])
+    spawn_util.assert_spawned(d, cfg, eng, np.arange(E), 11 + np.arange(E), 1, out, kw, "direct-control re-spawn")
     eng.close()
     assert not accel.any() and not steer.any()
 

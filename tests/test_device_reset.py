@@ -4,53 +4,16 @@ The device spawn draws from Philox-4x32-10 (counter-based, one stream per env), 
 stream; what must match the reference is the rule that turns draws into traffic
 (Vehicle.create_random, highway_env/vehicle/kinematics.py:50-104).  ``spawn.spawn_from_draws`` is
 that rule, verified against the reference's own reset states in tests/test_spawn.py; here the
-kernel is checked against it on the same Philox uniforms, computed independently in Python.
+kernel is checked against it on the same Philox uniforms, computed independently in Python
+(tests/spawn_util.py; every kernel path and size: tests/test_spawn_paths.py).
 """
 import numpy as np
 import pytest
 
-from highwayenv_amd import _abi, spawn
+from highwayenv_amd import _abi
 from oracle import oracle
 from tests.backends import BACKENDS, make_engine
-
-M32 = 0xFFFFFFFF
-
-
-def philox_uniform2(seed, vehicle, episode, draw):
-    """Philox-4x32-10 (Salmon et al. 2011), counter (vehicle, episode, draw, 'HWY1'), key = seed."""
-    c = [vehicle & M32, episode & M32, draw & M32, 0x48575931]
-    k0, k1 = seed & M32, (seed >> 32) & M32
-    for _ in range(10):
-        p0 = 0xD2511F53 * c[0]
-        p1 = 0xCD9E8D57 * c[2]
-        c = [((p1 >> 32) ^ c[1] ^ k0) & M32, p1 & M32, ((p0 >> 32) ^ c[3] ^ k1) & M32, p0 & M32]
-        k0 = (k0 + 0x9E3779B9) & M32
-        k1 = (k1 + 0xBB67AE85) & M32
-    a, b = (c[0] << 32) | c[1], (c[2] << 32) | c[3]
-    return (a >> 11) / 9007199254740992.0, (b >> 11) / 9007199254740992.0
-
-
-def expected_state(cfg, seeds, episode, ego_spacing, density, initial_lane_id):
-    E, N, L = len(seeds), cfg.num_vehicles, cfg.lanes_count
-    lane = np.zeros((E, N), np.int64)
-    us, up, ud = np.zeros((E, N)), np.zeros((E, N)), np.zeros((E, N))
-    ctrl = spawn.controlled_mask(cfg)
-    for e, sd in enumerate(seeds):
-        for i in range(N):
-            u_lane, u_speed = philox_uniform2(int(sd), i, episode, 0)
-            u_pos, u_delta = philox_uniform2(int(sd), i, episode, 1)
-            lane[e, i] = min(int(u_lane * L), L - 1)
-            if ctrl[i] and initial_lane_id >= 0:
-                lane[e, i] = initial_lane_id
-            us[e, i], up[e, i], ud[e, i] = u_speed, u_pos, u_delta
-    return spawn.spawn_from_draws(cfg, lane, us, up, ud, ego_spacing, density)
-
-
-def assert_spawn_equal(got, want, rows=slice(None)):
-    for k in ("lane", "target_lane", "flags", "speed_index"):
-        np.testing.assert_array_equal(got[k][rows], want[k][rows], err_msg=k)
-    for k in ("x", "y", "heading", "speed", "target_speed", "timer", "delta"):
-        np.testing.assert_allclose(got[k][rows], want[k][rows], rtol=0, atol=1e-9, err_msg=k)
+from tests.spawn_util import assert_spawn_equal, expected_state
 
 
 @pytest.mark.parametrize("backend", BACKENDS)

@@ -12,7 +12,7 @@ import pytest
 from highwayenv_amd import _abi
 from highwayenv_amd import intersection as hix
 from tests.backends import BACKENDS, make_engine
-from tests.test_device_reset import philox_uniform2
+from tests.spawn_util import philox_uniform2
 
 
 class PhiloxAsGenerator:

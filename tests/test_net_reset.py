@@ -13,7 +13,7 @@ import pytest
 from highwayenv_amd import _abi, merge
 from oracle import oracle
 from tests.backends import BACKENDS, make_engine
-from tests.test_device_reset import philox_uniform2
+from tests.spawn_util import philox_uniform2
 
 
 def expected_state(c, cfg, generic, seeds, episode):

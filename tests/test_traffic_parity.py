@@ -153,17 +153,25 @@ def _linear_cfg(E, **over):
 
 @pytest.mark.parametrize("backend", BACKENDS)
 def test_device_reset_draws_the_rule_on_philox_uniforms(backend):
-    """hwy_reset with Linear traffic: the parameters are spawn.behavior_from_draws of the Philox uniforms 2 .. 4 of every vehicle
-    (the method of tests/test_device_reset.py); the IDM planes of the spawn are those draws 0 and 1 give an IDM reset."""
+    """hwy_reset with Linear traffic against the yardstick of tests/spawn_util.py (the Python Philox and the reference's rule, nothing
+    compiled from the kernel source): the parameters are spawn.behavior_from_draws of the Philox uniforms 2 .. 4 of every vehicle, bit
+    for bit; the kinematic planes are the rule on draws 0 and 1 (what an IDM reset draws), the first observation is the oracle's of
+    that state.  Beside it, as before: the emulator's own Philox gives the same parameters (every draw of every vehicle), and every
+    state plane is, bit for bit, what the emulated IDM reset spawns on the same seeds."""
+    from tests import spawn_util
     from tests.emu import emu
     E = 8
     d, cfg = _linear_cfg(E)
     eng = make_engine(backend, cfg)
     seeds = np.arange(E, dtype=np.uint64) * 7919 + 3
-    eng.reset(seeds=seeds, ego_spacing=d["ego_spacing"], vehicles_density=d["vehicles_density"])
+    kw = dict(ego_spacing=d["ego_spacing"], vehicles_density=d["vehicles_density"])
+    obs = eng.reset(seeds=seeds, **kw)
     got = eng.get_behavior()
     st = eng.get_state()
+    want = spawn_util.assert_spawned(d, cfg, eng, np.arange(E), seeds, 0, obs, kw, "Linear reset")
     eng.close()
+    np.testing.assert_array_equal(got, want["behavior"])
+    assert (np.diff(want["x"], axis=1) > 0).all() and got[:, 1:].all()
     u = np.zeros((E, cfg.num_vehicles, 5))
     for e in range(E):
         for i in range(cfg.num_vehicles):
@@ -171,33 +179,43 @@ def test_device_reset_draws_the_rule_on_philox_uniforms(backend):
             a2, s0 = emu.philox_uniform2(int(seeds[e]), i, 0, 3)
             s1, _ = emu.philox_uniform2(int(seeds[e]), i, 0, 4)
             u[e, i] = [a0, a1, a2, s0, s1]
+            for draw in (0, 1):
+                assert emu.philox_uniform2(int(seeds[e]), i, 0, draw) == spawn_util.philox_uniform2(int(seeds[e]), i, 0, draw)
     np.testing.assert_array_equal(got, spawn.behavior_from_draws(cfg, u))
     # the kinematic spawn is the IDM reset's
     from tests.emu.emu import EmuEngine
     idm = EmuEngine(_abi.make_config(dict(d, other_vehicles_type="highway_env.vehicle.behavior.IDMVehicle"), E, fast=True))
-    idm.reset(seeds=seeds, ego_spacing=d["ego_spacing"], vehicles_density=d["vehicles_density"])
+    idm.reset(seeds=seeds, **kw)
     ref = idm.get_state()
+    idm.close()
     for k in _abi.STATE_F64 + _abi.STATE_I32:
         np.testing.assert_array_equal(st[k], ref[k], err_msg=k)
 
 
 @pytest.mark.parametrize("backend", BACKENDS)
 def test_autoreset_respawns_parameters(backend):
-    """An environment that ends is re-spawned with episode + 1's parameters (same rule, next Philox stream)."""
+    """An environment that ends is re-spawned with episode + 1's state and parameters: the rule on the next Philox stream of its
+    auto-reset seed, computed in Python (tests/spawn_util.py).  Beside it, the kernel's own draw function compiled for the CPU
+    (emu_traffic.behavior_draw) gives the same parameters."""
+    from tests import spawn_util
     E = 4
     d, cfg = _linear_cfg(E, vehicles_count=20, lanes_count=3, duration=2)
     eng = make_engine(backend, cfg)
-    eng.reset(seeds=np.arange(E, dtype=np.uint64), ego_spacing=d["ego_spacing"], vehicles_density=d["vehicles_density"])
-    eng.set_autoreset(True, base_seed=11, ego_spacing=d["ego_spacing"], vehicles_density=d["vehicles_density"])
+    kw = dict(ego_spacing=d["ego_spacing"], vehicles_density=d["vehicles_density"])
+    eng.reset(seeds=np.arange(E, dtype=np.uint64), **kw)
+    eng.set_autoreset(True, base_seed=11, **kw)
     idle = np.ones((E, 1), np.int32)
     _, _, te, tr, _ = eng.step(idle)
     assert not (te | tr).any()
     _, _, te, tr, _ = eng.step(idle)
     assert (te | tr).all()  # duration 2 at policy frequency 1: every environment ends in its second step ...
-    _, reward, te, tr, _ = eng.step(idle)  # ... and is re-spawned in the third (next-step auto-reset: reward 0, not done)
+    out = eng.step(idle)    # ... and is re-spawned in the third (next-step auto-reset: reward 0, not done)
+    _, reward, te, tr, _ = out
     assert not (te | tr).any() and not reward.any()
     got = eng.get_behavior()
+    spawn_util.assert_spawned(d, cfg, eng, np.arange(E), 11 + np.arange(E), 1, out, kw, "Linear re-spawn")
     eng.close()
+    np.testing.assert_array_equal(got, spawn_util.expected_behavior(cfg, 11 + np.arange(E), 1))
     from tests.emu import emu_traffic
     for e in range(E):
         for i in range(1, cfg.num_vehicles):
