@@ -23,6 +23,7 @@ HWY_MAX_GLANES = 24
 HWY_MAX_ROUTE = 11
 HWY_MAX_ACTIONS_PER_AXIS = 16
 HWY_MAX_LIDAR_CELLS = 64
+HWY_MAX_TTC_STEPS = 64
 
 # hwy_status
 HWY_OK, HWY_ERR_INVALID_ARG, HWY_ERR_HIP, HWY_ERR_UNSUPPORTED, HWY_ERR_NO_DEVICE, HWY_ERR_ACTION = 0, -1, -2, -3, -4, -5
@@ -228,6 +229,40 @@ class HwyConfig(C.Structure):
         ("lidar_normalize", C.c_int32),
         ("lidar_max_range", C.c_double),
     ]
+
+
+class HwyTtcParams(C.Structure):
+    """hwy_ttc_params (include/hwy_engine.h): the arguments of finite_mdp (envs/common/finite_mdp.py:17-19) and of its solver."""
+    _fields_ = [("horizon", C.c_double), ("time_quantization", C.c_double), ("gamma", C.c_double),
+                ("lane_change_reward", C.c_double), ("time_steps", C.c_int32), ("reserved", C.c_int32)]
+
+
+def ttc_params(config: dict, horizon: float = 10.0, time_quantization: float | None = None, gamma: float = 1.0) -> HwyTtcParams:
+    """``to_finite_mdp``'s arguments for a reference-style config dict: ``time_quantization`` defaults to ``1 / policy_frequency``
+    (abstract.py:453) and ``time_steps`` is the reference's own ``int(horizon / time_quantization)`` (finite_mdp.py:122-124)."""
+    tq = 1 / config["policy_frequency"] if time_quantization is None else float(time_quantization)
+    p = HwyTtcParams()
+    p.horizon, p.time_quantization, p.gamma = float(horizon), tq, float(gamma)
+    p.lane_change_reward = float(config.get("lane_change_reward", 0))
+    if not (tq > 0 and np.isfinite(tq) and np.isfinite(p.horizon) and p.horizon >= 0):
+        raise ValueError("horizon and time_quantization must be finite, time_quantization positive")
+    steps = int(horizon / tq)
+    if not (1 <= steps <= HWY_MAX_TTC_STEPS):
+        raise ValueError(f"int(horizon / time_quantization) = {steps}: the grid holds 1..{HWY_MAX_TTC_STEPS} time steps")
+    p.time_steps = steps
+    return p
+
+
+def check_finite_mdp_scope(cfg: "HwyConfig") -> None:
+    """What ``to_finite_mdp`` / ``ttc_grid`` / ``plan_finite_mdp`` run on (csrc/hwy_ttc.h: ttc_validate, the same rules)."""
+    if cfg.scenario != SCENARIO_HIGHWAY:
+        raise NotImplementedError("to_finite_mdp is in the MI355X hot-path scope on the highway scenario only")
+    if cfg.ego_control != EGO_META:
+        raise NotImplementedError("to_finite_mdp needs a DiscreteMetaAction ego (a plain Vehicle has no target_speeds) and is outside "
+                                  "the MI355X hot-path scope with DiscreteAction")
+    if cfg.action_set != ACTIONS_SET_ALL:
+        raise NotImplementedError("to_finite_mdp with longitudinal=False or lateral=False is outside the MI355X hot-path scope "
+                                  "(the reference builds a 5-column reward next to a 3-column transition there)")
 
 
 def obs_shape(cfg: "HwyConfig") -> tuple:

@@ -62,6 +62,11 @@ struct hwy_engine {
   uint8_t *d_mask = nullptr;
   uint64_t *d_seeds = nullptr;
   int32_t *d_grid_ws = nullptr;  // OccupancyGrid workspace [E][A][2][W*H]
+  // outputs of the host-pointer planner entry points (hwy_ttc_grid / hwy_mdp_plan), allocated on first use
+  float *d_ttc_grid = nullptr;   // [E][A][ttc_cells]
+  int ttc_cells = 0;
+  int32_t *d_plan_action = nullptr;  // [E][A]
+  double *d_plan_q = nullptr;        // [E][A][5]
   // pinned host staging
   void *h_pinned = nullptr;
   size_t h_pinned_bytes = 0;
@@ -513,7 +518,7 @@ extern "C" int hwy_destroy(hwy_engine *eng) {
   void *ptrs[] = {eng->d_f64, eng->d_packed, eng->d_time, eng->d_done, eng->d_episode, eng->d_actions, eng->d_out, eng->d_roll,
                   eng->d_mask, eng->d_seeds, eng->d_grid_ws, eng->d_route, eng->d_road_steps, eng->d_gnet,
                   eng->d_shadow_f64, eng->d_shadow_packed, eng->d_shadow_route, eng->d_shadow_meta, eng->d_counters, eng->d_block_env,
-                  eng->d_behavior, eng->d_controls};
+                  eng->d_behavior, eng->d_controls, eng->d_ttc_grid, eng->d_plan_action, eng->d_plan_q};
   for (void *q : ptrs) if (q) (void)hipFree(q);
   if (eng->h_pinned) (void)hipHostFree(eng->h_pinned);
   if (eng->own_stream && eng->stream) (void)hipStreamDestroy(eng->stream);
@@ -1076,6 +1081,79 @@ extern "C" int hwy_comm_destroy(hwy_engine *eng) {
     hwy::comm_destroy(eng->comm);
     eng->comm = nullptr;
   }
+  return HWY_OK;
+}
+
+// ---- time-to-collision grid and finite-MDP planner (hwy_ttc.h) -------------------------------------------------------------------
+static int ttc_check(hwy_engine *eng, const hwy_ttc_params *params, const char *who) {
+  const char *why = "";
+  if (const int rc = hwy::ttc_validate(eng->cfg, params, &why)) return fail(eng, rc, std::string(who) + ": " + why);
+  return HWY_OK;
+}
+static hipError_t ttc_launch(const hwy_engine *eng, const hwy_ttc_params &tp, bool plan, float *d_grid, int32_t *d_action, double *d_q) {
+  const size_t plane = (size_t)eng->cfg.num_envs * eng->pitch;
+  const double *f = eng->d_f64;  // planes: x | y | heading | speed | ...
+  const hwy::TtcParams p = hwy::ttc_params(eng->cfg, tp, f, f + 2 * plane, f + 3 * plane, eng->d_packed, eng->pitch, d_grid, d_action, d_q);
+  return hwy::launch_ttc(p, plan, (int)num_agent_rows(eng->cfg), eng->stream);
+}
+// the engine's own output buffers of the host-pointer forms (the grid's size depends on the call's time_steps)
+static int ttc_buffers(hwy_engine *eng, int cells) {
+  const size_t rows = num_agent_rows(eng->cfg);
+  if (eng->ttc_cells < cells) {
+    if (eng->d_ttc_grid) { HWY_HIP(eng, hipStreamSynchronize(eng->stream)); HWY_HIP(eng, hipFree(eng->d_ttc_grid)); eng->d_ttc_grid = nullptr; }
+    eng->ttc_cells = 0;
+    HWY_HIP(eng, hipMalloc((void **)&eng->d_ttc_grid, rows * cells * sizeof(float)));
+    eng->ttc_cells = cells;
+  }
+  if (!eng->d_plan_action) HWY_HIP(eng, hipMalloc((void **)&eng->d_plan_action, rows * sizeof(int32_t)));
+  if (!eng->d_plan_q) HWY_HIP(eng, hipMalloc((void **)&eng->d_plan_q, rows * 5 * sizeof(double)));
+  return HWY_OK;
+}
+
+extern "C" int hwy_ttc_grid_device(hwy_engine *eng, const hwy_ttc_params *params, float *d_grid) {
+  if (!eng) return HWY_ERR_INVALID_ARG;
+  if (int rc = ttc_check(eng, params, "hwy_ttc_grid_device")) return rc;
+  if (!d_grid) return fail(eng, HWY_ERR_INVALID_ARG, "hwy_ttc_grid_device: grid must be non-NULL");
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  HWY_HIP(eng, ttc_launch(eng, *params, false, d_grid, nullptr, nullptr));
+  return HWY_OK;
+}
+
+extern "C" int hwy_ttc_grid(hwy_engine *eng, const hwy_ttc_params *params, float *grid) {
+  if (!eng) return HWY_ERR_INVALID_ARG;
+  if (int rc = ttc_check(eng, params, "hwy_ttc_grid")) return rc;
+  if (!grid) return fail(eng, HWY_ERR_INVALID_ARG, "hwy_ttc_grid: grid must be non-NULL");
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  const int cells = hwy::ttc_cells(eng->cfg, *params);
+  if (int rc = ttc_buffers(eng, cells)) return rc;
+  HWY_HIP(eng, ttc_launch(eng, *params, false, eng->d_ttc_grid, nullptr, nullptr));
+  HWY_HIP(eng, hipMemcpyAsync(grid, eng->d_ttc_grid, num_agent_rows(eng->cfg) * cells * sizeof(float), hipMemcpyDeviceToHost, eng->stream));
+  HWY_HIP(eng, hipStreamSynchronize(eng->stream));
+  return HWY_OK;
+}
+
+extern "C" int hwy_mdp_plan_device(hwy_engine *eng, const hwy_ttc_params *params, int32_t *d_action, double *d_q, float *d_grid) {
+  if (!eng) return HWY_ERR_INVALID_ARG;
+  if (int rc = ttc_check(eng, params, "hwy_mdp_plan_device")) return rc;
+  if (!d_action) return fail(eng, HWY_ERR_INVALID_ARG, "hwy_mdp_plan_device: action must be non-NULL");
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  HWY_HIP(eng, ttc_launch(eng, *params, true, d_grid, d_action, d_q));
+  return HWY_OK;
+}
+
+extern "C" int hwy_mdp_plan(hwy_engine *eng, const hwy_ttc_params *params, int32_t *action, double *q, float *grid) {
+  if (!eng) return HWY_ERR_INVALID_ARG;
+  if (int rc = ttc_check(eng, params, "hwy_mdp_plan")) return rc;
+  if (!action) return fail(eng, HWY_ERR_INVALID_ARG, "hwy_mdp_plan: action must be non-NULL");
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  const int cells = hwy::ttc_cells(eng->cfg, *params);
+  const size_t rows = num_agent_rows(eng->cfg);
+  if (int rc = ttc_buffers(eng, cells)) return rc;
+  HWY_HIP(eng, ttc_launch(eng, *params, true, grid ? eng->d_ttc_grid : nullptr, eng->d_plan_action, q ? eng->d_plan_q : nullptr));
+  HWY_HIP(eng, hipMemcpyAsync(action, eng->d_plan_action, rows * sizeof(int32_t), hipMemcpyDeviceToHost, eng->stream));
+  if (q) HWY_HIP(eng, hipMemcpyAsync(q, eng->d_plan_q, rows * 5 * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+  if (grid) HWY_HIP(eng, hipMemcpyAsync(grid, eng->d_ttc_grid, rows * cells * sizeof(float), hipMemcpyDeviceToHost, eng->stream));
+  HWY_HIP(eng, hipStreamSynchronize(eng->stream));
   return HWY_OK;
 }
 

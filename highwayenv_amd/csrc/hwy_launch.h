@@ -1,6 +1,6 @@
 // hwy_launch.h -- host-visible launch functions of the kernels in hwy_kernels.hip, hwy_kernels_linear.hip and
 // hwy_kernels_direct.hip: one overload per kernel family, chosen by the type of its parameter struct; and of the
-// LidarObservation kernel in hwy_kernels_lidar.hip.  Each is the shared selection layer (hwy_launch_family.h, hwy_launch_rules.h)
+// LidarObservation kernel in hwy_kernels_lidar.hip and the time-to-collision / planner kernel in hwy_kernels_ttc.hip.  Each is the shared selection layer (hwy_launch_family.h, hwy_launch_rules.h)
 // with the HIP backend below.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -10,6 +10,7 @@
 #include "hwy_net.h"
 #include "hwy_ix.h"
 #include "hwy_lidar.h"
+#include "hwy_ttc.h"
 
 namespace hwy {
 // The HIP backend of the selection layer (hwy_launch_family.h, hwy_launch_rules.h), for the kernel translation units.
@@ -73,5 +74,8 @@ int step_resident_blocks(const NetParams &np, const Launch &l);
 inline int step_resident_blocks(const IxParams &, const Launch &) { return 0; }
 // LidarObservation of the current state (hwy_lidar.h): `rows` = environments x agents wavefronts, row r -> lp.obs + r * cells * 2
 hipError_t launch_lidar(const LidarParams &lp, bool normalize, int rows, hipStream_t stream);
+// Time-to-collision grid of the current state and, with `plan`, the value iteration on it (hwy_ttc.h): `rows` = environments x agents
+// wavefronts, row r -> tp.grid + r * V * L * T, tp.action + r, tp.q + r * 5
+hipError_t launch_ttc(const TtcParams &tp, bool plan, int rows, hipStream_t stream);
 hipError_t launch_math_probe(int op, const double *in, double *out, long long n, hipStream_t stream);
 }  // namespace hwy

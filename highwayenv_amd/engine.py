@@ -171,6 +171,38 @@ class Engine:
         self._check(self._lib.hwy_observe(self._h, _ptr(obs)))
         return obs
 
+    # -- time-to-collision grid and finite-MDP planner (csrc/hwy_ttc.h) ---------------------------
+    def _check_ttc(self, rc: int):
+        if rc == _abi.HWY_ERR_UNSUPPORTED:  # outside the planner's scope: the project's NotImplementedError
+            raise NotImplementedError(self._lib.hwy_last_error(self._h).decode())
+        self._check(rc)
+
+    def ttc_shape(self, params: _abi.HwyTtcParams) -> tuple:
+        return (self.cfg.num_target_speeds, self.cfg.lanes_count, params.time_steps)
+
+    def ttc_grid(self, params: _abi.HwyTtcParams) -> np.ndarray:
+        """hwy_ttc_grid: compute_ttc_grid for every controlled vehicle, f32 [E, A, V, L, T] (values 0, 0.5, 1)."""
+        grid = np.empty((self.E, self.A, *self.ttc_shape(params)), np.float32)
+        self._check_ttc(self._lib.hwy_ttc_grid(self._h, C.byref(params), _ptr(grid)))
+        return grid
+
+    def mdp_plan(self, params: _abi.HwyTtcParams, return_q: bool = False, return_grid: bool = False):
+        """hwy_mdp_plan: (actions int32 [E, A], Q f64 [E, A, 5] or None, grid f32 [E, A, V, L, T] or None)."""
+        action = np.empty((self.E, self.A), np.int32)
+        q = np.empty((self.E, self.A, 5), np.float64) if return_q else None
+        grid = np.empty((self.E, self.A, *self.ttc_shape(params)), np.float32) if return_grid else None
+        self._check_ttc(self._lib.hwy_mdp_plan(self._h, C.byref(params), _ptr(action), _ptr(q), _ptr(grid)))
+        return action, q, grid
+
+    def ttc_grid_device(self, params: _abi.HwyTtcParams, d_grid: int):
+        """Enqueue hwy_ttc_grid_device on a raw device pointer; does not synchronise."""
+        self._check_ttc(self._lib.hwy_ttc_grid_device(self._h, C.byref(params), C.c_void_p(d_grid)))
+
+    def mdp_plan_device(self, params: _abi.HwyTtcParams, d_action: int, d_q: int = 0, d_grid: int = 0):
+        """Enqueue hwy_mdp_plan_device on raw device pointers; does not synchronise."""
+        vp = C.c_void_p
+        self._check_ttc(self._lib.hwy_mdp_plan_device(self._h, C.byref(params), vp(d_action), vp(d_q or None), vp(d_grid or None)))
+
     # -- reset --------------------------------------------------------------------------------
     def reset(self, seeds=None, mask=None, ego_spacing=2.0, vehicles_density=1.0, initial_lane_id=-1, base_seed=0):
         """Device-side spawn (counter-based RNG; NOT numpy's stream -- see spawn.py for that)."""

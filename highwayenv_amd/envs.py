@@ -18,6 +18,7 @@ import copy
 import numpy as np
 
 from . import _abi, spawn
+from . import finite_mdp as _finite_mdp
 from . import merge as _merge
 from . import intersection as _ix
 from .engine import Engine
@@ -336,6 +337,41 @@ class BatchedHighwayEnv:
                 "high_speed_reward": float(np.clip(scaled, 0, 1)),
                 "on_road_reward": float(on_road)}
 
+    # ---- to_finite_mdp (abstract.py:452-453 -> envs/common/finite_mdp.py) -----------------------------------------
+    def _ttc_params(self, horizon, time_quantization=None, gamma=1.0):
+        _abi.check_finite_mdp_scope(self._hcfg)  # NotImplementedError outside the highway scenario / the five meta-actions
+        params = _abi.ttc_params(self.config, horizon, time_quantization, gamma)
+        if self._engine is None:
+            raise NotImplementedError("The road and vehicle must be initialized in the environment implementation")
+        return params
+
+    def ttc_grid(self, horizon: float = 10.0, time_quantization: float | None = None) -> np.ndarray:
+        """``compute_ttc_grid`` (finite_mdp.py:104-163) of every controlled vehicle of every environment, computed on the device:
+        f64 [E, A, V, L, T] (speeds x lanes x time steps; 0, 0.5 or 1).  ``time_quantization`` defaults to
+        ``1 / policy_frequency`` like ``to_finite_mdp``."""
+        params = self._ttc_params(horizon, time_quantization)
+        return self._engine.ttc_grid(params).astype(np.float64)
+
+    def to_finite_mdp(self, env_index: int = 0, horizon: float = 10.0) -> "_finite_mdp.FiniteMDP":
+        """``AbstractEnv.to_finite_mdp`` of environment ``env_index`` for its first controlled vehicle (``env.vehicle``): the grid
+        comes from the device, the tables are built on the host (``highwayenv_amd.finite_mdp``).  The result carries the
+        attributes the reference gives ``finite_mdp.mdp.DeterministicMDP``: ``transition``, ``reward``, ``terminal``, ``state``,
+        ``original_shape``.  (The device computes the grid of every environment in one launch; one row of it is converted.)"""
+        params = self._ttc_params(horizon, None)
+        grid = self._engine.ttc_grid(params)[env_index, 0].astype(np.float64)
+        st = self._engine.get_state()
+        i = int(self._ego_slots(st)[env_index])
+        return _finite_mdp.build(grid, int(st["speed_index"][env_index, i]), int(st["lane"][env_index, i]), self.config)
+
+    def plan_finite_mdp(self, gamma: float = 1.0, horizon: float = 10.0, return_q: bool = False):
+        """The reference's value-iteration policy on ``to_finite_mdp()`` for every controlled vehicle, solved on the device:
+        meta-action ids int32 [E] ([E, A] for several agents); with ``return_q`` also Q(state, .) f64 [E(, A), 5]."""
+        params = self._ttc_params(horizon, None, gamma)
+        action, q, _ = self._engine.mdp_plan(params, return_q=return_q)
+        if self._hcfg.num_agents == 1:
+            action, q = action[:, 0], (q[:, 0] if q is not None else None)
+        return (action, q) if return_q else action
+
     def close(self) -> None:
         if self._engine is not None:
             self._engine.close()
@@ -553,6 +589,10 @@ class _SingleEnvMixin:
         return (obs[0], float(reward[0]), bool(term[0]), bool(trunc[0]),
                 {"speed": float(info["speed"][0]), "crashed": bool(info["crashed"][0]), "action": action,
                  "rewards": self.rewards(0)})
+
+    def to_finite_mdp(self):
+        """``AbstractEnv.to_finite_mdp()`` (abstract.py:452-453): horizon 10 s, time step ``1 / policy_frequency``."""
+        return super().to_finite_mdp(0)
 
     @property
     def vehicle(self) -> VehicleView:

@@ -229,6 +229,29 @@ class HighwayVectorEnv(_Base):
             x.record_stream(self._stream)
         return (obs[:, :, 0] if A == 1 else obs), rew[:, :, 0], term.bool(), trunc.bool()
 
+    def plan(self, gamma: float = 1.0, horizon: float = 10.0):
+        """The reference's value-iteration policy on ``to_finite_mdp()`` (envs/common/finite_mdp.py) for every environment, solved
+        by the planner kernel: meta-action ids [E] ([E, A] for several agents).  ``output="torch"``: an int32 device tensor that
+        aliases the buffer the kernel writes (valid until the next ``plan()``), ordered on the current stream like ``step`` --
+        ``env.step(env.plan())`` never leaves the GPU."""
+        if self.output != "torch":
+            return self.env.plan_finite_mdp(gamma=gamma, horizon=horizon)
+        params = self.env._ttc_params(horizon, None, gamma)
+        t, A = self._torch, self.env._hcfg.num_agents
+        if self._dev is None:
+            raise RuntimeError("plan() before reset()")
+        if "plan" not in self._dev:
+            self._dev["plan"] = t.empty((self.num_envs, A), dtype=t.int32, device=self._dev["obs"].device)
+        out = self._dev["plan"]
+        cur = t.cuda.current_stream()
+        same = cur.cuda_stream == self._stream.cuda_stream
+        if not same:
+            self._stream.wait_stream(cur)      # the consumer of the previous plan comes first
+        self.env._engine.mdp_plan_device(params, out.data_ptr())
+        if not same:
+            cur.wait_stream(self._stream)
+        return out[:, 0] if A == 1 else out
+
     # ---- the rest of the interface ----------------------------------------------------------------------------------------------
     @property
     def stream(self):

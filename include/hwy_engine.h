@@ -48,6 +48,7 @@ extern "C" {
 #define HWY_MAX_GLANES 24  /* lanes of a general (any direction / circular) road network: HWY_SCENARIO_INTERSECTION */
 #define HWY_MAX_ACTIONS_PER_AXIS 16 /* DiscreteAction(actions_per_axis): points per axis of the throttle x steering table */
 #define HWY_MAX_LIDAR_CELLS 64 /* LidarObservation(cells): one lane of a wavefront per cell */
+#define HWY_MAX_TTC_STEPS 64 /* time cells of the time-to-collision grid (hwy_ttc_params.time_steps) */
 #define HWY_MAX_ROUTE 11   /* remaining roads of a planned route kept per vehicle (64-bit route word, 5 bits per road) */
 
 typedef enum hwy_status {
@@ -493,6 +494,49 @@ int hwy_observe(hwy_engine *eng, float *obs);
  */
 int hwy_set_autoreset(hwy_engine *eng, int32_t enabled, uint64_t base_seed, double ego_spacing,
                       double vehicles_density, int32_t initial_lane_id);
+
+/*
+ * Time-to-collision grid and finite-MDP planner (additive to ABI v8: hwy_config keeps its layout).  Replaces
+ * AbstractEnv.to_finite_mdp (envs/common/abstract.py:452-453) -> finite_mdp / compute_ttc_grid / transition_model / clip_position
+ * (envs/common/finite_mdp.py:17-203) for every (environment, agent) at once, in a kernel of its own (csrc/hwy_ttc.h) that reads the
+ * state planes on the engine's stream after whatever was launched last.
+ * HWY_SCENARIO_HIGHWAY with a HWY_EGO_META ego on the five-action table (HWY_ACTIONS_ALL) only; every traffic model, observation
+ * type and N.  HWY_ERR_UNSUPPORTED for the other scenarios, for a HWY_EGO_DIRECT ego (a plain Vehicle has no target_speeds: the
+ * reference fails there too) and for HWY_ACTIONS_LONGI / _LAT (the reference builds a 5-column reward table next to a 3-column
+ * transition table there).
+ *   horizon, time_quantization   finite_mdp(env, time_quantization, horizon); to_finite_mdp passes 1 / policy_frequency
+ *   time_steps                   int(horizon / time_quantization) as the HOST evaluates the reference's expression
+ *                                (finite_mdp.py:122-124), 1..HWY_MAX_TTC_STEPS; HWY_ERR_INVALID_ARG otherwise, or when it is not
+ *                                what the two doubles give
+ *   gamma                        discount of the value iteration (the reference's agents configure it; finite)
+ *   lane_change_reward           config["lane_change_reward"] (finite_mdp.py:72-78; HighwayEnv.default_config: 0)
+ * The grid has V = num_target_speeds speeds x L = lanes_count lanes x T = time_steps cells, values exactly 0, 0.5 or 1.
+ */
+typedef struct hwy_ttc_params {
+  double horizon, time_quantization, gamma, lane_change_reward;
+  int32_t time_steps;
+  int32_t reserved;
+} hwy_ttc_params;
+/*
+ * compute_ttc_grid (finite_mdp.py:104-163) with `vehicle` = every controlled vehicle in turn: d_grid f32 [E][A][V][L][T], DEVICE
+ * pointer; enqueues on the engine's stream and does not synchronise (like hwy_step_device).
+ */
+int hwy_ttc_grid_device(hwy_engine *eng, const hwy_ttc_params *params, float *d_grid);
+/* The same into a HOST pointer; synchronises. */
+int hwy_ttc_grid(hwy_engine *eng, const hwy_ttc_params *params, float *grid);
+/*
+ * finite_mdp (finite_mdp.py:17-101) solved exactly: the deterministic MDP over the grid's (speed, lane, time) states with
+ * transition_model / clip_position (:166-203), the reward table of :58-83 and the terminal states of :85-90, by one backward sweep
+ * over the time axis -- the fixed point of V <- max_a(reward + gamma * where(terminal, 0, V[transition])), bit for bit what numpy
+ * computes from the reference's tables.  From state = (speed_index, lane_index[2], 0) of each controlled vehicle (:47-49):
+ *   d_action int32 [E][A]     argmax_a Q(state, a), the first maximum (meta-action ids of HWY_ACTIONS_ALL: feed hwy_step_device)
+ *   d_q      f64   [E][A][5]  Q(state, .)                      (may be NULL)
+ *   d_grid   f32   [E][A][V][L][T]  the grid it planned on      (may be NULL)
+ * DEVICE pointers; enqueues on the engine's stream and does not synchronise.
+ */
+int hwy_mdp_plan_device(hwy_engine *eng, const hwy_ttc_params *params, int32_t *d_action, double *d_q, float *d_grid);
+/* The same into HOST pointers (q and grid may be NULL); synchronises. */
+int hwy_mdp_plan(hwy_engine *eng, const hwy_ttc_params *params, int32_t *action, double *q, float *grid);
 
 int hwy_sync(hwy_engine *eng); /* hipStreamSynchronize on the engine stream */
 
