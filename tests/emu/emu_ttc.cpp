@@ -2,6 +2,8 @@
 // (highwayenv_amd/csrc/hwy_ttc.h: hwy_ttc_kernel) on the CPU through hip_emu.h, on the host SoA arrays of a state, with the
 // validation (ttc_validate) and the choice of the LDS class that hwy_engine.hip / hwy_kernels_ttc.hip make.  The simulation itself
 // is the family's own driver's: tests/emu/emu_ttc.py runs it and then this, the way the engine launches the kernel on its stream.
+// The library also exports hip_emu.h's emu_set_schedule / emu_schedule_errors (defined in that header, once per emulator library):
+// tests/test_schedule_independence.py runs the kernel's LDS atomics, its barriers and its double-buffered value slices under them.
 #include "hip_emu.h"
 
 #include <string>

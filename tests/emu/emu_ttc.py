@@ -5,7 +5,9 @@
 family's own emulated engine (``EmuEngine`` for IDM traffic, ``EmuTrafficEngine`` for the Linear family, ``EmuLidarEngine`` under a
 Lidar observation; ``EmuControlEngine`` for a direct-control ego, which the planner refuses), and ``ttc_grid`` / ``mdp_plan`` run
 the kernel of ``hwy_ttc.h`` on the state the last call left behind, with the validation of ``ttc_validate`` in front of it like
-``hwy_engine.hip``.
+``hwy_engine.hip``.  ``HWY_EMU_TTC_LIB`` names a prebuilt (mutated) library instead (tests/test_ttc_mutations.py).
+``set_schedule`` puts the planner's launches (and the simulation's) under another fiber order of hip_emu.h
+(tests/test_schedule_independence.py).
 """
 from __future__ import annotations
 
@@ -25,6 +27,8 @@ _lib = None
 
 
 def build(force: bool = False) -> str:
+    if os.environ.get("HWY_EMU_TTC_LIB"):
+        return os.environ["HWY_EMU_TTC_LIB"]
     out = os.path.join(_HERE, "_build", "libhwy_emu_ttc.so")
     csrc = os.path.join(_ROOT, "highwayenv_amd", "csrc")
     srcs = [os.path.join(_HERE, f) for f in ("emu_ttc.cpp", "hip_emu.h")] + [
@@ -69,24 +73,29 @@ def status(cfg: _abi.HwyConfig, params) -> int:
     return lib().emu_ttc_validate(C.byref(cfg), None if params is None else C.byref(params))
 
 
-def ttc_grid(cfg: _abi.HwyConfig, st: dict, params: _abi.HwyTtcParams) -> np.ndarray:
-    """The kernel on a host state: grid f32 [E, A, V, L, T]."""
+def _run(sched, call):
+    return call() if sched is None else sched._scheduled(lib(), call)
+
+
+def ttc_grid(cfg: _abi.HwyConfig, st: dict, params: _abi.HwyTtcParams, sched=None) -> np.ndarray:
+    """The kernel on a host state: grid f32 [E, A, V, L, T].  `sched`: an emu.Scheduled whose schedule the launch runs under."""
     st = _host_state(st)
     s = _abi.state_struct(st)
     _check(status(cfg, params))  # (first: the shape of the outputs needs valid params)
     grid = np.full((cfg.num_envs, cfg.num_agents, *ttc_shape(cfg, params)), np.nan, np.float32)
-    _check(lib().emu_ttc_grid(C.byref(cfg), C.byref(s), C.byref(params), _p(grid, C.c_float)))
+    _check(_run(sched, lambda: lib().emu_ttc_grid(C.byref(cfg), C.byref(s), C.byref(params), _p(grid, C.c_float))))
     return grid
 
 
-def mdp_plan(cfg: _abi.HwyConfig, st: dict, params: _abi.HwyTtcParams, return_q=False, return_grid=False):
+def mdp_plan(cfg: _abi.HwyConfig, st: dict, params: _abi.HwyTtcParams, return_q=False, return_grid=False, sched=None):
     st = _host_state(st)
     s = _abi.state_struct(st)
     _check(status(cfg, params))
     action = np.full((cfg.num_envs, cfg.num_agents), -1, np.int32)
     q = np.full((cfg.num_envs, cfg.num_agents, 5), np.nan, np.float64) if return_q else None
     grid = np.full((cfg.num_envs, cfg.num_agents, *ttc_shape(cfg, params)), np.nan, np.float32) if return_grid else None
-    _check(lib().emu_mdp_plan(C.byref(cfg), C.byref(s), C.byref(params), _p(action, C.c_int32), _p(q, C.c_double), _p(grid, C.c_float)))
+    _check(_run(sched, lambda: lib().emu_mdp_plan(C.byref(cfg), C.byref(s), C.byref(params), _p(action, C.c_int32), _p(q, C.c_double),
+                                                  _p(grid, C.c_float))))
     return action, q, grid
 
 
@@ -106,6 +115,7 @@ class EmuTtcEngine:
             self.sim = EmuControlEngine(cfg)
         else:
             self.sim = emu.EmuEngine(cfg)
+        self.sched = emu.Scheduled()   # of the planner's own launches
 
     def __getattr__(self, name):  # stepping, state, behaviour parameters, auto-reset: the simulation's own
         return getattr(self.sim, name)
@@ -113,8 +123,18 @@ class EmuTtcEngine:
     def ttc_shape(self, params):
         return ttc_shape(self.cfg, params)
 
+    def set_schedule(self, **schedule):
+        self.sim.set_schedule(**schedule)
+        self.sched.set_schedule(**schedule)
+
+    def schedule_errors(self) -> int:
+        return self.sim.schedule_errors() + self.sched.schedule_errors()
+
+    def schedule_error_text(self) -> str:
+        return self.sim.schedule_error_text() or self.sched.schedule_error_text()
+
     def ttc_grid(self, params):
-        return ttc_grid(self.cfg, self.sim.get_state(), params)
+        return ttc_grid(self.cfg, self.sim.get_state(), params, self.sched)
 
     def mdp_plan(self, params, return_q=False, return_grid=False):
-        return mdp_plan(self.cfg, self.sim.get_state(), params, return_q, return_grid)
+        return mdp_plan(self.cfg, self.sim.get_state(), params, return_q, return_grid, self.sched)

@@ -73,6 +73,15 @@ MA = {"observation": {"type": "MultiAgentObservation", "observation_config": {"t
       "action": {"type": "MultiAgentAction", "action_config": {"type": "DiscreteMetaAction"}}}
 DENSE = {"vehicles_count": 30, "vehicles_density": 2.0, "lanes_count": 3, "ego_spacing": 1.0, "duration": 20}
 
+BOUNDARY = {"vehicles_count": 30, "vehicles_density": 2.0, "ego_spacing": 1.0, "duration": 20, "lane_change_reward": -0.05,
+            "right_lane_reward": 0.3}
+
+
+def speeds(n: int) -> dict:
+    """`n` target speeds from 16 m/s in steps of 3."""
+    return {"type": "DiscreteMetaAction", "target_speeds": [16.0 + 3.0 * k for k in range(n)]}
+
+
 SCENARIOS = [
     # highway-fast-v0 as it comes: 20 vehicles, 3 lanes, grid (3, 3, 10)
     dict(name="ttc_fast", cls=HighwayEnvFast, config={}, seeds=[0, 1, 2, 3], steps=6, action_seed=401),
@@ -107,6 +116,24 @@ SCENARIOS = [
     dict(name="ttc_rewards", cls=HighwayEnvFast,
          config={"lane_change_reward": -0.05, "right_lane_reward": 0.3, "collision_reward": -2.5, "high_speed_reward": 0.7},
          seeds=[27, 28], steps=4, action_seed=414),
+    # ---- the kernel's own boundaries (csrc/hwy_ttc.h) ----
+    # 1024 cells: the small LDS class exactly full (4 x 4 x 64, horizon 64 s at 1 Hz), last cell index 1023
+    dict(name="ttc_cells1024", cls=HighwayEnvFast, config=dict(BOUNDARY, lanes_count=4, action=speeds(4)), seeds=[2, 3], steps=2,
+         action_seed=415, horizon=64.0),
+    # 1025 cells: the first grid of the large class (5 x 5 x 41, horizon 41 s at 1 Hz)
+    dict(name="ttc_cells1025", cls=HighwayEnvFast, config=dict(BOUNDARY, lanes_count=5, action=speeds(5)), seeds=[32, 33], steps=2,
+         action_seed=416, horizon=41.0),
+    # 64 states (4 x 16): one full pass of the value sweep and no second
+    dict(name="ttc_states64", cls=HighwayEnvFast, config=dict(BOUNDARY, lanes_count=16, action=speeds(4)), seeds=[34, 35], steps=2,
+         action_seed=417),
+    # 65 states (5 x 13): a second pass with a tail of one thread, in the small class; and the hand-placed roads of STATE_ROADS
+    dict(name="ttc_states65", cls=HighwayEnvFast, config=dict(BOUNDARY, lanes_count=13, action=speeds(5)), seeds=[36, 37], steps=2,
+         action_seed=418, roads="ttc_states65"),
+    # 8 x 16 x 64 = 8192 cells, 128 states (horizon 6.4 s at 10 Hz): every limit at once; grids and states only (the tables of
+    # 8192 states do not fit the size of a committed fixture); and the hand-placed roads of STATE_ROADS
+    dict(name="ttc_max", cls=HighwayEnvFast,
+         config=dict(BOUNDARY, lanes_count=16, action=speeds(8), simulation_frequency=10, policy_frequency=10), seeds=[38, 39],
+         steps=2, action_seed=419, horizon=6.4, roads="ttc_max", tables=False),
 ]
 
 # ---- ttc_crafted: hand-placed roads ----------------------------------------------------------------------------------------------
@@ -134,6 +161,9 @@ CRAFTED = [
     [(150.0, 1, 0.0, 18.0), (60.0, 3, 0.1, 32.0)],
     # 9  nothing within the horizon
     [],
+    # 10 other.speed exactly a target speed (25), 37 mm ahead in the next lane: WITHOUT the `ego_speed == other.speed` skip
+    #    utils.not_zero(0) = 0.01 puts the centre point at 3.7 s (on road 0 that time is 3000 s: beyond any horizon either way)
+    [(100.037, 2, 0.0, 25.0)],
 ]
 CRAFTED_OBSERVER_HEADING = {8: 0.2}
 CRAFTED_SLOTS = 6
@@ -147,6 +177,40 @@ EXACT_ROADS = (0, 4, 5, 7)  # headings exactly 0 and candidates ON a cell bounda
 PASS_SLOTS = {63: (131.7, 0, 0.0, 21.3), 64: (153.3, 1, 0.0, 17.9), 65: (78.1, 2, 0.0, 31.4),
               127: (168.9, 2, 0.0, 22.6), 128: (118.3, 0, 0.0, 16.2), 129: (139.4, 3, 0.0, 13.6)}
 PASSES = {"ttc_passes65": 65, "ttc_passes130": 130}
+
+
+# ---- ttc_states65 / ttc_max: the observer in the second pass of the value sweep ----------------------------------------------------
+# The sweep gives thread `lane` the states s = h * L + i = lane and lane + 64.  On a spawned road the observer starts in the first
+# pass; these roads -- further environments of the two runs, after the spawned ones -- put it on s = 63 (the last state of the
+# first pass, whose RIGHT / FASTER neighbours lie in the second), 64 (the first of the second) and the last state.  Each road is
+# (observer (x, lane, heading, speed, speed index), {slot: (x, lane, heading, speed)}): one vehicle ahead in the observer's lane,
+# (`gap` m away: no crash within the recorded steps), which makes the five Q values differ, one in a neighbouring lane whose state lies in the second pass, one behind.
+def _state_road(L: int, s: int, speeds_: list, gap: float, dx: float):
+    h, i = divmod(s, L)
+    side = i - 1 if i == L - 1 else i + 1          # a lane next to the observer's whose state h * L + side ...
+    if h * L + side < 64:                          # ... lies in the second pass (s = 63: the one reached by FASTER instead)
+        side = i
+    ego = speeds_[h]
+    return ((100.0, i, 0.0, ego, h),
+            {1: (100.0 + gap + dx, i, 0.0, ego - 4.713), 2: (100.0 + 17.9 + dx, side, 0.0, ego - 2.917 + 3.0 * (side == i)),
+             3: (100.0 - 9.1 - dx, max(i - 1, 0), 0.0, ego + 3.331)})
+
+
+STATE_ROADS = {
+    "ttc_states65": [_state_road(13, s, [16.0 + 3.0 * k for k in range(5)], 31.3, 0.37 * n) for n, s in enumerate((63, 64))],
+    "ttc_max": [_state_road(16, s, [16.0 + 3.0 * k for k in range(8)], 21.3, 0.37 * n) for n, s in enumerate((63, 64, 127))],
+}
+
+
+def place(env, placed) -> None:
+    """Write (x, lane, heading, speed) onto the vehicles of a reference environment, in list order."""
+    for v, (x, lane, h, s) in zip(env.road.vehicles, placed):
+        v.position = np.array([x, 4.0 * lane])
+        v.heading, v.speed = h, s
+        v.lane_index = ("0", "1", lane)
+        v.lane = env.road.network.get_lane(v.lane_index)
+        if hasattr(v, "target_lane_index"):
+            v.target_lane_index = v.lane_index
 
 
 def crafted_roads(name: str):
@@ -182,13 +246,13 @@ def config_record(out: dict, cfg: dict, cls, A: int, horizon: float) -> None:
     out["cfg_horizon"] = np.float64(horizon)
 
 
-def planning_record(env, A: int, horizon: float) -> dict:
+def planning_record(env, A: int, horizon: float, tables: bool = True) -> dict:
     """The reference's grid of every controlled vehicle and, single agent, the tables of to_finite_mdp() (horizon 10) or of
     finite_mdp(env, 1 / policy_frequency, horizon) -- the same call with another horizon."""
     from highway_env.envs.common.finite_mdp import finite_mdp
     tq = 1 / env.config["policy_frequency"]
     rec = {"grid": np.stack([compute_ttc_grid(env, tq, horizon, vehicle=v) for v in env.controlled_vehicles])}
-    if A == 1:
+    if A == 1 and tables:
         mdp = env.to_finite_mdp() if horizon == HORIZON else finite_mdp(env, time_quantization=tq, horizon=horizon)
         assert mdp.original_shape == rec["grid"].shape[1:]
         rec.update(transition=np.asarray(mdp.transition, np.int32), reward=np.asarray(mdp.reward, np.float64),
@@ -225,6 +289,9 @@ def run(sc: dict, only_envs=None) -> dict:
     seeds, steps = sc["seeds"], sc["steps"]
     horizon = float(sc.get("horizon", HORIZON))
     A = int(sc["config"].get("controlled_vehicles", 1))
+    roads = STATE_ROADS[sc["roads"]] if "roads" in sc else []   # hand-placed environments after the spawned ones (seed 0)
+    tables = sc.get("tables", True)
+    seeds = list(seeds) + [0] * len(roads)
     actions = np.random.default_rng(sc["action_seed"]).integers(0, 5, size=(steps, len(seeds), A)).astype(np.int32)
     out = {"seeds": np.asarray(seeds, np.int64), "actions": actions}
     recs = []
@@ -233,12 +300,18 @@ def run(sc: dict, only_envs=None) -> dict:
             continue
         env = sc["cls"](dict(sc["config"]))
         env.reset(seed=int(seed))
-        rec = {"init": mgc.dump_state(env), "behavior": behavior_of(env), "plan0": planning_record(env, A, horizon), "plan": [],
-               "step_state": []}
+        if e >= len(seeds) - len(roads):
+            (x, lane, h, s, index), others = roads[e - (len(seeds) - len(roads))]
+            n, last = len(env.road.vehicles), sc["config"]["lanes_count"] - 1
+            assert env.road.vehicles[0] is env.vehicle and 0 not in others and max(others) < n
+            place(env, [(x, lane, h, s) if k == 0 else others.get(k, (6000.0 + 150.0 * k, last, 0.0, 20.0)) for k in range(n)])
+            env.vehicle.speed_index, env.vehicle.target_speed = index, env.vehicle.index_to_speed(index)
+        rec = {"init": mgc.dump_state(env), "behavior": behavior_of(env), "plan0": planning_record(env, A, horizon, tables),
+               "plan": [], "step_state": []}
         for t in range(steps):
             env.step(tuple(int(v) for v in actions[t, e]) if A > 1 else int(actions[t, e, 0]))
             rec["step_state"].append(mgc.dump_state(env))
-            rec["plan"].append(planning_record(env, A, horizon))
+            rec["plan"].append(planning_record(env, A, horizon, tables))
         rec["T"] = int(env.config["simulation_frequency"] // env.config["policy_frequency"])
         rec["cfg"] = dict(env.config)
         recs.append(rec)
@@ -269,13 +342,7 @@ def run_crafted(name: str = "ttc_crafted", only_envs=None) -> dict:
         placed = {0: OBSERVER[:2] + (headings.get(e, 0.0), OBSERVER[3]), **road}
         far = iter((6000.0 + 150.0 * k, 3, 0.0, 20.0) for k in range(slots))  # the slots a road does not use
         placed = [placed[k] if k in placed else next(far) for k in range(slots)]
-        for v, (x, lane, h, s) in zip(env.road.vehicles, placed):
-            v.position = np.array([x, 4.0 * lane])
-            v.heading, v.speed = h, s
-            v.lane_index = ("0", "1", lane)
-            v.lane = env.road.network.get_lane(v.lane_index)
-            if hasattr(v, "target_lane_index"):
-                v.target_lane_index = v.lane_index
+        place(env, placed)
         env.vehicle.speed_index, env.vehicle.target_speed = 1, 25.0
         recs.append({"init": mgc.dump_state(env), "plan0": planning_record(env, 1, HORIZON), "cfg": dict(env.config)})
     out = {"seeds": np.zeros(len(roads), np.int64), "actions": np.zeros((0, len(roads), 1), np.int32)}

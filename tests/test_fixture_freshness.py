@@ -4,8 +4,12 @@ Every generator records, next to each fixture it writes, a digest of the fixture
 (tests/golden/MANIFEST.json, tests/golden_util.record_fixture).  Everywhere, every committed fixture is held to its entry: a
 fixture edited by hand, or a generator edited without regenerating what it makes, fails here.  Where the reference package is
 installed (oracle/ref_stub.py), env 0 of every fixture is also regenerated and compared with the committed file, array by array,
-bit for bit (the recorded traces of tests/golden/live and the shortest paths: whole)."""
+bit for bit (the recorded traces of tests/golden/live and the shortest paths: whole).
+
+The planner's fixtures (tests/golden/ttc, with a manifest of their own next to them) are held the same way: every committed file
+to its digest, and env 0 regenerated where the reference is installed."""
 import importlib.util
+import json
 import os
 
 import numpy as np
@@ -86,3 +90,47 @@ def test_env0_of_the_committed_fixture_is_what_the_generator_makes(name):
         _regenerated_env0_matches(fname, name, z)
     else:
         _regenerated_whole_matches(entry, name, z)
+
+
+# ---- tests/golden/ttc: the time-to-collision grid / finite-MDP fixtures (make_golden_ttc.py, its own MANIFEST.json) ------------
+TTC = os.path.join(GOLDEN, "ttc")
+with open(os.path.join(TTC, "MANIFEST.json")) as _f:
+    TTC_MANIFEST = json.load(_f)
+
+
+def _ttc_digest(z):  # (make_golden_control.digest restated: the generator imports the reference)
+    import hashlib
+    h = hashlib.sha256()
+    for k in sorted(z.files):
+        a = z[k]
+        h.update(k.encode())
+        h.update(str(a.dtype).encode() + str(a.shape).encode())
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
+def test_every_ttc_fixture_has_a_manifest_entry():
+    from tests.ttc_util import FIXTURES
+    assert sorted(TTC_MANIFEST) == sorted(FIXTURES) == sorted(f[:-4] for f in os.listdir(TTC) if f.endswith(".npz"))
+
+
+@pytest.mark.parametrize("name", sorted(TTC_MANIFEST))
+def test_env0_of_the_committed_ttc_fixture_is_what_the_generator_makes(name):
+    with np.load(os.path.join(TTC, name + ".npz")) as z:
+        assert _ttc_digest(z) == TTC_MANIFEST[name], \
+            f"ttc/{name}.npz is not what its generator wrote: regenerate it with `python tests/golden/ttc/make_golden_ttc.py {name}`"
+        if not ref_stub.reference_available():
+            return
+        gen = _generator(os.path.join("ttc", "make_golden_ttc.py"))
+        assert set(gen.NAMES) == set(TTC_MANIFEST), f"scenarios without a committed fixture: {sorted(set(gen.NAMES) ^ set(TTC_MANIFEST))}"
+        fresh = gen.generate(name, only_envs={0})
+        assert set(fresh) == set(z.files), sorted(set(fresh) ^ set(z.files))
+        for k, a in fresh.items():
+            a, b = np.asarray(a), z[k]
+            if k == "meta":
+                a, b = a[1:], b[1:]   # (meta[0] = number of envs)
+            elif a.shape != b.shape:  # the env axis: the committed array holds all envs, the fresh one env 0
+                diff = [ax for ax in range(a.ndim) if a.shape[ax] != b.shape[ax]]
+                assert a.ndim == b.ndim and len(diff) == 1 and a.shape[diff[0]] == 1, (k, a.shape, b.shape)
+                b = np.take(b, [0], axis=diff[0])
+            _assert_bits_equal(a, b, k)

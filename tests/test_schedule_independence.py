@@ -248,6 +248,41 @@ def test_one_wavefront_kernels_are_schedule_independent(kind, schedule):
     _assert_identical(ref, rec, _sid(schedule))
 
 
+# ---- the time-to-collision grid / finite-MDP planner kernel (hwy_ttc.h: one wavefront per (environment, agent)) ----------------
+def _ttc_run(name, schedule):
+    """The first state of a fixture of tests/golden/ttc: ``ttc_max`` -- 8192 cells in LDS, two states per thread in the value sweep;
+    ``ttc_passes130`` -- three passes of 64 vehicles marking the same LDS grid."""
+    from tests.emu.emu_ttc import EmuTtcEngine
+    from tests.ttc_util import TtcGolden
+    g = TtcGolden(name)
+    eng = EmuTtcEngine(g.hwy_config())
+    if schedule is not None:
+        eng.set_schedule(**schedule)
+    g.load(eng)
+    params = g.params(0.8)
+    action, q, planned_on = eng.mdp_plan(params, return_q=True, return_grid=True)
+    return [("grid", eng.ttc_grid(params)), ("planner's grid", planned_on), ("Q", q.view(np.uint64)), ("action", action)], eng, g
+
+
+@functools.lru_cache(maxsize=None)
+def _ttc_default(name):
+    rec, eng, g = _ttc_run(name, None)
+    _assert_errors_free(eng, "default schedule")
+    np.testing.assert_array_equal(rec[0][1].astype(np.float64), g.get("grid"))   # (and it is the reference's grid)
+    return rec
+
+
+@pytest.mark.parametrize("schedule", ONE_WAVE_SCHEDULES, ids=_sid)
+@pytest.mark.parametrize("name", ["ttc_max", "ttc_passes130"])
+def test_ttc_planner_kernel_is_schedule_independent(name, schedule):
+    """The LDS atomic maxima of phase 1, the two barriers around it and the double-buffered value slices of the sweep: grid, Q and
+    action under every lane and block order are the default schedule's, bit for bit."""
+    ref = _ttc_default(name)
+    rec, eng, _ = _ttc_run(name, schedule)
+    _assert_errors_free(eng, _sid(schedule))
+    _assert_identical(ref, rec, _sid(schedule))
+
+
 # ---- the abort chain across wavefronts ----------------------------------------------------------------------------------------
 def _chain_state(cfg, placements, E):
     st = spawn.spawn_reference_stream(cfg, np.arange(E) + 9, 2.0, 1.0)

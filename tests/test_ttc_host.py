@@ -1,7 +1,7 @@
 """The time-to-collision grid / finite-MDP planner on the host side (no GPU): what it is accepted on and the errors elsewhere, the
 additive ABI, the Python surface (``ttc_grid`` / ``to_finite_mdp`` / ``plan_finite_mdp`` / the drop-in's ``to_finite_mdp()``) on the
 emulated kernels, the fixtures of tests/golden/ttc against their manifest and, where the reference is installed, the emulated
-kernel against the live reference on 24 random configurations."""
+kernel against the live reference on 32 random configurations."""
 import ctypes as C
 import importlib.util
 import json
@@ -13,7 +13,7 @@ import pytest
 
 from highwayenv_amd import _abi, _lib, envs, finite_mdp
 from oracle import ref_stub
-from tests.ttc_util import FIXTURES, RUNS, TTC_DIR, TtcGolden, fixed_point, highway_config, restate_grid
+from tests.ttc_util import BOUNDARIES, FIXTURES, RUNS, STATE_ROADS, TTC_DIR, TtcGolden, fixed_point, highway_config, restate_grid
 
 LINEAR = "highway_env.vehicle.behavior.LinearVehicle"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -267,6 +267,35 @@ def test_fixtures_cover_what_they_are_for():
             assert grid.dtype == np.float64 and np.isin(grid, (0.0, 0.5, 1.0)).all()
     assert any((g.get("grid", i) == 1.0).any() and (g.get("grid", i) == 0.5).any() for g in z.values() for i in g.indices())
     assert set(RUNS) < set(FIXTURES)
+    # the kernel's own boundaries: the capacity classes either side of 1024 cells, the value sweep either side of 64 states
+    assert shape["ttc_cells1024"] == (4, 4, 64) and shape["ttc_cells1025"] == (5, 5, 41)
+    assert shape["ttc_states64"] == (4, 16, 10) and shape["ttc_states65"] == (5, 13, 10) and shape["ttc_max"] == (8, 16, 64)
+    assert [int(np.prod(shape[n])) for n in BOUNDARIES] == [1024, 1025, 640, 650, 8192]
+    assert z["ttc_max"].params().time_quantization == 0.1 and not z["ttc_max"].has_tables
+    assert all(z[n].has_tables and z[n].steps == 2 for n in BOUNDARIES[:4])
+    full = z["ttc_cells1024"]
+    last = np.stack([full.get("grid", i) for i in full.indices()])        # [state, E, A, V, L, T]
+    assert (last[..., 63] > 0).any() and (last.reshape(-1, 1024)[:, 1023] > 0).any()   # time column T - 1 and cell index 1023
+    for name, roads in STATE_ROADS.items():
+        g = z[name]
+        V, L, T = shape[name]
+        st = g.state("init")
+        s = st["speed_index"][:, 0] * L + st["lane"][:, 0]                  # the observer's state in the sweep
+        assert [(e, int(s[e])) for e, _ in roads] == roads and roads[-1][1] == V * L - 1 and (s[:roads[0][0]] < 64).all()
+        second = (np.arange(V)[:, None] * L + np.arange(L)[None, :]) >= 64  # [V, L]: the states of the sweep's second pass
+        for e, _ in roads:
+            grid = g.get("grid")[e, 0]
+            assert (grid[second] > 0).any() and (grid == 1.0).any() and (grid == 0.5).any(), (name, e)
+            # a vehicle ahead in the observer's lane: the Q values differ -- all five, but that FASTER at the highest speed index is
+            # IDLE by clip_position (s = 63 and 64 of 5 x 13 and s = 127 are the highest speed; lane_change_reward keeps LEFT / RIGHT
+            # apart from IDLE in the outermost lanes)
+            if g.has_tables:
+                tables = [g.get(k)[e] for k in ("transition", "reward", "terminal")]
+            else:
+                m = finite_mdp.build(grid, int(st["speed_index"][e, 0]), int(st["lane"][e, 0]), g.config)
+                tables = [m.transition, m.reward, m.terminal]
+            _, q = fixed_point(*tables, 1.0, T + 1)
+            assert len(set(q[int(s[e]) * T])) == 5 - (st["speed_index"][e, 0] == V - 1), (name, e, q[int(s[e]) * T])
 
 
 @pytest.mark.parametrize("name,slots", [("ttc_passes65", (63, 64)), ("ttc_passes130", (63, 64, 65, 127, 128, 129))])
@@ -320,39 +349,81 @@ def test_env0_regenerates_bit_for_bit(name):
                 np.testing.assert_array_equal(got[k][:, 0], a[:, 0], err_msg=k)
             elif k not in ("meta", "seeds"):
                 np.testing.assert_array_equal(got[k], a, err_msg=k)
+    assert set(got) == set(z.files)
+
+
+@pytest.mark.parametrize("name,env", [pytest.param(n, e, marks=needs_reference) for n, roads in STATE_ROADS.items() for e, _ in roads])
+def test_hand_placed_state_roads_regenerate_bit_for_bit(name, env):
+    """The hand-placed roads of ttc_states65 / ttc_max are environments after env 0: each regenerated alone, every array."""
+    got = _generator().generate(name, only_envs={env})
+    with np.load(os.path.join(TTC_DIR, name + ".npz")) as z:
+        for k in z.files:
+            a = z[k]
+            if k.startswith("init_") or k.endswith("0"):
+                np.testing.assert_array_equal(got[k][0], a[env], err_msg=k)
+            elif k.startswith("step_") or k in ("grid", "transition", "reward", "terminal", "state"):
+                np.testing.assert_array_equal(got[k][:, 0], a[:, env], err_msg=k)
+
+
+LIVE_CASES = list(range(24)) + list(range(24, 32))   # 24 ..: the large LDS class and the second pass of the value sweep
 
 
 def _draw(case: int) -> dict:
-    mgt = _generator()
+    """Cases 0 .. 23: up to 8 speeds, 6 lanes and 60 time steps.  Cases 24 .. 31: 5 or 8 speeds on 9 .. 16 lanes with horizon /
+    frequency pairs up to T = 64 -- grids of the large capacity class, more than 64 states (test_live_cases_cover_the_large_shapes).
+    Needs no reference: ``fast`` names the environment class."""
     rng = np.random.default_rng(77_000 + case)
+    large = case >= 24
     fast = bool(rng.integers(0, 2))
     A = int(rng.choice([1, 1, 1, 2]))
-    n_speeds = int(rng.choice([2, 3, 3, 5, 8]))
+    if large:  # (the reference's to_finite_mdp() runs single-agent only: two agents in cases 24 and 28, tables in the other six)
+        A = 2 if case % 4 == 0 else 1
+    n_speeds = int(rng.choice([5, 8, 8] if large else [2, 3, 3, 5, 8]))
     lo = float(np.round(rng.uniform(8, 22), 1))
     act = {"type": "DiscreteMetaAction", "target_speeds": [float(v) for v in np.round(np.linspace(lo, lo + rng.uniform(4, 15), n_speeds), 2)]}
-    config = {"vehicles_count": int(rng.integers(3, 90)), "lanes_count": int(rng.integers(1, 7)),
+    config = {"vehicles_count": int(rng.integers(3, 90)), "lanes_count": int(rng.choice([9, 11, 13, 16, 16]) if large else rng.integers(1, 7)),
               "vehicles_density": float(np.round(rng.uniform(0.7, 2.5), 3)), "simulation_frequency": int(rng.choice([10, 15, 20])),
               "policy_frequency": int(rng.choice([1, 1, 2, 5])), "ego_spacing": float(np.round(rng.uniform(1.0, 2.5), 3)),
               "duration": 20, "action": act, "lane_change_reward": float(rng.choice([0.0, -0.1])),
               "right_lane_reward": float(np.round(rng.uniform(0, 0.5), 2)), "collision_reward": float(np.round(rng.uniform(-3, -0.5), 2))}
     if rng.integers(0, 3) == 0:
-        config["other_vehicles_type"] = mgt.LINEAR
+        config["other_vehicles_type"] = LINEAR
     if A > 1:
         config.update({"controlled_vehicles": A, "action": {"type": "MultiAgentAction", "action_config": act},
                        "observation": {"type": "MultiAgentObservation", "observation_config": {"type": "Kinematics"}}})
-    return dict(name=f"live_ttc_{case}", cls=mgt.HighwayEnvFast if fast else mgt.HighwayEnv, config=config,
-                seeds=[int(rng.integers(0, 2**31))], steps=2, action_seed=int(rng.integers(0, 2**31)),
-                horizon=float(rng.choice([10.0, 10.0, 6.0, 12.0])))
+    seed, action_seed = int(rng.integers(0, 2**31)), int(rng.integers(0, 2**31))
+    horizon = float(rng.choice([10.0, 10.0, 6.0, 12.0]))
+    if large:  # (policy_frequency, horizon): T = 64, 64, 64, 41, 50, 10
+        pf, horizon = [(1, 64.0), (2, 32.0), (5, 12.8), (1, 41.0), (5, 10.0), (1, 10.0)][int(rng.integers(0, 6))]
+        config["policy_frequency"] = pf
+    return dict(name=f"live_ttc_{case}", fast=fast, config=config,
+                seeds=[seed], steps=2, action_seed=action_seed, horizon=float(horizon))
 
 
-@pytest.mark.parametrize("case", [pytest.param(c, marks=needs_reference) for c in range(24)])
+def test_live_cases_cover_the_large_shapes():
+    """(no reference needed) Of the cases 24 .. 31 at least three have more than 1024 cells and at least three more than 64 states;
+    none of the cases 0 .. 23 has either."""
+    def shape(case):
+        sc = _draw(case)
+        act = sc["config"]["action"]
+        V = len(act.get("action_config", act)["target_speeds"])
+        return V, sc["config"]["lanes_count"], _abi.ttc_params(highway_config(**sc["config"]), horizon=sc["horizon"]).time_steps
+    old, new = [shape(c) for c in range(24)], [shape(c) for c in range(24, 32)]
+    assert all(V * L * T <= 1024 and V * L <= 64 for V, L, T in old)
+    assert sum(V * L * T > 1024 for V, L, T in new) >= 3 and sum(V * L > 64 for V, L, T in new) >= 3, new
+    assert max(L for _, L, _ in new) == 16 and max(T for _, _, T in new) == 64, new
+
+
+@pytest.mark.parametrize("case", [pytest.param(c, marks=needs_reference) for c in LIVE_CASES])
 def test_emulation_against_live_reference(case):
-    """24 random configurations (fixed list: seeds 0 .. 23 of `_draw`) against the live reference: the grids array-equal, the tables
+    """32 random configurations (fixed list: seeds 0 .. 31 of `_draw`) against the live reference: the grids array-equal, the tables
     of to_finite_mdp() exact / bit for bit, the planner equal to the numpy fixed point on the reference's tables.  No cell is excused
     (several cases hold crashed vehicles resting exactly a vehicle length apart)."""
     from tests.emu.emu_ttc import EmuTtcEngine
     sc = _draw(case)
-    g = TtcGolden(sc["name"], _generator().run(sc))
+    mgt = _generator()
+    sc["cls"] = mgt.HighwayEnvFast if sc.pop("fast") else mgt.HighwayEnv
+    g = TtcGolden(sc["name"], mgt.run(sc))
     what = f"{sc['name']} ({json.dumps(sc['config'])})"
     cfg, params = g.hwy_config(), g.params(0.9)
     eng = EmuTtcEngine(cfg)

@@ -9,7 +9,11 @@ bit.  The planner's Q row and action are compared with ``==`` to a numpy fixed-p
 
 On the engine's own states (GPU only) the device is held to the emulation bit for bit and to a numpy restatement of the grid
 (tests/ttc_util.py: restate_grid); a differing cell is accepted only where the restatement finds a candidate within 1e-9 of a
-cell boundary feeding it, in at most 1 grid of 1000 -- and in none when every heading is 0."""
+cell boundary feeding it, in at most 1 grid of 1000 -- and in none when every heading is 0.
+
+The device-pointer entry points (``hwy_ttc_grid_device`` / ``hwy_mdp_plan_device``, every combination of their optional outputs, into
+torch tensors on the engine's stream) are held to the host-pointer forms bit for bit, and the host-pointer forms' own buffer to a
+grid that grows between calls (GPU only)."""
 import functools
 
 import numpy as np
@@ -130,6 +134,8 @@ def test_crafted_roads_are_what_they_are_for():
     assert w[6].any() and w[8].any() and not w[9].any()
     assert w[7, 0, 2, 0] == 1.0 and w[7, 2, 2, 0] == 1.0       # distance 0: time 0 whatever the closing speed
     assert np.abs(g.z["init_heading"][6]).max() == 0.3 and g.z["init_heading"][8, 0] == 0.2
+    # the same equality within reach of not_zero(0) = 0.01: 0.037 / 0.01 = 3.7 s would mark cells 3 and 4 of ego speed 25
+    assert not w[10, 1].any() and w[10, 2, 2, 0] == 1.0 and w[10, 0, 2, 0] == 0.5
 
 
 # ---- the engine's own states (GPU) --------------------------------------------------------------------------------------------------
@@ -207,6 +213,99 @@ def test_hip_against_numpy_restatement_headings_zero():
         eng.set_state(st)
         want, _, _, _ = restate_grid(cfg, st, params)
         np.testing.assert_array_equal(eng.ttc_grid(params).astype(np.float64), want)
+    eng.close()
+
+
+def _device_case(case: str):
+    """(cfg, params, states): ``ttc_ma2`` -- two agents, the small capacity class; ``ttc_max`` -- 8192 cells, 128 states; ``fuzz4`` --
+    case 4 of tests/test_ttc_fuzz.py: four agents on 7 x 16 x 64 cells, 128 slots."""
+    if case == "fuzz4":
+        from tests.test_ttc_fuzz import _case
+        _, cfg, params, rows, _, _ = _case(4)
+        return cfg, params, [rows[0][0], rows[1][0]]
+    g = TtcGolden(case)
+    return g.hwy_config(), g.params(0.8), [g.state("init"), g.state("step", g.steps - 1)]
+
+
+GUARD = 64  # elements behind every device output that must stay as they were
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["ttc_ma2", "ttc_max", "fuzz4"])
+def test_device_entry_points_equal_the_host_pointer_forms(case):
+    """hwy_ttc_grid_device and hwy_mdp_plan_device with d_q / d_grid given or null, into torch tensors on the engine's stream: row
+    r = e * A + a writes grid + r * cells, action + r and q + r * 5 -- bit for bit what hwy_ttc_grid / hwy_mdp_plan copy to the
+    host for the same state -- an output that is not asked for is not written, and nothing is written behind an output's end."""
+    import itertools
+
+    import torch
+
+    from highwayenv_amd.engine import Engine
+    cfg, params, states = _device_case(case)
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(device=dev)
+    eng = Engine(cfg, device=0, stream=stream.cuda_stream)
+    rows, cells = cfg.num_envs * cfg.num_agents, int(np.prod(eng.ttc_shape(params)))
+    assert rows > cfg.num_envs or case == "ttc_max"
+    with torch.cuda.stream(stream):
+        for k, st in enumerate(states):
+            eng.set_state(st)
+            want_grid = eng.ttc_grid(params).reshape(rows, cells)
+            want_action, want_q, _ = eng.mdp_plan(params, return_q=True)
+            assert want_grid.any() and not np.isnan(want_q).any()
+            for with_q, with_grid in [(None, True)] + list(itertools.product((True, False), (True, False))):
+                grid = torch.full((rows * cells + GUARD,), -3.0, dtype=torch.float32, device=dev)
+                action = torch.full((rows + GUARD,), -7, dtype=torch.int32, device=dev)
+                q = torch.full((rows * 5 + GUARD,), -9.0, dtype=torch.float64, device=dev)
+                if with_q is None:
+                    eng.ttc_grid_device(params, grid.data_ptr())
+                else:
+                    eng.mdp_plan_device(params, action.data_ptr(), q.data_ptr() if with_q else 0, grid.data_ptr() if with_grid else 0)
+                stream.synchronize()
+                what = f"{case} state {k}: " + ("ttc_grid_device" if with_q is None else f"mdp_plan_device(q={with_q}, grid={with_grid})")
+                grid, action, q = grid.cpu().numpy(), action.cpu().numpy(), q.cpu().numpy()
+                if with_grid:
+                    np.testing.assert_array_equal(grid[:rows * cells].reshape(rows, cells), want_grid, err_msg=what + ": grid")
+                else:
+                    assert (grid == -3.0).all(), what + ": a grid was written that was not asked for"
+                if with_q:
+                    np.testing.assert_array_equal(_bits(q[:rows * 5]), _bits(want_q.reshape(-1)), err_msg=what + ": Q bits")
+                else:
+                    assert (q == -9.0).all(), what + ": Q was written that was not asked for"
+                if with_q is None:
+                    assert (action == -7).all(), what
+                else:
+                    np.testing.assert_array_equal(action[:rows], want_action.reshape(-1), err_msg=what + ": action")
+                assert (grid[rows * cells:] == -3.0).all() and (action[rows:] == -7).all() and (q[rows * 5:] == -9.0).all(), \
+                    what + ": written behind the end of an output"
+    eng.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("first", ["ttc_grid", "mdp_plan"])
+def test_host_pointer_buffer_grows_between_calls(first):
+    """One engine with 8 speeds and 16 lanes, T = 1 (128 cells), then T = 64 (8192 cells: the engine frees its grid buffer and
+    allocates a larger one), then T = 10 (the larger buffer stays): every result equals the emulation's for the same state and
+    params, whichever of the two host-pointer entry points meets the growing grid first."""
+    from highwayenv_amd.engine import Engine
+    from tests.emu import emu_ttc
+    g = TtcGolden("ttc_max")
+    cfg, st = g.hwy_config(), g.state("init")
+    eng = Engine(cfg)
+    eng.set_state(st)
+    for horizon, tq in ((1.0, 1.0), (6.4, 0.1), (10.0, 1.0)):
+        params = _abi.ttc_params(g.config, horizon=horizon, time_quantization=tq, gamma=0.8)
+        e_action, e_q, e_grid = emu_ttc.mdp_plan(cfg, st, params, return_q=True, return_grid=True)
+        assert e_grid.shape[2:] == (8, 16, params.time_steps) and e_grid.any()
+        got = {}
+        for call in (("ttc_grid", "mdp_plan") if first == "ttc_grid" else ("mdp_plan", "ttc_grid")):
+            got[call] = eng.ttc_grid(params) if call == "ttc_grid" else eng.mdp_plan(params, return_q=True, return_grid=True)
+        what = f"T = {params.time_steps}"
+        np.testing.assert_array_equal(got["ttc_grid"], e_grid, err_msg=what + ": grid entry point")
+        action, q, grid = got["mdp_plan"]
+        np.testing.assert_array_equal(grid, e_grid, err_msg=what + ": the planner's grid")
+        np.testing.assert_array_equal(_bits(q), _bits(e_q), err_msg=what + ": Q bits")
+        np.testing.assert_array_equal(action, e_action, err_msg=what + ": action")
     eng.close()
 
 

@@ -15,7 +15,11 @@ TTC_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "tt
 RUNS = ["ttc_fast", "ttc_lanes1", "ttc_lanes16", "ttc_speeds2", "ttc_speeds8", "ttc_pf5", "ttc_horizon1", "ttc_n64", "ttc_n65",
         "ttc_n130", "ttc_ma2", "ttc_linear", "ttc_crash", "ttc_rewards"]
 PASSES = ["ttc_passes65", "ttc_passes130"]  # hand-placed: vehicles within the horizon in the slots either side of a pass of 64
-FIXTURES = RUNS + ["ttc_crafted"] + PASSES
+# the kernel's own boundaries (csrc/hwy_ttc.h): the LDS capacity classes either side of 1024 cells, the value sweep either side of
+# 64 states, and every limit at once; ttc_states65 and ttc_max end with hand-placed roads (STATE_ROADS: (environment, observer's s))
+BOUNDARIES = ["ttc_cells1024", "ttc_cells1025", "ttc_states64", "ttc_states65", "ttc_max"]
+STATE_ROADS = {"ttc_states65": [(2, 63), (3, 64)], "ttc_max": [(2, 63), (3, 64), (4, 127)]}
+FIXTURES = RUNS + ["ttc_crafted"] + PASSES + BOUNDARIES
 BACKENDS = [pytest.param("emu", id="emu"), pytest.param("hip", id="hip", marks=pytest.mark.gpu)]
 KNIFE = 1e-9   # a candidate with |ttc / tq - rint(ttc / tq)| below this may fall into either neighbouring cell
 MARGIN = 5.0   # other.LENGTH / 2 + vehicle.LENGTH / 2
