@@ -38,6 +38,9 @@ HEADERS = sorted(os.path.basename(h) for h in glob.glob(os.path.join(CSRC, "*.h"
 # (tests/test_ix_parity.py, tests/golden_util.py: slow_atol) -- and the exact comparisons (lane indices, flags) now rest on the
 # decisions being well conditioned, not on identical arithmetic: DESIGN.md section 4 states both as part of the parity contract.
 # tests/emu builds the CPU emulator with the same front end and the same setting.
+# The unfused arithmetic is no longer only a record: build_engine_strict() below builds the same sources with "off" into a library
+# of its own, and tests/test_strict_arithmetic.py runs the reference fixtures on it (the intersection ones at the 1e-8 of rounds
+# 1-3) and holds the product to it decision by decision (profiles/strict_arithmetic.md).
 FP_CONTRACT = "on"
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", f"-ffp-contract={FP_CONTRACT}", "-fPIC", "-mllvm", "-disable-machine-licm",
                "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
@@ -144,6 +147,59 @@ def build_engine_asan(force: bool = False, verbose: bool = False) -> str:
         print(" ".join(cmd))
     subprocess.run(cmd, check=True)
     return ASAN_LIB_PATH
+
+
+STRICT_LIB_PATH = os.path.join(CSRC, "libhwy_engine_strict.so")
+
+
+def strict_flags_for(src: str) -> list:
+    """flags_for(src) with -ffp-contract=off in place of the product's setting.  One more unit is scheduled by the default strategy
+    here: unfused, hwy_kernels.hip runs into the register-allocator crash of ROCm 7.2 that flags_for() keeps the Linear and direct
+    units out of (RAGreedy, VirtRegAuxInfo::isRematerializable on hwy_step_kernel<1, 1> after the iterative-ilp scheduler).  A
+    scheduling strategy orders instructions; it rounds nothing."""
+    out = ["-ffp-contract=off" if f.startswith("-ffp-contract=") else f for f in flags_for(src)]
+    if src == "hwy_kernels.hip" and "-amdgpu-sched-strategy=iterative-ilp" in out:
+        k = out.index("-amdgpu-sched-strategy=iterative-ilp")
+        del out[k - 1:k + 1]
+    return out
+
+
+def is_stale_strict() -> bool:
+    """is_stale()'s rule for the strict library."""
+    if not os.path.exists(STRICT_LIB_PATH):
+        return True
+    t = os.path.getmtime(STRICT_LIB_PATH)
+    return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in SOURCES + HEADERS)
+
+
+def build_engine_strict(force: bool = False, verbose: bool = False) -> str:
+    """libhwy_engine_strict.so: the product's sources under the product's flags_for() rules, except -ffp-contract=off -- every
+    a*b+c rounds twice, like the reference's numpy scalars and the C oracle.  Test infrastructure (tests/test_strict_arithmetic.py
+    selects it with HWY_ENGINE_LIB in child processes): the second arithmetic the parity contract of DESIGN.md section 4 is held
+    against.  Its objects are *_strict.o; the product's objects and library are not touched.  The translation units compile side by
+    side (each is one hipcc process; the pool is a fixed size, not the machine's)."""
+    if not force and not is_stale_strict():
+        return STRICT_LIB_PATH
+    from concurrent.futures import ThreadPoolExecutor
+    hipcc = _hipcc()
+
+    def compile_one(src):
+        obj = os.path.join(CSRC, src.replace(".hip", "_strict.o"))
+        cmd = [hipcc, *strict_flags_for(src), "-c", os.path.join(CSRC, src), "-o", obj]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.run(cmd, check=True)
+        return obj
+
+    with ThreadPoolExecutor(min(len(SOURCES), 8)) as pool:
+        objs = list(pool.map(compile_one, SOURCES))
+    tmp = f"{STRICT_LIB_PATH}.{os.getpid()}.tmp"
+    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", tmp, *objs, "-ldl"]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+    os.replace(tmp, STRICT_LIB_PATH)
+    return STRICT_LIB_PATH
 
 
 def gfx950_code_objects(blob: bytes) -> list:

@@ -2053,6 +2053,9 @@ __device__ inline double math_probe(int op, double x) {
     // key is rounded up to
     case 40: return (double)HWY_WAVE_MAX_U32(reach_key(x));
     case 41: return __hiloint2double((int)(reach_key(x) + 1u), 0);
+    // which arithmetic this build has: ONE source expression, one v_fma_f64 under -ffp-contract=on (x = 1 + 2^-30 -> 2^-29 + 2^-60),
+    // a rounded product and a subtraction under -ffp-contract=off (-> 2^-29): tests/test_strict_arithmetic.py
+    case 42: return x * x - 1.0;
     default: return wrap_to_pi(x);
   }
 }

@@ -994,7 +994,7 @@ extern "C" int hwy_set_autoreset(hwy_engine *eng, int32_t enabled, uint64_t base
 }
 
 extern "C" int hwy_debug_math(hwy_engine *eng, int32_t op, const double *in, double *out, int64_t n) {
-  if (!eng || !in || !out || n < 0 || op < 0 || (op > 12 && (op < 20 || op > 33) && op != 40 && op != 41)) return HWY_ERR_INVALID_ARG;
+  if (!eng || !in || !out || n < 0 || op < 0 || (op > 12 && (op < 20 || op > 33) && (op < 40 || op > 42))) return HWY_ERR_INVALID_ARG;
   // op 40 (wave_max_u32) is a DPP reduction that is only correct with all 64 lanes of every wavefront enabled
   if (op == 40 && n % 64 != 0) return fail(eng, HWY_ERR_INVALID_ARG, "hwy_debug_math: op 40 takes whole wavefronts (n % 64 == 0)");
   if (n == 0) return HWY_OK;

@@ -18,11 +18,20 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(os.path.dirname(_HERE))
 # HWY_EMU_FLAGS: extra g++ flags for the emulator build (its own library file), e.g. "-ffp-contract=fast -mfma" -- how the test
 # suite's tolerances were tried against fused multiply-adds before the kernel build's -ffp-contract=off was put up for an A/B
-# (profiles/r03_history.md).  The default build rounds every a*b+c twice, like the kernel build and like numpy.
+# (profiles/r03_history.md).  Since the kernel build contracts (build.FP_CONTRACT = "on") the knob runs the other way:
+# "-ffp-contract=off" is the strict emulator of tests/test_strict_arithmetic.py.  Every emulator library of this package (this
+# driver, the Linear / direct drivers, the Lidar and the planner driver) honours it, each in a file named after the flags.
 _EXTRA = os.environ.get("HWY_EMU_FLAGS", "").split()
 _LIB = os.path.join(_HERE, "_build", "libhwy_emu.so" if not _EXTRA else
                     "libhwy_emu_%08x.so" % (__import__("zlib").crc32(" ".join(_EXTRA).encode()) & 0xffffffff))
 _lib = None
+
+
+def flagged(out_lib: str) -> str:
+    """The file an emulator library built under HWY_EMU_FLAGS goes to: never the file of the default build."""
+    if not _EXTRA:
+        return out_lib
+    return "%s_%08x.so" % (out_lib[:-3], __import__("zlib").crc32(" ".join(_EXTRA).encode()) & 0xffffffff)
 
 
 def compile_emulator(src_cpp: str, out_lib: str, extra=()) -> None:
@@ -139,14 +148,14 @@ class StraightFamilyEngine(Scheduled):
     def build(cls, force: bool = False) -> str:
         if cls.ENV and os.environ.get(cls.ENV):
             return os.environ[cls.ENV]
-        out = os.path.join(_HERE, "_build", f"libhwy_{cls.SYMBOL}.so")
+        out = flagged(os.path.join(_HERE, "_build", f"libhwy_{cls.SYMBOL}.so"))
         csrc = os.path.join(_ROOT, "highwayenv_amd", "csrc")
         srcs = [os.path.join(_HERE, f) for f in (cls.SOURCE, "emu_straight.h", "hip_emu.h")] + [
             os.path.join(csrc, f) for f in ("hwy_device.h", "hwy_wave.h", "hwy_math.h", "hwy_params.h", "hwy_launch_family.h")] + [
             os.path.join(_ROOT, "include", "hwy_engine.h")]
         if force or not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(s) for s in srcs):
             os.makedirs(os.path.dirname(out), exist_ok=True)
-            compile_emulator(srcs[0], out)
+            compile_emulator(srcs[0], out, _EXTRA)
         return out
 
     @classmethod

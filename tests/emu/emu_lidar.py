@@ -28,13 +28,13 @@ _lib = None
 def build(force: bool = False) -> str:
     if os.environ.get("HWY_EMU_LIDAR_LIB"):
         return os.environ["HWY_EMU_LIDAR_LIB"]
-    out = os.path.join(_HERE, "_build", "libhwy_emu_lidar.so")
+    out = emu.flagged(os.path.join(_HERE, "_build", "libhwy_emu_lidar.so"))
     csrc = os.path.join(_ROOT, "highwayenv_amd", "csrc")
     srcs = [os.path.join(_HERE, f) for f in ("emu_lidar.cpp", "hip_emu.h")] + [
         os.path.join(csrc, f) for f in ("hwy_lidar.h", "hwy_device.h", "hwy_math.h")] + [os.path.join(_ROOT, "include", "hwy_engine.h")]
     if force or not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(s) for s in srcs):
         os.makedirs(os.path.dirname(out), exist_ok=True)
-        emu.compile_emulator(srcs[0], out)
+        emu.compile_emulator(srcs[0], out, emu._EXTRA)
     return out
 
 
