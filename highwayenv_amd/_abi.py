@@ -265,6 +265,20 @@ def check_finite_mdp_scope(cfg: "HwyConfig") -> None:
                                   "(the reference builds a 5-column reward next to a 3-column transition there)")
 
 
+def fork_bytes(cfg: "HwyConfig", num_envs: int, k_steps: int = 0) -> int:
+    """Device bytes an engine of ``num_envs`` environments of ``cfg`` holds (state planes, behaviour planes, one step's outputs)
+    plus the planes of a ``k_steps`` rollout and its scores: what ``fork`` / ``score_sequences`` / ``plan_lookahead`` need."""
+    pitch = (cfg.num_vehicles + 7) // 8 * 8
+    obs = int(np.prod(obs_shape(cfg))) * 4
+    per_env = pitch * (9 * 8 + 4) + 8 + 1 + 4 + 1 + 8
+    if cfg.traffic_model == TRAFFIC_LINEAR:
+        per_env += pitch * HWY_BEHAVIOR_PARAMS * 8
+    if cfg.obs_type == OBS_OCCUPANCY_GRID:
+        per_env += cfg.num_agents * 2 * cfg.grid_shape[0] * cfg.grid_shape[1] * 4
+    per_step = cfg.num_agents * (4 + 8 + 8 + 1 + obs) + 2
+    return int(num_envs) * (per_env + (1 + int(k_steps)) * per_step + cfg.num_agents * 8)
+
+
 def obs_shape(cfg: "HwyConfig") -> tuple:
     """Per-agent observation shape: (V, F) Kinematics, (F, W, H) OccupancyGrid, (cells, 2) Lidar."""
     if cfg.obs_type == OBS_LIDAR:

@@ -67,6 +67,10 @@ struct hwy_engine {
   int ttc_cells = 0;
   int32_t *d_plan_action = nullptr;  // [E][A]
   double *d_plan_q = nullptr;        // [E][A][5]
+  // hwy_fork / hwy_fork_device: the uploaded source indices [E] (host form) and the event that orders this engine's stream behind
+  // the source engine's, both created on first use
+  int32_t *d_fork_src = nullptr;
+  hipEvent_t fork_event = nullptr;
   // pinned host staging
   void *h_pinned = nullptr;
   size_t h_pinned_bytes = 0;
@@ -518,8 +522,9 @@ extern "C" int hwy_destroy(hwy_engine *eng) {
   void *ptrs[] = {eng->d_f64, eng->d_packed, eng->d_time, eng->d_done, eng->d_episode, eng->d_actions, eng->d_out, eng->d_roll,
                   eng->d_mask, eng->d_seeds, eng->d_grid_ws, eng->d_route, eng->d_road_steps, eng->d_gnet,
                   eng->d_shadow_f64, eng->d_shadow_packed, eng->d_shadow_route, eng->d_shadow_meta, eng->d_counters, eng->d_block_env,
-                  eng->d_behavior, eng->d_controls, eng->d_ttc_grid, eng->d_plan_action, eng->d_plan_q};
+                  eng->d_behavior, eng->d_controls, eng->d_ttc_grid, eng->d_plan_action, eng->d_plan_q, eng->d_fork_src};
   for (void *q : ptrs) if (q) (void)hipFree(q);
+  if (eng->fork_event) (void)hipEventDestroy(eng->fork_event);
   if (eng->h_pinned) (void)hipHostFree(eng->h_pinned);
   if (eng->own_stream && eng->stream) (void)hipStreamDestroy(eng->stream);
   delete eng;
@@ -1153,6 +1158,126 @@ extern "C" int hwy_mdp_plan(hwy_engine *eng, const hwy_ttc_params *params, int32
   HWY_HIP(eng, hipMemcpyAsync(action, eng->d_plan_action, rows * sizeof(int32_t), hipMemcpyDeviceToHost, eng->stream));
   if (q) HWY_HIP(eng, hipMemcpyAsync(q, eng->d_plan_q, rows * 5 * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
   if (grid) HWY_HIP(eng, hipMemcpyAsync(grid, eng->d_ttc_grid, rows * cells * sizeof(float), hipMemcpyDeviceToHost, eng->stream));
+  HWY_HIP(eng, hipStreamSynchronize(eng->stream));
+  return HWY_OK;
+}
+
+// ---- environment fork and rollout scoring (hwy_lookahead.h) --------------------------------------------------------------------------
+static int fork_check(hwy_engine *dst, hwy_engine *src, int32_t branches, bool has_src_env, const char *who) {
+  if (!dst) return HWY_ERR_INVALID_ARG;
+  if (!src) return fail(dst, HWY_ERR_INVALID_ARG, std::string(who) + ": src is NULL");
+  const char *why = "";
+  if (const int rc = hwy::fork_validate(dst->cfg, src->cfg, dst == src, branches, has_src_env, &why)) return fail(dst, rc, std::string(who) + ": " + why);
+  if (dst->device != src->device) return fail(dst, HWY_ERR_INVALID_ARG, std::string(who) + ": the two engines are on different devices");
+  return HWY_OK;
+}
+
+extern "C" int hwy_fork_device(hwy_engine *dst, hwy_engine *src, int32_t branches, const int32_t *d_src_env) {
+  if (int rc = fork_check(dst, src, branches, d_src_env != nullptr, "hwy_fork_device")) return rc;
+  HWY_HIP(dst, hipSetDevice(dst->device));
+  if (dst->stream != src->stream) {  // what src's stream holds so far comes first
+    if (!dst->fork_event) HWY_HIP(dst, hipEventCreateWithFlags(&dst->fork_event, hipEventDisableTiming));
+    HWY_HIP(dst, hipEventRecord(dst->fork_event, src->stream));
+    HWY_HIP(dst, hipStreamWaitEvent(dst->stream, dst->fork_event, 0));
+  }
+  hwy::ForkParams p;
+  memset(&p, 0, sizeof p);
+  const size_t splane = (size_t)src->cfg.num_envs * src->pitch, dplane = (size_t)dst->cfg.num_envs * dst->pitch;
+  for (int f = 0; f < 9; ++f) { p.src_f64[f] = src->d_f64 + f * splane; p.dst_f64[f] = dst->d_f64 + f * dplane; }
+  p.n_f64 = 9;
+  if (is_linear(dst))
+    for (int f = 0; f < HWY_BEHAVIOR_PARAMS; ++f, ++p.n_f64) { p.src_f64[9 + f] = src->d_behavior + f * splane; p.dst_f64[9 + f] = dst->d_behavior + f * dplane; }
+  p.src_i32[0] = src->d_packed; p.dst_i32[0] = dst->d_packed;  // whole words: the rank hint travels
+  p.n_i32 = 1;
+  if (is_direct(dst)) { p.src_controls = src->d_controls; p.dst_controls = dst->d_controls; }
+  p.src_time = src->d_time; p.dst_time = dst->d_time;
+  p.src_episode = src->d_episode; p.dst_episode = dst->d_episode;
+  p.dst_done = dst->d_done;
+  p.src_env = d_src_env;
+  p.pitch = dst->pitch; p.A = dst->cfg.num_agents; p.branches = branches;
+  p.src_envs = src->cfg.num_envs; p.dst_envs = dst->cfg.num_envs;
+  HWY_HIP(dst, hwy::launch_fork(p, dst->stream));
+  return HWY_OK;
+}
+
+extern "C" int hwy_fork(hwy_engine *dst, hwy_engine *src, int32_t branches, const int32_t *src_env) {
+  if (!src_env) return hwy_fork_device(dst, src, branches, nullptr);
+  if (int rc = fork_check(dst, src, branches, true, "hwy_fork")) return rc;
+  const size_t E = dst->cfg.num_envs;
+  for (size_t j = 0; j < E; ++j)
+    if (src_env[j] < 0 || src_env[j] >= src->cfg.num_envs) return fail(dst, HWY_ERR_INVALID_ARG, "hwy_fork: source index outside [0, src.num_envs)");
+  HWY_HIP(dst, hipSetDevice(dst->device));
+  if (!dst->d_fork_src) HWY_HIP(dst, hipMalloc((void **)&dst->d_fork_src, E * sizeof(int32_t)));
+  std::memcpy(dst->h_pinned, src_env, E * sizeof(int32_t));
+  HWY_HIP(dst, hipMemcpyAsync(dst->d_fork_src, dst->h_pinned, E * sizeof(int32_t), hipMemcpyHostToDevice, dst->stream));
+  if (int rc = hwy_fork_device(dst, src, branches, dst->d_fork_src)) return rc;
+  HWY_HIP(dst, hipStreamSynchronize(dst->stream));  // (the staging buffer is the engine's)
+  return HWY_OK;
+}
+
+extern "C" int hwy_score_device(hwy_engine *eng, int32_t k_steps, int32_t branches, double gamma, const int32_t *d_first_action,
+                                const double *d_reward, const uint8_t *d_terminated, const uint8_t *d_truncated, double *d_return,
+                                double *d_q, int32_t *d_best_action, int32_t *d_best_branch) {
+  if (!eng) return HWY_ERR_INVALID_ARG;
+  const char *why = "";
+  if (const int rc = hwy::score_validate(eng->cfg, k_steps, branches, gamma, d_first_action != nullptr, d_reward && d_terminated && d_truncated,
+                                         d_q != nullptr, d_best_action != nullptr, &why))
+    return fail(eng, rc, std::string("hwy_score_device: ") + why);
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  hwy::ScoreParams p;
+  memset(&p, 0, sizeof p);
+  p.first_action = d_first_action; p.reward = d_reward; p.terminated = d_terminated; p.truncated = d_truncated;
+  p.ret = d_return; p.q = d_q; p.best_action = d_best_action; p.best_branch = d_best_branch;
+  p.gamma = gamma;
+  p.K = k_steps; p.branches = branches; p.A = eng->cfg.num_agents; p.n_ids = num_action_ids(eng);
+  p.groups = eng->cfg.num_envs / branches;
+  HWY_HIP(eng, hwy::launch_score(p, eng->stream));
+  return HWY_OK;
+}
+
+extern "C" int hwy_score_rollout(hwy_engine *eng, int32_t k_steps, int32_t branches, double gamma, const int32_t *actions,
+                                 double *reward, uint8_t *terminated, uint8_t *truncated, double *ret, double *q,
+                                 int32_t *best_action, int32_t *best_branch) {
+  if (!eng) return HWY_ERR_INVALID_ARG;
+  const bool single = eng->cfg.num_agents == 1;
+  const char *why = "";
+  if (const int rc = hwy::score_validate(eng->cfg, k_steps, branches, gamma, single, true, q != nullptr, best_action != nullptr, &why))
+    return fail(eng, rc, std::string("hwy_score_rollout: ") + why);
+  if (!actions) return fail(eng, HWY_ERR_INVALID_ARG, "hwy_score_rollout: actions must be non-NULL");
+  const size_t n_act = num_agent_rows(eng->cfg), n_obs = num_obs_floats(eng->cfg);
+  const size_t EB = eng->cfg.num_envs, K = (size_t)k_steps, E = EB / branches, ids = (size_t)num_action_ids(eng);
+  for (size_t k = 0; k < K * n_act; ++k)  // like hwy_rollout, before anything is simulated
+    if (actions[k] < 0 || actions[k] >= (int32_t)ids) return fail(eng, HWY_ERR_ACTION, "action id out of range");
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t o_act = 0, o_rew = up(K * n_act * 4), o_obs = o_rew + up(K * n_act * 8), o_term = o_obs + up(K * n_obs * 4),
+               o_trunc = o_term + up(K * EB), o_ret = o_trunc + up(K * EB), o_q = o_ret + up(n_act * 8), o_ba = o_q + up(E * ids * 8),
+               o_bb = o_ba + up(E * 4), total = o_bb + up(E * eng->cfg.num_agents * 4);
+  if (total > eng->roll_bytes) {
+    HWY_HIP(eng, hipStreamSynchronize(eng->stream));
+    if (eng->d_roll) (void)hipFree(eng->d_roll);
+    eng->d_roll = nullptr;
+    eng->roll_bytes = 0;
+    HWY_HIP(eng, hipMalloc((void **)&eng->d_roll, total));
+    eng->roll_bytes = total;
+  }
+  char *d = eng->d_roll;
+  HWY_HIP(eng, hipMemcpyAsync(d + o_act, actions, K * n_act * 4, hipMemcpyHostToDevice, eng->stream));
+  if (int rc = hwy_rollout_device(eng, k_steps, (const int32_t *)(d + o_act), (float *)(d + o_obs), (double *)(d + o_rew),
+                                  (uint8_t *)(d + o_term), (uint8_t *)(d + o_trunc), nullptr, nullptr))
+    return rc;
+  // single agent: q and the best first action are always folded (first_action and they go together)
+  if (int rc = hwy_score_device(eng, k_steps, branches, gamma, single ? (const int32_t *)(d + o_act) : nullptr, (const double *)(d + o_rew),
+                                (const uint8_t *)(d + o_term), (const uint8_t *)(d + o_trunc), (double *)(d + o_ret),
+                                single ? (double *)(d + o_q) : nullptr, single ? (int32_t *)(d + o_ba) : nullptr, (int32_t *)(d + o_bb)))
+    return rc;
+  if (reward) HWY_HIP(eng, hipMemcpyAsync(reward, d + o_rew, K * n_act * 8, hipMemcpyDeviceToHost, eng->stream));
+  if (terminated) HWY_HIP(eng, hipMemcpyAsync(terminated, d + o_term, K * EB, hipMemcpyDeviceToHost, eng->stream));
+  if (truncated) HWY_HIP(eng, hipMemcpyAsync(truncated, d + o_trunc, K * EB, hipMemcpyDeviceToHost, eng->stream));
+  if (ret) HWY_HIP(eng, hipMemcpyAsync(ret, d + o_ret, n_act * 8, hipMemcpyDeviceToHost, eng->stream));
+  if (q) HWY_HIP(eng, hipMemcpyAsync(q, d + o_q, E * ids * 8, hipMemcpyDeviceToHost, eng->stream));
+  if (best_action) HWY_HIP(eng, hipMemcpyAsync(best_action, d + o_ba, E * 4, hipMemcpyDeviceToHost, eng->stream));
+  if (best_branch) HWY_HIP(eng, hipMemcpyAsync(best_branch, d + o_bb, E * eng->cfg.num_agents * 4, hipMemcpyDeviceToHost, eng->stream));
   HWY_HIP(eng, hipStreamSynchronize(eng->stream));
   return HWY_OK;
 }

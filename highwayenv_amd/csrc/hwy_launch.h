@@ -11,6 +11,7 @@
 #include "hwy_ix.h"
 #include "hwy_lidar.h"
 #include "hwy_ttc.h"
+#include "hwy_lookahead.h"
 
 namespace hwy {
 // The HIP backend of the selection layer (hwy_launch_family.h, hwy_launch_rules.h), for the kernel translation units.
@@ -77,5 +78,9 @@ hipError_t launch_lidar(const LidarParams &lp, bool normalize, int rows, hipStre
 // Time-to-collision grid of the current state and, with `plan`, the value iteration on it (hwy_ttc.h): `rows` = environments x agents
 // wavefronts, row r -> tp.grid + r * V * L * T, tp.action + r, tp.q + r * 5
 hipError_t launch_ttc(const TtcParams &tp, bool plan, int rows, hipStream_t stream);
+// Environment fork (hwy_lookahead.h: a gather copy between the planes of two engines, fp.dst_envs workgroups) and the fold of a
+// rollout's outputs into returns, per-action maxima and the best first action / branch (sp.groups wavefronts)
+hipError_t launch_fork(const ForkParams &fp, hipStream_t stream);
+hipError_t launch_score(const ScoreParams &sp, hipStream_t stream);
 hipError_t launch_math_probe(int op, const double *in, double *out, long long n, hipStream_t stream);
 }  // namespace hwy

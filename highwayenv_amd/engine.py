@@ -203,6 +203,50 @@ class Engine:
         vp = C.c_void_p
         self._check_ttc(self._lib.hwy_mdp_plan_device(self._h, C.byref(params), vp(d_action), vp(d_q or None), vp(d_grid or None)))
 
+    # -- environment fork and scoring of action sequences (csrc/hwy_lookahead.h) -------------------
+    def fork_from(self, src: "Engine", branches: int = 1, source=None):
+        """hwy_fork / hwy_fork_device: environment j of this engine becomes a copy of environment ``source[j]`` of ``src``
+        (host indices, validated), or of ``j // branches``.  Without ``source`` the copy is only enqueued."""
+        if source is None:
+            self._check_ttc(self._lib.hwy_fork_device(self._h, src._h, int(branches), None))
+            return
+        idx = np.ascontiguousarray(source, dtype=np.int32)
+        if idx.shape != (self.E,):
+            raise ValueError(f"fork: source has shape {idx.shape}, this engine needs ({self.E},)")
+        self._check_ttc(self._lib.hwy_fork(self._h, src._h, int(branches), _ptr(idx)))
+
+    def fork_device(self, src: "Engine", branches: int = 1, d_src_env: int = 0):
+        """Enqueue hwy_fork_device with a raw device pointer to the source indices (0: ``j // branches``); does not synchronise."""
+        self._check_ttc(self._lib.hwy_fork_device(self._h, src._h, int(branches), C.c_void_p(d_src_env or None)))
+
+    def score_device(self, k_steps: int, branches: int, gamma: float, d_first_action: int, d_reward: int, d_terminated: int,
+                     d_truncated: int, d_return: int = 0, d_q: int = 0, d_best_action: int = 0, d_best_branch: int = 0):
+        """Enqueue hwy_score_device on raw device pointers; does not synchronise."""
+        vp = C.c_void_p
+        self._check_ttc(self._lib.hwy_score_device(self._h, int(k_steps), int(branches), float(gamma), vp(d_first_action or None),
+                                                   vp(d_reward or None), vp(d_terminated or None), vp(d_truncated or None),
+                                                   vp(d_return or None), vp(d_q or None), vp(d_best_action or None),
+                                                   vp(d_best_branch or None)))
+
+    def score_rollout(self, actions, branches: int, gamma: float = 1.0) -> dict:
+        """hwy_score_rollout (host arrays): actions [K, E*branches, A] are rolled out from the current state and folded.  Returns
+        ``reward`` [K, E*branches, A], ``terminated`` / ``truncated`` [K, E*branches], ``returns`` [E, branches, A],
+        ``best_branch`` [E, A] and, single agent, ``q`` [E, n_ids] and ``best_action`` [E].  Raises like ``rollout`` for an
+        action id outside the table."""
+        acts = np.ascontiguousarray(np.asarray(actions, np.int32).reshape(-1, self.E, self.A))
+        K, EB, A, B = acts.shape[0], self.E, self.A, int(branches)
+        if B < 1 or EB % B:
+            raise ValueError(f"score_rollout: branches={B} does not divide the engine's {EB} environments")
+        E, ids = EB // B, _abi.num_actions(self.cfg)
+        out = {"reward": np.empty((K, EB, A), np.float64), "terminated": np.empty((K, EB), np.uint8),
+               "truncated": np.empty((K, EB), np.uint8), "returns": np.empty((E, B, A), np.float64),
+               "q": np.empty((E, ids), np.float64) if A == 1 else None, "best_action": np.empty(E, np.int32) if A == 1 else None,
+               "best_branch": np.empty((E, A), np.int32)}
+        self._check_ttc(self._lib.hwy_score_rollout(self._h, K, B, float(gamma), _ptr(acts), *(_ptr(out[k]) for k in (
+            "reward", "terminated", "truncated", "returns", "q", "best_action", "best_branch"))))
+        out["terminated"], out["truncated"] = out["terminated"].astype(bool), out["truncated"].astype(bool)
+        return out
+
     # -- reset --------------------------------------------------------------------------------
     def reset(self, seeds=None, mask=None, ego_spacing=2.0, vehicles_density=1.0, initial_lane_id=-1, base_seed=0):
         """Device-side spawn (counter-based RNG; NOT numpy's stream -- see spawn.py for that)."""

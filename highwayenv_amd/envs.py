@@ -372,7 +372,164 @@ class BatchedHighwayEnv:
             action, q = action[:, 0], (q[:, 0] if q is not None else None)
         return (action, q) if return_q else action
 
+    # ---- fork / score_sequences / plan_lookahead: AbstractEnv.__deepcopy__ + step on the copy (abstract.py:455) ------------------
+    def _lookahead_scope(self, what: str):
+        if self._hcfg.scenario != _abi.SCENARIO_HIGHWAY:
+            raise NotImplementedError(f"{what} is in the MI355X hot-path scope on the highway scenario only")
+        if self._engine is None:
+            raise NotImplementedError("The road and vehicle must be initialized in the environment implementation")
+
+    def fork(self, branches: int = 1, source=None) -> "BatchedHighwayEnv":
+        """``copy.deepcopy(env)`` for every environment at once, on the device: an environment of ``E * branches`` environments
+        with this one's config, auto-reset off, already reset -- environment ``e * branches + b`` is copy ``b`` of environment
+        ``e`` (``hwy_fork_device``: the state never visits the host).  ``source``: int array [E'] of parent indices (repeated,
+        out of order, some omitted); the child then holds ``E' * branches`` environments, copies of ``source[j // branches]``.
+        The child is cached on the parent per (num_envs, branches) and OVERWRITTEN by the next such fork.  An environment that
+        awaits its NextStep re-spawn is forked as it stands: stepping the copy continues the ended episode, which is what
+        stepping the reference after ``done`` gives."""
+        self._lookahead_scope("fork")
+        B = int(branches)
+        if B < 1:
+            raise ValueError("branches must be >= 1")
+        idx = None
+        if source is not None:
+            idx = np.asarray(source)
+            if idx.ndim != 1 or idx.size < 1 or not np.issubdtype(idx.dtype, np.integer):
+                raise ValueError("source must be a non-empty 1-D integer array of parent indices")
+            if ((idx < 0) | (idx >= self.num_envs)).any():
+                raise ValueError(f"source holds an index outside [0, {self.num_envs})")
+            idx = np.repeat(idx.astype(np.int32), B)
+        n = (self.num_envs if idx is None else idx.size // B) * B
+        self._lookahead_fits(n, 0)
+        forks = self.__dict__.setdefault("_forks", {})
+        child = forks.get((n, B))
+        if child is None or child._parent_key != self._engine_key or child._engine is None:
+            if child is not None:
+                child.close()
+            cls = BatchedHighwayEnvFast if self.FAST else BatchedHighwayEnv
+            child = cls(_copy_config(self.config), num_envs=n, device=self.device, spawn_mode=self.spawn_mode, autoreset=False,
+                        stream=self._stream)
+            child._engine_factory = self._engine_factory
+            child._define_spaces()
+            try:
+                child._ensure_engine()
+            except Exception as exc:  # the device has no room for the branches
+                if "memory" in str(exc).lower():
+                    raise ValueError(f"fork: {n} environments need {_abi.fork_bytes(self._hcfg, n, 0)} bytes of device memory, "
+                                     f"which the device does not have") from exc
+                raise
+            child._engine.set_autoreset(False)
+            child._parent_key = self._engine_key
+            forks[(n, B)] = child
+        child._engine.fork_from(self._engine, B, idx)
+        if self._stream is None:  # each engine has a stream of its own: the copy is complete before the parent is written again
+            child._engine.sync()
+        src = np.arange(n) // B if idx is None else idx
+        child._np_randoms = [self._np_randoms[e] for e in src]
+        child.time = self.time[src].copy()
+        child.steps = self.steps
+        return child
+
+    def _lookahead_fits(self, n: int, k_steps: int):
+        need = _abi.fork_bytes(self._hcfg, n, k_steps)
+        limit = getattr(self, "max_fork_bytes", None)
+        if n > 2 ** 31 - 1 or (limit is not None and need > limit):
+            raise ValueError(f"{n} branch environments need {need} bytes of device memory"
+                             + (f" (max_fork_bytes = {limit})" if limit is not None else " and more than 2^31 - 1 environments"))
+
+    def _sequences(self, actions):
+        """``actions`` [B, K(, A)] or [E, B, K(, A)] -> int32 [E, B, K, A]."""
+        E, A = self.num_envs, self._hcfg.num_agents
+        a = np.asarray(actions)
+        if not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("action sequences must be integer ids")
+        if A == 1 and a.ndim in (2, 3):
+            a = a[..., None]
+        elif A == 1 and a.ndim == 4 and a.shape[-1] == 1:
+            pass
+        elif A > 1 and a.ndim in (3, 4) and a.shape[-1] == A:
+            pass
+        else:
+            raise ValueError(f"action sequences must have shape [B, K{', A' if A > 1 else ''}] or [E, B, K{', A' if A > 1 else ''}]; got {a.shape}")
+        if a.ndim == 3:
+            a = np.broadcast_to(a, (E, *a.shape))
+        if a.shape[0] != E or a.shape[1] < 1 or a.shape[2] < 1:
+            raise ValueError(f"action sequences for {E} environments needed (with at least one branch and one step); got {np.shape(actions)}")
+        return a.astype(np.int32)
+
+    def score_sequences(self, actions, gamma: float = 1.0, return_details: bool = False):
+        """Step B candidate action sequences of K steps from the CURRENT state of every environment with the true simulator and
+        return their discounted returns f64 [E, B] ([E, B, A] for several agents): fork -> ``hwy_rollout_device`` ->
+        ``hwy_score_device`` on one stream.  ``actions``: ids [B, K] (the same candidates everywhere) or [E, B, K], with a
+        trailing agent axis for several agents; validated like ``step`` (KeyError / IndexError).  An episode that ends within a
+        sequence is absorbing: its terminal reward counts, nothing after it.  This environment is left exactly as it was.
+        ``return_details``: also a dict with ``reward`` [E, B, K(, A)], ``terminated`` / ``truncated`` [E, B, K],
+        ``best_branch`` [E(, A)] and, single agent, ``q`` [E, n_ids] (the best return per first action, -inf where no
+        sequence starts with it) and ``best_action`` [E]."""
+        self._lookahead_scope("score_sequences")
+        if not np.isfinite(gamma):
+            raise ValueError("gamma must be finite")
+        a = self._sequences(actions)
+        E, B, K, A = a.shape
+        self._lookahead_fits(E * B, K)
+        child = self.fork(B)
+        out = child._engine.score_rollout(np.ascontiguousarray(a.transpose(2, 0, 1, 3)).reshape(K, E * B, A), B, gamma)
+        returns = out["returns"] if A > 1 else out["returns"][:, :, 0]
+        if not return_details:
+            return returns
+        reward = out["reward"].reshape(K, E, B, A).transpose(1, 2, 0, 3)
+        details = {"reward": reward if A > 1 else reward[..., 0],
+                   "terminated": out["terminated"].reshape(K, E, B).transpose(1, 2, 0),
+                   "truncated": out["truncated"].reshape(K, E, B).transpose(1, 2, 0),
+                   "best_branch": out["best_branch"] if A > 1 else out["best_branch"][:, 0]}
+        if A == 1:
+            details["q"], details["best_action"] = out["q"], out["best_action"]
+        return returns, details
+
+    def lookahead_table(self, depth: int, horizon: int | None = None) -> np.ndarray:
+        """The exhaustive depth-``depth`` candidates of ``plan_lookahead``: int32 [n_ids ** depth, horizon]; branch b's first
+        ``depth`` actions are the base-n_ids digits of b, most significant first, steps depth .. horizon - 1 are IDLE."""
+        if self._hcfg.num_agents > 1:
+            raise NotImplementedError("plan_lookahead plans for a single agent (joint-action trees are outside the MI355X hot-path "
+                                      "scope): score_sequences serves several agents")
+        if self._hcfg.ego_control != _abi.EGO_META:
+            raise NotImplementedError("plan_lookahead needs a DiscreteMetaAction ego (a DiscreteAction table has no IDLE) and is "
+                                      "outside the MI355X hot-path scope with DiscreteAction: score_sequences serves it")
+        depth = int(depth)
+        horizon = depth if horizon is None else int(horizon)
+        if depth < 1:
+            raise ValueError("depth must be >= 1")
+        if horizon < depth:
+            raise ValueError(f"horizon ({horizon}) must be >= depth ({depth})")
+        n_ids = _abi.num_actions(self._hcfg)
+        if n_ids ** depth > 2 ** 31 - 1:
+            raise ValueError(f"{n_ids} ** {depth} branches per environment do not fit")
+        key = (depth, horizon, n_ids)
+        cache = self.__dict__.setdefault("_lookahead_tables", {})
+        if key not in cache:
+            b = np.arange(n_ids ** depth)
+            table = np.full((b.size, horizon), 1, np.int32)  # IDLE: id 1 of every meta-action table (action.py:204-222)
+            for j in range(depth):
+                table[:, j] = (b // n_ids ** (depth - 1 - j)) % n_ids
+            cache[key] = table
+        return cache[key]
+
+    def plan_lookahead(self, depth: int, horizon: int | None = None, gamma: float = 1.0, return_q: bool = False):
+        """The best first meta-action int32 [E] of an exhaustive search of depth ``depth`` with the TRUE simulator (every traffic
+        vehicle reacts, changes lanes, crashes), where ``plan_finite_mdp`` plans on the reference's constant-speed TTC grid:
+        all ``n_ids ** depth`` sequences, padded with IDLE to ``horizon`` steps (default: ``depth``), are stepped from the
+        current state and the first action of the best discounted return is returned (the first maximum, numpy's argmax);
+        with ``return_q`` also the best return per first action f64 [E, n_ids].  Single agent with a meta-action ego;
+        ValueError when the ``E * n_ids ** depth`` branch environments do not fit."""
+        self._lookahead_scope("plan_lookahead")
+        table = self.lookahead_table(depth, horizon)
+        self._lookahead_fits(self.num_envs * table.shape[0], table.shape[1])
+        _, details = self.score_sequences(table, gamma=gamma, return_details=True)
+        return (details["best_action"], details["q"]) if return_q else details["best_action"]
+
     def close(self) -> None:
+        for child in self.__dict__.pop("_forks", {}).values():
+            child.close()
         if self._engine is not None:
             self._engine.close()
             self._engine = None

@@ -252,6 +252,96 @@ class HighwayVectorEnv(_Base):
             cur.wait_stream(self._stream)
         return out[:, 0] if A == 1 else out
 
+    # ---- simulator-based planning: fork -> rollout -> score on the engine's stream -----------------------------------------------------
+    def _lookahead_device(self, a, B, K, gamma):
+        """``a``: int32 device tensor [K, E * B, A] of action ids (not validated on this path, like ``step``).  Enqueues the fork
+        of the current state, the K-step rollout of the branches and the fold, ordered on the caller's stream like ``plan``;
+        returns the dict of device tensors the three wrote (cached per shape: valid until the next call of that shape)."""
+        t, env = self._torch, self.env
+        E, A = self.num_envs, env._hcfg.num_agents
+        if self._dev is None:
+            raise RuntimeError("plan_lookahead() / score_sequences() before reset()")
+        env._lookahead_fits(E * B, K)
+        n, ids, dev = E * B, _abi.num_actions(env._hcfg), self._dev["obs"].device
+        key = ("lookahead", B, K)
+        if key not in self._dev:
+            child = env.fork(B)   # (allocates the branch engine on the engine's stream; forks once more below)
+            self._dev[key] = {
+                "child": child, "obs": t.empty((K, n, A, *_abi.obs_shape(env._hcfg)), dtype=t.float32, device=dev),
+                "reward": t.empty((K, n, A), dtype=t.float64, device=dev), "terminated": t.empty((K, n), dtype=t.uint8, device=dev),
+                "truncated": t.empty((K, n), dtype=t.uint8, device=dev), "returns": t.empty((E, B, A), dtype=t.float64, device=dev),
+                "best_branch": t.empty((E, A), dtype=t.int32, device=dev),
+                "q": t.empty((E, ids), dtype=t.float64, device=dev) if A == 1 else None,
+                "best_action": t.empty(E, dtype=t.int32, device=dev) if A == 1 else None}
+        d = self._dev[key]
+        child = d["child"]._engine
+        ptr = lambda x: 0 if x is None else x.data_ptr()  # noqa: E731
+        cur = t.cuda.current_stream()
+        same = cur.cuda_stream == self._stream.cuda_stream
+        if not same:
+            self._stream.wait_stream(cur)      # the actions (and the consumer of the previous scores) come first
+        child.fork_device(env._engine, B)
+        child.rollout_device(K, a.data_ptr(), d["obs"].data_ptr(), d["reward"].data_ptr(), d["terminated"].data_ptr(),
+                             d["truncated"].data_ptr())
+        child.score_device(K, B, gamma, a.data_ptr() if A == 1 else 0, d["reward"].data_ptr(), d["terminated"].data_ptr(),
+                           d["truncated"].data_ptr(), d["returns"].data_ptr(), ptr(d["q"]), ptr(d["best_action"]),
+                           d["best_branch"].data_ptr())
+        if not same:
+            cur.wait_stream(self._stream)
+            a.record_stream(self._stream)
+        return d
+
+    def score_sequences(self, actions, gamma: float = 1.0, return_details: bool = False):
+        """``BatchedHighwayEnv.score_sequences`` for every environment.  ``output="torch"``: ``actions`` may be a device tensor
+        ([B, K(, A)] or [E, B, K(, A)]), the returns [E, B(, A)] (and, with ``return_details``, the per-step rewards and flags,
+        ``q``, ``best_action``, ``best_branch``) are device tensors ordered on the current stream like ``plan()``; nothing visits
+        the host, and action ids are not validated (as in ``step``)."""
+        if self.output != "torch":
+            return self.env.score_sequences(actions, gamma=gamma, return_details=return_details)
+        t, E, A = self._torch, self.num_envs, self.env._hcfg.num_agents
+        self.env._lookahead_scope("score_sequences")
+        a = actions if isinstance(actions, t.Tensor) else t.as_tensor(np.asarray(actions))
+        if A == 1 and a.dim() in (2, 3):
+            a = a.unsqueeze(-1)
+        if a.dim() == 3:
+            a = a.unsqueeze(0).expand(E, *a.shape)
+        if a.dim() != 4 or a.shape[0] != E or a.shape[3] != A:
+            raise ValueError(f"action sequences must have shape [B, K{', A' if A > 1 else ''}] or [E, B, K{', A' if A > 1 else ''}]")
+        B, K = int(a.shape[1]), int(a.shape[2])
+        dev = self._dev["obs"].device if self._dev is not None else None
+        a = a.to(device=dev, dtype=t.int32).permute(2, 0, 1, 3).reshape(K, E * B, A).contiguous()
+        d = self._lookahead_device(a, B, K, float(gamma))
+        returns = d["returns"] if A > 1 else d["returns"][:, :, 0]
+        if not return_details:
+            return returns
+        reward = d["reward"].view(K, E, B, A).permute(1, 2, 0, 3)
+        details = {"reward": reward if A > 1 else reward[..., 0], "terminated": d["terminated"].view(K, E, B).permute(1, 2, 0).bool(),
+                   "truncated": d["truncated"].view(K, E, B).permute(1, 2, 0).bool(),
+                   "best_branch": d["best_branch"] if A > 1 else d["best_branch"][:, 0]}
+        if A == 1:
+            details["q"], details["best_action"] = d["q"], d["best_action"]
+        return returns, details
+
+    def plan_lookahead(self, depth: int, horizon: int | None = None, gamma: float = 1.0, return_q: bool = False):
+        """``BatchedHighwayEnv.plan_lookahead``: the best first meta-action [E] of an exhaustive depth-``depth`` search with the true
+        simulator.  ``output="torch"``: an int32 device tensor (valid until the next call of that shape) ordered on the current
+        stream -- ``env.step(env.plan_lookahead(2))`` never leaves the GPU; the candidate table is built once on the host and
+        uploaded."""
+        if self.output != "torch":
+            return self.env.plan_lookahead(depth, horizon=horizon, gamma=gamma, return_q=return_q)
+        t, E = self._torch, self.num_envs
+        self.env._lookahead_scope("plan_lookahead")
+        table = self.env.lookahead_table(depth, horizon)
+        B, K = table.shape
+        if self._dev is None:
+            raise RuntimeError("plan_lookahead() before reset()")
+        key = ("lookahead_table", B, K)
+        if key not in self._dev:   # [K, E * B, 1]: the same candidates in every environment
+            planes = np.ascontiguousarray(np.broadcast_to(table.T[:, None, :], (K, E, B)).reshape(K, E * B, 1))
+            self._dev[key] = t.from_numpy(planes).to(self._dev["obs"].device)
+        d = self._lookahead_device(self._dev[key], B, K, float(gamma))
+        return (d["best_action"], d["q"]) if return_q else d["best_action"]
+
     # ---- the rest of the interface ----------------------------------------------------------------------------------------------
     @property
     def stream(self):

@@ -538,6 +538,60 @@ int hwy_mdp_plan_device(hwy_engine *eng, const hwy_ttc_params *params, int32_t *
 /* The same into HOST pointers (q and grid may be NULL); synchronises. */
 int hwy_mdp_plan(hwy_engine *eng, const hwy_ttc_params *params, int32_t *action, double *q, float *grid);
 
+/*
+ * Environment fork and scoring of action sequences (additive to ABI v8: hwy_config keeps its layout).  The device form of the
+ * reference's simulator-based planning seam: copy.deepcopy(env) (AbstractEnv.__deepcopy__, envs/common/abstract.py:455) and
+ * env.step on the copy (scripts/highway_planning.ipynb).  HWY_SCENARIO_HIGHWAY only -- every traffic model, ego control, observation
+ * type, agent count and N; a merge or intersection engine returns HWY_ERR_UNSUPPORTED (the intersection draws traffic while it runs
+ * and keeps shadow episodes).  Kernels of their own (csrc/hwy_lookahead.h); no step / reset / observe kernel is touched.
+ *
+ * hwy_fork_device: environment j of `dst` becomes a copy of environment d_src_env[j] of `src` (d_src_env: DEVICE pointer, int32
+ * [dst.num_envs]), or of environment j / branches when d_src_env is NULL.  Copied: everything a later step of `dst` can read -- the
+ * nine f64 planes, the packed words whole (rank hint included), the Linear family's behaviour planes, the stored controls of a
+ * HWY_EGO_DIRECT ego [E][A], `time` and the episode counter; the "ended, awaits its re-spawn" mark of `dst` is cleared (a source
+ * environment that awaits its NextStep re-spawn is forked as it stands: stepping the copy continues the ended episode, which is
+ * what stepping the reference after `done` gives).  Columns >= N of the pitch are copied as they are.
+ * Accepted: dst != src, both on the same device, both highway engines, configs equal in every field that is not num_envs or tune_*,
+ * branches >= 1, and dst.num_envs == src.num_envs * branches when d_src_env is NULL (with d_src_env any dst.num_envs); anything
+ * else is HWY_ERR_INVALID_ARG with a reason in hwy_last_error(dst).  The indices behind d_src_env are NOT validated (hwy_fork
+ * does): an index outside [0, src.num_envs) leaves that destination environment as it was.
+ * The copy is enqueued on dst's stream and does not synchronise (like hwy_step_device); when the two streams differ, dst's stream
+ * first waits on an event recorded on src's stream.  `src` is only read: the caller keeps later WRITES to src (a step on another
+ * stream) behind the copy.
+ */
+int hwy_fork_device(hwy_engine *dst, hwy_engine *src, int32_t branches, const int32_t *d_src_env);
+/* The same with HOST indices (src_env may be NULL), validated: HWY_ERR_INVALID_ARG for one outside [0, src.num_envs); synchronises. */
+int hwy_fork(hwy_engine *dst, hwy_engine *src, int32_t branches, const int32_t *src_env);
+/*
+ * Fold the outputs of a k_steps rollout (hwy_rollout_device, auto-reset off) of an engine of E * branches environments -- environment
+ * e * branches + b is branch b of group e -- into discounted returns and a decision.  Return of branch b, agent a:
+ *     g = 0; d = 1; alive = true
+ *     for k in 0 .. K-1:  if alive: t = d * r[k]; g = g + t
+ *                         alive = alive && !(terminated[k] | truncated[k]);  d = d * gamma
+ * (product and sum round separately; an episode that ends is absorbing: its terminal reward counts, nothing after it does).
+ *   d_first_action int32 [E*branches][A]  block 0 of the rollout's actions; NULL iff d_q and d_best_action are NULL
+ *   d_reward       f64   [K][E*branches][A],  d_terminated / d_truncated u8 [K][E*branches]
+ *   d_return       f64   [E][branches][A]   g                                                          (may be NULL)
+ *   d_q            f64   [E][n_ids]         max of g over the branches of group e whose first action is i, -inf where none starts
+ *                                           with i; n_ids = size of the action table (5, 3 or n_accel * n_steer)   (A == 1; may be NULL)
+ *   d_best_action  int32 [E]                the first maximum of d_q[e] (numpy's argmax)                 (A == 1; may be NULL)
+ *   d_best_branch  int32 [E][A]             the lowest branch holding the maximal g of agent a           (may be NULL)
+ * HWY_ERR_INVALID_ARG: k_steps < 1, branches < 1 or not a divisor of num_envs, a non-finite gamma, a NULL input plane, d_q or
+ * d_best_action with A > 1.  First actions outside the table (not validated here) count for no d_q column.  A NaN reward is outside
+ * the contract.  DEVICE pointers; enqueues on the engine's stream and does not synchronise.
+ */
+int hwy_score_device(hwy_engine *eng, int32_t k_steps, int32_t branches, double gamma, const int32_t *d_first_action,
+                     const double *d_reward, const uint8_t *d_terminated, const uint8_t *d_truncated, double *d_return,
+                     double *d_q, int32_t *d_best_action, int32_t *d_best_branch);
+/*
+ * hwy_rollout_device + hwy_score_device through HOST pointers: actions int32 [K][E*branches][A] are validated like hwy_rollout
+ * (HWY_ERR_ACTION), uploaded, rolled out and folded; every output may be NULL (reward [K][E*branches][A], terminated / truncated
+ * [K][E*branches], then the outputs of hwy_score_device; q and best_action with A == 1 only).  Synchronises.
+ */
+int hwy_score_rollout(hwy_engine *eng, int32_t k_steps, int32_t branches, double gamma, const int32_t *actions,
+                      double *reward, uint8_t *terminated, uint8_t *truncated, double *ret, double *q,
+                      int32_t *best_action, int32_t *best_branch);
+
 int hwy_sync(hwy_engine *eng); /* hipStreamSynchronize on the engine stream */
 
 /*

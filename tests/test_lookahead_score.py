@@ -1,0 +1,164 @@
+"""The scoring kernel (csrc/hwy_lookahead.h: hwy_score_kernel) on crafted rollout outputs, held bit for bit to the numpy restatement
+of the recurrence (tests/lookahead_util.py): E = 3 groups; B = 1, 25, 64, 65, 125 branches (the passes of 64 lanes); K = 1 and 4;
+one and two agents; gamma = 1 and 0.9; rewards quantised so that exact ties between branches and between first actions occur (the
+lowest index must win); episodes that end at every step, some at once; groups in which no branch starts with some action (-inf in
+q).  On the CPU emulation also under the emulator's other fiber orders (lanes, workgroups): identical outputs, no schedule error --
+the fork kernel too.  Marked ``gpu``: the same arrays through hwy_score_device on device buffers."""
+import numpy as np
+import pytest
+
+from highwayenv_amd import _abi
+from tests import lookahead_util as lu
+
+E = 3
+SHAPES = [(B, K, A, gamma) for B in (1, 25, 64, 65, 125) for K, A, gamma in ((1, 1, 1.0), (4, 1, 0.9), (4, 2, 0.9), (4, 1, 1.0))]
+MA = {"controlled_vehicles": 2, "action": {"type": "MultiAgentAction", "action_config": {"type": "DiscreteMetaAction"}},
+      "observation": {"type": "MultiAgentObservation", "observation_config": {"type": "Kinematics"}}}
+LANE_BLOCK_SCHEDULES = [dict(lane="desc"), dict(lane="seeded", seed=101), dict(lane="seeded", seed=102), dict(block="desc"),
+                        dict(block="seeded", seed=201), dict(lane="seeded", block="seeded", seed=301)]
+
+
+def crafted(B, K, A, seed=0):
+    """reward [K, E*B, A] on a grid of 1/8 (ties), flags [K, E*B] that end one episode in five per step, first actions [E*B, A]
+    drawn from {0, 1, 3}: ids 2 and 4 start no branch."""
+    rng = np.random.default_rng(1000 * B + 10 * K + A + seed)
+    n = E * B
+    reward = rng.integers(-8, 9, size=(K, n, A)) / 8.0
+    term = (rng.random((K, n)) < 0.2).astype(np.uint8)
+    trunc = (rng.random((K, n)) < 0.1).astype(np.uint8)
+    first = rng.choice([0, 1, 3], size=(n, A)).astype(np.int32)
+    if B >= 2:   # two branches of every group hold the largest possible return, under different first actions: a tie at the top
+        for b, action in ((B // 3, 3), (B - 1, 1)):
+            rows = np.arange(E) * B + b
+            reward[:, rows], term[:, rows], trunc[:, rows], first[rows] = 1.0, 0, 0, action
+    return reward, term, trunc, first
+
+
+def config(B, A):
+    return _abi.make_config(lu.highway_config(8, **(MA if A > 1 else {})), E * B, fast=True)
+
+
+def run_emu(cfg, B, K, A, gamma, arrays, schedule=None):
+    from tests.emu import emu, emu_lookahead
+    reward, term, trunc, first = arrays
+    sched = None
+    if schedule is not None:
+        sched = emu.Scheduled()
+        sched.set_schedule(**schedule)
+    want = ("returns", "q", "best_action", "best_branch") if A == 1 else ("returns", "best_branch")
+    out = emu_lookahead.score(cfg, K, B, gamma, first if A == 1 else None, reward, term, trunc, want=want, sched=sched)
+    if sched is not None:
+        assert sched.schedule_errors() == 0, sched.schedule_error_text()
+    return {k: v for k, v in out.items() if v is not None}
+
+
+def run_hip(cfg, B, K, A, gamma, arrays):
+    import torch
+
+    from highwayenv_amd.engine import Engine
+    reward, term, trunc, first = arrays
+    eng = Engine(cfg)
+    dev = torch.device("cuda", 0)
+    d = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (first, reward, term, trunc)]
+    ids = _abi.num_actions(cfg)
+    out = {"returns": torch.full((E, B, A), float("nan"), dtype=torch.float64, device=dev),
+           "best_branch": torch.full((E, A), -1, dtype=torch.int32, device=dev)}
+    if A == 1:
+        out["q"] = torch.full((E, ids), float("nan"), dtype=torch.float64, device=dev)
+        out["best_action"] = torch.full((E,), -1, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    eng.score_device(K, B, gamma, d[0].data_ptr() if A == 1 else 0, d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(),
+                     out["returns"].data_ptr(), out["q"].data_ptr() if A == 1 else 0, out["best_action"].data_ptr() if A == 1 else 0,
+                     out["best_branch"].data_ptr())
+    eng.sync()
+    res = {k: v.cpu().numpy() for k, v in out.items()}
+    eng.close()
+    return res
+
+
+@pytest.mark.parametrize("B,K,A,gamma", SHAPES, ids=[f"B{b}-K{k}-A{a}-g{g}" for b, k, a, g in SHAPES])
+@pytest.mark.parametrize("backend", lu.BACKENDS)
+def test_scores_equal_the_restatement_bit_for_bit(backend, B, K, A, gamma):
+    cfg, arrays = config(B, A), crafted(B, K, A)
+    reward, term, trunc, first = arrays
+    got = run_emu(cfg, B, K, A, gamma, arrays) if backend == "emu" else run_hip(cfg, B, K, A, gamma, arrays)
+    want = lu.restate_scores(reward, term, trunc, gamma, B, first[:, 0] if A == 1 else None, 5)
+    assert set(got) == set(want)
+    for k, v in want.items():
+        lu.assert_bits(got[k], v, k)
+    if A == 1:
+        assert np.isneginf(got["q"][:, [2, 4]]).all() and (B < 3 or np.isfinite(got["q"][:, [0, 1, 3]]).any())
+    if B >= 2:   # the tie at the top: the lowest branch and the lowest first action win
+        ret = want["returns"]
+        assert all((ret[e, :, a] == ret[e, :, a].max()).sum() > 1 for e in range(E) for a in range(A))
+        assert (got["best_branch"] <= B // 3).all() and (A > 1 or (got["best_action"] <= 1).all())
+
+
+@pytest.mark.parametrize("schedule", LANE_BLOCK_SCHEDULES, ids=lambda s: "-".join(f"{k}={v}" for k, v in s.items()))
+@pytest.mark.parametrize("B,K,A", [(65, 4, 1), (125, 4, 2)])
+def test_score_kernel_does_not_depend_on_the_schedule(schedule, B, K, A):
+    cfg, arrays = config(B, A), crafted(B, K, A, seed=5)
+    base = run_emu(cfg, B, K, A, 0.9, arrays)
+    other = run_emu(cfg, B, K, A, 0.9, arrays, schedule)
+    for k in base:
+        lu.assert_bits(other[k], base[k], k)
+
+
+@pytest.mark.parametrize("schedule", LANE_BLOCK_SCHEDULES + [dict(wave="desc"), dict(wave="seeded", seed=401)],
+                         ids=lambda s: "-".join(f"{k}={v}" for k, v in s.items()))
+def test_fork_kernel_does_not_depend_on_the_schedule(schedule):
+    """Four wavefronts per workgroup, N = 130 (more columns than half the workgroup) with Linear traffic's extra planes."""
+    conf = lu.highway_config(130, other_vehicles_type="highway_env.vehicle.behavior.LinearVehicle")
+    cfg = _abi.make_config(conf, E, fast=True)
+    parent = lu.make_engine("emu", cfg)
+    parent.reset(seeds=np.arange(E, dtype=np.uint64))
+    source = np.array([1, 1, 2, 0, 2], np.int32)
+    children = []
+    for sch in (None, schedule):
+        child = lu.make_engine("emu", lu.with_envs(cfg, len(source)))
+        if sch:
+            child.set_schedule(**sch)
+        child.fork_from(parent, 1, source)
+        assert child.schedule_errors() == 0, child.schedule_error_text()
+        children.append(child)
+    lu.assert_states_equal(children[0].get_state(), children[1].get_state(), "fork under another schedule")
+    lu.assert_bits(children[0].get_behavior(), children[1].get_behavior(), "behaviour")
+    lu.assert_states_equal(children[1].get_state(), lu.repeat_state(parent.get_state(), source), "fork")
+
+
+def test_an_episode_that_ends_is_absorbing():
+    """By hand: K = 4, gamma = 0.5.  Branch 0 never ends: 1 + 0.5 + 0.25 + 0.125.  Branch 1 terminates at step 1: its reward counts,
+    steps 2 and 3 do not.  Branch 2 is truncated at step 0.  Branch 3 ends at the last step: everything counts."""
+    B, K = 4, 4
+    cfg = _abi.make_config(lu.highway_config(8), B, fast=True)
+    reward = np.ones((K, B, 1))
+    term, trunc = np.zeros((K, B), np.uint8), np.zeros((K, B), np.uint8)
+    term[1, 1] = trunc[0, 2] = term[3, 3] = 1
+    first = np.array([[0], [1], [1], [3]], np.int32)
+    out = run_emu(cfg, B, K, 1, 0.5, (reward, term, trunc, first))
+    np.testing.assert_array_equal(out["returns"][0, :, 0], [1.875, 1.5, 1.0, 1.875])
+    np.testing.assert_array_equal(out["q"][0], [1.875, 1.5, -np.inf, 1.875, -np.inf])
+    assert out["best_action"][0] == 0 and out["best_branch"][0, 0] == 0   # ties: the lowest index
+
+
+def test_fused_and_unfused_returns_differ_here():
+    """Rewards and a discount whose product is inexact: g + d * r rounded once (a fused multiply-add) differs from the two roundings
+    of numpy's `t = d * r; g = g + t` in most branches.  The kernel must give the two roundings, bit for bit."""
+    B, K = 64, 4
+    cfg = _abi.make_config(lu.highway_config(8), B, fast=True)
+    rng = np.random.default_rng(77)
+    reward = rng.random((K, B, 1)) / 3.0
+    term, trunc = np.zeros((K, B), np.uint8), np.zeros((K, B), np.uint8)
+    first = np.zeros((B, 1), np.int32)
+    out = run_emu(cfg, B, K, 1, 0.9, (reward, term, trunc, first))
+    want = lu.restate_returns(reward, term, trunc, 0.9).reshape(1, B, 1)
+    import math
+    fused = np.zeros(B)
+    for b in range(B):
+        g, d = 0.0, 1.0
+        for k in range(K):
+            g = math.fma(d, float(reward[k, b, 0]), g) if hasattr(math, "fma") else float(np.longdouble(d) * np.longdouble(reward[k, b, 0]) + np.longdouble(g))
+            d = d * 0.9
+        fused[b] = g
+    assert (fused != want[0, :, 0]).any(), "the inputs do not tell a fused return from an unfused one"
+    lu.assert_bits(out["returns"], want, "returns")
