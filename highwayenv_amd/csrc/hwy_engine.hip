@@ -71,6 +71,10 @@ struct hwy_engine {
   // the source engine's, both created on first use
   int32_t *d_fork_src = nullptr;
   hipEvent_t fork_event = nullptr;
+  // hwy_opd_plan_device (this engine as `tree`): the trees' bookkeeping, the index arrays of the forks, the work engine's action
+  // plane and the host form's outputs, in one block allocated on first use
+  char *d_opd = nullptr;
+  size_t opd_bytes = 0;
   // pinned host staging
   void *h_pinned = nullptr;
   size_t h_pinned_bytes = 0;
@@ -522,7 +526,7 @@ extern "C" int hwy_destroy(hwy_engine *eng) {
   void *ptrs[] = {eng->d_f64, eng->d_packed, eng->d_time, eng->d_done, eng->d_episode, eng->d_actions, eng->d_out, eng->d_roll,
                   eng->d_mask, eng->d_seeds, eng->d_grid_ws, eng->d_route, eng->d_road_steps, eng->d_gnet,
                   eng->d_shadow_f64, eng->d_shadow_packed, eng->d_shadow_route, eng->d_shadow_meta, eng->d_counters, eng->d_block_env,
-                  eng->d_behavior, eng->d_controls, eng->d_ttc_grid, eng->d_plan_action, eng->d_plan_q, eng->d_fork_src};
+                  eng->d_behavior, eng->d_controls, eng->d_ttc_grid, eng->d_plan_action, eng->d_plan_q, eng->d_fork_src, eng->d_opd};
   for (void *q : ptrs) if (q) (void)hipFree(q);
   if (eng->fork_event) (void)hipEventDestroy(eng->fork_event);
   if (eng->h_pinned) (void)hipHostFree(eng->h_pinned);
@@ -1279,6 +1283,120 @@ extern "C" int hwy_score_rollout(hwy_engine *eng, int32_t k_steps, int32_t branc
   if (best_action) HWY_HIP(eng, hipMemcpyAsync(best_action, d + o_ba, E * 4, hipMemcpyDeviceToHost, eng->stream));
   if (best_branch) HWY_HIP(eng, hipMemcpyAsync(best_branch, d + o_bb, E * eng->cfg.num_agents * 4, hipMemcpyDeviceToHost, eng->stream));
   HWY_HIP(eng, hipStreamSynchronize(eng->stream));
+  return HWY_OK;
+}
+
+// ---- optimistic planning, one tree per environment (hwy_opd.h) -------------------------------------------------------------------------
+// `waiter`'s stream continues behind what `signaler`'s stream holds so far
+static int stream_after(hwy_engine *waiter, hwy_engine *signaler) {
+  if (waiter->stream == signaler->stream) return HWY_OK;
+  if (!waiter->fork_event) HWY_HIP(waiter, hipEventCreateWithFlags(&waiter->fork_event, hipEventDisableTiming));
+  HWY_HIP(waiter, hipEventRecord(waiter->fork_event, signaler->stream));
+  HWY_HIP(waiter, hipStreamWaitEvent(waiter->stream, waiter->fork_event, 0));
+  return HWY_OK;
+}
+
+static int opd_check(hwy_engine *src, hwy_engine *tree, hwy_engine *work, const hwy_opd_params *params, bool has_action, const char *who) {
+  if (!src) return HWY_ERR_INVALID_ARG;
+  if (!tree || !work) return fail(src, HWY_ERR_INVALID_ARG, std::string(who) + ": tree / work is NULL");
+  if (src == tree || src == work || tree == work) return fail(src, HWY_ERR_INVALID_ARG, std::string(who) + ": src, tree and work must be three engines");
+  const char *why = "";
+  if (const int rc = hwy::opd_validate(src->cfg, tree->cfg, work->cfg, params, has_action, &why)) return fail(src, rc, std::string(who) + ": " + why);
+  if (tree->autoreset || work->autoreset) return fail(src, HWY_ERR_INVALID_ARG, std::string(who) + ": tree and work must run with auto-reset off");
+  if (tree->device != src->device || work->device != src->device) return fail(src, HWY_ERR_INVALID_ARG, std::string(who) + ": the three engines are on different devices");
+  return HWY_OK;
+}
+
+// a failure of a call on `tree` / `work` is reported on `src`, the engine the caller asks
+static int opd_forward(hwy_engine *src, hwy_engine *other, int rc) {
+  if (rc != HWY_OK && other != src) src->err = other->err;
+  return rc;
+}
+
+// the block of `tree` that holds the planner's arrays: ret | disc | upper0 [E][M] f64, expanded_node [E][X], gather_src [E n],
+// scatter_src | root_src [E M], actions [E n], done [E][M] u8, then the host form's outputs: action [E], value | upper [E] f64,
+// sequence [E][X], expanded [E]
+struct OpdLayout {
+  size_t ret, disc, up0, node, gather, scatter, root, act, done, o_action, o_value, o_upper, o_sequence, o_expanded, total;
+};
+static OpdLayout opd_layout(size_t E, size_t n, size_t M, size_t X) {
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  OpdLayout l;
+  l.ret = 0; l.disc = l.ret + up(E * M * 8); l.up0 = l.disc + up(E * M * 8); l.node = l.up0 + up(E * M * 8);
+  l.gather = l.node + up(E * X * 4); l.scatter = l.gather + up(E * n * 4); l.root = l.scatter + up(E * M * 4);
+  l.act = l.root + up(E * M * 4); l.done = l.act + up(E * n * 4); l.o_action = l.done + up(E * M);
+  l.o_value = l.o_action + up(E * 4); l.o_upper = l.o_value + up(E * 8); l.o_sequence = l.o_upper + up(E * 8);
+  l.o_expanded = l.o_sequence + up(E * X * 4); l.total = l.o_expanded + up(E * 4);
+  return l;
+}
+static int opd_block(hwy_engine *src, hwy_engine *tree, hwy_engine *work, const OpdLayout &l) {
+  if (l.total <= tree->opd_bytes) return HWY_OK;
+  HWY_HIP(src, hipStreamSynchronize(work->stream));  // (a smaller block may still be in use)
+  if (tree->d_opd) (void)hipFree(tree->d_opd);
+  tree->d_opd = nullptr;
+  tree->opd_bytes = 0;
+  HWY_HIP(src, hipMalloc((void **)&tree->d_opd, l.total));
+  tree->opd_bytes = l.total;
+  return HWY_OK;
+}
+
+extern "C" int hwy_opd_plan_device(hwy_engine *src, hwy_engine *tree, hwy_engine *work, const hwy_opd_params *params, int32_t *d_action,
+                                   double *d_value, double *d_upper, int32_t *d_sequence, int32_t *d_expanded) {
+  if (int rc = opd_check(src, tree, work, params, d_action != nullptr, "hwy_opd_plan_device")) return rc;
+  HWY_HIP(src, hipSetDevice(src->device));
+  const size_t E = src->cfg.num_envs, n = params->n_ids, M = params->nodes, X = params->budget / params->n_ids;
+  const OpdLayout l = opd_layout(E, n, M, X);
+  if (int rc = opd_block(src, tree, work, l)) return rc;
+  char *d = tree->d_opd;
+  hwy::OpdParams p;
+  memset(&p, 0, sizeof p);
+  p.ret = (double *)(d + l.ret); p.disc = (double *)(d + l.disc); p.upper0 = (double *)(d + l.up0); p.done = (uint8_t *)(d + l.done);
+  p.expanded_node = (int32_t *)(d + l.node);
+  p.reward = work->d_reward; p.terminated = work->d_term; p.truncated = work->d_trunc;
+  p.gather_src = (int32_t *)(d + l.gather); p.scatter_src = (int32_t *)(d + l.scatter); p.root_src = (int32_t *)(d + l.root);
+  p.actions = (int32_t *)(d + l.act);
+  p.action = d_action; p.value = d_value; p.upper = d_upper; p.sequence = d_sequence; p.expanded = d_expanded;
+  p.gamma = params->gamma; p.bound = params->bound;
+  p.X = (int32_t)X; p.n = (int32_t)n; p.M = (int32_t)M; p.E = (int32_t)E;
+  // Everything of the planner's own runs on work's stream.  Before a tree kernel rewrites the scatter's indices, the scatter that
+  // reads them on tree's stream has to be over; hwy_fork_device orders the rest (destination behind source).
+  for (size_t x = 0; x <= X; ++x) {
+    if (int rc = stream_after(work, tree)) return opd_forward(src, work, rc);
+    p.x = (int32_t)x;
+    HWY_HIP(src, hwy::launch_opd(p, work->stream));
+    if (x == X) break;
+    if (x == 0) {  // the root's state into tree slot e * M, and the parent's into all n work environments of e
+      if (int rc = stream_after(tree, work)) return opd_forward(src, tree, rc);
+      if (int rc = hwy_fork_device(tree, src, 1, p.root_src)) return opd_forward(src, tree, rc);
+      if (int rc = hwy_fork_device(work, src, (int32_t)n, nullptr)) return opd_forward(src, work, rc);
+    } else {
+      if (int rc = hwy_fork_device(work, tree, 1, p.gather_src)) return opd_forward(src, work, rc);
+    }
+    if (int rc = hwy_step_device(work, p.actions, work->d_obs, work->d_reward, work->d_term, work->d_trunc, nullptr, nullptr))
+      return opd_forward(src, work, rc);
+    if (int rc = hwy_fork_device(tree, work, 1, p.scatter_src)) return opd_forward(src, tree, rc);
+  }
+  return HWY_OK;
+}
+
+extern "C" int hwy_opd_plan(hwy_engine *src, hwy_engine *tree, hwy_engine *work, const hwy_opd_params *params, int32_t *action, double *value,
+                            double *upper, int32_t *sequence, int32_t *expanded) {
+  if (int rc = opd_check(src, tree, work, params, action != nullptr, "hwy_opd_plan")) return rc;
+  HWY_HIP(src, hipSetDevice(src->device));
+  const size_t E = src->cfg.num_envs, X = params->budget / params->n_ids;
+  const OpdLayout l = opd_layout(E, params->n_ids, params->nodes, X);
+  if (int rc = opd_block(src, tree, work, l)) return rc;
+  char *d = tree->d_opd;
+  if (int rc = hwy_opd_plan_device(src, tree, work, params, (int32_t *)(d + l.o_action), (double *)(d + l.o_value), (double *)(d + l.o_upper),
+                                   (int32_t *)(d + l.o_sequence), (int32_t *)(d + l.o_expanded)))
+    return rc;
+  HWY_HIP(src, hipMemcpyAsync(action, d + l.o_action, E * 4, hipMemcpyDeviceToHost, work->stream));
+  if (value) HWY_HIP(src, hipMemcpyAsync(value, d + l.o_value, E * 8, hipMemcpyDeviceToHost, work->stream));
+  if (upper) HWY_HIP(src, hipMemcpyAsync(upper, d + l.o_upper, E * 8, hipMemcpyDeviceToHost, work->stream));
+  if (sequence) HWY_HIP(src, hipMemcpyAsync(sequence, d + l.o_sequence, E * X * 4, hipMemcpyDeviceToHost, work->stream));
+  if (expanded) HWY_HIP(src, hipMemcpyAsync(expanded, d + l.o_expanded, E * 4, hipMemcpyDeviceToHost, work->stream));
+  HWY_HIP(src, hipStreamSynchronize(work->stream));
+  if (tree->stream != work->stream) HWY_HIP(src, hipStreamSynchronize(tree->stream));  // (the last scatter)
   return HWY_OK;
 }
 

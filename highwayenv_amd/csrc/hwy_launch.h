@@ -12,6 +12,7 @@
 #include "hwy_lidar.h"
 #include "hwy_ttc.h"
 #include "hwy_lookahead.h"
+#include "hwy_opd.h"
 
 namespace hwy {
 // The HIP backend of the selection layer (hwy_launch_family.h, hwy_launch_rules.h), for the kernel translation units.
@@ -82,5 +83,7 @@ hipError_t launch_ttc(const TtcParams &tp, bool plan, int rows, hipStream_t stre
 // rollout's outputs into returns, per-action maxima and the best first action / branch (sp.groups wavefronts)
 hipError_t launch_fork(const ForkParams &fp, hipStream_t stream);
 hipError_t launch_score(const ScoreParams &sp, hipStream_t stream);
+// One step of the optimistic planner's tree (hwy_opd.h: ingest, backup, selection or the plan; op.E wavefronts)
+hipError_t launch_opd(const OpdParams &op, hipStream_t stream);
 hipError_t launch_math_probe(int op, const double *in, double *out, long long n, hipStream_t stream);
 }  // namespace hwy

@@ -247,6 +247,25 @@ class Engine:
         out["terminated"], out["truncated"] = out["terminated"].astype(bool), out["truncated"].astype(bool)
         return out
 
+    # -- optimistic planning, one tree per environment (csrc/hwy_opd.h) -----------------------------
+    def opd_plan(self, tree: "Engine", work: "Engine", params: _abi.HwyOpdParams) -> dict:
+        """hwy_opd_plan (host arrays): ``action`` int32 [E], ``value`` / ``upper`` f64 [E], ``sequence`` int32 [E, X],
+        ``expanded`` int32 [E].  ``tree`` / ``work``: engines of E * nodes and E * n_ids environments, auto-reset off."""
+        E, X = self.E, params.budget // max(params.n_ids, 1)
+        out = {"action": np.empty(E, np.int32), "value": np.empty(E, np.float64), "upper": np.empty(E, np.float64),
+               "sequence": np.empty((E, X), np.int32), "expanded": np.empty(E, np.int32)}
+        self._check_ttc(self._lib.hwy_opd_plan(self._h, tree._h, work._h, C.byref(params), *(_ptr(out[k]) for k in (
+            "action", "value", "upper", "sequence", "expanded"))))
+        return out
+
+    def opd_plan_device(self, tree: "Engine", work: "Engine", params: _abi.HwyOpdParams, d_action: int, d_value: int = 0,
+                        d_upper: int = 0, d_sequence: int = 0, d_expanded: int = 0):
+        """Enqueue hwy_opd_plan_device on raw device pointers; does not synchronise."""
+        vp = C.c_void_p
+        self._check_ttc(self._lib.hwy_opd_plan_device(self._h, tree._h, work._h, C.byref(params), vp(d_action or None),
+                                                      vp(d_value or None), vp(d_upper or None), vp(d_sequence or None),
+                                                      vp(d_expanded or None)))
+
     # -- reset --------------------------------------------------------------------------------
     def reset(self, seeds=None, mask=None, ego_spacing=2.0, vehicles_density=1.0, initial_lane_id=-1, base_seed=0):
         """Device-side spawn (counter-based RNG; NOT numpy's stream -- see spawn.py for that)."""

@@ -401,8 +401,20 @@ class BatchedHighwayEnv:
             idx = np.repeat(idx.astype(np.int32), B)
         n = (self.num_envs if idx is None else idx.size // B) * B
         self._lookahead_fits(n, 0)
+        child = self._fork_child((n, B), n, "fork")
+        child._engine.fork_from(self._engine, B, idx)
+        if self._stream is None:  # each engine has a stream of its own: the copy is complete before the parent is written again
+            child._engine.sync()
+        src = np.arange(n) // B if idx is None else idx
+        child._np_randoms = [self._np_randoms[e] for e in src]
+        child.time = self.time[src].copy()
+        child.steps = self.steps
+        return child
+
+    def _fork_child(self, key, n: int, what: str) -> "BatchedHighwayEnv":
+        """The cached child environment of ``n`` environments under ``key``: this one's config, auto-reset off, its engine built."""
         forks = self.__dict__.setdefault("_forks", {})
-        child = forks.get((n, B))
+        child = forks.get(key)
         if child is None or child._parent_key != self._engine_key or child._engine is None:
             if child is not None:
                 child.close()
@@ -415,19 +427,12 @@ class BatchedHighwayEnv:
                 child._ensure_engine()
             except Exception as exc:  # the device has no room for the branches
                 if "memory" in str(exc).lower():
-                    raise ValueError(f"fork: {n} environments need {_abi.fork_bytes(self._hcfg, n, 0)} bytes of device memory, "
+                    raise ValueError(f"{what}: {n} environments need {_abi.fork_bytes(self._hcfg, n, 0)} bytes of device memory, "
                                      f"which the device does not have") from exc
                 raise
             child._engine.set_autoreset(False)
             child._parent_key = self._engine_key
-            forks[(n, B)] = child
-        child._engine.fork_from(self._engine, B, idx)
-        if self._stream is None:  # each engine has a stream of its own: the copy is complete before the parent is written again
-            child._engine.sync()
-        src = np.arange(n) // B if idx is None else idx
-        child._np_randoms = [self._np_randoms[e] for e in src]
-        child.time = self.time[src].copy()
-        child.steps = self.steps
+            forks[key] = child
         return child
 
     def _lookahead_fits(self, n: int, k_steps: int):
@@ -526,6 +531,38 @@ class BatchedHighwayEnv:
         self._lookahead_fits(self.num_envs * table.shape[0], table.shape[1])
         _, details = self.score_sequences(table, gamma=gamma, return_details=True)
         return (details["best_action"], details["q"]) if return_q else details["best_action"]
+
+    # ---- plan_opd: the budgeted tree search of scripts/highway_planning.ipynb (OPD, csrc/hwy_opd.h) ------------------------------
+    def _opd_setup(self, budget, gamma):
+        """(params, tree, work) of ``plan_opd``: the checks, then the two cached child environments (E * nodes environments that
+        hold every node's state, E * n_ids that step the children), auto-reset off."""
+        self._lookahead_scope("plan_opd")
+        if self._hcfg.num_agents > 1:
+            raise NotImplementedError("plan_opd plans for a single agent (joint-action trees are outside the MI355X hot-path scope)")
+        params = _abi.opd_params(self._hcfg, budget, gamma)
+        E = self.num_envs
+        need, limit = _abi.opd_bytes(self._hcfg, E, params), getattr(self, "max_fork_bytes", None)
+        if E * params.nodes > 2 ** 31 - 1 or (limit is not None and need > limit):
+            raise ValueError(f"plan_opd: {E} trees of {params.nodes} nodes need {need} bytes of device memory"
+                             + (f" (max_fork_bytes = {limit})" if limit is not None else " and more than 2^31 - 1 environments"))
+        tree = self._fork_child(("opd", E * params.nodes), E * params.nodes, "plan_opd")
+        work = self._fork_child(("opd", E * params.n_ids), E * params.n_ids, "plan_opd")
+        return params, tree, work
+
+    def plan_opd(self, budget: int = 50, gamma: float = 0.7, return_details: bool = False):
+        """The first action int32 [E] of an optimistic plan (OPD, Hren & Munos 2008) of every environment: what the reference's
+        ``DeterministicPlannerAgent`` does with ``copy.deepcopy(env)`` + ``env.step`` in scripts/highway_planning.ipynb
+        (``budget = 50``, ``gamma = 0.7``), restated in DESIGN.md -- not bit parity with ``rl_agents``.  One tree of at most
+        ``1 + budget`` nodes per environment, grown where the optimistic bound is highest by ``budget // n_ids`` expansions with
+        the TRUE simulator, entirely on the device (``hwy_opd_plan``).  Single agent, either action type, ``normalize_reward``
+        on.  This environment is left exactly as it was.  ``return_details``: also a dict with ``value`` / ``upper`` f64 [E] (the
+        bounds on the best discounted return from here), ``sequence`` int32 [E, X] (the plan, padded with -1) and ``expanded``
+        int32 [E] (expansions made: fewer than X where the tree was solved)."""
+        params, tree, work = self._opd_setup(budget, gamma)
+        out = self._engine.opd_plan(tree._engine, work._engine, params)
+        if not return_details:
+            return out["action"]
+        return out["action"], {k: out[k] for k in ("value", "upper", "sequence", "expanded")}
 
     def close(self) -> None:
         for child in self.__dict__.pop("_forks", {}).values():

@@ -342,6 +342,36 @@ class HighwayVectorEnv(_Base):
         d = self._lookahead_device(self._dev[key], B, K, float(gamma))
         return (d["best_action"], d["q"]) if return_q else d["best_action"]
 
+    def plan_opd(self, budget: int = 50, gamma: float = 0.7, return_details: bool = False):
+        """``BatchedHighwayEnv.plan_opd``: the first action [E] of an optimistic plan (OPD) of every environment, grown by
+        ``budget // n_ids`` expansions with the true simulator.  ``output="torch"``: an int32 device tensor (and, with
+        ``return_details``, device tensors ``value``, ``upper``, ``sequence``, ``expanded``; all valid until the next call of that
+        shape), ordered on the current stream like ``plan()`` -- the whole loop is enqueued by one ``hwy_opd_plan_device`` call
+        and ``env.step(env.plan_opd())`` never leaves the GPU."""
+        if self.output != "torch":
+            return self.env.plan_opd(budget, gamma, return_details=return_details)
+        t, E, env = self._torch, self.num_envs, self.env
+        params, tree, work = env._opd_setup(budget, gamma)
+        if self._dev is None:
+            raise RuntimeError("plan_opd() before reset()")
+        X, dev = params.budget // params.n_ids, self._dev["obs"].device
+        key = ("opd", X)
+        if key not in self._dev:
+            self._dev[key] = {"action": t.empty(E, dtype=t.int32, device=dev), "value": t.empty(E, dtype=t.float64, device=dev),
+                              "upper": t.empty(E, dtype=t.float64, device=dev), "sequence": t.empty((E, X), dtype=t.int32, device=dev),
+                              "expanded": t.empty(E, dtype=t.int32, device=dev)}
+        d = self._dev[key]
+        cur = t.cuda.current_stream()
+        same = cur.cuda_stream == self._stream.cuda_stream
+        if not same:
+            self._stream.wait_stream(cur)      # the consumer of the previous plan comes first
+        env._engine.opd_plan_device(tree._engine, work._engine, params, *(d[k].data_ptr() for k in ("action", "value", "upper", "sequence", "expanded")))
+        if not same:
+            cur.wait_stream(self._stream)
+        if not return_details:
+            return d["action"]
+        return d["action"], {k: d[k] for k in ("value", "upper", "sequence", "expanded")}
+
     # ---- the rest of the interface ----------------------------------------------------------------------------------------------
     @property
     def stream(self):

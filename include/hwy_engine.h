@@ -592,6 +592,48 @@ int hwy_score_rollout(hwy_engine *eng, int32_t k_steps, int32_t branches, double
                       double *reward, uint8_t *terminated, uint8_t *truncated, double *ret, double *q,
                       int32_t *best_action, int32_t *best_branch);
 
+/*
+ * Optimistic planning of deterministic systems (OPD, Hren & Munos 2008), one tree per environment (additive to ABI v8): the budgeted
+ * tree search that scripts/highway_planning.ipynb runs on copy.deepcopy(env) + env.step, entirely on the device.  Kernel of its own
+ * (csrc/hwy_opd.h); the simulation is hwy_step_device, the state moves by hwy_fork_device.  HWY_SCENARIO_HIGHWAY, a single agent,
+ * either ego control (3, 5 or n_accel * n_steer action ids), every traffic model and observation type.
+ *   n = n_ids; X = budget / n expansions; nodes = M = 1 + X * n.  Node 0 is the root (the current state of `src`); expansion x creates
+ *   node 1 + x * n + a for action a.
+ *   root:   lower = 0, disc = 1, upper = bound, not done
+ *   child of p by a: the state of p stepped once with a (auto-reset off), r its reward:
+ *           t = disc_p * r;  lower = lower_p + t;  disc = disc_p * gamma;  done = terminated | truncated;
+ *           upper = done ? lower : lower + disc * bound     (every product and sum rounds on its own: lower is the return
+ *           hwy_score_device gives the node's action sequence, bit for bit)
+ *   backup after each expansion: value lower / upper of an expanded node = the maximum over its children
+ *   selection: the leaf of the largest value upper, ties to the lowest node index; when that leaf is done the tree is solved: this and
+ *           every later expansion is void (nothing is created)
+ *   bound = 1 / (1 - gamma), evaluated by the caller in f64.
+ * `tree` and `work` are engines of src.num_envs * nodes and src.num_envs * n_ids environments with src's config (as hwy_fork_device
+ * wants them) and auto-reset off: tree environment e * M + i holds the state of node i, work environment e * n + a steps child a.
+ *   d_action   int32 [E]      argmax over the root's children of value lower, ties to the lowest id
+ *   d_value    f64   [E]      value lower of the root                                   (may be NULL)
+ *   d_upper    f64   [E]      value upper of the root                                   (may be NULL)
+ *   d_sequence int32 [E][X]   the argmax-lower children from the root to a leaf, then -1  (may be NULL)
+ *   d_expanded int32 [E]      expansions made (< X: the tree was solved)                (may be NULL)
+ * HWY_ERR_UNSUPPORTED off the highway and for several agents; HWY_ERR_INVALID_ARG unless 0 < gamma < 1, bound positive and finite,
+ * n_ids the size of the action table, budget >= n_ids, nodes == 1 + X * n <= 1024, HWY_C_NORMALIZE_REWARD set (the bound assumes
+ * rewards in [0, 1]), the three engines distinct and on one device, and tree / work of those sizes with auto-reset off.
+ * DEVICE pointers.  Enqueues X x (hwy_opd_kernel, gather tree -> work, step of work, scatter work -> tree) and one more kernel launch
+ * without a host round trip and does not synchronise; the outputs are ordered on work's stream (streams that differ are chained by
+ * events, as in hwy_fork_device).  `src` is only read; the tree's bookkeeping lives in device memory owned by `tree`, allocated by
+ * the first call.
+ */
+typedef struct hwy_opd_params {
+  int32_t budget, n_ids, nodes;
+  int32_t reserved;
+  double gamma, bound;
+} hwy_opd_params;
+int hwy_opd_plan_device(hwy_engine *src, hwy_engine *tree, hwy_engine *work, const hwy_opd_params *params, int32_t *d_action,
+                        double *d_value, double *d_upper, int32_t *d_sequence, int32_t *d_expanded);
+/* The same into HOST pointers (all but action may be NULL); synchronises. */
+int hwy_opd_plan(hwy_engine *src, hwy_engine *tree, hwy_engine *work, const hwy_opd_params *params, int32_t *action, double *value,
+                 double *upper, int32_t *sequence, int32_t *expanded);
+
 int hwy_sync(hwy_engine *eng); /* hipStreamSynchronize on the engine stream */
 
 /*
