@@ -267,16 +267,17 @@ def check_finite_mdp_scope(cfg: "HwyConfig") -> None:
 
 class HwyOpdParams(C.Structure):
     """hwy_opd_params (include/hwy_engine.h): the budget and discount of the optimistic planner and what follows from them."""
-    _fields_ = [("budget", C.c_int32), ("n_ids", C.c_int32), ("nodes", C.c_int32), ("reserved", C.c_int32),
+    _fields_ = [("budget", C.c_int32), ("n_ids", C.c_int32), ("nodes", C.c_int32), ("flags", C.c_int32),
                 ("gamma", C.c_double), ("bound", C.c_double)]
 
 
 HWY_OPD_MAX_NODES = 1024  # csrc/hwy_opd.h
+HWY_OPD_MASKED = 1         # hwy_opd_params.flags
 
 
-def opd_params(cfg: "HwyConfig", budget: int, gamma: float) -> HwyOpdParams:
+def opd_params(cfg: "HwyConfig", budget: int, gamma: float, masked: bool = False) -> HwyOpdParams:
     """``hwy_opd_params`` of ``plan_opd(budget, gamma)`` on an engine of ``cfg``: ``budget // n_ids`` expansions of ``n_ids``
-    children each, ``bound = 1 / (1 - gamma)`` in f64.  ValueError for what hwy_opd_plan_device rejects as HWY_ERR_INVALID_ARG."""
+    children each, ``bound = 1 / (1 - gamma)`` in f64; ``masked`` sets ``HWY_OPD_MASKED``.  ValueError for what hwy_opd_plan_device rejects as HWY_ERR_INVALID_ARG."""
     gamma, budget, n = float(gamma), int(budget), num_actions(cfg)
     if not 0.0 < gamma < 1.0:
         raise ValueError("gamma must be in (0, 1)")
@@ -289,13 +290,14 @@ def opd_params(cfg: "HwyConfig", budget: int, gamma: float) -> HwyOpdParams:
         raise ValueError(f"{nodes} nodes per tree exceed HWY_OPD_MAX_NODES = {HWY_OPD_MAX_NODES}")
     p = HwyOpdParams()
     p.budget, p.n_ids, p.nodes, p.gamma, p.bound = budget, n, nodes, gamma, 1.0 / (1.0 - gamma)
+    p.flags = HWY_OPD_MASKED if masked else 0
     return p
 
 
 def opd_bytes(cfg: "HwyConfig", num_envs: int, params: HwyOpdParams) -> int:
     """Device bytes ``plan_opd`` holds beside the parent: the tree engine, the work engine and the trees' bookkeeping."""
     E, n, M = int(num_envs), params.n_ids, params.nodes
-    return fork_bytes(cfg, E * M) + fork_bytes(cfg, E * n) + E * (M * (3 * 8 + 2 * 4 + 1) + params.budget // n * 8 + n * 8 + 28)
+    return fork_bytes(cfg, E * M) + fork_bytes(cfg, E * n) + E * (M * (3 * 8 + 2 * 4 + 1) + params.budget // n * 8 + n * 8 + 28 + M + n * n)
 
 
 def fork_bytes(cfg: "HwyConfig", num_envs: int, k_steps: int = 0) -> int:

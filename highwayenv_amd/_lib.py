@@ -22,6 +22,7 @@ EXPORTS = [
     "hwy_comm_unique_id", "hwy_comm_init", "hwy_gather", "hwy_comm_destroy", "hwy_set_behavior", "hwy_get_behavior",
     "hwy_set_controls", "hwy_get_controls", "hwy_ttc_grid_device", "hwy_ttc_grid", "hwy_mdp_plan_device", "hwy_mdp_plan",
     "hwy_fork_device", "hwy_fork", "hwy_score_device", "hwy_score_rollout", "hwy_opd_plan_device", "hwy_opd_plan",
+    "hwy_action_mask_device", "hwy_action_mask",
 ]
 
 
@@ -100,6 +101,8 @@ def load() -> C.CDLL:
     lib.hwy_score_rollout.argtypes = [vp, i32, i32, f64] + [vp] * 8
     lib.hwy_opd_plan_device.argtypes = [vp] * 9
     lib.hwy_opd_plan.argtypes = [vp] * 9
+    lib.hwy_action_mask_device.argtypes = [vp, vp]
+    lib.hwy_action_mask.argtypes = [vp, vp]
     lib.hwy_profile_enable.argtypes = [vp, i32]
     lib.hwy_profile_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     lib.hwy_get_prio_turn.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
@@ -108,7 +111,7 @@ def load() -> C.CDLL:
         fn = getattr(lib, name)
         if fn.restype is C.c_int or name.startswith(("hwy_create", "hwy_destroy", "hwy_set", "hwy_get", "hwy_reset",
                                                       "hwy_step", "hwy_rollout", "hwy_observe", "hwy_sync", "hwy_profile", "hwy_debug", "hwy_comm", "hwy_gather",
-                                                      "hwy_ttc", "hwy_mdp", "hwy_fork", "hwy_score", "hwy_opd")):
+                                                      "hwy_ttc", "hwy_mdp", "hwy_fork", "hwy_score", "hwy_opd", "hwy_action")):
             if name not in ("hwy_status_string", "hwy_last_error", "hwy_config_size"):
                 fn.restype = C.c_int
     if lib.hwy_abi_version() != _abi.HWY_ABI_VERSION:

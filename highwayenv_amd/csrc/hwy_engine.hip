@@ -18,6 +18,7 @@
 #include "../../include/hwy_engine.h"
 #include "hwy_comm.h"
 #include "hwy_launch.h"
+#include "hwy_mask.h"
 #include "hwy_params.h"
 
 using hwy::StepParams;
@@ -67,6 +68,8 @@ struct hwy_engine {
   int ttc_cells = 0;
   int32_t *d_plan_action = nullptr;  // [E][A]
   double *d_plan_q = nullptr;        // [E][A][5]
+  // output of the host-pointer form of the action mask (hwy_action_mask), allocated on first use
+  uint8_t *d_action_mask = nullptr;  // [E][A][n_ids]
   // hwy_fork / hwy_fork_device: the uploaded source indices [E] (host form) and the event that orders this engine's stream behind
   // the source engine's, both created on first use
   int32_t *d_fork_src = nullptr;
@@ -526,7 +529,7 @@ extern "C" int hwy_destroy(hwy_engine *eng) {
   void *ptrs[] = {eng->d_f64, eng->d_packed, eng->d_time, eng->d_done, eng->d_episode, eng->d_actions, eng->d_out, eng->d_roll,
                   eng->d_mask, eng->d_seeds, eng->d_grid_ws, eng->d_route, eng->d_road_steps, eng->d_gnet,
                   eng->d_shadow_f64, eng->d_shadow_packed, eng->d_shadow_route, eng->d_shadow_meta, eng->d_counters, eng->d_block_env,
-                  eng->d_behavior, eng->d_controls, eng->d_ttc_grid, eng->d_plan_action, eng->d_plan_q, eng->d_fork_src, eng->d_opd};
+                  eng->d_behavior, eng->d_controls, eng->d_ttc_grid, eng->d_plan_action, eng->d_plan_q, eng->d_fork_src, eng->d_opd, eng->d_action_mask};
   for (void *q : ptrs) if (q) (void)hipFree(q);
   if (eng->fork_event) (void)hipEventDestroy(eng->fork_event);
   if (eng->h_pinned) (void)hipHostFree(eng->h_pinned);
@@ -1287,6 +1290,7 @@ extern "C" int hwy_score_rollout(hwy_engine *eng, int32_t k_steps, int32_t branc
 }
 
 // ---- optimistic planning, one tree per environment (hwy_opd.h) -------------------------------------------------------------------------
+extern "C" int hwy_action_mask_device(hwy_engine *eng, uint8_t *d_mask);  // (below)
 // `waiter`'s stream continues behind what `signaler`'s stream holds so far
 static int stream_after(hwy_engine *waiter, hwy_engine *signaler) {
   if (waiter->stream == signaler->stream) return HWY_OK;
@@ -1317,7 +1321,7 @@ static int opd_forward(hwy_engine *src, hwy_engine *other, int rc) {
 // scatter_src | root_src [E M], actions [E n], done [E][M] u8, then the host form's outputs: action [E], value | upper [E] f64,
 // sequence [E][X], expanded [E]
 struct OpdLayout {
-  size_t ret, disc, up0, node, gather, scatter, root, act, done, o_action, o_value, o_upper, o_sequence, o_expanded, total;
+  size_t ret, disc, up0, node, gather, scatter, root, act, done, o_action, o_value, o_upper, o_sequence, o_expanded, created, child_mask, total;
 };
 static OpdLayout opd_layout(size_t E, size_t n, size_t M, size_t X) {
   auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
@@ -1326,7 +1330,8 @@ static OpdLayout opd_layout(size_t E, size_t n, size_t M, size_t X) {
   l.gather = l.node + up(E * X * 4); l.scatter = l.gather + up(E * n * 4); l.root = l.scatter + up(E * M * 4);
   l.act = l.root + up(E * M * 4); l.done = l.act + up(E * n * 4); l.o_action = l.done + up(E * M);
   l.o_value = l.o_action + up(E * 4); l.o_upper = l.o_value + up(E * 8); l.o_sequence = l.o_upper + up(E * 8);
-  l.o_expanded = l.o_sequence + up(E * X * 4); l.total = l.o_expanded + up(E * 4);
+  l.o_expanded = l.o_sequence + up(E * X * 4); l.created = l.o_expanded + up(E * 4);
+  l.child_mask = l.created + up(E * M); l.total = l.child_mask + up(E * n * n);  // (the masked search's two arrays, at the end)
   return l;
 }
 static int opd_block(hwy_engine *src, hwy_engine *tree, hwy_engine *work, const OpdLayout &l) {
@@ -1358,6 +1363,8 @@ extern "C" int hwy_opd_plan_device(hwy_engine *src, hwy_engine *tree, hwy_engine
   p.action = d_action; p.value = d_value; p.upper = d_upper; p.sequence = d_sequence; p.expanded = d_expanded;
   p.gamma = params->gamma; p.bound = params->bound;
   p.X = (int32_t)X; p.n = (int32_t)n; p.M = (int32_t)M; p.E = (int32_t)E;
+  const bool masked = (params->flags & HWY_OPD_MASKED) != 0;
+  if (masked) { p.created = (uint8_t *)(d + l.created); p.child_mask = (const uint8_t *)(d + l.child_mask); }
   // Everything of the planner's own runs on work's stream.  Before a tree kernel rewrites the scatter's indices, the scatter that
   // reads them on tree's stream has to be over; hwy_fork_device orders the rest (destination behind source).
   for (size_t x = 0; x <= X; ++x) {
@@ -1372,6 +1379,9 @@ extern "C" int hwy_opd_plan_device(hwy_engine *src, hwy_engine *tree, hwy_engine
     } else {
       if (int rc = hwy_fork_device(work, tree, 1, p.gather_src)) return opd_forward(src, work, rc);
     }
+    // the mask of the selected leaf: work's n copies of its state (row e * n is read), before the step moves them
+    if (masked)
+      if (int rc = hwy_action_mask_device(work, (uint8_t *)(d + l.child_mask))) return opd_forward(src, work, rc);
     if (int rc = hwy_step_device(work, p.actions, work->d_obs, work->d_reward, work->d_term, work->d_trunc, nullptr, nullptr))
       return opd_forward(src, work, rc);
     if (int rc = hwy_fork_device(tree, work, 1, p.scatter_src)) return opd_forward(src, tree, rc);
@@ -1397,6 +1407,36 @@ extern "C" int hwy_opd_plan(hwy_engine *src, hwy_engine *tree, hwy_engine *work,
   if (expanded) HWY_HIP(src, hipMemcpyAsync(expanded, d + l.o_expanded, E * 4, hipMemcpyDeviceToHost, work->stream));
   HWY_HIP(src, hipStreamSynchronize(work->stream));
   if (tree->stream != work->stream) HWY_HIP(src, hipStreamSynchronize(tree->stream));  // (the last scatter)
+  return HWY_OK;
+}
+
+// ---- action mask (hwy_mask.h) ------------------------------------------------------------------------------------------------------
+static int mask_check(hwy_engine *eng, const void *out, const char *who) {
+  if (!eng) return HWY_ERR_INVALID_ARG;
+  if (!out) return fail(eng, HWY_ERR_INVALID_ARG, std::string(who) + ": mask must be non-NULL");
+  const char *why = "";
+  if (const int rc = hwy::mask_validate(eng->cfg, &why)) return fail(eng, rc, std::string(who) + ": " + why);
+  return HWY_OK;
+}
+
+extern "C" int hwy_action_mask_device(hwy_engine *eng, uint8_t *d_mask) {
+  if (int rc = mask_check(eng, d_mask, "hwy_action_mask_device")) return rc;
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  const size_t plane = (size_t)eng->cfg.num_envs * eng->pitch;
+  const double *f = eng->d_f64;  // planes: x | y | heading | speed | ...
+  const hwy::MaskParams p = hwy::mask_params(eng->cfg, f, f + plane, eng->d_packed, eng->pitch, d_mask);
+  HWY_HIP(eng, hwy::launch_mask(p, eng->stream));
+  return HWY_OK;
+}
+
+extern "C" int hwy_action_mask(hwy_engine *eng, uint8_t *mask) {
+  if (int rc = mask_check(eng, mask, "hwy_action_mask")) return rc;
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  const size_t bytes = num_agent_rows(eng->cfg) * (size_t)hwy::mask_num_ids(eng->cfg);
+  if (!eng->d_action_mask) HWY_HIP(eng, hipMalloc((void **)&eng->d_action_mask, bytes));
+  if (int rc = hwy_action_mask_device(eng, eng->d_action_mask)) return rc;
+  HWY_HIP(eng, hipMemcpyAsync(mask, eng->d_action_mask, bytes, hipMemcpyDeviceToHost, eng->stream));
+  HWY_HIP(eng, hipStreamSynchronize(eng->stream));
   return HWY_OK;
 }
 

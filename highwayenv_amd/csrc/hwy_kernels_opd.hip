@@ -14,7 +14,9 @@ hipError_t launch_opd(const OpdParams &op, hipStream_t stream) {
       !op.disc || !op.upper0 || !op.done || !op.expanded_node || !op.reward || !op.terminated || !op.truncated || !op.gather_src ||
       !op.scatter_src || !op.root_src || !op.actions || !op.action)
     return hipErrorInvalidValue;
-  hipLaunchKernelGGL(hwy_opd_kernel<HWY_OPD_MAX_NODES>, dim3(op.E), dim3(64), 0, stream, op);
+  if ((op.child_mask != nullptr) != (op.created != nullptr)) return hipErrorInvalidValue;
+  if (op.created) hipLaunchKernelGGL(hwy_opd_masked_kernel<HWY_OPD_MAX_NODES>, dim3(op.E), dim3(64), 0, stream, op);
+  else hipLaunchKernelGGL(hwy_opd_kernel<HWY_OPD_MAX_NODES>, dim3(op.E), dim3(64), 0, stream, op);
   return hipGetLastError();
 }
 

@@ -85,5 +85,8 @@ hipError_t launch_fork(const ForkParams &fp, hipStream_t stream);
 hipError_t launch_score(const ScoreParams &sp, hipStream_t stream);
 // One step of the optimistic planner's tree (hwy_opd.h: ingest, backup, selection or the plan; op.E wavefronts)
 hipError_t launch_opd(const OpdParams &op, hipStream_t stream);
+// Action mask of the current state (hwy_mask.h, hwy_kernels_mask.hip: one thread per (environment, agent), row r -> mp.mask + r * n_ids)
+struct MaskParams;
+hipError_t launch_mask(const MaskParams &mp, hipStream_t stream);
 hipError_t launch_math_probe(int op, const double *in, double *out, long long n, hipStream_t stream);
 }  // namespace hwy

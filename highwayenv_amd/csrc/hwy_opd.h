@@ -24,6 +24,10 @@
 // product and sum a statement of its own (the rule of score_return), so the path return of a node equals what hwy_score_kernel
 // computes for its action sequence, bit for bit.
 //
+// hwy_opd_masked_kernel (hwy_opd_params.flags & HWY_OPD_MASKED) is the same tree step with one rule added: a node's unavailable
+// actions -- the action mask of its state, written by hwy_mask.h's kernel on the work engine between the gather and the step -- get
+// no child.  The two kernels share the __device__ body opd_tree_step<CAP, MASKED>; see there.
+//
 // Like hwy_lookahead.h this header includes no HIP runtime.
 #pragma once
 
@@ -55,6 +59,9 @@ struct OpdParams {
   int32_t *expanded;     // [E]            (may be null)
   double gamma, bound;
   int32_t x, X, n, M, E;
+  // the masked search (HWY_OPD_MASKED; both null: the unmasked one)
+  const uint8_t *child_mask;  // [E * n][n]: the mask kernel's output on the work engine -- row e * n holds the mask of the selected leaf
+  uint8_t *created;           // [E][M]: 1 where the node was created (its action was available in its parent's state)
 };
 
 // host side: what hwy_opd_plan_device accepts (include/hwy_engine.h).  Shared by hwy_engine.hip and the CPU emulation.
@@ -70,6 +77,11 @@ inline int opd_validate(const hwy_config &src, const hwy_config &tree, const hwy
     return HWY_ERR_UNSUPPORTED;
   }
   if (!params) { *why = "params is NULL"; return HWY_ERR_INVALID_ARG; }
+  if (params->flags & ~HWY_OPD_MASKED) { *why = "unknown bits in flags"; return HWY_ERR_INVALID_ARG; }
+  if ((params->flags & HWY_OPD_MASKED) && src.ego_control != HWY_EGO_META) {
+    *why = "the masked search needs a DiscreteMetaAction ego (a DiscreteAction ego has no get_available_actions)";
+    return HWY_ERR_UNSUPPORTED;
+  }
   if (!has_action) { *why = "action must be non-NULL"; return HWY_ERR_INVALID_ARG; }
   if (!(src.flags & HWY_C_NORMALIZE_REWARD)) { *why = "OPD needs normalize_reward (its bound assumes rewards in [0, 1])"; return HWY_ERR_INVALID_ARG; }
   if (!(params->gamma > 0.0 && params->gamma < 1.0)) { *why = "gamma must be in (0, 1)"; return HWY_ERR_INVALID_ARG; }
@@ -85,8 +97,12 @@ inline int opd_validate(const hwy_config &src, const hwy_config &tree, const hwy
   return HWY_OK;
 }
 
-template <int CAP>
-__global__ void __launch_bounds__(64) hwy_opd_kernel(const OpdParams p) {
+// The tree step shared by the two kernels below.  MASKED: a node's unavailable actions get no child -- the slot 1 + x * n + a stays
+// reserved and counts as never created (sh_exp == -2): it is not ingested, and the backup, the selection and the plan run over
+// created children only (IDLE always exists, so an expanded node always has a child).  The values of a never-created slot are
+// +inf in LDS, so that a read which forgets the guard cannot go unnoticed.
+template <int CAP, bool MASKED>
+__device__ __forceinline__ void opd_tree_step(const OpdParams &p) {
   __shared__ double sh_lo[CAP], sh_up[CAP];   // value lower / upper of every node
   __shared__ int32_t sh_exp[CAP];             // the expansion that expanded the node; -1: a leaf; -2: never created
   __shared__ int32_t sh_node[CAP];            // the node expansion j expanded (-1: void)
@@ -102,8 +118,11 @@ __global__ void __launch_bounds__(64) hwy_opd_kernel(const OpdParams p) {
   // ---- 1. the tree as the earlier launches left it, and the children of expansion x - 1 ----------------------------------------------
   for (int j = lane; j < x; j += 64) sh_node[j] = p.expanded_node[xrow + j];
   for (int i = lane; i < M; i += 64) {
-    const bool created = i == 0 || ((i - 1) / n < x && p.expanded_node[xrow + (i - 1) / n] >= 0);
+    bool created = i == 0 || ((i - 1) / n < x && p.expanded_node[xrow + (i - 1) / n] >= 0);
+    if (MASKED && created && i > 0)  // (the children that arrive now: from the mask kernel's output; the older ones: as recorded)
+      created = ((i - 1) / n == x - 1 ? p.child_mask[(size_t)e * n * n + (i - 1) % n] : p.created[row + i]) != 0;
     sh_exp[i] = created ? -1 : -2;
+    if (MASKED && !created) { sh_lo[i] = __builtin_inf(); sh_up[i] = __builtin_inf(); }
     if (i < old && created && x > 0) {
       sh_lo[i] = p.ret[row + i];
       sh_up[i] = p.upper0[row + i];
@@ -119,6 +138,11 @@ __global__ void __launch_bounds__(64) hwy_opd_kernel(const OpdParams p) {
     for (int a = lane; a < n; a += 64) {
       const int c = old + a;
       const size_t w = (size_t)e * n + a;
+      if (MASKED) {
+        const bool available = p.child_mask[(size_t)e * n * n + a] != 0;
+        p.created[row + c] = available ? 1 : 0;
+        if (!available) continue;  // no child: nothing is ingested
+      }
       const double t = disc_p * p.reward[w];
       const double lower = ret_p + t;
       const double disc = disc_p * p.gamma;
@@ -144,6 +168,7 @@ __global__ void __launch_bounds__(64) hwy_opd_kernel(const OpdParams p) {
     const int node = sh_node[j];
     if (node < 0) continue;  // (uniform) a void expansion
     for (int a = lane; a < n; a += 64) {
+      if (MASKED && sh_exp[1 + j * n + a] == -2) continue;  // never created
       const unsigned long long klo = score_key(sh_lo[1 + j * n + a]), kup = score_key(sh_up[1 + j * n + a]);
       __hip_atomic_fetch_max(&sh_key[0], klo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       __hip_atomic_fetch_max(&sh_key[1], kup, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -191,9 +216,18 @@ __global__ void __launch_bounds__(64) hwy_opd_kernel(const OpdParams p) {
     const int j = node >= 0 ? sh_exp[node] : -1;   // (uniform)
     int a_best = -1;
     if (j >= 0) {
-      const unsigned long long want = score_key(sh_lo[node]);
+      unsigned long long want = score_key(sh_lo[node]);
+      if (MASKED) {  // the maximum over the created children themselves (what the backup gave the node)
+        for (int a = lane; a < n; a += 64)
+          if (sh_exp[1 + j * n + a] != -2) __hip_atomic_fetch_max(&sh_key[0], score_key(sh_lo[1 + j * n + a]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __syncthreads();
+        want = sh_key[0];
+        __syncthreads();               // everyone has read it
+        if (lane == 0) sh_key[0] = 0ull;
+        __syncthreads();
+      }
       for (int a = lane; a < n; a += 64)
-        if (score_key(sh_lo[1 + j * n + a]) == want) __hip_atomic_fetch_min(&sh_arg, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if ((!MASKED || sh_exp[1 + j * n + a] != -2) && score_key(sh_lo[1 + j * n + a]) == want) __hip_atomic_fetch_min(&sh_arg, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       __syncthreads();
       a_best = sh_arg;
       __syncthreads();                 // everyone has read it
@@ -211,6 +245,16 @@ __global__ void __launch_bounds__(64) hwy_opd_kernel(const OpdParams p) {
     if (p.upper) p.upper[e] = sh_up[0];
     if (p.expanded) p.expanded[e] = made;
   }
+}
+
+template <int CAP>
+__global__ void __launch_bounds__(64) hwy_opd_kernel(const OpdParams p) {
+  opd_tree_step<CAP, false>(p);
+}
+// the masked search (hwy_opd_params.flags & HWY_OPD_MASKED): p.child_mask and p.created are set
+template <int CAP>
+__global__ void __launch_bounds__(64) hwy_opd_masked_kernel(const OpdParams p) {
+  opd_tree_step<CAP, true>(p);
 }
 
 }  // namespace hwy

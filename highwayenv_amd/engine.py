@@ -172,10 +172,12 @@ class Engine:
         return obs
 
     # -- time-to-collision grid and finite-MDP planner (csrc/hwy_ttc.h) ---------------------------
-    def _check_ttc(self, rc: int):
-        if rc == _abi.HWY_ERR_UNSUPPORTED:  # outside the planner's scope: the project's NotImplementedError
+    def _check_scope(self, rc: int):
+        if rc == _abi.HWY_ERR_UNSUPPORTED:  # outside the entry point's scope: the project's NotImplementedError
             raise NotImplementedError(self._lib.hwy_last_error(self._h).decode())
         self._check(rc)
+
+    _check_ttc = _check_scope  # (the name the planner entry points below were written with)
 
     def ttc_shape(self, params: _abi.HwyTtcParams) -> tuple:
         return (self.cfg.num_target_speeds, self.cfg.lanes_count, params.time_steps)
@@ -265,6 +267,18 @@ class Engine:
         self._check_ttc(self._lib.hwy_opd_plan_device(self._h, tree._h, work._h, C.byref(params), vp(d_action or None),
                                                       vp(d_value or None), vp(d_upper or None), vp(d_sequence or None),
                                                       vp(d_expanded or None)))
+
+    # -- action mask (csrc/hwy_mask.h) ---------------------------------------------------------------
+    def action_mask(self) -> np.ndarray:
+        """hwy_action_mask: ``get_available_actions`` of every controlled vehicle, bool [E, A, n_ids] in the order of the engine's
+        action table.  NotImplementedError on a DiscreteAction engine, like the reference's ``ActionType``."""
+        mask = np.empty((self.E, self.A, _abi.num_actions(self.cfg)), np.uint8)
+        self._check_scope(self._lib.hwy_action_mask(self._h, _ptr(mask)))
+        return mask.astype(bool)
+
+    def action_mask_device(self, d_mask: int):
+        """Enqueue hwy_action_mask_device on a raw device pointer (uint8 [E, A, n_ids]); does not synchronise."""
+        self._check_scope(self._lib.hwy_action_mask_device(self._h, C.c_void_p(d_mask or None)))
 
     # -- reset --------------------------------------------------------------------------------
     def reset(self, seeds=None, mask=None, ego_spacing=2.0, vehicles_density=1.0, initial_lane_id=-1, base_seed=0):

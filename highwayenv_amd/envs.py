@@ -14,6 +14,7 @@ types (obs ``(5,5) float32``, ``float`` reward, ``bool`` flags, ``info`` dict wi
 from __future__ import annotations
 
 import copy
+import itertools
 
 import numpy as np
 
@@ -337,6 +338,18 @@ class BatchedHighwayEnv:
                 "high_speed_reward": float(np.clip(scaled, 0, 1)),
                 "on_road_reward": float(on_road)}
 
+    # ---- get_available_actions (abstract.py:357 -> action.py:262-298) ---------------------------------------------------
+    def get_available_actions(self) -> np.ndarray:
+        """``AbstractEnv.get_available_actions`` of every controlled vehicle of every environment, computed on the device
+        (csrc/hwy_mask.h): bool [E, n_ids] ([E, A, n_ids] for several agents), column i = action id i of the action table is
+        available now.  NotImplementedError with ``DiscreteAction``, like the reference's ``ActionType``."""
+        if self._hcfg.ego_control != _abi.EGO_META:
+            raise NotImplementedError("get_available_actions needs a DiscreteMetaAction ego")
+        if self._engine is None:
+            raise NotImplementedError("The road and vehicle must be initialized in the environment implementation")
+        mask = self._engine.action_mask()
+        return mask[:, 0] if self._hcfg.num_agents == 1 else mask
+
     # ---- to_finite_mdp (abstract.py:452-453 -> envs/common/finite_mdp.py) -----------------------------------------
     def _ttc_params(self, horizon, time_quantization=None, gamma=1.0):
         _abi.check_finite_mdp_scope(self._hcfg)  # NotImplementedError outside the highway scenario / the five meta-actions
@@ -519,27 +532,36 @@ class BatchedHighwayEnv:
             cache[key] = table
         return cache[key]
 
-    def plan_lookahead(self, depth: int, horizon: int | None = None, gamma: float = 1.0, return_q: bool = False):
+    def plan_lookahead(self, depth: int, horizon: int | None = None, gamma: float = 1.0, return_q: bool = False, masked: bool = False):
         """The best first meta-action int32 [E] of an exhaustive search of depth ``depth`` with the TRUE simulator (every traffic
         vehicle reacts, changes lanes, crashes), where ``plan_finite_mdp`` plans on the reference's constant-speed TTC grid:
         all ``n_ids ** depth`` sequences, padded with IDLE to ``horizon`` steps (default: ``depth``), are stepped from the
         current state and the first action of the best discounted return is returned (the first maximum, numpy's argmax);
         with ``return_q`` also the best return per first action f64 [E, n_ids].  Single agent with a meta-action ego;
-        ValueError when the ``E * n_ids ** depth`` branch environments do not fit."""
+        ValueError when the ``E * n_ids ** depth`` branch environments do not fit.
+        ``masked``: only the FIRST action is masked -- ``q[e, i] = -inf`` where action ``i`` is not available now
+        (``get_available_actions``) and the action returned is the first maximum over the rest.  Masks at the deeper states of
+        the open-loop sequences are not applied."""
         self._lookahead_scope("plan_lookahead")
         table = self.lookahead_table(depth, horizon)
         self._lookahead_fits(self.num_envs * table.shape[0], table.shape[1])
         _, details = self.score_sequences(table, gamma=gamma, return_details=True)
-        return (details["best_action"], details["q"]) if return_q else details["best_action"]
+        action, q = details["best_action"], details["q"]
+        if masked:
+            q = np.where(self.get_available_actions(), q, -np.inf)
+            action = q.argmax(axis=1).astype(np.int32)
+        return (action, q) if return_q else action
 
     # ---- plan_opd: the budgeted tree search of scripts/highway_planning.ipynb (OPD, csrc/hwy_opd.h) ------------------------------
-    def _opd_setup(self, budget, gamma):
+    def _opd_setup(self, budget, gamma, masked=False):
         """(params, tree, work) of ``plan_opd``: the checks, then the two cached child environments (E * nodes environments that
         hold every node's state, E * n_ids that step the children), auto-reset off."""
         self._lookahead_scope("plan_opd")
         if self._hcfg.num_agents > 1:
             raise NotImplementedError("plan_opd plans for a single agent (joint-action trees are outside the MI355X hot-path scope)")
-        params = _abi.opd_params(self._hcfg, budget, gamma)
+        if masked and self._hcfg.ego_control != _abi.EGO_META:
+            raise NotImplementedError("plan_opd(masked=True) needs a DiscreteMetaAction ego")
+        params = _abi.opd_params(self._hcfg, budget, gamma, masked)
         E = self.num_envs
         need, limit = _abi.opd_bytes(self._hcfg, E, params), getattr(self, "max_fork_bytes", None)
         if E * params.nodes > 2 ** 31 - 1 or (limit is not None and need > limit):
@@ -549,7 +571,7 @@ class BatchedHighwayEnv:
         work = self._fork_child(("opd", E * params.n_ids), E * params.n_ids, "plan_opd")
         return params, tree, work
 
-    def plan_opd(self, budget: int = 50, gamma: float = 0.7, return_details: bool = False):
+    def plan_opd(self, budget: int = 50, gamma: float = 0.7, return_details: bool = False, masked: bool = False):
         """The first action int32 [E] of an optimistic plan (OPD, Hren & Munos 2008) of every environment: what the reference's
         ``DeterministicPlannerAgent`` does with ``copy.deepcopy(env)`` + ``env.step`` in scripts/highway_planning.ipynb
         (``budget = 50``, ``gamma = 0.7``), restated in DESIGN.md -- not bit parity with ``rl_agents``.  One tree of at most
@@ -557,8 +579,11 @@ class BatchedHighwayEnv:
         the TRUE simulator, entirely on the device (``hwy_opd_plan``).  Single agent, either action type, ``normalize_reward``
         on.  This environment is left exactly as it was.  ``return_details``: also a dict with ``value`` / ``upper`` f64 [E] (the
         bounds on the best discounted return from here), ``sequence`` int32 [E, X] (the plan, padded with -1) and ``expanded``
-        int32 [E] (expansions made: fewer than X where the tree was solved)."""
-        params, tree, work = self._opd_setup(budget, gamma)
+        int32 [E] (expansions made: fewer than X where the tree was solved).  ``masked``: a node's unavailable actions
+        (``get_available_actions`` of its state, by the mask kernel on the work engine) get no child, as in the reference's node
+        expansion; the budget still buys ``budget // n_ids`` expansions, and no action of the returned sequence is unavailable
+        in the state it is applied to."""
+        params, tree, work = self._opd_setup(budget, gamma, masked)
         out = self._engine.opd_plan(tree._engine, work._engine, params)
         if not return_details:
             return out["action"]
@@ -787,6 +812,19 @@ class _SingleEnvMixin:
     def to_finite_mdp(self):
         """``AbstractEnv.to_finite_mdp()`` (abstract.py:452-453): horizon 10 s, time step ``1 / policy_frequency``."""
         return super().to_finite_mdp(0)
+
+    def get_available_actions(self):
+        """``AbstractEnv.get_available_actions()`` (abstract.py:357): the list of available action ids in the reference's order
+        -- IDLE, then LANE_LEFT, LANE_RIGHT, FASTER, SLOWER where available (action.py:262-298) -- or, under
+        ``MultiAgentAction``, the ``itertools.product`` of the agents' lists (action.py:327-333)."""
+        mask = super().get_available_actions()[0].reshape(self._hcfg.num_agents, -1)
+        order = {3: (1, 0, 2), 5: (1, 0, 2, 3, 4)}[mask.shape[1]]   # ids of IDLE, LANE_LEFT, LANE_RIGHT, FASTER, SLOWER
+        if mask.shape[1] == 3 and (self._hcfg.scenario == _abi.SCENARIO_INTERSECTION or self._hcfg.action_set == _abi.ACTIONS_SET_LONGI):
+            order = (1, 2, 0)                                       # ids of IDLE, FASTER, SLOWER
+        lists = [[i for i in order if row[i]] for row in mask]
+        if self.config["action"]["type"] == "MultiAgentAction":
+            return itertools.product(*lists)
+        return lists[0]
 
     @property
     def vehicle(self) -> VehicleView:

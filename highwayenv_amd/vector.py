@@ -66,7 +66,8 @@ class HighwayVectorEnv(_Base):
     "intersection-v0", ...)."""
 
     def __init__(self, env="highway-fast-v0", num_envs: int = 1, config: dict | None = None, autoreset_mode: str = "NextStep",
-                 output: str = "numpy", device: int = 0, spawn_mode: str = "device", stream=None, **kwargs):
+                 output: str = "numpy", device: int = 0, spawn_mode: str = "device", stream=None, action_masks: bool = False,
+                 **kwargs):
         mode = getattr(autoreset_mode, "value", autoreset_mode)  # gymnasium.vector.AutoresetMode or its string
         mode = {"next_step": "NextStep", "same_step": "SameStep", "disabled": "Disabled"}.get(str(mode).lower(), str(mode))
         if mode not in AUTORESET_MODES:
@@ -77,6 +78,10 @@ class HighwayVectorEnv(_Base):
             raise ValueError("output='torch' supports the NextStep and Disabled autoreset modes (SameStep merges a masked reset on the host)")
         self.autoreset_mode = mode
         self.output = output
+        # action_masks: reset() and step() put info["action_mask"] (gymnasium's convention) into the info dict: bool [E, n_ids]
+        # ([E, A, n_ids] for several agents), the mask of the state whose observation is returned (csrc/hwy_mask.h).  With
+        # output="torch" it is the device tensor the kernel wrote.  False: nothing more is launched.
+        self.action_masks = bool(action_masks)
         if output == "torch":
             import torch  # the device-pointer path: torch owns the output tensors and the stream
             self._torch = torch
@@ -128,7 +133,12 @@ class HighwayVectorEnv(_Base):
         if self.output == "torch":
             self._bind_device_buffers()
             t = self._torch
+            if self.action_masks:
+                self._mask_into(self._dev["action_mask"])
+                infos["action_mask"] = self._views["action_mask"]
             return t.from_numpy(np.ascontiguousarray(obs)).to(self._dev["obs"].device), infos
+        if self.action_masks:
+            infos["action_mask"] = self.env.get_available_actions()
         return obs, infos
 
     def step_async(self, actions) -> None:
@@ -149,6 +159,8 @@ class HighwayVectorEnv(_Base):
             if k in info:
                 infos[k] = info[k]
         done = term | trunc
+        if self.action_masks:
+            infos["action_mask"] = self.env.get_available_actions()
         if self.autoreset_mode == "SameStep" and done.any():
             obs = np.array(obs, copy=True)
             final_obs = np.full(self.num_envs, None, dtype=object)
@@ -156,7 +168,11 @@ class HighwayVectorEnv(_Base):
             for e in np.nonzero(done)[0]:
                 final_obs[e] = obs[e].copy()
                 final_info[e] = {"speed": float(infos["speed"][e]), "crashed": bool(infos["crashed"][e])}
+                if self.action_masks:  # the ended episode's mask
+                    final_info[e]["action_mask"] = infos["action_mask"][e].copy()
             obs[done] = self.env.reset_done(done)
+            if self.action_masks:      # ... and the new episode's, next to its observation
+                infos["action_mask"] = self.env.get_available_actions()
             infos.update({"final_obs": final_obs, "_final_obs": done.copy(), "final_info": final_info, "_final_info": done.copy()})
         return obs, np.asarray(reward, np.float64), term, trunc, infos
 
@@ -169,6 +185,10 @@ class HighwayVectorEnv(_Base):
                      "terminated": t.empty(E, dtype=t.uint8, device=dev), "truncated": t.empty(E, dtype=t.uint8, device=dev),
                      "speed": t.empty((E, A), dtype=t.float64, device=dev), "crashed": t.empty((E, A), dtype=t.uint8, device=dev)}
         d = self._dev
+        if self.action_masks:
+            if self.env._hcfg.ego_control != _abi.EGO_META:
+                raise NotImplementedError("action_masks needs a DiscreteMetaAction ego")
+            d["action_mask"] = t.empty((E, A, _abi.num_actions(self.env._hcfg)), dtype=t.uint8, device=dev)
         self._n_actions = E * A
         self._out_ptrs = tuple(d[k].data_ptr() for k in ("obs", "reward", "terminated", "truncated", "speed", "crashed"))
         # what step() hands out: views of the planes the kernel writes (bool views of the 0 / 1 flag bytes; the intersection's
@@ -177,6 +197,19 @@ class HighwayVectorEnv(_Base):
         self._views = {"obs": d["obs"][:, 0] if A == 1 else d["obs"], "reward": d["reward"][:, 0],
                        "terminated": d["terminated"].view(t.bool), "truncated": d["truncated"].view(t.bool),
                        "speed": d["speed"][:, 0], "crashed": d["crashed"][:, 0].view(t.bool) if plain_crashed else None}
+        if self.action_masks:  # the 0 / 1 bytes the mask kernel writes, as a zero-copy bool view
+            self._views["action_mask"] = (d["action_mask"][:, 0] if A == 1 else d["action_mask"]).view(t.bool)
+
+    def _mask_into(self, out):
+        """Enqueue the mask kernel into the uint8 device tensor ``out`` on the engine's stream, ordered after the caller's current
+        stream and the caller's stream after it (nothing to order when they are the same stream)."""
+        cur = self._torch.cuda.current_stream()
+        same = cur.cuda_stream == self._stream.cuda_stream
+        if not same:
+            self._stream.wait_stream(cur)
+        self.env._engine.action_mask_device(out.data_ptr())
+        if not same:
+            cur.wait_stream(self._stream)
 
     def _device_actions(self, actions, lead=()):
         t, E, A = self._torch, self.num_envs, self.env._hcfg.num_agents
@@ -201,11 +234,15 @@ class HighwayVectorEnv(_Base):
         if not same:
             self._stream.wait_stream(cur)      # the actions (and the consumer of the previous outputs) come first
         self.env._engine.step_device(actions.data_ptr(), *self._out_ptrs)
+        if self.action_masks:                  # of the state this step left, behind it on the engine's stream
+            self.env._engine.action_mask_device(d["action_mask"].data_ptr())
         if not same:
             cur.wait_stream(self._stream)      # whatever the caller enqueues next sees this step's outputs
             actions.record_stream(self._stream)
         v = self._views
         infos = {"speed": v["speed"], "crashed": v["crashed"] if v["crashed"] is not None else (d["crashed"][:, 0] & 1).bool()}
+        if self.action_masks:
+            infos["action_mask"] = v["action_mask"]
         return v["obs"], v["reward"], v["terminated"], v["truncated"], infos
 
     def rollout(self, actions):
@@ -322,13 +359,14 @@ class HighwayVectorEnv(_Base):
             details["q"], details["best_action"] = d["q"], d["best_action"]
         return returns, details
 
-    def plan_lookahead(self, depth: int, horizon: int | None = None, gamma: float = 1.0, return_q: bool = False):
+    def plan_lookahead(self, depth: int, horizon: int | None = None, gamma: float = 1.0, return_q: bool = False, masked: bool = False):
         """``BatchedHighwayEnv.plan_lookahead``: the best first meta-action [E] of an exhaustive depth-``depth`` search with the true
         simulator.  ``output="torch"``: an int32 device tensor (valid until the next call of that shape) ordered on the current
         stream -- ``env.step(env.plan_lookahead(2))`` never leaves the GPU; the candidate table is built once on the host and
-        uploaded."""
+        uploaded.  ``masked``: ``q`` is -inf where the FIRST action is not available now (the mask kernel's output, on the device)
+        and the action is the first maximum over the rest; deeper states of the open-loop sequences are not masked."""
         if self.output != "torch":
-            return self.env.plan_lookahead(depth, horizon=horizon, gamma=gamma, return_q=return_q)
+            return self.env.plan_lookahead(depth, horizon=horizon, gamma=gamma, return_q=return_q, masked=masked)
         t, E = self._torch, self.num_envs
         self.env._lookahead_scope("plan_lookahead")
         table = self.env.lookahead_table(depth, horizon)
@@ -340,18 +378,26 @@ class HighwayVectorEnv(_Base):
             planes = np.ascontiguousarray(np.broadcast_to(table.T[:, None, :], (K, E, B)).reshape(K, E * B, 1))
             self._dev[key] = t.from_numpy(planes).to(self._dev["obs"].device)
         d = self._lookahead_device(self._dev[key], B, K, float(gamma))
+        if masked:
+            if "lookahead_mask" not in self._dev:
+                self._dev["lookahead_mask"] = t.empty((E, 1, _abi.num_actions(self.env._hcfg)), dtype=t.uint8, device=self._dev["obs"].device)
+            m = self._dev["lookahead_mask"]
+            self._mask_into(m)
+            q = t.where(m[:, 0].view(t.bool), d["q"], t.full_like(d["q"], float("-inf")))
+            action = q.argmax(dim=1).to(t.int32)   # (torch's argmax returns the first maximum on ties, like numpy's)
+            return (action, q) if return_q else action
         return (d["best_action"], d["q"]) if return_q else d["best_action"]
 
-    def plan_opd(self, budget: int = 50, gamma: float = 0.7, return_details: bool = False):
+    def plan_opd(self, budget: int = 50, gamma: float = 0.7, return_details: bool = False, masked: bool = False):
         """``BatchedHighwayEnv.plan_opd``: the first action [E] of an optimistic plan (OPD) of every environment, grown by
         ``budget // n_ids`` expansions with the true simulator.  ``output="torch"``: an int32 device tensor (and, with
         ``return_details``, device tensors ``value``, ``upper``, ``sequence``, ``expanded``; all valid until the next call of that
         shape), ordered on the current stream like ``plan()`` -- the whole loop is enqueued by one ``hwy_opd_plan_device`` call
-        and ``env.step(env.plan_opd())`` never leaves the GPU."""
+        and ``env.step(env.plan_opd())`` never leaves the GPU.  ``masked``: unavailable actions get no child."""
         if self.output != "torch":
-            return self.env.plan_opd(budget, gamma, return_details=return_details)
+            return self.env.plan_opd(budget, gamma, return_details=return_details, masked=masked)
         t, E, env = self._torch, self.num_envs, self.env
-        params, tree, work = env._opd_setup(budget, gamma)
+        params, tree, work = env._opd_setup(budget, gamma, masked)
         if self._dev is None:
             raise RuntimeError("plan_opd() before reset()")
         X, dev = params.budget // params.n_ids, self._dev["obs"].device

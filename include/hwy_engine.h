@@ -622,10 +622,16 @@ int hwy_score_rollout(hwy_engine *eng, int32_t k_steps, int32_t branches, double
  * without a host round trip and does not synchronise; the outputs are ordered on work's stream (streams that differ are chained by
  * events, as in hwy_fork_device).  `src` is only read; the tree's bookkeeping lives in device memory owned by `tree`, allocated by
  * the first call.
+ * flags & HWY_OPD_MASKED (a HWY_EGO_META ego; HWY_ERR_UNSUPPORTED otherwise): a node's unavailable actions (hwy_action_mask_device
+ * of its state) get no child.  X, the node numbering and every rule above stay: the slot 1 + x * n + a of an unavailable action stays
+ * reserved and counts as never created; backup, selection, the root's argmax and the greedy sequence run over created children only
+ * (IDLE always exists).  Per expansion one more small launch: the mask kernel on `work` after the gather, whose n copies of the
+ * leaf's state give that leaf's mask; the next tree launch (hwy_opd_masked_kernel) ingests only the available children.
  */
+enum { HWY_OPD_MASKED = 1 }; /* hwy_opd_params.flags */
 typedef struct hwy_opd_params {
   int32_t budget, n_ids, nodes;
-  int32_t reserved;
+  int32_t flags;                /* 0: every node gets all n_ids children; HWY_OPD_MASKED: see above; any other bit: HWY_ERR_INVALID_ARG */
   double gamma, bound;
 } hwy_opd_params;
 int hwy_opd_plan_device(hwy_engine *src, hwy_engine *tree, hwy_engine *work, const hwy_opd_params *params, int32_t *d_action,
@@ -633,6 +639,25 @@ int hwy_opd_plan_device(hwy_engine *src, hwy_engine *tree, hwy_engine *work, con
 /* The same into HOST pointers (all but action may be NULL); synchronises. */
 int hwy_opd_plan(hwy_engine *src, hwy_engine *tree, hwy_engine *work, const hwy_opd_params *params, int32_t *action, double *value,
                  double *upper, int32_t *sequence, int32_t *expanded);
+
+/*
+ * Action mask (additive to ABI v8: hwy_config keeps its layout).  AbstractEnv.get_available_actions (envs/common/abstract.py:357) ->
+ * DiscreteMetaAction.get_available_actions (envs/common/action.py:262-298) for every (environment, agent) at once, in a kernel of
+ * its own (csrc/hwy_mask.h) that reads the state planes on the engine's stream after whatever was launched last.
+ *   d_mask  uint8 [E][A][n_ids]  1 = the action is available, 0 = it is not; columns in the order of the engine's action table
+ *           (hwy_config.action_set: HWY_ACTIONS_ALL {LANE_LEFT, IDLE, LANE_RIGHT, FASTER, SLOWER}, HWY_ACTIONS_LONGI {SLOWER, IDLE,
+ *           FASTER}, HWY_ACTIONS_LAT {LANE_LEFT, IDLE, LANE_RIGHT}; HWY_SCENARIO_INTERSECTION: the longitudinal table)
+ * IDLE is always available; LANE_LEFT / LANE_RIGHT when the table has the lateral axis, the lane _id -/+ 1 exists on the road of the
+ * vehicle's CURRENT lane_index (RoadNetwork.side_lanes, road/road.py:200-211) and is_reachable_from(position) (road/lane.py:104-118:
+ * not forbidden, |lateral| <= 2 * width, 0 <= s < length + 5); FASTER / SLOWER when the table has the longitudinal axis and
+ * speed_index < num_target_speeds - 1 / speed_index > 0.
+ * All three scenario families with a HWY_EGO_META ego; HWY_ERR_UNSUPPORTED for HWY_EGO_DIRECT (the reference's
+ * ActionType.get_available_actions raises NotImplementedError); HWY_ERR_INVALID_ARG for a NULL pointer.
+ * DEVICE pointer; enqueues on the engine's stream and does not synchronise (like hwy_step_device).
+ */
+int hwy_action_mask_device(hwy_engine *eng, uint8_t *d_mask);
+/* The same into a HOST pointer; synchronises. */
+int hwy_action_mask(hwy_engine *eng, uint8_t *mask);
 
 int hwy_sync(hwy_engine *eng); /* hipStreamSynchronize on the engine stream */
 

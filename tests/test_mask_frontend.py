@@ -1,0 +1,102 @@
+"""``get_available_actions`` through the front ends, on the CPU emulation of the kernels: the batched classes return the bool table,
+the single-environment drop-ins the reference's list in the reference's order (IDLE, then LANE_LEFT, LANE_RIGHT, FASTER, SLOWER as
+available; under MultiAgentAction the product of the agents' lists), ``DiscreteAction`` raises NotImplementedError, and
+``HighwayVectorEnv(action_masks=True)`` puts the mask of the state whose observation it returns into the info dict."""
+import itertools
+
+import numpy as np
+import pytest
+
+from highwayenv_amd import _abi, envs
+from highwayenv_amd.vector import HighwayVectorEnv
+from tests import mask_util
+from tests.mask_util import MaskGolden
+
+
+def _action_set(g):
+    return g.hwy_config().action_set
+
+
+@pytest.mark.parametrize("name", ["mask_fast", "mask_longi", "mask_lat", "mask_placed", "mask_merge", "mask_intersection"])
+def test_single_environment_returns_the_reference_list(name):
+    g = MaskGolden(name)
+    env = mask_util.emu_class(g.single)(dict(g.overrides))
+    seen = set()
+    for index in g.indices():
+        for e in range(g.E):
+            env.set_state(g.state(index, envs=[e]))
+            got = env.get_available_actions()
+            want = mask_util.reference_list(g.mask(index)[e, 0], _action_set(g))
+            assert isinstance(got, list) and all(isinstance(i, int) for i in got)
+            assert got == want, (name, index, e)
+            seen.add(tuple(got))
+    assert len(seen) > 1 and all(s[0] == 1 for s in seen)   # IDLE (id 1 of every table) comes first
+
+
+@pytest.mark.parametrize("name", ["mask_ma2", "mask_intersection_ma"])
+def test_multi_agent_returns_the_product(name):
+    g = MaskGolden(name)
+    env = mask_util.emu_class(g.single if name != "mask_ma2" else envs.HighwayEnvFast)(dict(g.overrides))
+    for index in g.indices()[:5]:
+        env.set_state(g.state(index, envs=[0]))
+        lists = [mask_util.reference_list(g.mask(index)[0, a], _action_set(g)) for a in range(g.A)]
+        assert list(env.get_available_actions()) == list(itertools.product(*lists))
+
+
+@pytest.mark.parametrize("name", ["mask_fast", "mask_ma2", "mask_merge_generic", "mask_intersection_ma"])
+def test_batched_table(name):
+    g = MaskGolden(name)
+    env = mask_util.emu_class(g.batched)(dict(g.overrides), num_envs=g.E)
+    env.set_state(g.state(3))
+    got = env.get_available_actions()
+    assert got.dtype == bool and got.shape == ((g.E, g.n_ids) if g.A == 1 else (g.E, g.A, g.n_ids))
+    np.testing.assert_array_equal(got.reshape(g.E, g.A, g.n_ids), g.mask(3))
+
+
+def test_every_registered_batched_class_has_it():
+    for env_id, (single, batched) in envs.REGISTRY.items():
+        assert callable(getattr(batched, "get_available_actions")) and callable(getattr(single, "get_available_actions")), env_id
+
+
+def test_discrete_action_raises():
+    from tests.emu.emu_control import EmuControlEngine
+    cls = type("EmuDirect", (envs.BatchedHighwayEnvFast,), {"_engine_factory": staticmethod(lambda cfg, device, stream: EmuControlEngine(cfg))})
+    env = cls({"action": {"type": "DiscreteAction"}, "vehicles_count": 5}, num_envs=2)
+    env.reset(seed=0)
+    with pytest.raises(NotImplementedError):
+        env.get_available_actions()
+
+
+def test_before_reset_raises_like_the_reference():
+    with pytest.raises(NotImplementedError):
+        mask_util.emu_class(envs.BatchedHighwayEnvFast)(num_envs=2).get_available_actions()
+
+
+@pytest.mark.parametrize("mode", ["NextStep", "SameStep"])
+def test_vector_env_info_mask(mode):
+    """info["action_mask"] is the mask of the state whose observation is returned: it equals what the engine answers after the
+    call; in SameStep mode final_info carries the ended episode's mask.  Without action_masks the infos carry no such key."""
+    cls = mask_util.emu_class(envs.BatchedHighwayEnvFast)
+    cfg = {"vehicles_count": 8, "duration": 3}
+    venv = HighwayVectorEnv(cls, num_envs=3, config=cfg, autoreset_mode=mode, action_masks=True)
+    plain = HighwayVectorEnv(cls, num_envs=3, config=cfg, autoreset_mode=mode)
+    _, info = venv.reset(seed=5)
+    _, info0 = plain.reset(seed=5)
+    assert "action_mask" not in info0
+    np.testing.assert_array_equal(info["action_mask"], venv.env.get_available_actions())
+    assert info["action_mask"].shape == (3, 5) and info["action_mask"].dtype == bool
+    ended = 0
+    for t in range(8):
+        a = np.array([3, 0, 2]) if t % 2 else np.array([4, 2, 1])
+        obs, rew, term, trunc, info = venv.step(a)
+        obs0, rew0, term0, trunc0, info0 = plain.step(a)
+        assert "action_mask" not in info0
+        np.testing.assert_array_equal(obs, obs0)                       # the masks change nothing else
+        np.testing.assert_array_equal(rew, rew0)
+        np.testing.assert_array_equal(info["action_mask"], venv.env.get_available_actions())
+        if mode == "SameStep" and (term | trunc).any():
+            for e in np.flatnonzero(term | trunc):
+                m = info["final_info"][e]["action_mask"]
+                assert m.shape == (5,) and m.dtype == bool and m[1]
+                ended += 1
+    assert mode == "NextStep" or ended >= 3                            # duration 3: every environment is truncated at least once
