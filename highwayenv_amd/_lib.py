@@ -23,6 +23,7 @@ EXPORTS = [
     "hwy_set_controls", "hwy_get_controls", "hwy_ttc_grid_device", "hwy_ttc_grid", "hwy_mdp_plan_device", "hwy_mdp_plan",
     "hwy_fork_device", "hwy_fork", "hwy_score_device", "hwy_score_rollout", "hwy_opd_plan_device", "hwy_opd_plan",
     "hwy_action_mask_device", "hwy_action_mask",
+    "hwy_step_shapes", "hwy_last_step_shape",
 ]
 
 
@@ -103,6 +104,8 @@ def load() -> C.CDLL:
     lib.hwy_opd_plan.argtypes = [vp] * 9
     lib.hwy_action_mask_device.argtypes = [vp, vp]
     lib.hwy_action_mask.argtypes = [vp, vp]
+    lib.hwy_step_shapes.argtypes = [i32]
+    lib.hwy_last_step_shape.argtypes = []
     lib.hwy_profile_enable.argtypes = [vp, i32]
     lib.hwy_profile_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     lib.hwy_get_prio_turn.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]

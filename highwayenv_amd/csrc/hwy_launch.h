@@ -39,6 +39,8 @@ struct HipBackend {
   template <typename Fn>
   static auto pick_wpe(int v, Fn &&fn) { return dispatch_1_4(v, fn); }
 };
+// the shape kernels of the one-wavefront step (hwy_wave.h: FixedShape) and their launch: hwy_kernels_shapes.hip
+extern template hipError_t launch_step_shape<HipBackend>(int, const StepParams &, const Launch &);
 // One overload per kernel family, chosen by the type of its parameter struct; `l`: hwy_launch_family.h.
 // Straight road, IDM traffic and meta-actions (hwy_kernels.hip): the one-wavefront kernel for N <= 64, the wide kernel of hwy_wave2.h
 // for 64 < N <= 256 with the Kinematics observation, the workgroup kernel otherwise or when forced.

@@ -41,6 +41,48 @@ struct Launch {
 
 static inline int waves_for(int n_vehicles) { return (n_vehicles + 63) / 64; }
 
+// ---- shapes of the one-wavefront step kernel (hwy_wave.h: FixedShape) -------------------------------------------------------
+// Whether launches may take a shape kernel, and which one the last step launch of a straight-road family took (0 = the generic
+// kernel): ONE state per library, behind the two exports below -- the product's library and the CPU emulation's carry the same
+// two symbols, because this header is what both are built from.  Initially on, unless the environment says HWY_STEP_SHAPES=0
+// (read once, at the first use).
+struct StepShapeState {
+  bool enabled;
+  int last;
+};
+inline StepShapeState &step_shape_state() {
+  static StepShapeState s = [] {
+    const char *v = std::getenv("HWY_STEP_SHAPES");
+    return StepShapeState{!(v && v[0] == '0' && v[1] == 0), 0};
+  }();
+  return s;
+}
+// The shape whose EVERY fixed field equals the StepParams of THIS launch (full_step, autoreset and the pointers change from call to
+// call), or 0: the generic kernel -- a frames-only call, a call without actions, an engine before hwy_set_autoreset, a multi-step
+// launch, any other configuration.  IDM traffic with meta-actions on the one-wavefront kernel only.
+inline int step_shape_of(const StepParams &p, const Launch &l, bool rollout) {
+  if (!step_shape_state().enabled || rollout || p.N > 64 || l.force_block_kernel) return 0;
+  if (FastShape3::matches(p)) return FastShape3::ID;
+  if (FastShape4::matches(p)) return FastShape4::ID;
+  if (V0Shape4::matches(p)) return V0Shape4::ID;
+  return 0;
+}
+// the launch of shape `id` (> 0, from step_shape_of) in the register-allocation build the Launch asks for.  With the HIP backend it
+// is instantiated in hwy_kernels_shapes.hip alone (hwy_launch.h declares it extern): the shape kernels are a translation unit of
+// their own.
+template <typename B> hipError_t launch_step_shape(int id, const StepParams &p, const Launch &l) {
+  step_shape_state().last = id;
+  return B::pick_wpe(l.waves_per_eu, [&](auto W) {
+    constexpr int WPE = decltype(W)::value;
+    switch (id) {
+      case FastShape3::ID: return B::launch(hwy_shape_wave_kernel<FastShape3, WPE>, l.num_envs, 64, l.extra_lds, l, p);
+      case FastShape4::ID: return B::launch(hwy_shape_wave_kernel<FastShape4, WPE>, l.num_envs, 64, l.extra_lds, l, p);
+      case V0Shape4::ID: return B::launch(hwy_shape_wave_kernel<V0Shape4, WPE>, l.num_envs, 64, l.extra_lds, l, p);
+      default: return hipErrorInvalidValue;
+    }
+  });
+}
+
 // fn(std::integral_constant<int, v>{}) for a run-time v in 1 .. 4 (anything else: 4, the register-allocation variants' default)
 template <typename Fn>
 static auto dispatch_1_4(int v, Fn &&fn) {
@@ -92,6 +134,7 @@ struct FamilyLaunch {
   static hipError_t step(const P &a, const Launch &l, bool rollout) {
     const StepParams &p = F::step_params(a);
     const int nw = waves_for(p.N);
+    step_shape_state().last = 0;  // (a shape launch does not come through here: hwy_launch_rules.h, select_step)
     if (wave_applies(p, l)) {
       // FULL_SCAN = every vehicle checks collisions (highway-v0).  lds = hwy_config.tune_extra_lds: dynamic LDS reserved per
       // workgroup, i.e. fewer resident wavefronts per SIMD, so that part of the grid is dispatched as wavefronts retire (the
@@ -160,3 +203,16 @@ template <typename B> hipError_t select_observe(const LinearParams &a, const Lau
 template <typename B> hipError_t select_observe(const DirectParams &a, const Launch &l) { return select_observe<B>(a.s, l); }
 
 }  // namespace hwy
+
+// hwy_step_shapes(on): 1 = launches whose StepParams match a shape take its kernel, 0 = every launch takes the generic kernel,
+// anything else = no change; returns what was in force.  hwy_last_step_shape(): the shape id of the last step launch of a
+// straight-road family (0 = generic; hwy_wave.h: FastShape3 = 1, FastShape4 = 2, V0Shape4 = 3).  Process-wide, for A/B runs and tests.
+extern "C" {
+__attribute__((used, visibility("default"))) inline int hwy_step_shapes(int on) {
+  hwy::StepShapeState &s = hwy::step_shape_state();
+  const int was = s.enabled ? 1 : 0;
+  if (on == 0 || on == 1) s.enabled = on == 1;
+  return was;
+}
+__attribute__((used, visibility("default"))) inline int hwy_last_step_shape(void) { return hwy::step_shape_state().last; }
+}

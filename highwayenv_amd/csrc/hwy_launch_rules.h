@@ -21,7 +21,12 @@ static inline bool wide_kernel_applies(const StepParams &p, const Launch &l) {
 // Straight road, IDM traffic and meta-actions: the one-wavefront kernel for N <= 64, the wide kernel where it applies (one
 // register-allocation variant per K: waves_per_eu does not count), the workgroup kernel otherwise or when forced
 template <typename B> hipError_t select_step(const StepParams &p, const Launch &l, bool rollout) {
-  if (!wide_kernel_applies(p, l)) return FamilyLaunch<IdmFamily, B>::step(p, l, rollout);
+  if (!wide_kernel_applies(p, l)) {
+    // a launch whose every structural field is that of a registered shape runs the kernel compiled for it (hwy_wave.h: FixedShape)
+    if (const int shape = step_shape_of(p, l, rollout)) return launch_step_shape<B>(shape, p, l);
+    return FamilyLaunch<IdmFamily, B>::step(p, l, rollout);
+  }
+  step_shape_state().last = 0;
   switch (waves_for(p.N)) {
     case 2: return rollout ? B::launch(hwy_rollout_wide_kernel<2, 2>, l.num_envs, 64, 0, l, p)
                            : B::launch(hwy_step_wide_kernel<2, 2>, l.num_envs, 64, 0, l, p);

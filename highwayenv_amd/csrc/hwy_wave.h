@@ -77,6 +77,54 @@ __device__ inline int wave_send_i(int v, int dst) { return __builtin_amdgcn_ds_p
 #define HWY_WAVE_LDS_FENCE() __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront")
 #endif
 
+// ---- compile-time shapes of the step kernel ---------------------------------------------------------------------------------
+// The step kernel takes its whole configuration from StepParams at run time, yet most of it -- lanes, agents, the observation's
+// shape and flags, the action table, whether the output planes exist, full_step / autoreset / k_steps -- is fixed for the life of an
+// engine.  A SHAPE is the kernel's view of that structural part.  RuntimeShape promises nothing: the kernel reads every field (the
+// generic build, whose device code is what it was before shapes existed).  FixedShape<...> promises the integer, flag, table-id and
+// pointer-PRESENCE fields of one registered configuration; the optimiser folds them into the code, which then holds fewer scalar
+// loads from the argument segment, fewer SGPRs spilled to VGPR lanes across the frame loop, and none of the paths the configuration
+// cannot take.  N, pitch, every pointer VALUE, the issue-priority turn and all doubles stay at run time (N fixed unrolls the rank
+// and scan loops: measured worse).  ONE list (HWY_FIXED_SHAPE_FIELDS) states the promise: the kernel assumes it (fix), the launch
+// layer tests it against the StepParams of the launch (matches: hwy_launch_family.h, step_shape_of) and launches the generic kernel
+// on any mismatch.  The CPU emulation CHECKS the promise instead of assuming it: a launch that breaks it traps.
+#ifndef HWY_SHAPE_FIXED
+#if defined(__HIP_DEVICE_COMPILE__)
+#define HWY_SHAPE_FIXED(c) __builtin_assume(c)
+#else
+#define HWY_SHAPE_FIXED(c) ((c) ? (void)0 : __builtin_trap())
+#endif
+#endif
+struct RuntimeShape {
+  static constexpr int ID = 0;
+  __device__ static inline void fix(const StepParams &) {}
+};
+// ID: what hwy_last_step_shape reports (> 0); L: lanes; FLAGS: hwy_config.flags; T: frames per policy step.  Everything else is what
+// the registered highway configurations share: one agent at index 0, the default Kinematics observation (5 vehicles x [presence,
+// x, y, vx, vy]), three target speeds, the full meta-action table, a full policy step with auto-reset, all output planes bound.
+#define HWY_FIXED_SHAPE_FIELDS(X, p)                                                                                          \
+  X((p).A == 1) X((p).agent_index[0] == 0) X((p).L == L_) X((p).T == T_) X((p).flags == FLAGS_) X((p).V == 5) X((p).F == 5)  \
+  X((p).n_ts == 3) X((p).action_set == HWY_ACTIONS_ALL) X((p).obs_type == HWY_OBS_KINEMATICS) X((p).obs_std5 == 1)            \
+  X((p).k_steps == 0) X((p).n_frames == T_) X((p).full_step == 1) X((p).autoreset == 1) X((p).actions != nullptr)             \
+  X((p).obs != nullptr) X((p).info_speed != nullptr) X((p).info_crashed != nullptr)
+template <int ID_, int L_, int FLAGS_, int T_>
+struct FixedShape {
+  static constexpr int ID = ID_;
+  static constexpr bool FULL_SCAN = !(FLAGS_ & HWY_C_EGO_ONLY_COLLISIONS);
+#define HWY_SHAPE_X(c) HWY_SHAPE_FIXED(c);
+  __device__ static __forceinline__ void fix(const StepParams &p) { HWY_FIXED_SHAPE_FIELDS(HWY_SHAPE_X, p) }
+#undef HWY_SHAPE_X
+#define HWY_SHAPE_X(c) && (c)
+  static bool matches(const StepParams &p) { return true HWY_FIXED_SHAPE_FIELDS(HWY_SHAPE_X, p); }  // host
+#undef HWY_SHAPE_X
+};
+// the registered shapes: highway-fast-v0's structure (ego-only collisions, 5 frames per step) on 3 and 4 lanes, highway-v0's
+// (every vehicle checks collisions, 15 frames per step) on 4 lanes
+#define HWY_FLAGS_HIGHWAY_V0 (HWY_C_OBS_NORMALIZE | HWY_C_OBS_CLIP | HWY_C_NORMALIZE_REWARD)
+using FastShape3 = FixedShape<1, 3, HWY_FLAGS_HIGHWAY_V0 | HWY_C_EGO_ONLY_COLLISIONS, 5>;
+using FastShape4 = FixedShape<2, 4, HWY_FLAGS_HIGHWAY_V0 | HWY_C_EGO_ONLY_COLLISIONS, 5>;
+using V0Shape4 = FixedShape<3, 4, HWY_FLAGS_HIGHWAY_V0, 15>;
+
 struct WaveShared {
   // frame snapshot in RANK order (slot r == r-th vehicle along the road)
   double x[64], v[64], c[64], s[64], lr[64];  // lr = log(v/v0), see EnvBlock::idm_log_ratio
@@ -184,10 +232,12 @@ __device__ inline void wave_update_rank(double x, bool active, int N, int &rank,
 // env_time: the environment's clock at the start of the step (requested with the state by the caller: a load here, at the end of
 // the wavefront's life, is a round trip nothing hides); only read when write_reward is set
 // EG: the ego control (hwy_device.h: ego_reward_lane)
-template <bool BY_RANK, typename EG = MetaEgo>
+// SH: the shape (RuntimeShape / FixedShape above) `p` is read through
+template <bool BY_RANK, typename EG = MetaEgo, typename SH = RuntimeShape>
 __device__ inline void observe_wave(const StepParams &p, int e, int eo, const Veh &me, bool write_reward, int rank = 0,
                                     double env_time = 0.0) {
   typedef EnvBlock<1> B;
+  SH::fix(p);
   const int i = threadIdx.x;
   const bool active = i < p.N;
   const int V = p.V, F = p.F;
@@ -314,10 +364,12 @@ __device__ inline void observe_wave(const StepParams &p, int e, int eo, const Ve
 // One policy step of environment e by its wavefront; eo = row of the action / output planes (see observe_wave).
 // TM: the traffic model (hwy_device.h: IdmTraffic / LinearTraffic, compile time); la: the Linear family's parameters (unused by IDM).
 // EG: the ego control (hwy_device.h: MetaEgo / DirectEgo, compile time); da: the direct-control arguments (DirectEgo only).
-template <bool FULL_SCAN, typename TM = IdmTraffic, typename EG = MetaEgo>
+// SH: the shape the step reads its structural configuration through (RuntimeShape: from `p`; FixedShape: constants).
+template <bool FULL_SCAN, typename TM = IdmTraffic, typename EG = MetaEgo, typename SH = RuntimeShape>
 __device__ __forceinline__ void wave_policy_step(const StepParams &p, WaveShared &sh, const int e, const int eo,
                                                  const LinearArgs &la = LinearArgs{}, const DirectArgs *da = nullptr) {
   typedef EnvBlock<1> B;
+  SH::fix(p);
   const int i = threadIdx.x;
   const int N = p.N;
   const bool active = i < N;
@@ -354,7 +406,7 @@ __device__ __forceinline__ void wave_policy_step(const StepParams &p, WaveShared
     if constexpr (TM::LINEAR) {
       if (active) spawn_behavior(p, la, e, i, p.rp.base_seed + (uint64_t)e, episode, (me.flags & HWY_F_CONTROLLED) != 0);
     }
-    observe_wave<false>(p, e, eo, me, false);
+    observe_wave<false, MetaEgo, SH>(p, e, eo, me, false);
     store_vehicle<1>(p, e, me);
     if (active && (me.flags & HWY_F_CONTROLLED)) {
       for (int a = 0; a < p.A; ++a)
@@ -936,9 +988,10 @@ __device__ __forceinline__ void wave_policy_step(const StepParams &p, WaveShared
   // again from the kernel-argument segment, through a pointer the compiler cannot see through, instead of
   // keeping them live -- i.e. spilled to VGPR lanes and re-read with v_readlane -- across the frame loop.
   HWY_RELOAD_PARAMS(q, p);
+  SH::fix(q);  // (the second view is opaque: what the shape fixes is stated for it again)
   if (q.full_step) wave_update_rank(me.x, active, N, rank, has_tie);  // positions moved in the last frame
   // (state stores before or after the observation: 40.8 / 40.6 us, within the noise -- profiles/r05_history.md)
-  if (q.full_step) observe_wave<true, EG>(q, e, eo, me, true, rank, env_time);
+  if (q.full_step) observe_wave<true, EG, SH>(q, e, eo, me, true, rank, env_time);
   if constexpr (EG::DIRECT) {
     if (controlled) {
       me.tgt = me.lane;  // (a plain Vehicle has no target lane: the slot mirrors its lane from step to step)
@@ -958,6 +1011,16 @@ __global__ void __launch_bounds__(64, WPE) hwy_step_wave_kernel(const StepParams
   HWY_KERNARG_TOUCH(StepParams);
   const int e = p.block_env ? (int)p.block_env[blockIdx.x] : (int)blockIdx.x;
   wave_policy_step<FULL_SCAN>(p, sh, e, e);
+}
+
+// The same kernel compiled for ONE shape (SH = a FixedShape): launched only when the StepParams of the launch match the shape field
+// by field (hwy_launch_family.h: step_shape_of), instantiated in hwy_kernels_shapes.hip.  The rollout kernel below stays generic.
+template <typename SH, int WPE>
+__global__ void __launch_bounds__(64, WPE) hwy_shape_wave_kernel(const StepParams p) {
+  __shared__ WaveShared sh;
+  HWY_KERNARG_TOUCH(StepParams);
+  const int e = p.block_env ? (int)p.block_env[blockIdx.x] : (int)blockIdx.x;
+  wave_policy_step<SH::FULL_SCAN, IdmTraffic, MetaEgo, SH>(p, sh, e, e);
 }
 
 // hwy_rollout_device: p.k_steps consecutive policy steps of every environment in ONE launch (actions of step k in row

@@ -367,5 +367,16 @@ class Engine:
         return turn.value, state.value
 
 
+def step_shapes(on: bool | None = None) -> bool:
+    """hwy_step_shapes: whether step launches may run the kernel builds compiled for the registered configurations (process-wide;
+    ``None`` only asks).  Returns the setting that was in force."""
+    return bool(_lib.load().hwy_step_shapes(-1 if on is None else int(bool(on))))
+
+
+def last_step_shape() -> int:
+    """hwy_last_step_shape: 0 = the last step launch ran the generic kernel, 1 / 2 = highway-fast-v0 on 3 / 4 lanes, 3 = highway-v0."""
+    return int(_lib.load().hwy_last_step_shape())
+
+
 def device_count() -> int:
     return _lib.load().hwy_device_count()

@@ -684,6 +684,21 @@ int hwy_get_counters(hwy_engine *eng, uint64_t *out, int32_t n, int32_t reset);
 int hwy_set_block_order(hwy_engine *eng, const int32_t *env_of_block);
 
 /*
+ * Shapes of the one-wavefront step kernel (tuning; never changes a result).  A policy step of HWY_SCENARIO_HIGHWAY with IDM traffic
+ * and meta-actions whose structure is that of a registered configuration -- highway-fast-v0 on 3 or 4 lanes, highway-v0 on 4 lanes:
+ * one agent, the default Kinematics observation, three target speeds, the five-action table, auto-reset on, every output plane
+ * bound -- runs a build of the kernel compiled for that structure; every other launch (another configuration, hwy_step_frames, a
+ * step without actions or info planes, an engine before hwy_set_autoreset, hwy_rollout*) runs the generic kernel.
+ * hwy_step_shapes(on): 1 = as above (the default, unless the environment holds HWY_STEP_SHAPES=0 when the library is first used),
+ * 0 = every launch runs the generic kernel, any other value = no change; returns the setting that was in force.  Process-wide.
+ * hwy_last_step_shape(): which build the last step launch of a straight-road engine ran: 0 = generic, 1 = highway-fast-v0 / 3
+ * lanes, 2 = highway-fast-v0 / 4 lanes, 3 = highway-v0 / 4 lanes.  The reference has no counterpart (one Python code path:
+ * envs/common/abstract.py:287-317).
+ */
+int hwy_step_shapes(int on);
+int hwy_last_step_shape(void);
+
+/*
  * Self-test hook: evaluate one of the step kernel's own math routines (csrc/hwy_math.h -- bounded-domain
  * log / exp / sincos / asin, Newton-refined v_rcp_f64 / v_rsq_f64, floor-mod angle wrap) on n doubles on
  * the device.  Host pointers.  op: 0 log_pos, 1 exp_bounded, 2 sin, 3 cos, 4 asin_bounded, 5 fast_rcp, 8 atan_fd,

@@ -2,7 +2,7 @@
 # Developer tool (GPU box): SQ instruction / cycle counters of the step kernel of a bench workload, three rocprofv3 --pmc
 # passes -> gpurun_out/pmc_sq_<workload>.json (mean over the last 30 launches, per wave == per env-step).
 #   bash tools/pmc_sq.sh [workload] [envs] [kernel-name-substring]
-W=${1:-fast}; E=${2:-4096}; K=${3:-hwy_step_wave}
+W=${1:-fast}; E=${2:-4096}; K=${3:-_wave_kernel<}  # (hwy_step_wave_kernel<..> or, with the step shapes on, hwy_shape_wave_kernel<..>)
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p $R/gpurun_out/pmc_$W
 cd /tmp && export TMPDIR=/tmp
