@@ -1179,6 +1179,22 @@ static int fork_check(hwy_engine *dst, hwy_engine *src, int32_t branches, bool h
   return HWY_OK;
 }
 
+// the engine's planes as a fork sees them: whole packed words (the rank hint travels)
+static hwy::ForkView fork_view(const hwy_engine *eng) {
+  hwy::ForkView v;
+  memset(&v, 0, sizeof v);
+  v.cfg = &eng->cfg;
+  const size_t plane = (size_t)eng->cfg.num_envs * eng->pitch;
+  for (int f = 0; f < 9; ++f) v.f64[f] = eng->d_f64 + f * plane;
+  v.behavior = eng->d_behavior;
+  v.i32[0] = eng->d_packed;
+  v.n_i32 = 1;
+  v.controls = eng->d_controls;
+  v.time = eng->d_time; v.episode = eng->d_episode; v.done = eng->d_done;
+  v.pitch = eng->pitch;
+  return v;
+}
+
 extern "C" int hwy_fork_device(hwy_engine *dst, hwy_engine *src, int32_t branches, const int32_t *d_src_env) {
   if (int rc = fork_check(dst, src, branches, d_src_env != nullptr, "hwy_fork_device")) return rc;
   HWY_HIP(dst, hipSetDevice(dst->device));
@@ -1187,22 +1203,7 @@ extern "C" int hwy_fork_device(hwy_engine *dst, hwy_engine *src, int32_t branche
     HWY_HIP(dst, hipEventRecord(dst->fork_event, src->stream));
     HWY_HIP(dst, hipStreamWaitEvent(dst->stream, dst->fork_event, 0));
   }
-  hwy::ForkParams p;
-  memset(&p, 0, sizeof p);
-  const size_t splane = (size_t)src->cfg.num_envs * src->pitch, dplane = (size_t)dst->cfg.num_envs * dst->pitch;
-  for (int f = 0; f < 9; ++f) { p.src_f64[f] = src->d_f64 + f * splane; p.dst_f64[f] = dst->d_f64 + f * dplane; }
-  p.n_f64 = 9;
-  if (is_linear(dst))
-    for (int f = 0; f < HWY_BEHAVIOR_PARAMS; ++f, ++p.n_f64) { p.src_f64[9 + f] = src->d_behavior + f * splane; p.dst_f64[9 + f] = dst->d_behavior + f * dplane; }
-  p.src_i32[0] = src->d_packed; p.dst_i32[0] = dst->d_packed;  // whole words: the rank hint travels
-  p.n_i32 = 1;
-  if (is_direct(dst)) { p.src_controls = src->d_controls; p.dst_controls = dst->d_controls; }
-  p.src_time = src->d_time; p.dst_time = dst->d_time;
-  p.src_episode = src->d_episode; p.dst_episode = dst->d_episode;
-  p.dst_done = dst->d_done;
-  p.src_env = d_src_env;
-  p.pitch = dst->pitch; p.A = dst->cfg.num_agents; p.branches = branches;
-  p.src_envs = src->cfg.num_envs; p.dst_envs = dst->cfg.num_envs;
+  const hwy::ForkParams p = hwy::fork_params(fork_view(dst), fork_view(src), branches, d_src_env);
   HWY_HIP(dst, hwy::launch_fork(p, dst->stream));
   return HWY_OK;
 }
@@ -1231,13 +1232,8 @@ extern "C" int hwy_score_device(hwy_engine *eng, int32_t k_steps, int32_t branch
                                          d_q != nullptr, d_best_action != nullptr, &why))
     return fail(eng, rc, std::string("hwy_score_device: ") + why);
   HWY_HIP(eng, hipSetDevice(eng->device));
-  hwy::ScoreParams p;
-  memset(&p, 0, sizeof p);
-  p.first_action = d_first_action; p.reward = d_reward; p.terminated = d_terminated; p.truncated = d_truncated;
-  p.ret = d_return; p.q = d_q; p.best_action = d_best_action; p.best_branch = d_best_branch;
-  p.gamma = gamma;
-  p.K = k_steps; p.branches = branches; p.A = eng->cfg.num_agents; p.n_ids = num_action_ids(eng);
-  p.groups = eng->cfg.num_envs / branches;
+  const hwy::ScoreParams p = hwy::score_params(eng->cfg, k_steps, branches, gamma, d_first_action, d_reward, d_terminated, d_truncated,
+                                               d_return, d_q, d_best_action, d_best_branch);
   HWY_HIP(eng, hwy::launch_score(p, eng->stream));
   return HWY_OK;
 }
@@ -1353,40 +1349,31 @@ extern "C" int hwy_opd_plan_device(hwy_engine *src, hwy_engine *tree, hwy_engine
   const OpdLayout l = opd_layout(E, n, M, X);
   if (int rc = opd_block(src, tree, work, l)) return rc;
   char *d = tree->d_opd;
-  hwy::OpdParams p;
-  memset(&p, 0, sizeof p);
-  p.ret = (double *)(d + l.ret); p.disc = (double *)(d + l.disc); p.upper0 = (double *)(d + l.up0); p.done = (uint8_t *)(d + l.done);
-  p.expanded_node = (int32_t *)(d + l.node);
-  p.reward = work->d_reward; p.terminated = work->d_term; p.truncated = work->d_trunc;
-  p.gather_src = (int32_t *)(d + l.gather); p.scatter_src = (int32_t *)(d + l.scatter); p.root_src = (int32_t *)(d + l.root);
-  p.actions = (int32_t *)(d + l.act);
-  p.action = d_action; p.value = d_value; p.upper = d_upper; p.sequence = d_sequence; p.expanded = d_expanded;
-  p.gamma = params->gamma; p.bound = params->bound;
-  p.X = (int32_t)X; p.n = (int32_t)n; p.M = (int32_t)M; p.E = (int32_t)E;
-  const bool masked = (params->flags & HWY_OPD_MASKED) != 0;
-  if (masked) { p.created = (uint8_t *)(d + l.created); p.child_mask = (const uint8_t *)(d + l.child_mask); }
-  // Everything of the planner's own runs on work's stream.  Before a tree kernel rewrites the scatter's indices, the scatter that
-  // reads them on tree's stream has to be over; hwy_fork_device orders the rest (destination behind source).
-  for (size_t x = 0; x <= X; ++x) {
-    if (int rc = stream_after(work, tree)) return opd_forward(src, work, rc);
-    p.x = (int32_t)x;
-    HWY_HIP(src, hwy::launch_opd(p, work->stream));
-    if (x == X) break;
-    if (x == 0) {  // the root's state into tree slot e * M, and the parent's into all n work environments of e
-      if (int rc = stream_after(tree, work)) return opd_forward(src, tree, rc);
-      if (int rc = hwy_fork_device(tree, src, 1, p.root_src)) return opd_forward(src, tree, rc);
-      if (int rc = hwy_fork_device(work, src, (int32_t)n, nullptr)) return opd_forward(src, work, rc);
-    } else {
-      if (int rc = hwy_fork_device(work, tree, 1, p.gather_src)) return opd_forward(src, work, rc);
+  const hwy::OpdTree t = {(double *)(d + l.ret), (double *)(d + l.disc), (double *)(d + l.up0), (uint8_t *)(d + l.done),
+                          (int32_t *)(d + l.node), (int32_t *)(d + l.gather), (int32_t *)(d + l.scatter), (int32_t *)(d + l.root),
+                          (int32_t *)(d + l.act), (uint8_t *)(d + l.created), (uint8_t *)(d + l.child_mask)};
+  const hwy::OpdParams p = hwy::opd_params(*params, (int32_t)E, t, work->d_reward, work->d_term, work->d_trunc,
+                                           hwy::OpdPlan{d_action, d_value, d_upper, d_sequence, d_expanded});
+  // the operations of hwy_opd.h's sequence on the three engines' streams; a failure of a call on `tree` / `work` is reported on
+  // `src`, the engine the caller asks
+  struct Ops {
+    hwy_engine *eng[3];  // by hwy::OpdEngine
+    uint8_t *child_mask;
+    int after(int waiter, int signaler) { return opd_forward(eng[0], eng[waiter], stream_after(eng[waiter], eng[signaler])); }
+    int kernel(const hwy::OpdParams &p) {
+      HWY_HIP(eng[0], hwy::launch_opd(p, eng[hwy::OPD_WORK]->stream));
+      return HWY_OK;
     }
-    // the mask of the selected leaf: work's n copies of its state (row e * n is read), before the step moves them
-    if (masked)
-      if (int rc = hwy_action_mask_device(work, (uint8_t *)(d + l.child_mask))) return opd_forward(src, work, rc);
-    if (int rc = hwy_step_device(work, p.actions, work->d_obs, work->d_reward, work->d_term, work->d_trunc, nullptr, nullptr))
-      return opd_forward(src, work, rc);
-    if (int rc = hwy_fork_device(tree, work, 1, p.scatter_src)) return opd_forward(src, tree, rc);
-  }
-  return HWY_OK;
+    int fork(int dst, int src, int32_t branches, const int32_t *src_env) {
+      return opd_forward(eng[0], eng[dst], hwy_fork_device(eng[dst], eng[src], branches, src_env));
+    }
+    int mask() { return opd_forward(eng[0], eng[hwy::OPD_WORK], hwy_action_mask_device(eng[hwy::OPD_WORK], child_mask)); }
+    int step(const int32_t *actions) {
+      hwy_engine *w = eng[hwy::OPD_WORK];
+      return opd_forward(eng[0], w, hwy_step_device(w, actions, w->d_obs, w->d_reward, w->d_term, w->d_trunc, nullptr, nullptr));
+    }
+  };
+  return hwy::opd_expand(p, Ops{{src, tree, work}, t.child_mask});
 }
 
 extern "C" int hwy_opd_plan(hwy_engine *src, hwy_engine *tree, hwy_engine *work, const hwy_opd_params *params, int32_t *action, double *value,

@@ -8,13 +8,9 @@
 
 namespace hwy {
 
-// `rows` (environment, agent) pairs, row r written to lp.obs + r * cells * 2.  A plain launch: the dispatch timestamps of
-// hwy_profile_* belong to the step kernel.
+// the unit's rules (hwy_launch_units.h) with the HIP backend
 hipError_t launch_lidar(const LidarParams &lp, bool normalize, int rows, hipStream_t stream) {
-  if (rows < 1 || lp.cells < 1 || lp.cells > HWY_MAX_LIDAR_CELLS) return hipErrorInvalidValue;
-  if (normalize) hipLaunchKernelGGL(hwy_lidar_kernel<true>, dim3(rows), dim3(64), 0, stream, lp);
-  else hipLaunchKernelGGL(hwy_lidar_kernel<false>, dim3(rows), dim3(64), 0, stream, lp);
-  return hipGetLastError();
+  return select_lidar<HipBackend>(lp, normalize, rows, stream);
 }
 
 }  // namespace hwy

@@ -4,18 +4,13 @@
 #include <hip/hip_runtime.h>
 
 #include "hwy_mask.h"
+#include "hwy_launch.h"
 
 namespace hwy {
 
-// mp.rows (environment, agent) pairs, row r written to mp.mask + r * n_ids.  A plain launch: the dispatch timestamps of
-// hwy_profile_* belong to the step kernel.
+// the unit's rules (hwy_launch_units.h) with the HIP backend
 hipError_t launch_mask(const MaskParams &mp, hipStream_t stream) {
-  if (mp.rows < 1 || mp.A < 1 || mp.N < 1 || mp.N > mp.pitch || mp.n_lanes < 0 || mp.n_lanes > HWY_MAX_LANES || !mp.x || !mp.y ||
-      !mp.packed || !mp.mask || mp.n_ids != HWY_NUM_ACTIONS(mp.action_set))
-    return hipErrorInvalidValue;
-  const unsigned blocks = ((unsigned)mp.rows + HWY_MASK_BLOCK - 1) / HWY_MASK_BLOCK;
-  hipLaunchKernelGGL(hwy_mask_kernel<HWY_MASK_BLOCK>, dim3(blocks), dim3(HWY_MASK_BLOCK), 0, stream, mp);
-  return hipGetLastError();
+  return select_mask<HipBackend>(mp, stream);
 }
 
 }  // namespace hwy

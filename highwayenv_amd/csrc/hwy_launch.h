@@ -1,7 +1,7 @@
 // hwy_launch.h -- host-visible launch functions of the kernels in hwy_kernels.hip, hwy_kernels_linear.hip and
-// hwy_kernels_direct.hip: one overload per kernel family, chosen by the type of its parameter struct; and of the
-// LidarObservation kernel in hwy_kernels_lidar.hip and the time-to-collision / planner kernel in hwy_kernels_ttc.hip.  Each is the shared selection layer (hwy_launch_family.h, hwy_launch_rules.h)
-// with the HIP backend below.
+// hwy_kernels_direct.hip: one overload per kernel family, chosen by the type of its parameter struct; and of the add-on units
+// (hwy_kernels_lidar.hip, _ttc.hip, _lookahead.hip, _opd.hip, _mask.hip).  Each is the shared selection layer (hwy_launch_family.h,
+// hwy_launch_rules.h; the add-on units: hwy_launch_units.h) with the HIP backend below.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -13,9 +13,12 @@
 #include "hwy_ttc.h"
 #include "hwy_lookahead.h"
 #include "hwy_opd.h"
+#include "hwy_mask.h"
+#include "hwy_launch_units.h"
 
 namespace hwy {
-// The HIP backend of the selection layer (hwy_launch_family.h, hwy_launch_rules.h), for the kernel translation units.
+// The HIP backend of the selection layer (hwy_launch_family.h, hwy_launch_rules.h, hwy_launch_units.h), for the kernel translation
+// units.
 struct HipBackend {
   // Kernel timing (hwy_profile_enable, the turn tuner): every launch goes through hipExtLaunchKernelGGL, which records the DISPATCH's
   // own begin and end timestamps into the two events of the Launch -- the same clock readings rocprofv3 --kernel-trace reports, with
@@ -24,6 +27,12 @@ struct HipBackend {
   template <typename K, typename... A>
   static hipError_t launch(K kernel, unsigned grid, int block, int lds, const Launch &l, const A &...a) {
     hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, l.stream, l.start, l.stop, 0, a...);
+    return hipGetLastError();
+  }
+  // The add-on units (hwy_launch_units.h): a plain launch, never the timed path.
+  template <typename K, typename A>
+  static hipError_t launch_plain(K kernel, unsigned grid, int block, int lds, hipStream_t stream, const A &a) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, stream, a);
     return hipGetLastError();
   }
   // How many workgroups of a kernel the device holds at once (occupancy x compute units): the issue-priority turns (hwy_wave.h:
@@ -88,7 +97,6 @@ hipError_t launch_score(const ScoreParams &sp, hipStream_t stream);
 // One step of the optimistic planner's tree (hwy_opd.h: ingest, backup, selection or the plan; op.E wavefronts)
 hipError_t launch_opd(const OpdParams &op, hipStream_t stream);
 // Action mask of the current state (hwy_mask.h, hwy_kernels_mask.hip: one thread per (environment, agent), row r -> mp.mask + r * n_ids)
-struct MaskParams;
 hipError_t launch_mask(const MaskParams &mp, hipStream_t stream);
 hipError_t launch_math_probe(int op, const double *in, double *out, long long n, hipStream_t stream);
 }  // namespace hwy

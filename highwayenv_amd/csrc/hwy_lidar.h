@@ -24,7 +24,7 @@
 // the same code on the GPU and in the CPU emulation).
 //
 // Like hwy_device.h this header includes no HIP runtime: hwy_kernels_lidar.hip includes <hip/hip_runtime.h> first, the CPU
-// emulation (tests/emu/emu_lidar.cpp) its shim.
+// emulation (tests/emu/emu_lidar.cpp) its shim, hip_emu.h.  The launch rule is hwy_launch_units.h's (select_lidar), for both.
 #pragma once
 
 #include <stdint.h>
@@ -34,6 +34,8 @@
 #include "hwy_device.h"
 
 namespace hwy {
+
+#define HWY_LIDAR_UNIT  // (hwy_launch_units.h: this unit's kernel is in the translation unit)
 
 struct LidarParams {
   const double *x, *y, *heading, *speed;  // [E][pitch]

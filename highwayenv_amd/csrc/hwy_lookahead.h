@@ -18,7 +18,8 @@
 // statements, so -ffp-contract=on fuses nothing: the returns are bit for bit what numpy computes by the same recurrence.
 //
 // Like hwy_ttc.h this header includes no HIP runtime: hwy_kernels_lookahead.hip includes <hip/hip_runtime.h> first, the CPU
-// emulation (tests/emu/emu_lookahead.cpp) its shim.
+// emulation (tests/emu/emu_lookahead.cpp, emu_opd.cpp) its shim, hip_emu.h.  The launch rules of the two kernels are
+// hwy_launch_units.h's, for both.
 #pragma once
 
 #include <stdint.h>
@@ -108,6 +109,55 @@ inline int score_validate(const hwy_config &c, int32_t k_steps, int32_t branches
   if ((has_q || has_best_action) != has_first) { *why = "first_action must be NULL iff q and best_action are NULL"; return HWY_ERR_INVALID_ARG; }
   if (lookahead_num_ids(c) > HWY_SCORE_MAX_IDS) { *why = "action table too large"; return HWY_ERR_INVALID_ARG; }
   return HWY_OK;
+}
+
+// host side: the planes of ONE engine that a fork reads or writes ([envs][pitch] each, envs = cfg->num_envs).  The engine passes its
+// packed words (n_i32 = 1: whole words, the rank hint travels), the CPU emulation its four integer planes lane | target | speed
+// index | flags (n_i32 = 4).
+struct ForkView {
+  const hwy_config *cfg;
+  double *f64[9];      // x | y | heading | speed | timer | target_speed | delta | impact_x | impact_y
+  double *behavior;    // [HWY_BEHAVIOR_PARAMS][envs][pitch] of a Linear engine
+  int32_t *i32[HWY_FORK_MAX_I32_PLANES];
+  int32_t n_i32;
+  double *controls;    // [2][envs][A] of a direct-control engine
+  double *time;        // [envs]
+  uint32_t *episode;   // [envs]
+  uint8_t *done;       // [envs]
+  int32_t pitch;
+};
+// ... and the arguments of a fork between two of them (fork_validate has passed: the configs agree)
+inline ForkParams fork_params(const ForkView &dst, const ForkView &src, int32_t branches, const int32_t *src_env) {
+  ForkParams p;
+  memset(&p, 0, sizeof p);
+  const size_t splane = (size_t)src.cfg->num_envs * src.pitch, dplane = (size_t)dst.cfg->num_envs * dst.pitch;
+  for (int f = 0; f < 9; ++f) { p.src_f64[f] = src.f64[f]; p.dst_f64[f] = dst.f64[f]; }
+  p.n_f64 = 9;
+  if (dst.cfg->traffic_model == HWY_TRAFFIC_LINEAR)
+    for (int f = 0; f < HWY_BEHAVIOR_PARAMS; ++f, ++p.n_f64) { p.src_f64[9 + f] = src.behavior + f * splane; p.dst_f64[9 + f] = dst.behavior + f * dplane; }
+  for (int f = 0; f < dst.n_i32; ++f) { p.src_i32[f] = src.i32[f]; p.dst_i32[f] = dst.i32[f]; }
+  p.n_i32 = dst.n_i32;
+  if (dst.cfg->ego_control == HWY_EGO_DIRECT) { p.src_controls = src.controls; p.dst_controls = dst.controls; }
+  p.src_time = src.time; p.dst_time = dst.time;
+  p.src_episode = src.episode; p.dst_episode = dst.episode;
+  p.dst_done = dst.done;
+  p.src_env = src_env;
+  p.pitch = dst.pitch; p.A = dst.cfg->num_agents; p.branches = branches;
+  p.src_envs = src.cfg->num_envs; p.dst_envs = dst.cfg->num_envs;
+  return p;
+}
+// host side: the arguments of the fold of a K-step rollout of a config's environments (score_validate has passed)
+inline ScoreParams score_params(const hwy_config &c, int32_t k_steps, int32_t branches, double gamma, const int32_t *first_action,
+                                const double *reward, const uint8_t *terminated, const uint8_t *truncated, double *ret, double *q,
+                                int32_t *best_action, int32_t *best_branch) {
+  ScoreParams p;
+  memset(&p, 0, sizeof p);
+  p.first_action = first_action; p.reward = reward; p.terminated = terminated; p.truncated = truncated;
+  p.ret = ret; p.q = q; p.best_action = best_action; p.best_branch = best_branch;
+  p.gamma = gamma;
+  p.K = k_steps; p.branches = branches; p.A = c.num_agents; p.n_ids = lookahead_num_ids(c);
+  p.groups = c.num_envs / branches;
+  return p;
 }
 
 // ---- hwy_fork_kernel -------------------------------------------------------------------------------------------------------------------

@@ -26,7 +26,7 @@
 // read from the config's table instead of the step kernels' LDS copy (this kernel uses no LDS).
 //
 // Like hwy_lidar.h this header includes no HIP runtime: hwy_kernels_mask.hip includes <hip/hip_runtime.h> first, the CPU emulation
-// (tests/emu/emu_mask.cpp) its shim.
+// (tests/emu/emu_mask.cpp) its shim, hip_emu.h.  The launch rule is hwy_launch_units.h's (select_mask), for both.
 #pragma once
 
 #include <stdint.h>

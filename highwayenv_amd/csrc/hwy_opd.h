@@ -28,7 +28,8 @@
 // actions -- the action mask of its state, written by hwy_mask.h's kernel on the work engine between the gather and the step -- get
 // no child.  The two kernels share the __device__ body opd_tree_step<CAP, MASKED>; see there.
 //
-// Like hwy_lookahead.h this header includes no HIP runtime.
+// Like hwy_lookahead.h this header includes no HIP runtime.  The launch rule of the two kernels is hwy_launch_units.h's and the
+// sequence of launches around them opd_expand's below, for the product and for the CPU emulation (tests/emu/emu_opd.cpp).
 #pragma once
 
 #include "hwy_lookahead.h"
@@ -94,6 +95,72 @@ inline int opd_validate(const hwy_config &src, const hwy_config &tree, const hwy
   if (params->nodes != nodes) { *why = "nodes must be 1 + (budget / n_ids) * n_ids"; return HWY_ERR_INVALID_ARG; }
   if ((int64_t)tree.num_envs != (int64_t)src.num_envs * nodes) { *why = "tree.num_envs must be src.num_envs * nodes"; return HWY_ERR_INVALID_ARG; }
   if ((int64_t)work.num_envs != (int64_t)src.num_envs * n) { *why = "work.num_envs must be src.num_envs * n_ids"; return HWY_ERR_INVALID_ARG; }
+  return HWY_OK;
+}
+
+// host side: the planner's own arrays (the layout of OpdParams' fields of the same names; created / child_mask: the masked search's)
+struct OpdTree {
+  double *ret, *disc, *upper0;
+  uint8_t *done;
+  int32_t *expanded_node, *gather_src, *scatter_src, *root_src, *actions;
+  uint8_t *created, *child_mask;
+};
+// ... the plan's outputs (everything but action may be null)
+struct OpdPlan {
+  int32_t *action;
+  double *value, *upper;
+  int32_t *sequence, *expanded;
+};
+// ... and the arguments of the tree kernel over them and the work engine's step outputs (opd_validate has passed); p.x is the
+// launch's own
+inline OpdParams opd_params(const hwy_opd_params &params, int32_t num_envs, const OpdTree &t, const double *reward,
+                            const uint8_t *terminated, const uint8_t *truncated, const OpdPlan &out) {
+  OpdParams p;
+  memset(&p, 0, sizeof p);
+  p.ret = t.ret; p.disc = t.disc; p.upper0 = t.upper0; p.done = t.done;
+  p.expanded_node = t.expanded_node;
+  p.reward = reward; p.terminated = terminated; p.truncated = truncated;
+  p.gather_src = t.gather_src; p.scatter_src = t.scatter_src; p.root_src = t.root_src;
+  p.actions = t.actions;
+  p.action = out.action; p.value = out.value; p.upper = out.upper; p.sequence = out.sequence; p.expanded = out.expanded;
+  p.gamma = params.gamma; p.bound = params.bound;
+  p.X = params.budget / params.n_ids; p.n = params.n_ids; p.M = params.nodes; p.E = num_envs;
+  if (params.flags & HWY_OPD_MASKED) { p.created = t.created; p.child_mask = t.child_mask; }
+  return p;
+}
+
+// host side: THE sequence of a plan -- per expansion x the tree kernel, the root's state into tree slot e * M and the parent's into all
+// n work environments of e (x == 0) or the gather tree -> work, the mask of the selected leaf on the work engine (masked search:
+// work's n copies of its state, row e * n is read, before the step moves them), one step of the work engine with the action plane
+// the kernel wrote, the scatter work -> tree; and one more kernel for the plan.  Generic over what enqueues (hwy_engine.hip:
+// hwy_opd_plan_device, on streams) or runs (tests/emu/emu_opd.cpp) the operations, each returning 0 or the status the plan ends with:
+//   ops.after(waiter, signaler)             waiter's stream continues behind what signaler's holds so far (the emulation: nothing)
+//   ops.kernel(const OpdParams &)           the tree kernel
+//   ops.fork(dst, src, branches, src_env)   hwy_fork_device between two of the three engines (it orders destination behind source)
+//   ops.mask()                              the action mask of the work engine into p.child_mask
+//   ops.step(actions)                       one policy step of the work engine, outputs to p.reward / p.terminated / p.truncated
+// Everything of the planner's own runs on work's stream.  Before a tree kernel rewrites the scatter's indices, the scatter that reads
+// them on tree's stream has to be over.
+enum OpdEngine { OPD_SRC, OPD_TREE, OPD_WORK };
+template <typename Ops>
+int opd_expand(OpdParams p, Ops &&ops) {
+  for (int32_t x = 0; x <= p.X; ++x) {
+    if (int rc = ops.after(OPD_WORK, OPD_TREE)) return rc;
+    p.x = x;
+    if (int rc = ops.kernel(p)) return rc;
+    if (x == p.X) break;
+    if (x == 0) {
+      if (int rc = ops.after(OPD_TREE, OPD_WORK)) return rc;
+      if (int rc = ops.fork(OPD_TREE, OPD_SRC, 1, p.root_src)) return rc;
+      if (int rc = ops.fork(OPD_WORK, OPD_SRC, p.n, nullptr)) return rc;
+    } else {
+      if (int rc = ops.fork(OPD_WORK, OPD_TREE, 1, p.gather_src)) return rc;
+    }
+    if (p.child_mask)
+      if (int rc = ops.mask()) return rc;
+    if (int rc = ops.step(p.actions)) return rc;
+    if (int rc = ops.fork(OPD_TREE, OPD_WORK, 1, p.scatter_src)) return rc;
+  }
   return HWY_OK;
 }
 

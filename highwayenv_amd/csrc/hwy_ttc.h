@@ -22,7 +22,7 @@
 // the reference's own).
 //
 // Like hwy_lidar.h this header includes no HIP runtime: hwy_kernels_ttc.hip includes <hip/hip_runtime.h> first, the CPU emulation
-// (tests/emu/emu_ttc.cpp) its shim.
+// (tests/emu/emu_ttc.cpp) its shim, hip_emu.h.  The launch rule is hwy_launch_units.h's (select_ttc), for both.
 #pragma once
 
 #include <stdint.h>

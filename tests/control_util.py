@@ -1,21 +1,20 @@
 """Shared helpers of the direct-ego-control (``DiscreteAction``) tests: the fixtures of tests/golden/control and the backends
-(``emu`` = tests/emu/emu_control.py on the CPU, ``hip`` = the engine on the MI355X)."""
+(``emu`` = tests/emu/emu.py on the CPU, ``hip`` = the engine on the MI355X)."""
 from __future__ import annotations
 
 import json
 import os
 
 import numpy as np
-import pytest
 
 from highwayenv_amd import _abi
+from tests.backends import BACKENDS, make_engine  # noqa: F401  (re-exported)
 from tests.golden_util import Golden
 
 CONTROL_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "control")
 FIXTURES = ["direct_fast", "direct_v0", "direct_k5", "direct_throttle", "direct_brake", "direct_offroad", "direct_offroad_terminal",
             "direct_longi_only", "direct_lat_only", "direct_ma2", "direct_n100", "direct_crash_many", "direct_rival"]
 WITH_FRAMES = [n for n in FIXTURES if n not in ("direct_offroad_terminal", "direct_crash_many", "direct_rival")]
-BACKENDS = [pytest.param("emu", id="emu"), pytest.param("hip", id="hip", marks=pytest.mark.gpu)]
 
 
 class ControlGolden(Golden):
@@ -50,11 +49,3 @@ class ControlGolden(Golden):
                 a = a[envs]
             out.append(np.ascontiguousarray(a[:, agents]))
         return out[0], out[1]
-
-
-def make_engine(backend: str, cfg):
-    if backend == "emu":
-        from tests.emu.emu_control import EmuControlEngine
-        return EmuControlEngine(cfg)
-    from highwayenv_amd.engine import Engine
-    return Engine(cfg)

@@ -1,13 +1,14 @@
-// emu_opd.cpp -- TEST INFRASTRUCTURE ONLY.  Runs the optimistic planner's tree kernel of the product source
-// (highwayenv_amd/csrc/hwy_opd.h: hwy_opd_kernel) on the CPU through hip_emu.h, with the validation (opd_validate) that
-// hwy_engine.hip makes, and hwy_fork_kernel in its DEVICE form: the source indices are not validated, an index outside the source
-// copies nothing -- which is what the planner's scatter relies on.  The simulation is the family's own driver's:
-// tests/emu/emu_opd.py launches kernel, gather, step and scatter behind each other the way hwy_opd_plan_device enqueues them.
+// emu_opd.cpp -- TEST INFRASTRUCTURE ONLY.  Runs a plan of the optimistic planner on the CPU through hip_emu.h: the product's
+// validation (opd_validate), arguments (opd_params), launch rule (hwy_launch_units.h: select_opd -- masked or not) and SEQUENCE
+// (highwayenv_amd/csrc/hwy_opd.h: opd_expand, the template hwy_opd_plan_device enqueues on the device), with the tree kernels and the
+// forks (emu_fork.h: hwy_fork_kernel in its device form) run here, inside the one call that holds the schedule, and the work engine's
+// mask and step -- which live in other emulator libraries -- called back into tests/emu/emu.py.
 #include "hip_emu.h"
 
 #include <string>
 
 #include "../../highwayenv_amd/csrc/hwy_opd.h"
+#include "emu_fork.h"
 
 static std::string g_error;
 
@@ -15,6 +16,7 @@ extern "C" {
 
 size_t emu_opd_config_size(void) { return sizeof(hwy_config); }
 size_t emu_opd_params_size(void) { return sizeof(hwy_opd_params); }
+size_t emu_opd_tree_size(void) { return sizeof(hwy::OpdTree) + sizeof(hwy::OpdPlan); }
 int emu_opd_max_nodes(void) { return HWY_OPD_MAX_NODES; }
 const char *emu_opd_last_error(void) { return g_error.c_str(); }
 
@@ -26,54 +28,53 @@ int emu_opd_validate(const hwy_config *src, const hwy_config *tree, const hwy_co
   return rc;
 }
 
-// hwy_fork_device with source indices (tests/emu/emu_lookahead.cpp: emu_lookahead_fork is the validated host form)
-int emu_opd_fork_device(const hwy_config *dst_cfg, const hwy_config *src_cfg, const hwy_state *dst, const hwy_state *src, double *dst_extra,
-                        const double *src_extra, uint8_t *dst_done, uint32_t *dst_episode, const uint32_t *src_episode, int32_t branches,
-                        const int32_t *src_env) {
-  const char *why = "";
-  if (const int rc = hwy::fork_validate(*dst_cfg, *src_cfg, dst->x == src->x, branches, src_env != nullptr, &why)) { g_error = why; return rc; }
-  hwy::ForkParams p;
-  memset(&p, 0, sizeof p);
-  const double *sf[9] = {src->x, src->y, src->heading, src->speed, src->timer, src->target_speed, src->delta, src->impact_x, src->impact_y};
-  double *df[9] = {dst->x, dst->y, dst->heading, dst->speed, dst->timer, dst->target_speed, dst->delta, dst->impact_x, dst->impact_y};
-  for (int f = 0; f < 9; ++f) { p.src_f64[f] = sf[f]; p.dst_f64[f] = df[f]; }
-  p.n_f64 = 9;
-  const int N = dst_cfg->num_vehicles;
-  if (dst_cfg->traffic_model == HWY_TRAFFIC_LINEAR)
-    for (int f = 0; f < HWY_BEHAVIOR_PARAMS; ++f, ++p.n_f64) {
-      p.src_f64[9 + f] = src_extra + (size_t)f * src_cfg->num_envs * N;
-      p.dst_f64[9 + f] = dst_extra + (size_t)f * dst_cfg->num_envs * N;
+// the work engine's mask into t->child_mask / its step with t->actions, outputs to reward | terminated | truncated: 0 or a status
+typedef int (*emu_opd_callback)(void);
+
+// The launches behind a passed emu_opd_validate: hwy_opd_plan_device on the host arrays of three engines and of the planner.
+int emu_opd_plan(const emu_engine_view *src, const emu_engine_view *tree, const emu_engine_view *work, const hwy_opd_params *params,
+                 const hwy::OpdTree *t, const double *reward, const uint8_t *terminated, const uint8_t *truncated, const hwy::OpdPlan *out,
+                 emu_opd_callback mask, emu_opd_callback step) {
+  struct Ops {
+    const emu_engine_view *eng[3];  // by hwy::OpdEngine
+    emu_opd_callback mask_, step_;
+    int after(int, int) { return HWY_OK; }  // (no streams: every operation is over when it returns)
+    int kernel(const hwy::OpdParams &p) { return emu::launch_status(hwy::select_opd<emu::PlainBackend>(p, nullptr)); }
+    int fork(int dst, int src, int32_t branches, const int32_t *src_env) {
+      const char *why = "";
+      if (const int rc = hwy::fork_validate(*eng[dst]->cfg, *eng[src]->cfg, false, branches, src_env != nullptr, &why)) { g_error = why; return rc; }
+      return emu_fork::fork(*eng[dst], *eng[src], branches, src_env);
     }
-  const int32_t *si[4] = {src->lane, src->target_lane, src->speed_index, src->flags};
-  int32_t *di[4] = {dst->lane, dst->target_lane, dst->speed_index, dst->flags};
-  for (int f = 0; f < 4; ++f) { p.src_i32[f] = si[f]; p.dst_i32[f] = di[f]; }
-  p.n_i32 = 4;
-  if (dst_cfg->ego_control == HWY_EGO_DIRECT) { p.src_controls = src_extra; p.dst_controls = dst_extra; }
-  p.src_time = src->time; p.dst_time = dst->time;
-  p.src_episode = src_episode; p.dst_episode = dst_episode;
-  p.dst_done = dst_done;
-  p.src_env = src_env;
-  p.pitch = N; p.A = dst_cfg->num_agents; p.branches = branches;
-  p.src_envs = src_cfg->num_envs; p.dst_envs = dst_cfg->num_envs;
-  emu::launch([](const hwy::ForkParams &a) { hwy::hwy_fork_kernel<HWY_FORK_THREADS>(a); }, p.dst_envs, HWY_FORK_THREADS, p);
-  return HWY_OK;
+    int mask() { return mask_(); }
+    int step(const int32_t *) { return step_(); }
+  };
+  g_error = "a launch rule refused the arguments";
+  return hwy::opd_expand(hwy::opd_params(*params, src->cfg->num_envs, *t, reward, terminated, truncated, *out), Ops{{src, tree, work}, mask, step});
 }
 
-// launch x of hwy_opd_kernel on host arrays (the layout of hwy::OpdParams)
-int emu_opd_kernel(int32_t E, int32_t n, int32_t X, int32_t x, double gamma, double bound, double *ret, double *disc, double *upper0,
-                   uint8_t *done, int32_t *expanded_node, const double *reward, const uint8_t *terminated, const uint8_t *truncated,
-                   int32_t *gather_src, int32_t *scatter_src, int32_t *root_src, int32_t *actions, int32_t *action, double *value,
-                   double *upper, int32_t *sequence, int32_t *expanded) {
-  hwy::OpdParams p;
-  memset(&p, 0, sizeof p);
-  p.ret = ret; p.disc = disc; p.upper0 = upper0; p.done = done; p.expanded_node = expanded_node;
-  p.reward = reward; p.terminated = terminated; p.truncated = truncated;
-  p.gather_src = gather_src; p.scatter_src = scatter_src; p.root_src = root_src; p.actions = actions;
-  p.action = action; p.value = value; p.upper = upper; p.sequence = sequence; p.expanded = expanded;
-  p.gamma = gamma; p.bound = bound;
-  p.x = x; p.X = X; p.n = n; p.M = 1 + X * n; p.E = E;
-  if (p.M > HWY_OPD_MAX_NODES || x < 0 || x > X) { g_error = "launch outside the kernel's capacity"; return HWY_ERR_INVALID_ARG; }
-  emu::launch([](const hwy::OpdParams &a) { hwy::hwy_opd_kernel<HWY_OPD_MAX_NODES>(a); }, E, 64, p);
-  return HWY_OK;
+// The sequence opd_expand runs for n action ids, X expansions, masked or not, as text: one word per operation, in order.
+int emu_opd_sequence(int32_t n, int32_t X, int masked, char *buf, int len) {
+  static const char *who[3] = {"src", "tree", "work"};
+  struct Ops {
+    std::string text;
+    hwy::OpdParams q;
+    int after(int waiter, int signaler) { text += std::string("after(") + who[waiter] + "," + who[signaler] + ") "; return 0; }
+    int kernel(const hwy::OpdParams &p) { text += "kernel(" + std::to_string(p.x) + ") "; return 0; }
+    int fork(int dst, int src, int32_t branches, const int32_t *src_env) {
+      const char *idx = !src_env ? "none" : src_env == q.root_src ? "root" : src_env == q.gather_src ? "gather" : src_env == q.scatter_src ? "scatter" : "?";
+      text += std::string("fork(") + who[dst] + "," + who[src] + "," + std::to_string(branches) + "," + idx + ") ";
+      return 0;
+    }
+    int mask() { text += "mask "; return 0; }
+    int step(const int32_t *actions) { text += actions == q.actions ? "step " : "step(?) "; return 0; }
+  };
+  int32_t idx[4];  // (only their addresses are used)
+  uint8_t bytes[2];
+  const hwy_opd_params params = {X * n, n, 1 + X * n, masked ? HWY_OPD_MASKED : 0, 0.5, 2.0};
+  const hwy::OpdTree t = {nullptr, nullptr, nullptr, nullptr, nullptr, &idx[0], &idx[1], &idx[2], &idx[3], &bytes[0], &bytes[1]};
+  Ops ops{"", hwy::opd_params(params, 2, t, nullptr, nullptr, nullptr, hwy::OpdPlan{})};
+  const int rc = hwy::opd_expand(ops.q, ops);
+  if (len > 0) { strncpy(buf, ops.text.c_str(), (size_t)len - 1); buf[len - 1] = 0; }
+  return rc;
 }
 }

@@ -422,6 +422,17 @@ void launch(K kernel, int grid, int block, const P &params) {
   fibers = nullptr;
   cur = nullptr;
 }
+// the emulation's backend of the add-on units' launch layer (highwayenv_amd/csrc/hwy_launch_units.h): the workgroups run one after
+// the other on the CPU, LDS is the kernel's own statics and there is no stream
+struct PlainBackend {
+  template <typename K, typename A>
+  static hipError_t launch_plain(K kernel, int grid, int block, int, hipStream_t, const A &a) {
+    launch(kernel, grid, block, a);
+    return hipSuccess;
+  }
+};
+// the status a driver answers for a launch its rule refused (hwy_engine.hip: HWY_HIP)
+inline int launch_status(hipError_t e) { return e == hipSuccess ? 0 : -2; }
 }  // namespace emu
 
 // the schedule and its checks, for the Python drivers (tests/emu/emu.py: EmuEngine.set_schedule / schedule_errors).  Defined here,

@@ -9,26 +9,9 @@ import numpy as np
 
 from highwayenv_amd import _abi, spawn
 from oracle import oracle
+from tests.backends import make_engine  # noqa: F401  (re-exported)
 from tests.golden_util import assert_obs_close, assert_state_close
 from tests.lidar_util import cells_off
-
-
-def make_engine(backend: str, cfg):
-    """``hip``: the product on the MI355X; ``emu``: the emulation of the kernels that configuration runs."""
-    if backend != "emu":
-        from highwayenv_amd.engine import Engine
-        return Engine(cfg)
-    if cfg.obs_type == _abi.OBS_LIDAR:
-        from tests.emu.emu_lidar import EmuLidarEngine
-        return EmuLidarEngine(cfg)
-    if cfg.traffic_model == _abi.TRAFFIC_LINEAR:
-        from tests.emu.emu_traffic import EmuTrafficEngine
-        return EmuTrafficEngine(cfg)
-    if cfg.ego_control == _abi.EGO_DIRECT:
-        from tests.emu.emu_control import EmuControlEngine
-        return EmuControlEngine(cfg)
-    from tests.emu.emu import EmuEngine
-    return EmuEngine(cfg)
 
 
 def load_engine(eng, st: dict) -> None:
@@ -112,7 +95,6 @@ def check_free_running_steps(g):
             np.testing.assert_array_equal(st["speed"][rows][:, agents], want["speed"][rows][:, agents], err_msg=f"{what}: the egos' speed")
         alive &= ~term
     return cells, worst
-
 
 
 def assert_lidar_of_own_state(cfg, eng, obs, what: str, rows=None) -> None:

@@ -1,20 +1,19 @@
 """Shared helpers of the LidarObservation tests: the fixtures of tests/golden/lidar and the backends (``emu`` =
-tests/emu/emu_lidar.py on the CPU, ``hip`` = the engine on the MI355X)."""
+tests/emu/emu.py on the CPU, ``hip`` = the engine on the MI355X)."""
 from __future__ import annotations
 
 import json
 import os
 
 import numpy as np
-import pytest
 
 from highwayenv_amd import _abi
+from tests.backends import BACKENDS, make_engine  # noqa: F401  (re-exported)
 from tests.golden_util import Golden
 
 LIDAR_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lidar")
 RUNS = ["lidar_fast", "lidar_v0", "lidar_cells64_raw", "lidar_ma2", "lidar_n100", "lidar_linear", "lidar_direct", "lidar_crash"]
 FIXTURES = RUNS + ["lidar_crafted"]
-BACKENDS = [pytest.param("emu", id="emu"), pytest.param("hip", id="hip", marks=pytest.mark.gpu)]
 OBS_ATOL = 1e-6  # the project's observation tolerance (an f32 ulp at 1 is 6e-8)
 
 
@@ -54,14 +53,6 @@ class LidarGolden(Golden):
     def reference_obs(self, index=None) -> np.ndarray:
         """[E, A, cells, 2]: the reference's observation at reset (None) or after step `index`."""
         return self.z["obs0"] if index is None else self.z["obs"][index]
-
-
-def make_engine(backend: str, cfg):
-    if backend == "emu":
-        from tests.emu.emu_lidar import EmuLidarEngine
-        return EmuLidarEngine(cfg)
-    from highwayenv_amd.engine import Engine
-    return Engine(cfg)
 
 
 def cells_off(got: np.ndarray, want: np.ndarray, atol: float = OBS_ATOL) -> int:

@@ -1,21 +1,21 @@
 """Shared helpers of the lookahead tests (environment fork, scoring of action sequences, plan_lookahead): the fixtures of
-tests/golden/lookahead, the backends (``emu`` = tests/emu/emu_lookahead.py on the CPU, ``hip`` = the engine on the MI355X), the
+tests/golden/lookahead, the backends (``emu`` = tests/emu/emu.py on the CPU, ``hip`` = the engine on the MI355X), the
 environment classes on either backend, and the numpy restatement of the return recurrence every output is held to bit for bit."""
 from __future__ import annotations
 
 import os
 
 import numpy as np
-import pytest
 
 from highwayenv_amd import _abi, envs
+from tests import backends
+from tests.backends import BACKENDS, make_engine  # noqa: F401  (re-exported)
 from tests.ttc_util import TtcGolden
 
 DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lookahead")
 TREE = ["la_fast", "la_trunc", "la_v0", "la_linear"]   # single agent, meta-actions: the 25 depth-2 sequences padded to K = 4
 EXPLICIT = ["la_ma2", "la_direct"]                     # explicit sequences
 FIXTURES = TREE + EXPLICIT
-BACKENDS = [pytest.param("emu", id="emu"), pytest.param("hip", id="hip", marks=pytest.mark.gpu)]
 REWARD_ATOL = 1e-9   # tests/golden_util.py's tolerance for rewards
 
 
@@ -44,21 +44,9 @@ class LookaheadGolden(TtcGolden):
                              np.ascontiguousarray(self.z["init_act_steering"][:, agents]))
 
 
-def make_engine(backend: str, cfg):
-    if backend == "emu":
-        from tests.emu.emu_lookahead import EmuLookaheadEngine
-        return EmuLookaheadEngine(cfg)
-    from highwayenv_amd.engine import Engine
-    return Engine(cfg)
-
-
 def env_class(backend: str, fast: bool = True):
-    """BatchedHighwayEnv(Fast) on the backend: the tests substitute the CPU emulation of the same kernel source."""
-    base = envs.BatchedHighwayEnvFast if fast else envs.BatchedHighwayEnv
-    if backend != "emu":
-        return base
-    from tests.emu.emu_lookahead import EmuLookaheadEngine
-    return type("Emu" + base.__name__, (base,), {"_engine_factory": staticmethod(lambda cfg, device, stream: EmuLookaheadEngine(cfg))})
+    """BatchedHighwayEnv(Fast) on the backend."""
+    return backends.env_class(backend, envs.BatchedHighwayEnvFast if fast else envs.BatchedHighwayEnv)
 
 
 def with_envs(cfg: _abi.HwyConfig, num_envs: int) -> _abi.HwyConfig:

@@ -1,19 +1,18 @@
 """Shared helpers of the action-mask tests: the fixtures of tests/golden/masks (make_golden_masks.py's record), the backends
-(``emu`` = tests/emu/emu_mask.py on the CPU, ``hip`` = the engine on the MI355X) and the reference's list order."""
+(``emu`` = tests/emu/emu.py on the CPU, ``hip`` = the engine on the MI355X) and the reference's list order."""
 from __future__ import annotations
 
 import json
 import os
 
 import numpy as np
-import pytest
 
 from highwayenv_amd import _abi, envs
+from tests.backends import BACKENDS, emu_class, make_engine  # noqa: F401  (re-exported)
 
 MASK_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "masks")
 FIXTURES = ["mask_fast", "mask_lanes1", "mask_lanes2", "mask_speeds2", "mask_speeds8", "mask_longi", "mask_lat", "mask_ma2",
             "mask_placed", "mask_merge", "mask_merge_generic", "mask_intersection", "mask_intersection_ma"]
-BACKENDS = [pytest.param("emu", id="emu"), pytest.param("hip", id="hip", marks=pytest.mark.gpu)]
 # columns of the three action tables (include/hwy_engine.h: hwy_config.action_set)
 COLUMNS = {_abi.ACTIONS_SET_ALL: ("LANE_LEFT", "IDLE", "LANE_RIGHT", "FASTER", "SLOWER"),
            _abi.ACTIONS_SET_LONGI: ("SLOWER", "IDLE", "FASTER"), _abi.ACTIONS_SET_LAT: ("LANE_LEFT", "IDLE", "LANE_RIGHT")}
@@ -79,20 +78,6 @@ def generator():
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
-
-
-def make_engine(backend: str, cfg):
-    if backend == "emu":
-        from tests.emu.emu_mask import EmuMaskEngine
-        return EmuMaskEngine(cfg)
-    from highwayenv_amd.engine import Engine
-    return Engine(cfg)
-
-
-def emu_class(base):
-    """`base` (a Batched*Env or a single-environment drop-in) on the CPU emulation of the kernels."""
-    from tests.emu.emu_mask import EmuMaskEngine
-    return type("EmuMask" + base.__name__, (base,), {"_engine_factory": staticmethod(lambda cfg, device, stream: EmuMaskEngine(cfg))})
 
 
 def reference_list(row, action_set: int) -> list:

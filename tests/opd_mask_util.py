@@ -6,26 +6,10 @@ from __future__ import annotations
 
 import numpy as np
 
-from highwayenv_amd import _abi, envs
+from highwayenv_amd import _abi
 from tests import opd_util
 from tests.lookahead_util import with_envs
-from tests.opd_util import BACKENDS, HostStates, assert_plan_equals, fast_config  # noqa: F401  (re-exported)
-
-
-def make_engine(backend: str, cfg):
-    if backend == "emu":
-        from tests.emu.emu_opd_mask import EmuOpdMaskEngine
-        return EmuOpdMaskEngine(cfg)
-    from highwayenv_amd.engine import Engine
-    return Engine(cfg)
-
-
-def env_class(backend: str):
-    base = envs.BatchedHighwayEnvFast
-    if backend != "emu":
-        return base
-    from tests.emu.emu_opd_mask import EmuOpdMaskEngine
-    return type("EmuOpdMask" + base.__name__, (base,), {"_engine_factory": staticmethod(lambda cfg, device, stream: EmuOpdMaskEngine(cfg))})
+from tests.opd_util import BACKENDS, HostStates, assert_plan_equals, env_class, fast_config, make_engine  # noqa: F401  (re-exported)
 
 
 def make_env(backend: str, config: dict, num_envs: int, seed: int, warm=()):

@@ -1,4 +1,4 @@
-"""Shared helpers of the optimistic-planner tests (``plan_opd``, csrc/hwy_opd.h): the backends (``emu`` = tests/emu/emu_opd.py on
+"""Shared helpers of the optimistic-planner tests (``plan_opd``, csrc/hwy_opd.h): the backends (``emu`` = tests/emu/emu.py on
 the CPU, ``hip`` = the engine on the MI355X), the environment classes on either, and the YARDSTICK: ``restate_opd``, a plain
 Python / NumPy restatement of the rules of DESIGN.md ("OPD on the device").  It keeps every node's state on the host (get_state /
 set_state, Linear behaviour and stored controls included), steps the children with the ordinary ``step`` of a scratch engine of the
@@ -7,30 +7,12 @@ Comparisons with it are exact: action, sequence, expanded, and the bits of value
 from __future__ import annotations
 
 import numpy as np
-import pytest
 
-from highwayenv_amd import _abi, envs
-from tests.lookahead_util import assert_bits, with_envs  # noqa: F401  (re-exported)
+from highwayenv_amd import _abi
+from tests.backends import BACKENDS, make_engine  # noqa: F401  (re-exported)
+from tests.lookahead_util import assert_bits, env_class, with_envs  # noqa: F401  (re-exported)
 
-BACKENDS = [pytest.param("emu", id="emu"), pytest.param("hip", id="hip", marks=pytest.mark.gpu)]
 STATE_KEYS = _abi.STATE_F64 + _abi.STATE_I32 + ["time"]
-
-
-def make_engine(backend: str, cfg):
-    if backend == "emu":
-        from tests.emu.emu_opd import EmuOpdEngine
-        return EmuOpdEngine(cfg)
-    from highwayenv_amd.engine import Engine
-    return Engine(cfg)
-
-
-def env_class(backend: str, fast: bool = True):
-    """BatchedHighwayEnv(Fast) on the backend: the tests substitute the CPU emulation of the same kernel source."""
-    base = envs.BatchedHighwayEnvFast if fast else envs.BatchedHighwayEnv
-    if backend != "emu":
-        return base
-    from tests.emu.emu_opd import EmuOpdEngine
-    return type("EmuOpd" + base.__name__, (base,), {"_engine_factory": staticmethod(lambda cfg, device, stream: EmuOpdEngine(cfg))})
 
 
 def fast_config(vehicles: int = 8, **over) -> dict:

@@ -113,8 +113,8 @@ def test_host_spawn_gives_the_ego_the_state_it_gives_it_today(name):
 class _EmuHighwayEnvFast(envs.HighwayEnvFast):
     @staticmethod
     def _engine_factory(cfg, device, stream):
-        from tests.emu.emu_control import EmuControlEngine
-        return EmuControlEngine(cfg)
+        from tests.emu.emu import EmuEngine
+        return EmuEngine(cfg)
 
 
 def test_single_env_drop_in_replays_direct_fast_env0():

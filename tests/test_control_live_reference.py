@@ -1,4 +1,4 @@
-"""The direct-ego-control kernels (CPU emulation, tests/emu/emu_control.py) against the LIVE unmodified reference on random
+"""The direct-ego-control kernels (CPU emulation, tests/emu/emu.py) against the LIVE unmodified reference on random
 configurations: drawn over vehicles_count, lanes_count, vehicles_density, simulation / policy frequency, controlled_vehicles,
 highway-v0 / highway-fast-v0 and the DiscreteAction keys (actions_per_axis, the two ranges, longitudinal / lateral, clip).  The
 reference is driven by the fixture generator (tests/golden/control/make_golden_control.py: run) and the emulation is held to the

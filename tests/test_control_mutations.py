@@ -47,8 +47,8 @@ def run_selection(lib, selection):
 @pytest.mark.parametrize("mutant,selection", CASES, ids=[c[0] for c in CASES])
 def test_broken_rule_fails_the_comparison_that_covers_it(mutant, selection):
     from concurrent.futures import ThreadPoolExecutor
-    from tests.emu import emu_control
-    emu_control.build()   # (the suite's own emulator build, before two processes could both start building it)
+    from tests.emu import emu
+    emu.build("control")   # (the suite's own emulator build, before two processes could both start building it)
     with ThreadPoolExecutor(2) as pool:   # the control and the mutant side by side (two subprocesses)
         f_good = pool.submit(run_selection, None, selection)
         f_bad = pool.submit(lambda: run_selection(build_mutant(mutant), selection))

@@ -278,7 +278,8 @@ def test_ulp_noise_only_moves_post_termination_wrecks():
                     "-DHWY_EMU_ULP_NOISE", "-o", noisy, src], check=True, capture_output=True)
     lib = C.CDLL(noisy)
     lib.emu_config_size.restype = C.c_size_t
-    saved, emu._lib = emu._lib, lib
+    emu.lib()
+    saved, emu._libs["sim"] = emu._libs["sim"], lib
     try:
         cfg_d = _abi.highway_fast_default_config()
         cfg_d.update({"vehicles_count": 50, "lanes_count": 4})
@@ -308,4 +309,4 @@ def test_ulp_noise_only_moves_post_termination_wrecks():
         assert live_bad == 0            # live episodes: immune to ulp noise
         print(f"ulp-noise probe: live mismatches {live_bad}, post-termination wreck mismatches {wreck_bad}")
     finally:
-        emu._lib = saved
+        emu._libs["sim"] = saved

@@ -179,10 +179,10 @@ def test_autoreset_against_the_oracle(backend, family):
         episode += done_prev
         respawns += int(done_prev.sum())
         if linear:
-            from tests.emu import emu_traffic
+            from tests.emu import emu
             for e in np.flatnonzero(done_prev):
                 for i in range(1, cfg.num_vehicles):
-                    np.testing.assert_array_equal(got["behavior"][e, i], emu_traffic.behavior_draw(BASE + e, i, int(episode[e])),
+                    np.testing.assert_array_equal(got["behavior"][e, i], emu.behavior_draw(BASE + e, i, int(episode[e])),
                                                   err_msg=f"{what}: env {e} vehicle {i}")
         if direct:  # Vehicle.__init__: the new ego's stored action is zero
             assert not got["ctl_accel"][done_prev].any() and not got["ctl_steer"][done_prev].any(), what

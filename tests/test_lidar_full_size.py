@@ -13,7 +13,7 @@ E, STEPS, CELLS = 4096, 30, 16
 @pytest.mark.gpu
 def test_headline_shape_hip_equals_emulator_and_properties():
     from highwayenv_amd.engine import Engine
-    from tests.emu import emu_lidar
+    from tests.emu import emu
     cfg_d = _abi.highway_fast_default_config()
     cfg_d.update({"vehicles_count": 50, "lanes_count": 4, "observation": {"type": "LidarObservation", "cells": CELLS}})
     cfg = _abi.make_config(cfg_d, E, fast=True)
@@ -33,7 +33,7 @@ def test_headline_shape_hip_equals_emulator_and_properties():
         assert untouched.any() and (~untouched).any(), what
         # |relative radial speed| <= |v_obstacle| + |v_observer| <= 2 * MAX_SPEED = 80 m/s
         assert np.abs(vel[~untouched]).max() <= 80.0 / 60.0, what
-        want = emu_lidar.trace(sub, {k: np.ascontiguousarray(v[watch]) for k, v in st.items()})
+        want = emu.trace(sub, {k: np.ascontiguousarray(v[watch]) for k, v in st.items()})
         bad = np.abs(obs[watch].astype(np.float64) - want) > 1e-6
         assert not bad.any(), f"{what}: {int(bad.any(-1).sum())} of {want[..., 0].size} watched cells differ from the emulation"
 

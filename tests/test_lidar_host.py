@@ -92,8 +92,8 @@ def test_spaces_and_shapes():
 def test_abi_struct_size_against_sizeof():
     """hwy_config as the C compilers lay it out (the engine library and the emulator's translation unit) against the ctypes
     mirror; the appended fields are the last 16 bytes."""
-    from tests.emu import emu_lidar
-    assert emu_lidar.lib().emu_lidar_config_size() == C.sizeof(_abi.HwyConfig)
+    from tests.emu import emu
+    assert emu.lib("lidar").emu_lidar_config_size() == C.sizeof(_abi.HwyConfig)
     lib = _lib.load()
     assert lib.hwy_abi_version() == 8 and lib.hwy_config_size() == C.sizeof(_abi.HwyConfig)
     assert _abi.HwyConfig.lidar_cells.offset == C.sizeof(_abi.HwyConfig) - 16
@@ -138,8 +138,8 @@ def test_create_rejects_bad_lidar_fields_before_it_needs_a_gpu():
 class _EmuHighwayEnvFast(envs.HighwayEnvFast):
     @staticmethod
     def _engine_factory(cfg, device, stream):
-        from tests.emu.emu_lidar import EmuLidarEngine
-        return EmuLidarEngine(cfg)
+        from tests.emu.emu import EmuEngine
+        return EmuEngine(cfg)
 
 
 def test_single_env_drop_in_replays_lidar_fast_env0():

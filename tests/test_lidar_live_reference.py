@@ -1,4 +1,4 @@
-"""The LidarObservation kernel (CPU emulation, tests/emu/emu_lidar.py) against the LIVE unmodified reference on random
+"""The LidarObservation kernel (CPU emulation, tests/emu/emu.py) against the LIVE unmodified reference on random
 configurations: drawn over cells, maximum_range, normalize, vehicles_count, lanes_count, vehicles_density, the frequencies,
 controlled_vehicles, highway-v0 / highway-fast-v0 and the family (IDM traffic, LinearVehicle traffic, DiscreteAction ego).  The
 reference is driven by the fixture generator (tests/golden/lidar/make_golden_lidar.py: run).  Every recorded state is loaded and

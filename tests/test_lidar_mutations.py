@@ -49,9 +49,8 @@ def run_selection(lib, selection):
 @pytest.mark.parametrize("mutant,selection", CASES, ids=[c[0] for c in CASES])
 def test_broken_rule_fails_the_comparison_that_covers_it(mutant, selection):
     from concurrent.futures import ThreadPoolExecutor
-    from tests.emu import emu, emu_control, emu_lidar, emu_traffic
-    for mod in (emu, emu_control, emu_traffic, emu_lidar):  # (the suite's own emulator builds, before two processes could both start one)
-        mod.build()
+    from tests.emu import emu
+    emu.build_all()  # (the suite's own emulator builds, before two processes could both start one)
     with ThreadPoolExecutor(2) as pool:   # the control and the mutant side by side (two subprocesses)
         f_good = pool.submit(run_selection, None, selection)
         f_bad = pool.submit(lambda: run_selection(build_mutant(mutant), selection))

@@ -117,7 +117,7 @@ def test_rollout_equals_steps(backend, name):
 def test_autoreset_step_returns_the_new_episodes_lidar(backend):
     """Next-step auto-reset: the step that re-spawns an environment returns the lidar of the NEW episode's first state (reward 0),
     i.e. of the state that step left behind -- checked against the emulated kernel on the engine's own state."""
-    from tests.emu import emu_lidar
+    from tests.emu import emu
     g = LidarGolden("lidar_crash")
     cfg = g.hwy_config()
     eng = make_engine(backend, cfg)
@@ -129,12 +129,12 @@ def test_autoreset_step_returns_the_new_episodes_lidar(backend):
         before = eng.get_state()
         obs, reward, term, trunc, info = eng.step(g.actions_at(t % g.steps))
         st = eng.get_state()
-        want = emu_lidar.trace(cfg, st)
+        want = emu.trace(cfg, st)
         assert cells_off(obs, want) == 0, f"step {t}"
         for e in np.flatnonzero(done):
             respawned += 1
             assert st["time"][e] == 0.0 and reward[e, 0] == 0.0 and not term[e]
-            assert cells_off(obs[e], emu_lidar.trace(cfg, before)[e]) > 0  # not the finished episode's last state
+            assert cells_off(obs[e], emu.trace(cfg, before)[e]) > 0  # not the finished episode's last state
         done = np.asarray(term | trunc, bool)
     eng.close()
     assert respawned >= 3

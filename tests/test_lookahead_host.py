@@ -26,10 +26,10 @@ def _other_scenarios():
 
 
 def test_abi_is_additive():
-    from tests.emu import emu_lookahead
+    from tests.emu import emu
     lib = _lib.load()
     assert lib.hwy_abi_version() == _abi.HWY_ABI_VERSION == 8
-    assert lib.hwy_config_size() == C.sizeof(_abi.HwyConfig) == emu_lookahead.lib().emu_lookahead_config_size() == 6304
+    assert lib.hwy_config_size() == C.sizeof(_abi.HwyConfig) == emu.lib("lookahead").emu_lookahead_config_size() == 6304
     header = open(os.path.join(ROOT, "include", "hwy_engine.h")).read()
     assert "#define HWY_ABI_VERSION 8" in header
     for name in ("hwy_fork_device", "hwy_fork", "hwy_score_device", "hwy_score_rollout"):
@@ -46,7 +46,7 @@ def test_abi_is_additive():
 
 def test_fork_validation_statuses():
     """fork_validate: the statuses hwy_fork_device returns before any launch."""
-    from tests.emu.emu_lookahead import fork_status
+    from tests.emu.emu import fork_status
     src = _cfg()
     assert fork_status(lu.with_envs(src, 6), src, branches=2) == 0
     assert fork_status(lu.with_envs(src, 5), src, branches=1, has_source=True) == 0          # any size with source indices
@@ -67,28 +67,28 @@ def test_fork_validation_statuses():
 
 def test_score_validation_statuses():
     from highwayenv_amd.engine import EngineError
-    from tests.emu import emu_lookahead
+    from tests.emu import emu
     cfg = _cfg(envs_=6)
     r, f, a = np.zeros((2, 6, 1)), np.zeros((2, 6), np.uint8), np.zeros((6, 1), np.int32)
-    emu_lookahead.score(cfg, 2, 3, 0.9, a, r, f, f)
-    emu_lookahead.score(cfg, 2, 3, 0.9, None, r, f, f, want=("returns", "best_branch"))
+    emu.score(cfg, 2, 3, 0.9, a, r, f, f)
+    emu.score(cfg, 2, 3, 0.9, None, r, f, f, want=("returns", "best_branch"))
     for kw in (dict(k_steps=0), dict(branches=0), dict(branches=4), dict(gamma=np.inf), dict(gamma=np.nan), dict(reward=None),
                dict(terminated=None), dict(first_action=None), dict(want=("returns",))):
         args = dict(k_steps=2, branches=3, gamma=0.9, first_action=a, reward=r, terminated=f, truncated=f)
         want = kw.pop("want", ("returns", "q", "best_action", "best_branch"))
         args.update(kw)
         with pytest.raises(EngineError, match=f"status {_abi.HWY_ERR_INVALID_ARG}:"):
-            emu_lookahead.score(cfg, want=want, **args)
+            emu.score(cfg, want=want, **args)
     two = _abi.make_config(lu.highway_config(8, controlled_vehicles=2, action={"type": "MultiAgentAction", "action_config": {"type": "DiscreteMetaAction"}},
                                              observation={"type": "MultiAgentObservation", "observation_config": {"type": "Kinematics"}}), 6, fast=True)
     r2, a2 = np.zeros((2, 6, 2)), np.zeros((6, 2), np.int32)
-    emu_lookahead.score(two, 2, 3, 0.9, None, r2, f, f, want=("returns", "best_branch"))
+    emu.score(two, 2, 3, 0.9, None, r2, f, f, want=("returns", "best_branch"))
     for want in (("q",), ("best_action",)):   # A > 1
         with pytest.raises(EngineError, match="single agent"):
-            emu_lookahead.score(two, 2, 3, 0.9, a2, r2, f, f, want=want)
+            emu.score(two, 2, 3, 0.9, a2, r2, f, f, want=want)
     for name, other in _other_scenarios().items():
         with pytest.raises(NotImplementedError, match="hot-path scope"):
-            emu_lookahead.score(other, 1, 1, 1.0, None, np.zeros((1, 2, other.num_agents)), np.zeros((1, 2), np.uint8), np.zeros((1, 2), np.uint8),
+            emu.score(other, 1, 1, 1.0, None, np.zeros((1, 2, other.num_agents)), np.zeros((1, 2), np.uint8), np.zeros((1, 2), np.uint8),
                                 want=("returns",))
 
 
@@ -186,10 +186,10 @@ def test_lookahead_table_digits():
 
 def test_single_env_drop_in_plans():
     """The E == 1 drop-in offers the same calls (its child is the batched class)."""
-    from tests.emu.emu_lookahead import EmuLookaheadEngine
+    from tests.emu.emu import EmuEngine
 
     class Emu(envs.HighwayEnvFast):
-        _engine_factory = staticmethod(lambda cfg, device, stream: EmuLookaheadEngine(cfg))
+        _engine_factory = staticmethod(lambda cfg, device, stream: EmuEngine(cfg))
     env = Emu(lu.highway_config(8))
     best = env.plan_lookahead(2)
     assert best.shape == (1,) and 0 <= int(best[0]) < 5

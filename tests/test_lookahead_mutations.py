@@ -52,9 +52,8 @@ def run_selection(lib, selection):
 
 
 def _build_the_suites_own():
-    from tests.emu import emu, emu_control, emu_lidar, emu_lookahead, emu_traffic
-    for mod in (emu, emu_control, emu_traffic, emu_lidar, emu_lookahead):  # (before two processes could both start one)
-        mod.build()
+    from tests.emu import emu
+    emu.build_all()  # (before two processes could both start one)
 
 
 @pytest.mark.parametrize("mutant,selection", CASES, ids=[f"{c[0]}-{c[1][0].split('_')[-1][:-3]}" for c in CASES])

@@ -39,14 +39,14 @@ def config(B, A):
 
 
 def run_emu(cfg, B, K, A, gamma, arrays, schedule=None):
-    from tests.emu import emu, emu_lookahead
+    from tests.emu import emu
     reward, term, trunc, first = arrays
     sched = None
     if schedule is not None:
         sched = emu.Scheduled()
         sched.set_schedule(**schedule)
     want = ("returns", "q", "best_action", "best_branch") if A == 1 else ("returns", "best_branch")
-    out = emu_lookahead.score(cfg, K, B, gamma, first if A == 1 else None, reward, term, trunc, want=want, sched=sched)
+    out = emu.score(cfg, K, B, gamma, first if A == 1 else None, reward, term, trunc, want=want, sched=sched)
     if sched is not None:
         assert sched.schedule_errors() == 0, sched.schedule_error_text()
     return {k: v for k, v in out.items() if v is not None}

@@ -59,8 +59,8 @@ def test_every_registered_batched_class_has_it():
 
 
 def test_discrete_action_raises():
-    from tests.emu.emu_control import EmuControlEngine
-    cls = type("EmuDirect", (envs.BatchedHighwayEnvFast,), {"_engine_factory": staticmethod(lambda cfg, device, stream: EmuControlEngine(cfg))})
+    from tests.emu.emu import EmuEngine
+    cls = type("EmuDirect", (envs.BatchedHighwayEnvFast,), {"_engine_factory": staticmethod(lambda cfg, device, stream: EmuEngine(cfg))})
     env = cls({"action": {"type": "DiscreteAction"}, "vehicles_count": 5}, num_envs=2)
     env.reset(seed=0)
     with pytest.raises(NotImplementedError):

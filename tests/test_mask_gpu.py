@@ -20,7 +20,7 @@ SHAPES = [("highway-fast-v0", {"vehicles_count": 19}, 5), ("highway-fast-v0", {"
 
 
 def _hip_vs_emulator(env_id, config, E, steps=10):
-    from tests.emu import emu_mask
+    from tests.emu import emu
     cls = envs.batched_class(env_id)
     env = cls(dict(config), num_envs=E, spawn_mode="device", autoreset=True)
     env.reset(seed=11)
@@ -29,7 +29,7 @@ def _hip_vs_emulator(env_id, config, E, steps=10):
     seen = np.zeros(n_ids, int)
     for t in range(steps + 1):
         got = env._engine.action_mask()
-        want = emu_mask.action_mask(cfg, env._engine.get_state())
+        want = emu.action_mask(cfg, env._engine.get_state())
         np.testing.assert_array_equal(got, want, err_msg=f"{env_id} step {t}")
         seen += got.reshape(-1, n_ids).sum(axis=0)
         env.step(rng.integers(0, n_ids, size=(E, A)))

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from tests import mask_util, mutation_util
-from tests.emu import emu_mask
+from tests.emu import emu
 from tests.mask_util import MaskGolden
 
 H = "hwy_mask.h"
@@ -32,13 +32,13 @@ _libs = {}
 
 def mutant(name: str):
     if name not in _libs:
-        _libs[name] = emu_mask.load(mutation_util.build_mutant(MUTANTS[name], "emu_mask.cpp", f"libhwy_emu_mask_mut_{name}.so"))
+        _libs[name] = emu.load("mask", mutation_util.build_mutant(MUTANTS[name], "emu_mask.cpp", f"libhwy_emu_mask_mut_{name}.so"))
     return _libs[name]
 
 
 def mismatches(g: MaskGolden, L=None) -> int:
     cfg = g.hwy_config()
-    return sum(int((emu_mask.action_mask(cfg, g.state(i), L) != g.mask(i)).sum()) for i in g.indices())
+    return sum(int((emu.action_mask(cfg, g.state(i), L) != g.mask(i)).sum()) for i in g.indices())
 
 
 @pytest.mark.parametrize("name,fixture", CASES, ids=[f"{m}-{f}" for m, f in CASES])
@@ -64,8 +64,8 @@ def test_length_margin():
     g = MaskGolden("mask_merge")
     cfg = g.hwy_config()
     inside, outside = end_of_lane_state(g, 3.0), end_of_lane_state(g, 5.5)
-    assert emu_mask.action_mask(cfg, inside)[0, 0, 0] and not emu_mask.action_mask(cfg, outside)[0, 0, 0]
-    assert not emu_mask.action_mask(cfg, inside, mutant("no_length_margin"))[0, 0, 0]
+    assert emu.action_mask(cfg, inside)[0, 0, 0] and not emu.action_mask(cfg, outside)[0, 0, 0]
+    assert not emu.action_mask(cfg, inside, mutant("no_length_margin"))[0, 0, 0]
 
 
 # ---- the masked optimistic planner (csrc/hwy_opd.h: opd_tree_step<CAP, true>) -------------------------------------------------------
@@ -85,14 +85,14 @@ OPD_MUTANTS = {
 @pytest.mark.parametrize("name", sorted(OPD_MUTANTS))
 def test_broken_masked_search_fails_the_restatement(name):
     from tests import opd_mask_util as omu
-    from tests.emu import emu_opd_mask
+    from tests.emu import emu
     from tests.test_opd_mask import _env
     env = _env("emu", "lanes3_speeds3")
     want = omu.restate_masked_opd("emu", env, 50, 0.7)
     assert want["masked_out"].sum() > 0
     action, got = env.plan_opd(50, 0.7, return_details=True, masked=True)
     omu.assert_plan_equals(action, got, want, "the unmutated kernel source")
-    env._engine.masked_lib = emu_opd_mask.load(mutation_util.build_mutant(OPD_MUTANTS[name], "emu_opd_mask.cpp", f"libhwy_emu_opd_mask_mut_{name}.so"))
+    env._engine.opd_lib = emu.load("opd", mutation_util.build_mutant(OPD_MUTANTS[name], "emu_opd.cpp", f"libhwy_emu_opd_mask_mut_{name}.so"))
     action, got = env.plan_opd(50, 0.7, return_details=True, masked=True)
     with pytest.raises(AssertionError):
         omu.assert_plan_equals(action, got, want, name)

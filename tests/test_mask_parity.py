@@ -58,11 +58,11 @@ def test_fixtures_cover_what_they_are_for():
 
 
 def test_direct_control_is_refused():
-    from tests.emu import emu_mask
+    from tests.emu import emu
     cfg = _abi.make_config(dict(_abi.highway_fast_default_config(), action={"type": "DiscreteAction"}), 2, fast=True)
-    assert emu_mask.status(cfg) == _abi.HWY_ERR_UNSUPPORTED
+    assert emu.mask_status(cfg) == _abi.HWY_ERR_UNSUPPORTED
     with pytest.raises(NotImplementedError):
-        emu_mask.EmuMaskEngine(cfg).action_mask()
+        emu.EmuEngine(cfg).action_mask()
 
 
 def _reference_present() -> bool:
@@ -74,7 +74,7 @@ def _reference_present() -> bool:
 def test_live_reference_random_configurations():
     """Where the reference is present: random configurations run through the generator's own recorder (the unmodified reference,
     its knife-edge assertion included) and compared like the fixtures."""
-    from tests.emu import emu_mask
+    from tests.emu import emu
     gen = mask_util.generator()
     rng = np.random.default_rng(2024)
     for k in range(6):
@@ -89,7 +89,7 @@ def test_live_reference_random_configurations():
         g = MaskGolden(sc["name"], gen.run(sc))
         cfg = g.hwy_config()
         for index in g.indices():
-            np.testing.assert_array_equal(emu_mask.action_mask(cfg, g.state(index)), g.mask(index), err_msg=f"{sc}: state {index}")
+            np.testing.assert_array_equal(emu.action_mask(cfg, g.state(index)), g.mask(index), err_msg=f"{sc}: state {index}")
 
 
 def test_manifest_matches_the_fixtures():

@@ -26,12 +26,12 @@ def _other_scenarios():
 
 
 def test_abi_is_additive_and_the_kernel_is_lean():
-    from tests.emu import emu_opd
+    from tests.emu import emu
     lib = _lib.load()
     assert lib.hwy_abi_version() == _abi.HWY_ABI_VERSION == 8
-    assert lib.hwy_config_size() == C.sizeof(_abi.HwyConfig) == emu_opd.lib().emu_opd_config_size() == 6304
-    assert emu_opd.lib().emu_opd_params_size() == C.sizeof(_abi.HwyOpdParams) == 32
-    assert emu_opd.lib().emu_opd_max_nodes() == _abi.HWY_OPD_MAX_NODES >= 1024
+    assert lib.hwy_config_size() == C.sizeof(_abi.HwyConfig) == emu.lib("opd").emu_opd_config_size() == 6304
+    assert emu.lib("opd").emu_opd_params_size() == C.sizeof(_abi.HwyOpdParams) == 32
+    assert emu.lib("opd").emu_opd_max_nodes() == _abi.HWY_OPD_MAX_NODES >= 1024
     header = open(os.path.join(ROOT, "include", "hwy_engine.h")).read()
     for name in ("hwy_opd_plan_device", "hwy_opd_plan", "hwy_opd_params"):
         assert name in header
@@ -46,7 +46,8 @@ def test_abi_is_additive_and_the_kernel_is_lean():
 
 def test_opd_validation_statuses():
     """opd_validate: the statuses hwy_opd_plan_device returns before any launch, each with its reason."""
-    from tests.emu.emu_opd import last_error, validate
+    from tests.emu import emu
+    validate, last_error = emu.opd_validate, lambda: emu.last_error("opd")
     src = _cfg()
     p = _abi.opd_params(src, 50, 0.7)
     assert (p.budget, p.n_ids, p.nodes, p.bound) == (50, 5, 51, 1.0 / (1.0 - 0.7))
@@ -118,10 +119,10 @@ def test_python_errors_on_the_highway():
 
 
 def test_single_env_drop_in_plans():
-    from tests.emu.emu_opd import EmuOpdEngine
+    from tests.emu.emu import EmuEngine
 
     class Emu(envs.HighwayEnvFast):
-        _engine_factory = staticmethod(lambda cfg, device, stream: EmuOpdEngine(cfg))
+        _engine_factory = staticmethod(lambda cfg, device, stream: EmuEngine(cfg))
     env = Emu(ou.fast_config(8))
     best = env.plan_opd(10, 0.7)
     assert best.shape == (1,) and 0 <= int(best[0]) < 5

@@ -67,21 +67,21 @@ def test_no_unavailable_action_in_a_returned_sequence(shape, backend):
 
 
 def test_unknown_flags_bits_are_rejected():
-    from tests.emu import emu_opd
+    from tests.emu import emu
     cfg = _abi.make_config(omu.fast_config(8), 2, fast=True)
     p = _abi.opd_params(cfg, 15, 0.7)
     tree, work = with_envs(cfg, 2 * p.nodes), with_envs(cfg, 2 * p.n_ids)
-    assert emu_opd.validate(cfg, tree, work, p) == 0
+    assert emu.opd_validate(cfg, tree, work, p) == 0
     p.flags = _abi.HWY_OPD_MASKED
-    assert emu_opd.validate(cfg, tree, work, p) == 0
+    assert emu.opd_validate(cfg, tree, work, p) == 0
     for bad in (2, 3, 4, 1 << 30, -1):
         p.flags = bad
-        assert emu_opd.validate(cfg, tree, work, p) == _abi.HWY_ERR_INVALID_ARG, bad
+        assert emu.opd_validate(cfg, tree, work, p) == _abi.HWY_ERR_INVALID_ARG, bad
     direct = _abi.make_config(omu.fast_config(8, action={"type": "DiscreteAction"}), 2, fast=True)
     q = _abi.opd_params(direct, 18, 0.7, masked=True)
-    assert emu_opd.validate(direct, with_envs(direct, 2 * q.nodes), with_envs(direct, 2 * q.n_ids), q) == _abi.HWY_ERR_UNSUPPORTED
+    assert emu.opd_validate(direct, with_envs(direct, 2 * q.nodes), with_envs(direct, 2 * q.n_ids), q) == _abi.HWY_ERR_UNSUPPORTED
     q.flags = 0
-    assert emu_opd.validate(direct, with_envs(direct, 2 * q.nodes), with_envs(direct, 2 * q.n_ids), q) == 0
+    assert emu.opd_validate(direct, with_envs(direct, 2 * q.nodes), with_envs(direct, 2 * q.n_ids), q) == 0
 
 
 @pytest.mark.gpu

@@ -43,9 +43,8 @@ def run_selection(lib, selection):
 
 
 def _build_the_suites_own():
-    from tests.emu import emu, emu_control, emu_lidar, emu_lookahead, emu_opd, emu_traffic
-    for mod in (emu, emu_control, emu_traffic, emu_lidar, emu_lookahead, emu_opd):  # (before two processes could both start one)
-        mod.build()
+    from tests.emu import emu
+    emu.build_all()  # (before two processes could both start one)
 
 
 @pytest.mark.parametrize("mutant,selection", CASES, ids=[f"{c[0]}-{c[1][-1].split(' and ')[-1]}" for c in CASES])

@@ -125,13 +125,13 @@ LINEAR_CLASSES = {"linear": "LinearVehicle", "aggressive": "AggressiveVehicle", 
 
 
 def _linear_run(cls, N, schedule):
-    from tests.emu.emu_traffic import EmuTrafficEngine
+    from tests.emu.emu import EmuEngine
     cfg_d = _abi.highway_default_config()
     cfg_d.update({"vehicles_count": N - 1, "lanes_count": 4, "vehicles_density": 2.0, "duration": 12,
                   "other_vehicles_type": "highway_env.vehicle.behavior." + LINEAR_CLASSES[cls]})
     E = 2
     cfg = _abi.make_config(cfg_d, E, fast=False)
-    eng = EmuTrafficEngine(cfg)
+    eng = EmuEngine(cfg)
     if schedule is not None:
         eng.set_schedule(**schedule)
     kw = dict(ego_spacing=cfg_d["ego_spacing"], vehicles_density=cfg_d["vehicles_density"])
@@ -252,10 +252,10 @@ def test_one_wavefront_kernels_are_schedule_independent(kind, schedule):
 def _ttc_run(name, schedule):
     """The first state of a fixture of tests/golden/ttc: ``ttc_max`` -- 8192 cells in LDS, two states per thread in the value sweep;
     ``ttc_passes130`` -- three passes of 64 vehicles marking the same LDS grid."""
-    from tests.emu.emu_ttc import EmuTtcEngine
+    from tests.emu.emu import EmuEngine
     from tests.ttc_util import TtcGolden
     g = TtcGolden(name)
-    eng = EmuTtcEngine(g.hwy_config())
+    eng = EmuEngine(g.hwy_config())
     if schedule is not None:
         eng.set_schedule(**schedule)
     g.load(eng)

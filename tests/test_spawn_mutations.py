@@ -68,9 +68,8 @@ def build_mutant(name: str) -> str:
 @pytest.mark.parametrize("mutant", list(MUTANTS))
 def test_the_spawn_paths_kill_the_mutant(mutant):
     from concurrent.futures import ThreadPoolExecutor
-    from tests.emu import emu, emu_traffic
-    for mod in (emu, emu_traffic):  # (the suite's own emulator builds, before two processes could both start one)
-        mod.build()
+    from tests.emu import emu
+    emu.build_all()  # (the suite's own emulator builds, before two processes could both start one)
     _, env_var, row, _ = MUTANTS[mutant]
     with ThreadPoolExecutor(2) as pool:   # the control and the mutant side by side (two subprocesses)
         f_good = pool.submit(mutation_util.run_selection, None, selection(row), env_var)

@@ -1,4 +1,4 @@
-"""The LinearVehicle family's kernels (CPU emulation, tests/emu/emu_traffic.py) against the LIVE unmodified reference on random
+"""The LinearVehicle family's kernels (CPU emulation, tests/emu/emu.py) against the LIVE unmodified reference on random
 configurations: about 12 per class (LinearVehicle, AggressiveVehicle, DefensiveVehicle), drawn over vehicles_count, lanes_count,
 vehicles_density, simulation / policy frequency, controlled_vehicles and highway-v0 / highway-fast-v0.  The reference is driven by
 the fixture generator (tests/golden/traffic/make_golden_traffic.py: run) and the emulation is held to the fixtures' checks: the

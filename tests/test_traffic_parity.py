@@ -196,7 +196,7 @@ def test_device_reset_draws_the_rule_on_philox_uniforms(backend):
 def test_autoreset_respawns_parameters(backend):
     """An environment that ends is re-spawned with episode + 1's state and parameters: the rule on the next Philox stream of its
     auto-reset seed, computed in Python (tests/spawn_util.py).  Beside it, the kernel's own draw function compiled for the CPU
-    (emu_traffic.behavior_draw) gives the same parameters."""
+    (emu.behavior_draw) gives the same parameters."""
     from tests import spawn_util
     E = 4
     d, cfg = _linear_cfg(E, vehicles_count=20, lanes_count=3, duration=2)
@@ -216,10 +216,10 @@ def test_autoreset_respawns_parameters(backend):
     spawn_util.assert_spawned(d, cfg, eng, np.arange(E), 11 + np.arange(E), 1, out, kw, "Linear re-spawn")
     eng.close()
     np.testing.assert_array_equal(got, spawn_util.expected_behavior(cfg, 11 + np.arange(E), 1))
-    from tests.emu import emu_traffic
+    from tests.emu import emu
     for e in range(E):
         for i in range(1, cfg.num_vehicles):
-            np.testing.assert_array_equal(got[e, i], emu_traffic.behavior_draw(11 + e, i, 1), err_msg=f"env {e} vehicle {i}")
+            np.testing.assert_array_equal(got[e, i], emu.behavior_draw(11 + e, i, 1), err_msg=f"env {e} vehicle {i}")
 
 
 def test_tan_bounded_within_2_ulp_emu():

@@ -176,8 +176,8 @@ def test_random_shapes_against_the_restatement_and_the_fixed_point(backend, seed
         only_action, none_q, none_grid = eng.mdp_plan(params)
         assert none_q is None and none_grid is None and np.array_equal(only_action, action)
         if backend == "hip":
-            from tests.emu import emu_ttc
-            e_action, e_q, e_grid = emu_ttc.mdp_plan(cfg, st, params, return_q=True, return_grid=True)
+            from tests.emu import emu
+            e_action, e_q, e_grid = emu.mdp_plan(cfg, st, params, return_q=True, return_grid=True)
             np.testing.assert_array_equal(grid, e_grid, err_msg=f"{what} state {k}: grid, device against emulation")
             np.testing.assert_array_equal(q.view(np.uint64), e_q.view(np.uint64), err_msg=f"{what} state {k}: Q bits, device against emulation")
             np.testing.assert_array_equal(action, e_action, err_msg=f"{what} state {k}: action, device against emulation")

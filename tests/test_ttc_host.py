@@ -20,8 +20,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _emu_factory(cfg, device, stream):
-    from tests.emu.emu_ttc import EmuTtcEngine
-    return EmuTtcEngine(cfg)
+    from tests.emu.emu import EmuEngine
+    return EmuEngine(cfg)
 
 
 class _EmuBatchedFast(envs.BatchedHighwayEnvFast):
@@ -63,28 +63,28 @@ def _unsupported_configs():
 
 def test_c_validation_statuses():
     """csrc/hwy_ttc.h: ttc_validate -- the function the entry points of hwy_engine.hip call first -- through the emulator library."""
-    from tests.emu import emu_ttc
+    from tests.emu import emu
     good = _abi.make_config(highway_config(), 2, fast=True)
     params = _abi.ttc_params(highway_config())
-    assert emu_ttc.status(good, params) == _abi.HWY_OK
-    assert emu_ttc.status(good, None) == _abi.HWY_ERR_INVALID_ARG
+    assert emu.ttc_status(good, params) == _abi.HWY_OK
+    assert emu.ttc_status(good, None) == _abi.HWY_ERR_INVALID_ARG
     for what, cfg in _unsupported_configs():
-        assert emu_ttc.status(cfg, params) == _abi.HWY_ERR_UNSUPPORTED, what
-        assert emu_ttc.lib().emu_ttc_last_error().decode(), what
+        assert emu.ttc_status(cfg, params) == _abi.HWY_ERR_UNSUPPORTED, what
+        assert emu.last_error("ttc"), what
     for other in (dict(other_vehicles_type=LINEAR), dict(observation={"type": "LidarObservation"}),
                   dict(observation={"type": "OccupancyGrid"}), dict(vehicles_count=255), dict(lanes_count=16)):
-        assert emu_ttc.status(_abi.make_config(highway_config(**other), 2, fast=True), params) == _abi.HWY_OK, other
+        assert emu.ttc_status(_abi.make_config(highway_config(**other), 2, fast=True), params) == _abi.HWY_OK, other
     for field, value in (("time_steps", 0), ("time_steps", 65), ("time_steps", 9), ("time_steps", 11), ("time_quantization", 0.0),
                          ("time_quantization", float("nan")), ("horizon", float("inf")), ("gamma", float("nan")),
                          ("lane_change_reward", float("inf"))):
         p = _abi.HwyTtcParams.from_buffer_copy(bytes(params))
         setattr(p, field, value)
-        assert emu_ttc.status(good, p) == _abi.HWY_ERR_INVALID_ARG, (field, value)
+        assert emu.ttc_status(good, p) == _abi.HWY_ERR_INVALID_ARG, (field, value)
     p = _abi.HwyTtcParams.from_buffer_copy(bytes(params))
     p.horizon, p.time_quantization, p.time_steps = 65.0, 1.0, 65
-    assert emu_ttc.status(good, p) == _abi.HWY_ERR_INVALID_ARG
+    assert emu.ttc_status(good, p) == _abi.HWY_ERR_INVALID_ARG
     p.horizon, p.time_steps = 64.0, 64
-    assert emu_ttc.status(good, p) == _abi.HWY_OK
+    assert emu.ttc_status(good, p) == _abi.HWY_OK
 
 
 def test_python_raises_not_implemented_outside_the_scope():
@@ -111,8 +111,8 @@ def test_python_raises_not_implemented_outside_the_scope():
 
 
 def test_emulated_engine_refuses_like_the_entry_points():
-    from tests.emu.emu_ttc import EmuTtcEngine
-    eng = EmuTtcEngine(_abi.make_config(highway_config(action={"type": "DiscreteAction"}), 2, fast=True))
+    from tests.emu.emu import EmuEngine
+    eng = EmuEngine(_abi.make_config(highway_config(action={"type": "DiscreteAction"}), 2, fast=True))
     with pytest.raises(NotImplementedError, match="DiscreteMetaAction"):
         eng.ttc_grid(_abi.ttc_params(highway_config()))
     with pytest.raises(NotImplementedError):
@@ -144,11 +144,11 @@ def test_time_to_collision_observation_type_stays_out():
 def test_abi_is_additive():
     """HWY_ABI_VERSION stays 8 and hwy_config keeps its layout (6304 bytes, the parent's); the new struct is 40 bytes in the
     engine library's, the emulator's and the ctypes mirror's view; the entry points are exported and refuse a NULL engine."""
-    from tests.emu import emu_ttc
+    from tests.emu import emu
     lib = _lib.load()
     assert lib.hwy_abi_version() == _abi.HWY_ABI_VERSION == 8
-    assert lib.hwy_config_size() == C.sizeof(_abi.HwyConfig) == emu_ttc.lib().emu_ttc_config_size() == 6304
-    assert C.sizeof(_abi.HwyTtcParams) == emu_ttc.lib().emu_ttc_params_size() == 40
+    assert lib.hwy_config_size() == C.sizeof(_abi.HwyConfig) == emu.lib("ttc").emu_ttc_config_size() == 6304
+    assert C.sizeof(_abi.HwyTtcParams) == emu.lib("ttc").emu_ttc_params_size() == 40
     assert _abi.HwyConfig.lidar_max_range.offset == C.sizeof(_abi.HwyConfig) - 8  # (still the last field)
     header = open(os.path.join(ROOT, "include", "hwy_engine.h")).read()
     assert "#define HWY_ABI_VERSION 8" in header and "#define HWY_MAX_TTC_STEPS 64" in header and _abi.HWY_MAX_TTC_STEPS == 64
@@ -419,14 +419,14 @@ def test_emulation_against_live_reference(case):
     """32 random configurations (fixed list: seeds 0 .. 31 of `_draw`) against the live reference: the grids array-equal, the tables
     of to_finite_mdp() exact / bit for bit, the planner equal to the numpy fixed point on the reference's tables.  No cell is excused
     (several cases hold crashed vehicles resting exactly a vehicle length apart)."""
-    from tests.emu.emu_ttc import EmuTtcEngine
+    from tests.emu.emu import EmuEngine
     sc = _draw(case)
     mgt = _generator()
     sc["cls"] = mgt.HighwayEnvFast if sc.pop("fast") else mgt.HighwayEnv
     g = TtcGolden(sc["name"], mgt.run(sc))
     what = f"{sc['name']} ({json.dumps(sc['config'])})"
     cfg, params = g.hwy_config(), g.params(0.9)
-    eng = EmuTtcEngine(cfg)
+    eng = EmuEngine(cfg)
     for index in g.indices():
         g.load(eng, index)
         grid = eng.ttc_grid(params).astype(np.float64)

@@ -66,9 +66,8 @@ def run_selection(lib, selection):
 
 
 def _build_the_suites_own():
-    from tests.emu import emu, emu_control, emu_lidar, emu_traffic, emu_ttc
-    for mod in (emu, emu_control, emu_traffic, emu_lidar, emu_ttc):  # (before two processes could both start one)
-        mod.build()
+    from tests.emu import emu
+    emu.build_all()  # (before two processes could both start one)
 
 
 @pytest.mark.parametrize("mutant,selection", CASES, ids=[c[0] for c in CASES])

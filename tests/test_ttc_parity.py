@@ -170,11 +170,11 @@ def _engine_run(n_vehicles: int):
 def test_hip_equals_emulation_on_engine_states(n_vehicles):
     """The MI355X against the CPU emulation of the same kernel source on the states the engine itself produced: grid, Q and action
     bit for bit."""
-    from tests.emu import emu_ttc
+    from tests.emu import emu
     cfg, params, record = _engine_run(n_vehicles)
     episodes = 0
     for t, (st, grid, action, q, grid_alone) in enumerate(record):
-        e_action, e_q, e_grid = emu_ttc.mdp_plan(cfg, st, params, return_q=True, return_grid=True)
+        e_action, e_q, e_grid = emu.mdp_plan(cfg, st, params, return_q=True, return_grid=True)
         np.testing.assert_array_equal(grid, e_grid, err_msg=f"N={n_vehicles} step {t}: grid")
         np.testing.assert_array_equal(grid_alone, e_grid, err_msg=f"N={n_vehicles} step {t}: grid entry point")
         np.testing.assert_array_equal(_bits(q), _bits(e_q), err_msg=f"N={n_vehicles} step {t}: Q")
@@ -288,14 +288,14 @@ def test_host_pointer_buffer_grows_between_calls(first):
     allocates a larger one), then T = 10 (the larger buffer stays): every result equals the emulation's for the same state and
     params, whichever of the two host-pointer entry points meets the growing grid first."""
     from highwayenv_amd.engine import Engine
-    from tests.emu import emu_ttc
+    from tests.emu import emu
     g = TtcGolden("ttc_max")
     cfg, st = g.hwy_config(), g.state("init")
     eng = Engine(cfg)
     eng.set_state(st)
     for horizon, tq in ((1.0, 1.0), (6.4, 0.1), (10.0, 1.0)):
         params = _abi.ttc_params(g.config, horizon=horizon, time_quantization=tq, gamma=0.8)
-        e_action, e_q, e_grid = emu_ttc.mdp_plan(cfg, st, params, return_q=True, return_grid=True)
+        e_action, e_q, e_grid = emu.mdp_plan(cfg, st, params, return_q=True, return_grid=True)
         assert e_grid.shape[2:] == (8, 16, params.time_steps) and e_grid.any()
         got = {}
         for call in (("ttc_grid", "mdp_plan") if first == "ttc_grid" else ("mdp_plan", "ttc_grid")):

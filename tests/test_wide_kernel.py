@@ -204,16 +204,16 @@ def test_abort_chain_on_the_emulator():
     emu.build()
     assert soak(6, 14) > 20  # ongoing lane changes at the step boundaries alone (the mutant below shows that links do abort)
     src = emu.os.path.join(emu._HERE, "emu_engine.cpp")
-    saved = emu._lib
+    saved = emu.lib()
     try:
         mutant = emu.os.path.join(emu._HERE, "_build", "libhwy_emu_noabort.so")
         emu.compile_emulator(src, mutant, ["-DHWY_WIDE_MUTANT_NO_ABORT=1"])
-        emu._lib = C.CDLL(mutant)
-        emu._lib.emu_config_size.restype = C.c_size_t
+        emu._libs["sim"] = C.CDLL(mutant)
+        emu._libs["sim"].emu_config_size.restype = C.c_size_t
         with pytest.raises(AssertionError):
             soak(6, 14)
     finally:
-        emu._lib = saved
+        emu._libs["sim"] = saved
 
 
 def test_one_wavefront_abort_chain_on_the_emulator():
@@ -247,16 +247,16 @@ def test_one_wavefront_abort_chain_on_the_emulator():
     emu.build()
     assert soak(12, 16) > 20
     src = emu.os.path.join(emu._HERE, "emu_engine.cpp")
-    saved = emu._lib
+    saved = emu.lib()
     try:
         mutant = emu.os.path.join(emu._HERE, "_build", "libhwy_emu_wave_noabort.so")
         emu.compile_emulator(src, mutant, ["-DHWY_WAVE_MUTANT_NO_ABORT=1"])
-        emu._lib = C.CDLL(mutant)
-        emu._lib.emu_config_size.restype = C.c_size_t
+        emu._libs["sim"] = C.CDLL(mutant)
+        emu._libs["sim"].emu_config_size.restype = C.c_size_t
         with pytest.raises(AssertionError):
             soak(12, 16)
     finally:
-        emu._lib = saved
+        emu._libs["sim"] = saved
 
 
 def test_workgroup_kernel_abort_chain_against_its_literal_build():
@@ -292,14 +292,14 @@ def test_workgroup_kernel_abort_chain_against_its_literal_build():
     ours = [soak(*r) for r in runs]
     assert sum(int((s["lane"] != s["target_lane"]).sum()) for tr in ours for s in tr) > 20
     src = emu.os.path.join(emu._HERE, "emu_engine.cpp")
-    saved = emu._lib
+    saved = emu.lib()
     try:
         for flag, lib, must_match in (("-DHWY_BLOCK_LITERAL_CHAIN=1", "libhwy_emu_block_literal.so", True),
                                       ("-DHWY_BLOCK_MUTANT_NO_ABORT=1", "libhwy_emu_block_noabort.so", False)):
             path = emu.os.path.join(emu._HERE, "_build", lib)
             emu.compile_emulator(src, path, [flag])
-            emu._lib = C.CDLL(path)
-            emu._lib.emu_config_size.restype = C.c_size_t
+            emu._libs["sim"] = C.CDLL(path)
+            emu._libs["sim"].emu_config_size.restype = C.c_size_t
             theirs = [soak(*r) for r in runs]
             if must_match:
                 for a, b in zip(ours, theirs):
@@ -309,7 +309,7 @@ def test_workgroup_kernel_abort_chain_against_its_literal_build():
                     for a, b in zip(ours, theirs):
                         same(a, b)
     finally:
-        emu._lib = saved
+        emu._libs["sim"] = saved
 
 
 @pytest.mark.parametrize("backend", BACKENDS)

@@ -1,19 +1,18 @@
 """Shared helpers of the LinearVehicle-family tests: the fixtures of tests/golden/traffic and the backends
-(``emu`` = tests/emu/emu_traffic.py on the CPU, ``hip`` = the engine on the MI355X)."""
+(``emu`` = tests/emu/emu.py on the CPU, ``hip`` = the engine on the MI355X)."""
 from __future__ import annotations
 
 import json
 import os
 
 import numpy as np
-import pytest
 
 from highwayenv_amd import _abi
+from tests.backends import BACKENDS, make_engine  # noqa: F401  (re-exported)
 from tests.golden_util import Golden
 
 TRAFFIC_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "traffic")
 FIXTURES = ["linear_fast", "linear_v0", "aggressive_dense", "defensive_ma2", "linear_n100", "crash_many_linear"]
-BACKENDS = [pytest.param("emu", id="emu"), pytest.param("hip", id="hip", marks=pytest.mark.gpu)]
 
 
 class TrafficGolden(Golden):
@@ -45,11 +44,3 @@ class TrafficGolden(Golden):
 
     def actions_at(self, t: int) -> np.ndarray:
         return np.asarray(self.actions[t], np.int32).reshape(self.E, self.A)
-
-
-def make_engine(backend: str, cfg):
-    if backend == "emu":
-        from tests.emu.emu_traffic import EmuTrafficEngine
-        return EmuTrafficEngine(cfg)
-    from highwayenv_amd.engine import Engine
-    return Engine(cfg)

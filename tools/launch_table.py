@@ -11,8 +11,11 @@ covers every branch of the kernel selection (csrc/hwy_launch_family.h, hwy_launc
 without FULL_SCAN, the wide kernel, the workgroup kernel (OccupancyGrid, forced, N > 128), the Linear and direct families on both
 sides of N = 64, the Lidar trace, the road-network kernels with both observations, the intersection kernel with and without helper
 lanes, its 64-slot build and the doubled grid of next-episode pre-warming -- and then every row of tests/variants_util.py (the
-branches in which hwy_config.tune_waves_per_eu picks a register-allocation build) at every value of the knob.  --compare reads the
-two kernel traces in dispatch order and requires equal sequences of (kernel name, grid size, workgroup size, LDS).  --covers reads
+branches in which hwy_config.tune_waves_per_eu picks a register-allocation build) at every value of the knob -- and then the
+launches of the add-on units (csrc/hwy_launch_units.h): the TTC grid and plan on both sides of the 1024-cell LDS class, the Lidar
+trace with and without normalisation, the fork with and without indices, the score of one and of several agents, an OPD plan of
+budget 10 unmasked and masked, and the action mask on the highway, the merge and the intersection.  --compare reads the
+two kernel traces in the order of the dispatch ids and requires equal sequences of (kernel name, grid size, workgroup size, LDS).  --covers reads
 one trace and lists which step and rollout kernels of the built code object (highwayenv_amd.build.kernel_resources) were and were
 not launched: the evidence that the selection rules as tests/variants_util.py restates them are what the engine really launches."""
 from __future__ import annotations
@@ -90,12 +93,69 @@ def run() -> None:
         print(f"{label}: N={cfg.num_vehicles} obs {obs.shape} rollout {out[0].shape}", flush=True)
 
 
+def run_units() -> None:
+    """The add-on units' launches on 4-environment engines, every branch of csrc/hwy_launch_units.h."""
+    import numpy as np
+
+    from highwayenv_amd import _abi, intersection, merge
+    from highwayenv_amd.engine import Engine
+
+    E = 4
+
+    def engine(d, num_envs=E, **kw):
+        eng = Engine(_abi.make_config(d, num_envs, **kw))
+        eng.reset(base_seed=11)
+        return eng
+
+    def hwy(**over):
+        return dict(_abi.highway_fast_default_config(), vehicles_count=19, **over)
+
+    # the TTC grid and the plan on it: 3 x 3 x 10 cells, and 3 x 6 x 64 = 1152 (the large LDS class)
+    for d, horizon, tq in ((hwy(), 10.0, 1.0), (hwy(lanes_count=6), 6.4, 0.1)):
+        eng, params = engine(d, fast=True), _abi.ttc_params(d, horizon=horizon, time_quantization=tq)
+        grid = eng.ttc_grid(params)
+        eng.mdp_plan(params, return_q=True, return_grid=True)
+        eng.close()
+        print(f"TTC {grid.shape[2:]}", flush=True)
+    for normalize in (True, False):
+        eng = engine(hwy(observation={"type": "LidarObservation", "normalize": normalize}), fast=True)
+        print(f"Lidar normalize={normalize}: obs {eng.observe().shape}", flush=True)
+        eng.close()
+    # fork without and with indices; the score of a rollout of the branches, one agent and two
+    for agents in (1, 2):
+        d = hwy(controlled_vehicles=agents)
+        src, dst = engine(d, fast=True), engine(d, 3 * E, fast=True)
+        dst.fork_from(src, 3)
+        dst.fork_from(src, 1, np.arange(3 * E, dtype=np.int32) % E)
+        out = dst.score_rollout(np.ones((2, 3 * E, agents), np.int32), 3, 0.9)
+        print(f"fork + score, {agents} agent(s): returns {out['returns'].shape}", flush=True)
+        for e in (src, dst):
+            e.close()
+    for masked in (False, True):
+        d = hwy(normalize_reward=True)
+        src = engine(d, fast=True)
+        params = _abi.opd_params(src.cfg, 10, 0.7, masked=masked)
+        tree, work = engine(d, E * params.nodes, fast=True), engine(d, E * params.n_ids, fast=True)
+        out = src.opd_plan(tree, work, params)
+        print(f"opd_plan budget 10 masked={masked}: expanded {out['expanded'].tolist()}", flush=True)
+        for e in (src, tree, work):
+            e.close()
+    ix = dict(intersection.intersection_default_config(), max_vehicles=30, host_traffic=False)
+    for label, d, kw in (("highway", hwy(), {"fast": True}), ("merge", merge.merge_default_config(), {"scenario": "merge"}),
+                         ("intersection", ix, {"scenario": "intersection"})):
+        eng = engine(d, **kw)
+        print(f"action mask {label}: {eng.action_mask().shape}", flush=True)
+        eng.close()
+
+
 def launches(out_dir: str) -> list:
     files = sorted(glob.glob(os.path.join(out_dir, "**", "*kernel_trace.csv"), recursive=True))
     if not files:
         raise SystemExit(f"no *kernel_trace.csv under {out_dir}")
     rows = [r for f in files for r in csv.DictReader(open(f))]
-    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    # in the order the host enqueued them: the three engines of an OPD plan have streams of their own, and two launches on different
+    # streams (the root fork into `tree`, the parent fork into `work`) may START in either order
+    rows.sort(key=lambda r: int(r["Dispatch_Id"]))
 
     def cols(r, prefix):
         return tuple(int(r[k]) for k in sorted(r) if k.startswith(prefix))
@@ -137,3 +197,4 @@ if __name__ == "__main__":
     if len(sys.argv) == 3 and sys.argv[1] == "--covers":
         sys.exit(covers(sys.argv[2]))
     run()
+    run_units()

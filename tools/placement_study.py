@@ -62,9 +62,8 @@ def build_variant():
 
 def worker(k, E, steps):
     from highwayenv_amd import _abi
+    os.environ["HWY_EMU_LIB"] = os.path.join(OUT, "libhwy_emu_events.so")  # (tests/emu/emu.py: UNITS, a prebuilt library)
     from tests.emu import emu
-    emu._LIB = os.path.join(OUT, "libhwy_emu_events.so")
-    emu.build = lambda force=False: emu._LIB
     cfg_d = _abi.highway_fast_default_config()
     cfg_d.update({"vehicles_count": 50, "lanes_count": 4})
     eng = emu.EmuEngine(_abi.make_config(cfg_d, E, fast=True))
