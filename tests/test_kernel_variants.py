@@ -6,10 +6,12 @@ kernel (WPE 3 on the straight road, 4 on the road network, 2 on the intersection
 uninitialised value, an LDS ordering that holds at one occupancy only, or a wrong spill would change a result.  Here:
 
 1. (CPU) the table of tests/variants_util.py is COMPLETE against the code object's own metadata: every kernel it names exists, and
-   every step / rollout kernel of the code object is named by some (row, value) or listed below with the reason it has one build;
+   every step / rollout kernel of the code object -- the step kernels compiled for the registered configurations (hwy_shape_wave_kernel)
+   among them -- is named by some (row, value) or listed below with the reason it has one build;
 2. every (row, value) runs on the MI355X, step() and rollout(), with auto-reset inside the run, and is EQUAL -- outputs of every
    step, final state, drawn behaviour parameters, stored controls -- to the untuned engine, whose builds the rest of the suite holds
-   to the oracle; builds no test has executed are also compared with the oracle directly, free running, at the suite's tolerances;
+   to the oracle; after every launch the library's own report of the kernel it ran (hwy_last_step_shape) must be what the table
+   says, so a row cannot name one kernel while another runs; builds no test has executed are also compared with the oracle directly, free running, at the suite's tolerances;
 3. the build the engine itself takes above its batch-size threshold equals the 3- and the 4-wave build;
 4. ``tune_extra_lds`` (dynamic LDS on the one-wavefront launches) changes nothing.
 
@@ -74,8 +76,16 @@ def test_every_step_and_rollout_build_is_reached_by_the_table(res):
     one_build = {k.format(stage): why for k, why in ONE_BUILD.items() for stage in ("step", "rollout")}
     listed = {**one_build, **UNREACHABLE}
     assert all(why.strip() for why in listed.values())
-    in_object = [k for k in res if vu.STEP_OR_ROLLOUT.match(k)]
+    in_object = [k for k in res if vu.STEP_OR_ROLLOUT.match(k) or vu.SHAPE_KERNEL.match(k)]
     assert len(in_object) > 100  # (the pattern still finds them)
+    # the kernels compiled for the registered configurations: three shapes x four register-allocation builds, every one of them
+    # named by a (row, value), and the table names no other; the generic one-wavefront step builds beside them likewise
+    shapes = sorted(k for k in in_object if vu.SHAPE_KERNEL.match(k))
+    assert shapes == sorted(vu.shape_kernel(s, w) for s in vu.SHAPES for w in (1, 2, 3, 4)), shapes
+    assert sorted(k for k in named if vu.SHAPE_KERNEL.match(k)) == shapes
+    for w in (1, 2, 3, 4):
+        for scan in ("true", "false"):
+            assert f"hwy::hwy_step_wave_kernel<{w}, {scan}>" in named and f"hwy::hwy_step_wave_kernel<{w}, {scan}>" in res
     unreached = [k for k in in_object if k not in named and k not in listed]
     assert not unreached, f"step / rollout kernels in the code object that no (row, value) of tests/variants_util.py launches: {unreached}"
     # the exceptions stay honest: each exists, and none is something the table launches after all
@@ -100,6 +110,22 @@ def test_the_restated_selection_on_known_launches():
     assert vu.launched(dict(merge.merge_default_config(), **vu.GRID), {"scenario": "merge"}, 4)[0] == "hwy::hwy_net_step_kernel<3, true>"
     assert vu.launched(vu.ix(40), {"scenario": "intersection"}, 3)[1] == "hwy::hwy_ix_rollout_kernel<2, 64, 64>"
     assert vu.launched(vu.ix(30), {"scenario": "intersection"}, 4)[0] == "hwy::hwy_ix_step_kernel<3, 32, 64>"
+    # the registered configurations run the kernel compiled for them (a full step with auto-reset), their rollout the generic one;
+    # one field off each -- a fifth lane, 15 frames per step with ego-only collisions, 65 vehicles, the workgroup kernel forced --
+    # is the generic kernel again
+    fast3, fast4, v0 = _abi.highway_fast_default_config(), dict(_abi.highway_fast_default_config(), lanes_count=4), d
+    assert (vu.step_shape(fast3, {"fast": True}), vu.step_shape(fast4, {"fast": True}), vu.step_shape(v0, {})) == (1, 2, 3)
+    assert vu.launched(fast3, {"fast": True}, 3) == ("hwy::hwy_shape_wave_kernel<hwy::FixedShape<1, 3, 89, 5>, 3>", "hwy::hwy_rollout_wave_kernel<3, false>")
+    assert vu.launched(fast4, {"fast": True}, 1) == ("hwy::hwy_shape_wave_kernel<hwy::FixedShape<2, 4, 89, 5>, 1>", "hwy::hwy_rollout_wave_kernel<1, false>")
+    assert vu.launched(v0, {}, 4) == ("hwy::hwy_shape_wave_kernel<hwy::FixedShape<3, 4, 25, 15>, 4>", "hwy::hwy_rollout_wave_kernel<4, true>")
+    assert vu.launched(dict(fast3, lanes_count=5), {"fast": True}, 3)[0] == "hwy::hwy_step_wave_kernel<3, false>"
+    assert vu.launched(fast3, {}, 3)[0] == "hwy::hwy_step_wave_kernel<3, true>"  # (highway-fast-v0's dict without its collision rule)
+    assert vu.launched(dict(fast4, simulation_frequency=15), {"fast": True}, 2)[0] == "hwy::hwy_step_wave_kernel<2, false>"
+    assert vu.launched(dict(v0, lanes_count=3), {}, 4)[0] == "hwy::hwy_step_wave_kernel<4, true>"
+    assert vu.launched(dict(v0, vehicles_count=64), {}, 3)[0] == "hwy::hwy_step_wide_kernel<2, 2>"
+    assert vu.launched(v0, dict(vu.BLOCK), 3)[0] == "hwy::hwy_step_kernel<1, 3>" and vu.step_shape(v0, dict(vu.BLOCK)) == 0
+    assert vu.step_shape(dict(v0, vehicles_count=63), {}) == 3 and vu.step_shape(dict(v0, vehicles_count=64), {"tuning": {"block_kernel": 1}}) == 0
+    assert vu.step_shape(dict(v0, other_vehicles_type=vu.LINEAR), {}) == 0 and vu.step_shape(dict(v0, **vu.DIRECT), {}) == 0
     # hwy_create's own choice: 3 / 4 on the two sides of 3 wavefronts per SIMD of a 256-CU part
     lin = dict(d, vehicles_count=100, other_vehicles_type=vu.LINEAR)
     assert vu.default_waves_per_eu(lin, {}, 1536) == 3 and vu.default_waves_per_eu(lin, {}, 1537) == 4
@@ -123,6 +149,7 @@ def test_every_build_equals_the_default_build(backend, label, d, kw):
     K calls of step() and one rollout() of K more -- EQUAL after every step and in the final state.  Episodes last 3 steps, so
     every environment ends and is re-spawned inside the run, in every build."""
     n = _abi.make_config(d, 1, **kw).num_vehicles
+    assert vu.label_shape(label) == vu.step_shape(d, kw), f"{label}: its step() runs shape {vu.step_shape(d, kw)}"
     if backend == "emu":
         E, K, vals = 2, 2, (4,)
     else:
@@ -153,6 +180,24 @@ def test_the_comparison_raises_on_engines_reset_with_different_seeds():
         vu.assert_builds_identical(a, {"other stream": b}, K=2)
     with pytest.raises(AssertionError, match="nothing to compare"):
         vu.assert_builds_identical(a, {}, K=2)
+
+
+def test_the_comparison_raises_when_the_table_names_another_kernel(monkeypatch):
+    """The shape assertion of the comparison is live: highway-v0 on 4 lanes runs the kernel compiled for it on every step(); a
+    table that says "the generic kernel" for it (the state of this file before the shapes had rows) fails on the first step."""
+    def pair():
+        d = dict(vu.hwy(12), simulation_frequency=15)
+        a, b = vu.make_engine("emu", d, {}, 2), vu.make_engine("emu", d, vu.with_tuning({}, waves_per_eu=4), 2)
+        for eng in (a, b):
+            vu.reset_for_comparison(eng, d, [5, 6], base_seed=9)
+        return a, b
+    assert vu.step_shape(dict(vu.hwy(12), simulation_frequency=15), {}) == 3
+    a, b = pair()
+    assert vu.assert_builds_identical(a, {"same": b}, K=3) >= 2
+    monkeypatch.setattr(vu, "step_shape_of_config", lambda c: 0)
+    a, b = pair()
+    with pytest.raises(AssertionError, match="default: step 0: the launch ran shape 3"):
+        vu.assert_builds_identical(a, {"same": b}, K=3)
 
 
 # Builds no test has executed, against the ORACLE (free running, tests/families_util.py: rollout, its tolerances): this does not
@@ -206,12 +251,17 @@ def test_the_engines_own_choice_above_the_threshold(label, d, E):
 @pytest.mark.gpu
 @pytest.mark.parametrize("label,d,kw", [
     ("idm ego-only", vu.hwy(50), {"fast": True}),
-    ("idm full-scan", vu.hwy(50), {}),
+    ("idm full-scan V0Shape4", vu.hwy(50), {}),
+    ("idm full-scan generic", vu.hwy(50, lanes_count=5), {}),
+    ("idm FastShape4", vu.fast(50, 4), {"fast": True}),
     ("linear", vu.hwy(50, other_vehicles_type=vu.LINEAR), {}),
     ("direct", vu.hwy(50, **vu.DIRECT), {}),
-], ids=["idm-ego-only", "idm-full-scan", "linear", "direct"])
+], ids=["idm-ego-only", "idm-full-scan", "idm-full-scan-generic", "idm-fast-shape", "linear", "direct"])
 def test_extra_lds_changes_nothing(label, d, kw):
     """Dynamic LDS on the one-wavefront launches (fewer resident wavefronts per SIMD) against none: 8 KB and 32 KB, both under
-    64 KB per workgroup with the kernels' static share (under 10 KB, tests/test_kernel_resources.py)."""
+    64 KB per workgroup with the kernels' static share (under 10 KB, tests/test_kernel_resources.py).  idm-full-scan is highway-v0
+    on 4 lanes, whose step() runs the kernel compiled for it (V0Shape4); idm-full-scan-generic (5 lanes) is the generic full-scan
+    kernel and idm-fast-shape the kernel of highway-fast-v0 on 4 lanes."""
+    assert vu.label_shape(label) == vu.step_shape(d, kw), label
     n_done = vu.compare_row("hip", d, kw, {f"extra_lds={v}": {"extra_lds": v} for v in (8192, 32768)}, E=8, K=6)
     assert n_done >= 8

@@ -3,7 +3,8 @@ against the generic kernel, and the rule that picks between them (csrc/hwy_launc
 
 1. Bit-identity: an engine whose launches take the shape kernel and one held to the generic kernel (hwy_step_shapes) take the same
    random actions through 12 policy steps with device spawn and auto-reset, in dense traffic; every output plane and the whole
-   state are EQUAL after every step, with and without a block order.  The run is only accepted if the GENERIC engine's own
+   state are EQUAL after every step, with and without a block order -- at 12 vehicles, at the edges of N (1, 2, 5, 64), on the
+   MI355X in every register-allocation build at N = 64, and through the HighwayVectorEnv front end in both autoreset modes.  The run is only accepted if the GENERIC engine's own
    trajectory shows what the specialised code could get wrong: an ego crash (SAT and impact), an auto-reset, an observation with
    zeroed rows, FASTER at the top and SLOWER at the bottom of the speed ladder, LANE_LEFT on lane 0, a vehicle on two lanes.
 2. Selection: every field a shape fixes, flipped one at a time, sends the launch to the generic kernel (hwy_last_step_shape == 0)
@@ -110,12 +111,10 @@ def events_of_step(before, acts, done_before, out, after, lanes):
     }
 
 
-@pytest.mark.parametrize("backend", BACKENDS)
-@pytest.mark.parametrize("block_order", [False, True], ids=["identity", "block-order"])
-@pytest.mark.parametrize("kind", list(SHAPES))
-def test_shape_kernel_equals_generic_kernel(backend, kind, block_order, shapes):
-    d, fast = _config(kind)
-    seeds = SEEDS[kind]
+def _run_against_generic(backend, kind, seeds, block_order, shapes, **over):
+    """STEPS policy steps of an engine on the shape kernel and of one held to the generic kernel, EQUAL after every step; returns
+    which events the generic engine's trajectory showed (events_of_step)."""
+    d, fast = _config(kind, **over)
     spec, gen = _fresh(backend, d, fast, seeds), _fresh(backend, d, fast, seeds)
     rng = np.random.default_rng(seeds[2])
     if block_order:
@@ -140,7 +139,91 @@ def test_shape_kernel_equals_generic_kernel(backend, kind, block_order, shapes):
     finally:
         spec.close()
         gen.close()
+    return seen
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+@pytest.mark.parametrize("block_order", [False, True], ids=["identity", "block-order"])
+@pytest.mark.parametrize("kind", list(SHAPES))
+def test_shape_kernel_equals_generic_kernel(backend, kind, block_order, shapes):
+    seen = _run_against_generic(backend, kind, SEEDS[kind], block_order, shapes)
     assert all(seen.values()), f"the run does not exercise: {[k for k, v in seen.items() if not v]}"
+
+
+# The edges of N: the ego alone (every other observation row zeroed), fewer vehicles than the 5 observation rows, exactly as many,
+# and a wavefront without an idle lane.  Episodes of 3 policy steps: whatever the traffic does, every environment is truncated and
+# re-spawned by the kernel within the 12 steps -- the one event required here (the six of N = 12 need traffic to happen in).
+EDGE_SIZES = (1, 2, 5, 64)
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+@pytest.mark.parametrize("block_order", [False, True], ids=["identity", "block-order"])
+@pytest.mark.parametrize("n", EDGE_SIZES, ids=[f"N{n}" for n in EDGE_SIZES])
+@pytest.mark.parametrize("kind", list(SHAPES))
+def test_shape_kernel_equals_generic_kernel_at_the_edges_of_n(backend, kind, n, block_order, shapes):
+    seen = _run_against_generic(backend, kind, (7 + n, 8 + n, 9 + n), block_order, shapes, vehicles_count=n - 1, duration=3)
+    assert seen["auto-reset"], "no environment was re-spawned within the run"
+
+
+@pytest.mark.parametrize("backend", [pytest.param("hip", id="hip", marks=pytest.mark.gpu)])
+@pytest.mark.parametrize("w", [1, 2, 3, 4])
+@pytest.mark.parametrize("kind", list(SHAPES))
+def test_every_build_of_a_shape_kernel_equals_the_generic_build(backend, kind, w, shapes):
+    """hwy_shape_wave_kernel<shape, w> against hwy_step_wave_kernel<w, ...>, w = waves per SIMD the register allocator leaves room
+    for: 64 vehicles, no idle lane.  (The emulation compiles one build: nothing of its own to show.)"""
+    seen = _run_against_generic(backend, kind, (71, 72, 73), False, shapes, vehicles_count=63, duration=3, tuning={"waves_per_eu": w})
+    assert seen["auto-reset"], "no environment was re-spawned within the run"
+
+
+# --------------------------------------------------------------------------- the front end
+
+FRONT_ENDS = {"highway-fast-v0": ({}, 1), "highway-fast-v0, 4 lanes": ({"lanes_count": 4}, 2), "highway-v0": ({}, 3)}
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+@pytest.mark.parametrize("mode", ["NextStep", "SameStep"])
+@pytest.mark.parametrize("which", list(FRONT_ENDS), ids=["fast", "fast-4", "v0"])
+def test_the_vector_front_end_computes_the_same_with_shapes_on_and_off(backend, which, mode, shapes):
+    """HighwayVectorEnv over the registered ids, numpy outputs: 8 steps with the shape kernels allowed equal the same 8 steps with
+    every launch held to the generic kernel -- observation, reward, terminated, truncated, the info planes and, in SameStep
+    mode, the terminal observations.  NextStep is the device's auto-reset, so every step() runs the shape's kernel.  SameStep
+    steps WITHOUT the device's auto-reset (ended environments are re-spawned by a masked reset behind the step), so its launches
+    match no shape and run the generic kernel whatever the switch says: hwy_last_step_shape() == 0."""
+    from highwayenv_amd import envs, vector
+    from tests.backends import env_class
+    over, shape = FRONT_ENDS[which]
+    cls = env_class(backend, envs.batched_class(which.split(",")[0]))
+    config = {"vehicles_count": N_OTHERS, "duration": 3, **over}
+    runs = []
+    for on in (True, False):
+        shapes.set(on)
+        venv = vector.HighwayVectorEnv(cls, num_envs=E, config=config, autoreset_mode=mode)
+        try:
+            obs, infos = venv.reset(seed=21)
+            trace = [(obs, infos["speed"], infos["crashed"])]
+            rng = np.random.default_rng(22)
+            for t in range(8):
+                obs, reward, term, trunc, infos = venv.step(rng.integers(0, 5, size=E))
+                assert shapes.last() == (shape if on and mode == "NextStep" else 0), f"{which} {mode}, shapes {on}, step {t}: shape {shapes.last()}"
+                final = [None if o is None else np.array(o) for o in infos["final_obs"]] if "final_obs" in infos else None
+                trace.append((np.array(obs), np.array(reward), np.array(term), np.array(trunc), np.array(infos["speed"]),
+                              np.array(infos["crashed"]), final))
+        finally:
+            venv.close()
+        runs.append(trace)
+    n_done = n_final = 0
+    for t, (a, b) in enumerate(zip(*runs)):
+        for x, y in zip(a[:6], b[:6]):
+            np.testing.assert_array_equal(x, y, err_msg=f"{which} {mode}: call {t}")
+        if t > 0:
+            n_done += int((a[2] | a[3]).sum())
+            assert (a[6] is None) == (b[6] is None)
+            for fa, fb in zip(a[6] or [], b[6] or []):
+                assert (fa is None) == (fb is None)
+                if fa is not None:
+                    n_final += 1
+                    np.testing.assert_array_equal(fa, fb, err_msg=f"{which} {mode}: final_obs of call {t}")
+    assert n_done >= E and (n_final == n_done if mode == "SameStep" else n_final == 0), (n_done, n_final)
 
 
 # --------------------------------------------------------------------------- selection

@@ -23,6 +23,19 @@ DIRECT = {"action": {"type": "DiscreteAction", "steering_range": [-0.1, 0.1]}}
 BLOCK = {"tuning": {"block_kernel": 1}}
 # the step and rollout kernels among the keys of kernel_resources(): hwy_[net_|ix_](step|rollout)[_wave|_wide][_linear|_direct]_kernel<...>
 STEP_OR_ROLLOUT = re.compile(r"^hwy::hwy_(?:[a-z]+_)?(?:step|rollout)_(?:[a-z_]+_)?kernel<")
+# the one-wavefront step kernel compiled for a registered configuration (csrc/hwy_wave.h: FixedShape; hwy_kernels_shapes.hip)
+SHAPE_KERNEL = re.compile(r"^hwy::hwy_shape_wave_kernel<")
+# shape id (hwy_last_step_shape) -> (lanes, hwy_config.flags, frames per policy step) of FastShape3, FastShape4 and V0Shape4
+_V0_FLAGS = _abi.C_OBS_NORMALIZE | _abi.C_OBS_CLIP | _abi.C_NORMALIZE_REWARD
+SHAPES = {1: (3, _V0_FLAGS | _abi.C_EGO_ONLY_COLLISIONS, 5), 2: (4, _V0_FLAGS | _abi.C_EGO_ONLY_COLLISIONS, 5), 3: (4, _V0_FLAGS, 15)}
+SHAPE_NAMES = {1: "FastShape3", 2: "FastShape4", 3: "V0Shape4"}  # (csrc/hwy_wave.h)
+
+
+def label_shape(label: str) -> int:
+    """The shape id a row's label names (0: none): a row says in its label which kernel its step() runs."""
+    named = [shape for shape, name in SHAPE_NAMES.items() if name in label]
+    assert len(named) <= 1, label
+    return named[0] if named else 0
 
 
 def hwy(n: int, **over) -> dict:
@@ -30,6 +43,14 @@ def hwy(n: int, **over) -> dict:
     short run, and twice the default density, so that lane changes and collisions happen in it."""
     d = _abi.highway_default_config()
     d.update({"vehicles_count": n - 1, "duration": 3, "vehicles_density": 2.0, **over})
+    return d
+
+
+def fast(n: int, lanes: int, **over) -> dict:
+    """highway-fast-v0's structure (5 frames per policy step; with make_config's fast=True: ego-only collisions) with n vehicles in
+    all on `lanes` lanes: episodes of 3 policy steps and twice the default density, like hwy()."""
+    d = _abi.highway_fast_default_config()
+    d.update({"vehicles_count": n - 1, "lanes_count": lanes, "duration": 3, "vehicles_density": 2.0, **over})
     return d
 
 
@@ -61,9 +82,15 @@ def rows() -> list:
     than 32 slots (<2, 64>), every reset and observe kernel (one build each) and the Lidar kernel."""
     out = [
         # IDM traffic, meta-actions.  The workgroup kernel is forced (block_kernel=1) where the engine would take the one-wavefront
-        # or the wide kernel; the OccupancyGrid row is the engine's own route to it for N > 64
+        # or the wide kernel; the OccupancyGrid row is the engine's own route to it for N > 64.
+        # The registered configurations run the kernel compiled for them on every step() (auto-reset is on in every comparison:
+        # step_shape); their rollout() and the rows beside them run the generic one-wavefront kernel: highway-v0's structure
+        # with ego-only collisions (15 frames per step: no shape) and highway-v0 on 5 lanes (no shape has 5)
         ("idm wave ego-only N=64", hwy(64), {"fast": True}),
-        ("idm wave full-scan N=64", hwy(64), {}),
+        ("idm wave full-scan N=64 generic L=5", hwy(64, lanes_count=5), {}),
+        ("idm wave full-scan N=64 V0Shape4", hwy(64), {}),
+        ("idm wave FastShape3 N=64", fast(64, 3), {"fast": True}),
+        ("idm wave FastShape4 N=64", fast(64, 4), {"fast": True}),
         ("idm block NW=1 N=64", hwy(64), dict(BLOCK)),
         ("idm block NW=2 N=65", hwy(65), dict(BLOCK)),
         ("idm block NW=3 N=129", hwy(129), dict(BLOCK)),
@@ -101,11 +128,50 @@ def with_tuning(kw: dict, **knobs) -> dict:
     return {**kw, "tuning": {**kw.get("tuning", {}), **knobs}}
 
 
+def step_shape(d: dict, kw: dict) -> int:
+    """The shape id (hwy_last_step_shape: 1 = FastShape3, 2 = FastShape4, 3 = V0Shape4) of the kernel a FULL policy step with
+    auto-reset on and every output plane bound launches for a configuration, or 0: the generic kernel.  HWY_FIXED_SHAPE_FIELDS
+    (csrc/hwy_wave.h) and step_shape_of (hwy_launch_family.h) restated on the hwy_config: IDM traffic with meta-actions on the
+    straight road, at most 64 vehicles, the one-wavefront kernel not overridden, one agent at index 0, the default Kinematics
+    observation, three target speeds, the full meta-action table -- and the shape's lanes, flags and frames per step."""
+    return step_shape_of_config(_abi.make_config(d, 1, **kw))
+
+
+def step_shape_of_config(c) -> int:
+    if c.scenario != _abi.SCENARIO_HIGHWAY or c.traffic_model != _abi.TRAFFIC_IDM or c.ego_control != _abi.EGO_META:
+        return 0
+    if c.num_vehicles > 64 or c.tune_block_kernel == 1:
+        return 0
+    std5 = c.obs_type == _abi.OBS_KINEMATICS and c.obs_features == 5 and list(c.obs_feature_ids[:5]) == [0, 1, 2, 3, 4]
+    if not (c.num_agents == 1 and c.agent_index[0] == 0 and std5 and c.obs_vehicles == 5 and c.num_target_speeds == 3
+            and c.action_set == _abi.ACTIONS_SET_ALL):
+        return 0
+    for shape, fixed in SHAPES.items():
+        if (c.lanes_count, c.flags, c.frames_per_step) == fixed:
+            return shape
+    return 0
+
+
+def shape_kernel(shape: int, waves_per_eu: int) -> str:
+    lanes, flags, frames = SHAPES[shape]
+    return f"hwy::hwy_shape_wave_kernel<hwy::FixedShape<{shape}, {lanes}, {flags}, {frames}>, {waves_per_eu}>"
+
+
 def launched(d: dict, kw: dict, waves_per_eu: int) -> tuple:
     """(step kernel, rollout kernel) the engine launches for a configuration whose waves-per-EU value is `waves_per_eu` (1 .. 4:
-    hwy_config.tune_waves_per_eu, or what hwy_create chose), as keys of kernel_resources().  The selection rules of
-    csrc/hwy_params.h (force_block_kernel), hwy_launch_family.h and hwy_launch_rules.h, restated."""
+    hwy_config.tune_waves_per_eu, or what hwy_create chose), as keys of kernel_resources().  The step kernel is that of a full
+    step() with auto-reset on, as every comparison here runs it: the kernel compiled for the configuration where it is a
+    registered one (step_shape); the rollout kernel is always the generic one.  The selection rules of csrc/hwy_params.h
+    (force_block_kernel), hwy_launch_family.h and hwy_launch_rules.h, restated."""
     assert 1 <= waves_per_eu <= 4
+    shape = step_shape(d, kw)
+    if shape:
+        return shape_kernel(shape, waves_per_eu), generic_launched(d, kw, waves_per_eu)[1]
+    return generic_launched(d, kw, waves_per_eu)
+
+
+def generic_launched(d: dict, kw: dict, waves_per_eu: int) -> tuple:
+    """launched() with the shape kernels set aside (hwy_step_shapes(0), an engine before hwy_set_autoreset, a frames-only call)."""
     c = _abi.make_config(d, 1, **kw)
     n, w = c.num_vehicles, waves_per_eu
     grid = c.obs_type != _abi.OBS_KINEMATICS
@@ -184,12 +250,41 @@ def extras(eng) -> dict:
     return out
 
 
+def _shape_library(eng):
+    """The library whose launch layer runs an engine's launches: the emulation's unit of the engine's family, or the product's."""
+    if hasattr(eng, "family"):
+        from tests.emu import emu
+        return emu.lib(eng.family)
+    from highwayenv_amd import _lib
+    return _lib.load()
+
+
+def last_step_shape(eng) -> int:
+    """hwy_last_step_shape() of the library behind `eng`: highwayenv_amd.engine.last_step_shape() on the product."""
+    if hasattr(eng, "family"):
+        return int(_shape_library(eng).hwy_last_step_shape())
+    from highwayenv_amd import engine
+    return engine.last_step_shape()
+
+
+def assert_launched_shape(eng, rollout: bool, what: str) -> None:
+    """The launch `eng` just made -- a full step() with auto-reset on (reset_for_comparison), or a rollout() -- ran the kernel
+    step_shape() / launched() name for its configuration: the table cannot say one kernel while another runs.  The report is that
+    of the straight-road families' launch layer; a road-network or intersection launch leaves it alone, and nothing is asserted."""
+    if eng.cfg.scenario != _abi.SCENARIO_HIGHWAY:
+        return
+    enabled = _shape_library(eng).hwy_step_shapes(-1) == 1
+    want = 0 if rollout or not enabled else step_shape_of_config(eng.cfg)
+    got = last_step_shape(eng)
+    assert got == want, f"{what}: the launch ran shape {got}, tests/variants_util.py: step_shape() says {want}"
+
+
 def assert_builds_identical(ref, others: dict, K: int, seed: int = 5) -> int:
     """`ref` and every engine of `others` ({label: engine}; all reset alike by the caller: reset_for_comparison) take the same
     random actions through K calls of step() and then one rollout() of K more steps.  Every output of every step, the state
     afterwards and the engines' extras must be EQUAL, array_equal, on each of `others` against `ref`; an engine that counts them
-    must have stored no non-finite value.  Returns the number of episodes that ended on `ref` (each one an auto-reset inside a
-    launch)."""
+    must have stored no non-finite value; every launch must have run the kernel the table names (assert_launched_shape).  Returns
+    the number of episodes that ended on `ref` (each one an auto-reset inside a launch)."""
     assert others, "nothing to compare"
     cfg = ref.cfg
     E, A = cfg.num_envs, cfg.num_agents
@@ -203,14 +298,20 @@ def assert_builds_identical(ref, others: dict, K: int, seed: int = 5) -> int:
     n_done = 0
     for k in range(K):
         want = ref.step(acts[k])
+        assert_launched_shape(ref, False, f"default: step {k}")
         n_done += int((want[2] | want[3]).sum())
         for label, eng in others.items():
-            _assert_outputs_equal(eng.step(acts[k]), want, f"{label}: step {k}")
+            got = eng.step(acts[k])
+            assert_launched_shape(eng, False, f"{label}: step {k}")
+            _assert_outputs_equal(got, want, f"{label}: step {k}")
     want = ref.rollout(acts[K:])
+    assert_launched_shape(ref, True, "default: rollout")
     assert want[0].shape[0] == K
     n_done += int((want[2] | want[3]).sum())
     for label, eng in others.items():
-        _assert_outputs_equal(eng.rollout(acts[K:]), want, f"{label}: rollout")
+        got = eng.rollout(acts[K:])
+        assert_launched_shape(eng, True, f"{label}: rollout")
+        _assert_outputs_equal(got, want, f"{label}: rollout")
     want_state, want_extras = ref.get_state(), extras(ref)
     for label, eng in others.items():
         st, ex = eng.get_state(), extras(eng)
