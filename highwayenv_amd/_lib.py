@@ -22,7 +22,7 @@ EXPORTS = [
     "hwy_comm_unique_id", "hwy_comm_init", "hwy_gather", "hwy_comm_destroy", "hwy_set_behavior", "hwy_get_behavior",
     "hwy_set_controls", "hwy_get_controls", "hwy_ttc_grid_device", "hwy_ttc_grid", "hwy_mdp_plan_device", "hwy_mdp_plan",
     "hwy_fork_device", "hwy_fork", "hwy_score_device", "hwy_score_rollout", "hwy_opd_plan_device", "hwy_opd_plan",
-    "hwy_action_mask_device", "hwy_action_mask",
+    "hwy_action_mask_device", "hwy_action_mask", "hwy_step_same_step_device",
     "hwy_step_shapes", "hwy_last_step_shape",
 ]
 
@@ -104,6 +104,7 @@ def load() -> C.CDLL:
     lib.hwy_opd_plan.argtypes = [vp] * 9
     lib.hwy_action_mask_device.argtypes = [vp, vp]
     lib.hwy_action_mask.argtypes = [vp, vp]
+    lib.hwy_step_same_step_device.argtypes = [vp] + [vp] * 13
     lib.hwy_step_shapes.argtypes = [i32]
     lib.hwy_last_step_shape.argtypes = []
     lib.hwy_profile_enable.argtypes = [vp, i32]

@@ -1207,6 +1207,63 @@ __global__ void __launch_bounds__(NW * 64) hwy_reset_direct_kernel(const DirectP
   reset_env<NW, IdmTraffic>(dp.s, sh, LinearArgs{}, &dp.da);
 }
 
+// =============================================================================================
+// Re-spawn kernels (hwy_step_same_step_device), the workgroup form (the launches whose step runs on the workgroup kernel; hwy_wave.h
+// and hwy_wave2.h have the forms of the one-wavefront and the wide kernel): the step launch before them wrote done[e]; every environment that ended starts its
+// next episode HERE, in the same call, exactly as the auto-reset branch of the step kernels would at the following call -- seed
+// base_seed + e, episode + 1, the same spawn rule and draws, the stored controls of a direct-control ego zeroed -- and then:
+// first observation, the new ego's info_speed, info_crashed 0, time 0, done 0, the episode number stored.  What differs from that
+// branch: reward / terminated / truncated of the row are NOT touched (they stay the ending step's: gymnasium's SameStep).  What
+// differs from reset_env: the mask is st.done, the episode number is episode + 1 and is stored.
+// A workgroup whose environment did not end leaves after one (scalar) load of its flag.
+template <int NW, typename TM>
+__device__ __forceinline__ void respawn_env(const StepParams &p, typename EnvBlock<NW>::Shared &sh, const LinearArgs &la,
+                                            const DirectArgs *da = nullptr) {
+  const int e = blockIdx.x, i = threadIdx.x;
+  if (!p.st.done[e]) return;  // block-uniform
+  const bool active = i < p.N;
+  Veh me = Veh{};
+  const uint64_t seed = p.rp.base_seed + (uint64_t)e;
+  const uint32_t episode = p.st.episode[e] + 1u;  // the next episode's stream
+  spawn_env<NW>(p, sh.aux0, sh.aux1, e, seed, episode, me);
+  if constexpr (TM::LINEAR) {
+    if (active) spawn_behavior(p, la, e, i, seed, episode, (me.flags & HWY_F_CONTROLLED) != 0);
+  }
+  publish<NW>(sh, me, active);
+  __syncthreads();  // (also: every thread has read done[e] before thread 0 clears it below)
+  observe_env<NW>(p, sh, e, me, false);
+  store_vehicle<NW>(p, e, me);
+  if (active && (me.flags & HWY_F_CONTROLLED)) {
+    for (int a = 0; a < p.A; ++a)
+      if (p.agent_index[a] == i) {  // (p.reward stays the ending step's)
+        if (p.info_speed) p.info_speed[(size_t)e * p.A + a] = me.v;
+        if (p.info_crashed) p.info_crashed[(size_t)e * p.A + a] = 0;
+        if (da) da->ctl_accel[(size_t)e * p.A + a] = da->ctl_steer[(size_t)e * p.A + a] = 0.0;  // Vehicle.__init__
+      }
+  }
+  if (i == 0) {
+    p.st.time[e] = 0.0;
+    p.st.done[e] = 0;
+    p.st.episode[e] = episode;
+  }
+}
+
+template <int NW>
+__global__ void __launch_bounds__(NW * 64) hwy_respawn_kernel(const StepParams p) {
+  __shared__ typename EnvBlock<NW>::Shared sh;
+  respawn_env<NW, IdmTraffic>(p, sh, LinearArgs{});
+}
+template <int NW>
+__global__ void __launch_bounds__(NW * 64) hwy_respawn_linear_kernel(const LinearParams lp) {
+  __shared__ typename EnvBlock<NW>::Shared sh;
+  respawn_env<NW, LinearTraffic>(lp.s, sh, lp.la);
+}
+template <int NW>
+__global__ void __launch_bounds__(NW * 64) hwy_respawn_direct_kernel(const DirectParams dp) {
+  __shared__ typename EnvBlock<NW>::Shared sh;
+  respawn_env<NW, IdmTraffic>(dp.s, sh, LinearArgs{}, &dp.da);
+}
+
 // Observation-only kernel (hwy_observe).
 template <int NW>
 __global__ void __launch_bounds__(NW * 64) hwy_observe_kernel(const StepParams p) {

@@ -351,7 +351,8 @@ static hwy::Launch launch_of(const hwy_engine *eng, hipEvent_t start = nullptr, 
 // One launch of the engine's family -- its step kernel (p.full_step / p.n_frames as bound by the caller), its reset or its observe
 // kernel, with the observation going to p.obs -- and, on a Lidar engine, the trace behind it: the family's kernel runs with a null
 // `obs` (the observe kernel has nothing else to do and is not launched), then hwy_lidar.h's kernel observes the state it left.
-enum Stage { STEP, RESET, OBSERVE };
+// RESPAWN (hwy_step_same_step_device): the family's re-spawn kernel for the environments the step launch before it marked done.
+enum Stage { STEP, RESET, OBSERVE, RESPAWN };
 static hipError_t launch_stage(const hwy_engine *eng, Stage stage, StepParams p, hipEvent_t start = nullptr, hipEvent_t stop = nullptr) {
   float *obs = p.obs;
   if (is_lidar(eng)) p.obs = nullptr;
@@ -359,6 +360,7 @@ static hipError_t launch_stage(const hwy_engine *eng, Stage stage, StepParams p,
   hipError_t e = hipSuccess;
   if (stage == STEP) e = with_family(eng, p, [&](const auto &a) { return hwy::launch_step(a, l); });
   else if (stage == RESET) e = with_family(eng, p, [&](const auto &a) { return hwy::launch_reset(a, l); });
+  else if (stage == RESPAWN) e = with_family(eng, p, [&](const auto &a) { return hwy::launch_respawn(a, l); });
   else if (!is_lidar(eng)) e = with_family(eng, p, [&](const auto &a) { return hwy::launch_observe(a, l); });
   if (e != hipSuccess || !is_lidar(eng) || !obs) return e;
   const size_t plane = (size_t)eng->cfg.num_envs * eng->pitch;
@@ -1425,6 +1427,47 @@ extern "C" int hwy_action_mask(hwy_engine *eng, uint8_t *mask) {
   HWY_HIP(eng, hipMemcpyAsync(mask, eng->d_action_mask, bytes, hipMemcpyDeviceToHost, eng->stream));
   HWY_HIP(eng, hipStreamSynchronize(eng->stream));
   return HWY_OK;
+}
+
+// ---- SameStep autoreset on the device (hwy_same_step.h) -----------------------------------------------------------------------------
+extern "C" int hwy_step_same_step_device(hwy_engine *eng, const int32_t *d_actions, float *d_obs, double *d_reward, uint8_t *d_terminated,
+                                         uint8_t *d_truncated, double *d_info_speed, uint8_t *d_info_crashed, float *d_final_obs,
+                                         double *d_final_info_speed, uint8_t *d_final_info_crashed, uint8_t *d_final_mask,
+                                         uint8_t *d_action_mask, uint8_t *d_final_action_mask) {
+  static const char *who = "hwy_step_same_step_device";
+  if (!eng) return HWY_ERR_INVALID_ARG;
+  const char *why = "";
+  if (const int rc = hwy::same_step_validate(eng->cfg, eng->autoreset != 0, d_final_obs != nullptr, d_final_mask != nullptr, &why))
+    return fail(eng, rc, std::string(who) + ": " + why);
+  if (!d_actions || !d_obs || !d_reward || !d_terminated || !d_truncated)
+    return fail(eng, HWY_ERR_INVALID_ARG, std::string(who) + ": actions/obs/reward/terminated/truncated must be non-NULL");
+  if ((d_final_info_speed && !d_info_speed) || (d_final_info_crashed && !d_info_crashed))
+    return fail(eng, HWY_ERR_INVALID_ARG, std::string(who) + ": a final info plane needs the info plane it is copied from");
+  if (d_action_mask || d_final_action_mask)  // what hwy_action_mask_device answers for this engine
+    if (int rc = mask_check(eng, d_action_mask ? d_action_mask : d_final_action_mask, who)) return rc;
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  if (eng->profiling && eng->events_used >= 65536)
+    if (int rc = drain_events(eng)) return rc;
+  struct Ops {
+    hwy_engine *eng;
+    StepParams p;  // the full step around the caller's planes: the step launch's and the re-spawn's arguments
+    hwy::FinalParams fp;
+    uint8_t *action_mask, *final_action_mask;
+    int step() { return timed_launch(eng, p); }  // exactly hwy_step_device's launch: it writes done[e]
+    int mask(bool final) { return hwy_action_mask_device(eng, final ? final_action_mask : action_mask); }
+    int stash() {
+      HWY_HIP(eng, hwy::launch_final(fp, eng->stream));
+      return HWY_OK;
+    }
+    int respawn() {
+      HWY_HIP(eng, launch_stage(eng, RESPAWN, p));
+      return HWY_OK;
+    }
+  } ops{eng, {}, {}, d_action_mask, d_final_action_mask};
+  bind_full_step(eng, ops.p, d_actions, d_obs, d_reward, d_terminated, d_truncated, d_info_speed, d_info_crashed);
+  ops.fp = hwy::final_params(eng->cfg, hwy::obs_len(eng->cfg), eng->d_done, d_final_mask, d_obs, d_final_obs, d_info_speed,
+                             d_final_info_speed, d_info_crashed, d_final_info_crashed);
+  return hwy::same_step_sequence(ops, d_final_action_mask != nullptr, d_action_mask != nullptr);
 }
 
 extern "C" int hwy_sync(hwy_engine *eng) {

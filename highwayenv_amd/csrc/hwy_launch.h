@@ -14,6 +14,7 @@
 #include "hwy_lookahead.h"
 #include "hwy_opd.h"
 #include "hwy_mask.h"
+#include "hwy_same_step.h"
 #include "hwy_launch_units.h"
 
 namespace hwy {
@@ -73,6 +74,13 @@ hipError_t launch_reset(const LinearParams &lp, const Launch &l);
 hipError_t launch_reset(const DirectParams &dp, const Launch &l);
 hipError_t launch_reset(const NetParams &np, const Launch &l);
 hipError_t launch_reset(const IxParams &ip, const Launch &l);
+// the re-spawn of the environments that ended in the step launch before it (hwy_step_same_step_device; hwy_kernels_respawn.hip).
+// The intersection scenario has none: its next episodes are pre-warmed in shadow planes (the entry point refuses it before).
+hipError_t launch_respawn(const StepParams &p, const Launch &l);
+hipError_t launch_respawn(const LinearParams &lp, const Launch &l);
+hipError_t launch_respawn(const DirectParams &dp, const Launch &l);
+hipError_t launch_respawn(const NetParams &np, const Launch &l);
+inline hipError_t launch_respawn(const IxParams &, const Launch &) { return hipErrorInvalidValue; }
 // (the observation of a straight road does not depend on the traffic model or the ego control)
 hipError_t launch_observe(const StepParams &p, const Launch &l);
 inline hipError_t launch_observe(const LinearParams &lp, const Launch &l) { return launch_observe(lp.s, l); }
@@ -98,5 +106,7 @@ hipError_t launch_score(const ScoreParams &sp, hipStream_t stream);
 hipError_t launch_opd(const OpdParams &op, hipStream_t stream);
 // Action mask of the current state (hwy_mask.h, hwy_kernels_mask.hip: one thread per (environment, agent), row r -> mp.mask + r * n_ids)
 hipError_t launch_mask(const MaskParams &mp, hipStream_t stream);
+// SameStep stash (hwy_same_step.h, hwy_kernels_final.hip: one workgroup per environment, the rows of those that ended -> the final planes)
+hipError_t launch_final(const FinalParams &fp, hipStream_t stream);
 hipError_t launch_math_probe(int op, const double *in, double *out, long long n, hipStream_t stream);
 }  // namespace hwy

@@ -12,7 +12,8 @@
 //   using Params = ...;                                      the kernel argument (StepParams / LinearParams / DirectParams)
 //   step_params(Params &)                                    the StepParams inside it
 //   step_wave<WPE, FULL_SCAN>() / rollout_wave<WPE, FULL_SCAN>()   the one-wavefront kernels (hwy_wave.h, N <= 64)
-//   step_block<NW, WPE>() / rollout_block<NW, WPE>() / reset_block<NW>()   the workgroup kernels (hwy_device.h, NW wavefronts)
+//   step_block<NW, WPE>() / rollout_block<NW, WPE>() / reset_block<NW>() / respawn_block<NW>()   the workgroup kernels (hwy_device.h,
+//                                                                  NW wavefronts); respawn_wave(): hwy_wave.h's
 // each returning the address of the kernel (taking it is what instantiates the kernel: a translation unit holds the kernels of the
 // families it launches and no others).
 // hipError_t / hipStream_t / hipEvent_t come from the HIP runtime (the emulation: from hip_emu.h).
@@ -103,6 +104,8 @@ struct IdmFamily {  // IDM traffic, meta-actions (hwy_kernels.hip)
   template <int NW, int WPE> static auto step_block() { return hwy_step_kernel<NW, WPE>; }
   template <int NW, int WPE> static auto rollout_block() { return hwy_rollout_kernel<NW, WPE>; }
   template <int NW> static auto reset_block() { return hwy_reset_kernel<NW>; }
+  template <int NW> static auto respawn_block() { return hwy_respawn_kernel<NW>; }
+  static auto respawn_wave() { return hwy_respawn_wave_kernel<1>; }
 };
 struct LinearFamily {  // hwy_config.traffic_model == HWY_TRAFFIC_LINEAR (hwy_kernels_linear.hip)
   using Params = LinearParams;
@@ -113,6 +116,8 @@ struct LinearFamily {  // hwy_config.traffic_model == HWY_TRAFFIC_LINEAR (hwy_ke
   template <int NW, int WPE> static auto step_block() { return hwy_step_linear_kernel<NW, WPE>; }
   template <int NW, int WPE> static auto rollout_block() { return hwy_rollout_linear_kernel<NW, WPE>; }
   template <int NW> static auto reset_block() { return hwy_reset_linear_kernel<NW>; }
+  template <int NW> static auto respawn_block() { return hwy_respawn_linear_kernel<NW>; }
+  static auto respawn_wave() { return hwy_respawn_wave_linear_kernel<1>; }
 };
 struct DirectFamily {  // hwy_config.ego_control == HWY_EGO_DIRECT (hwy_kernels_direct.hip)
   using Params = DirectParams;
@@ -123,6 +128,8 @@ struct DirectFamily {  // hwy_config.ego_control == HWY_EGO_DIRECT (hwy_kernels_
   template <int NW, int WPE> static auto step_block() { return hwy_step_direct_kernel<NW, WPE>; }
   template <int NW, int WPE> static auto rollout_block() { return hwy_rollout_direct_kernel<NW, WPE>; }
   template <int NW> static auto reset_block() { return hwy_reset_direct_kernel<NW>; }
+  template <int NW> static auto respawn_block() { return hwy_respawn_direct_kernel<NW>; }
+  static auto respawn_wave() { return hwy_respawn_wave_direct_kernel<1>; }
 };
 
 template <typename F, typename B>
@@ -165,6 +172,19 @@ struct FamilyLaunch {
       return B::launch(F::template reset_block<NW>(), l.num_envs, NW * 64, 0, l, a);
     });
   }
+  // the re-spawn of the environments that ended in the step launch before it (hwy_step_same_step_device).  Chosen by the STEP's
+  // rule, not the reset's: the first observation of an episode must come from the code that writes it under the next-step
+  // auto-reset -- the one-wavefront kernel's observe_wave where the step runs on that kernel (the register-allocation builds and
+  // the shapes share it), the workgroup kernel's observe_env (the kernel beside the reset kernel, NW by the reset's rule) otherwise
+  static hipError_t respawn(const P &a, const Launch &l) {
+    if (wave_applies(F::step_params(a), l)) return B::launch(F::respawn_wave(), l.num_envs, 64, 0, l, a);
+    const int nw = waves_for(F::step_params(a).N);
+    if (nw < 1 || nw > 4) return hipErrorInvalidValue;
+    return dispatch_1_4(nw, [&](auto V) {
+      constexpr int NW = decltype(V)::value;
+      return B::launch(F::template respawn_block<NW>(), l.num_envs, NW * 64, 0, l, a);
+    });
+  }
   // workgroups of the step kernel this launch would run that the device holds at once (0 = unknown)
   static int resident_blocks(const P &a, const Launch &l) {
     const StepParams &p = F::step_params(a);
@@ -181,14 +201,17 @@ struct FamilyLaunch {
   }
 };
 
-// The selection of every family is the overload set select_step / select_reset / select_observe / select_resident_blocks<B>, chosen
+// The selection of every family is the overload set select_step / select_reset / select_respawn / select_observe /
+// select_resident_blocks<B>, chosen
 // by the type of the kernel argument (StepParams, NetParams and IxParams: hwy_launch_rules.h).  Linear traffic and direct ego control:
 // the one-wavefront kernel for N <= 64 (unless force_block_kernel), the workgroup kernel otherwise -- hwy_wave2.h is IDM-only.
 template <typename B> hipError_t select_step(const LinearParams &a, const Launch &l, bool rollout) { return FamilyLaunch<LinearFamily, B>::step(a, l, rollout); }
 template <typename B> hipError_t select_reset(const LinearParams &a, const Launch &l) { return FamilyLaunch<LinearFamily, B>::reset(a, l); }
+template <typename B> hipError_t select_respawn(const LinearParams &a, const Launch &l) { return FamilyLaunch<LinearFamily, B>::respawn(a, l); }
 template <typename B> int select_resident_blocks(const LinearParams &a, const Launch &l) { return FamilyLaunch<LinearFamily, B>::resident_blocks(a, l); }
 template <typename B> hipError_t select_step(const DirectParams &a, const Launch &l, bool rollout) { return FamilyLaunch<DirectFamily, B>::step(a, l, rollout); }
 template <typename B> hipError_t select_reset(const DirectParams &a, const Launch &l) { return FamilyLaunch<DirectFamily, B>::reset(a, l); }
+template <typename B> hipError_t select_respawn(const DirectParams &a, const Launch &l) { return FamilyLaunch<DirectFamily, B>::respawn(a, l); }
 template <typename B> int select_resident_blocks(const DirectParams &a, const Launch &l) { return FamilyLaunch<DirectFamily, B>::resident_blocks(a, l); }
 // (the observation of a straight road does not depend on the traffic model or the ego control)
 template <typename B> hipError_t select_observe(const StepParams &p, const Launch &l) {

@@ -37,6 +37,15 @@ template <typename B> hipError_t select_step(const StepParams &p, const Launch &
   }
 }
 template <typename B> hipError_t select_reset(const StepParams &p, const Launch &l) { return FamilyLaunch<IdmFamily, B>::reset(p, l); }
+// the re-spawn follows the step's rule (hwy_launch_family.h: FamilyLaunch::respawn says why): the wide kernel's where the step runs on it
+template <typename B> hipError_t select_respawn(const StepParams &p, const Launch &l) {
+  if (!wide_kernel_applies(p, l)) return FamilyLaunch<IdmFamily, B>::respawn(p, l);
+  switch (waves_for(p.N)) {
+    case 2: return B::launch(hwy_respawn_wide_kernel<2, 2>, l.num_envs, 64, 0, l, p);
+    case 3: return B::launch(hwy_respawn_wide_kernel<3, 1>, l.num_envs, 64, 0, l, p);
+    default: return B::launch(hwy_respawn_wide_kernel<4, 1>, l.num_envs, 64, 0, l, p);
+  }
+}
 template <typename B> int select_resident_blocks(const StepParams &p, const Launch &l) {
   if (wide_kernel_applies(p, l)) return 0;  // (the wide kernel takes no issue-priority turns)
   return FamilyLaunch<IdmFamily, B>::resident_blocks(p, l);
@@ -57,6 +66,10 @@ template <typename B> hipError_t select_step(const NetParams &np, const Launch &
 template <typename B> hipError_t select_reset(const NetParams &np, const Launch &l) {
   if (np.s.obs_type != HWY_OBS_KINEMATICS) return B::launch(hwy_net_reset_kernel<1, true>, l.num_envs, 64, 0, l, np);
   return B::launch(hwy_net_reset_kernel<1>, l.num_envs, 64, 0, l, np);
+}
+template <typename B> hipError_t select_respawn(const NetParams &np, const Launch &l) {
+  if (np.s.obs_type != HWY_OBS_KINEMATICS) return B::launch(hwy_net_respawn_kernel<1, true>, l.num_envs, 64, 0, l, np);
+  return B::launch(hwy_net_respawn_kernel<1>, l.num_envs, 64, 0, l, np);
 }
 template <typename B> hipError_t select_observe(const NetParams &np, const Launch &l) {
   if (np.s.obs_type != HWY_OBS_KINEMATICS) return B::launch(hwy_net_observe_kernel<1, true>, l.num_envs, 64, 0, l, np);

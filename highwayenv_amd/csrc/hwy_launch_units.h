@@ -94,3 +94,18 @@ template <typename B> hipError_t select_mask(const MaskParams &mp, hipStream_t s
 }
 }  // namespace hwy
 #endif
+
+// ---- SameStep stash (hwy_same_step.h): fp.E workgroups, one per environment; the workgroup size by the length of a row ---------------
+#if defined(HWY_FINAL_BLOCK) && !defined(HWY_LAUNCH_FINAL_UNIT)
+#define HWY_LAUNCH_FINAL_UNIT
+namespace hwy {
+template <typename B> hipError_t select_final(const FinalParams &fp, hipStream_t stream) {
+  if (fp.E < 1 || fp.A < 1 || fp.row_floats < 1 || !fp.done || !fp.final_mask || !fp.obs || !fp.final_obs ||
+      (fp.info_speed != nullptr) != (fp.final_info_speed != nullptr) || (fp.info_crashed != nullptr) != (fp.final_info_crashed != nullptr) ||
+      (fp.vec4 && fp.row_floats % 4 != 0))
+    return hipErrorInvalidValue;
+  return fp.row_floats <= HWY_FINAL_SMALL_FLOATS ? B::launch_plain(hwy_final_kernel<HWY_FINAL_BLOCK>, fp.E, HWY_FINAL_BLOCK, 0, stream, fp)
+                                                 : B::launch_plain(hwy_final_kernel<HWY_FINAL_BLOCK_LARGE>, fp.E, HWY_FINAL_BLOCK_LARGE, 0, stream, fp);
+}
+}  // namespace hwy
+#endif

@@ -1114,6 +1114,33 @@ __global__ void __launch_bounds__(64, WPE) hwy_net_reset_kernel(const NetParams 
   }
 }
 
+// Re-spawn kernel (hwy_step_same_step_device; hwy_device.h: respawn_env has the contract): the environments whose done[e] the step
+// launch before it set start their next episode -- seed base_seed + e, episode + 1, as the auto-reset branch of net_policy_step
+// would at the following call -- and reward / terminated / truncated stay the ending step's.  A wavefront whose environment did
+// not end leaves after one load of its flag, before the lane table is copied.
+template <int WPE, bool GRID = false>
+__global__ void __launch_bounds__(64, WPE) hwy_net_respawn_kernel(const NetParams np) {
+  const StepParams &p = np.s;
+  __shared__ NetShared sh;
+  const int e = blockIdx.x, i = threadIdx.x;
+  if (!p.st.done[e]) return;  // block-uniform
+  net_load_table(np, sh);
+  Veh me;
+  const uint32_t episode = p.st.episode[e] + 1u;  // the next episode's stream
+  net_spawn_env(np, sh, p.rp.base_seed + (uint64_t)e, episode, me);
+  net_observe<GRID>(np, sh, e, e, me, false);
+  store_vehicle<1>(p, e, me);
+  if (i < p.A) {  // agent a == slot a (p.reward stays the ending step's)
+    if (p.info_speed) p.info_speed[(size_t)e * p.A + i] = me.v;
+    if (p.info_crashed) p.info_crashed[(size_t)e * p.A + i] = 0;
+  }
+  if (i == 0) {
+    p.st.time[e] = 0.0;
+    p.st.done[e] = 0;
+    p.st.episode[e] = episode;
+  }
+}
+
 // Observation-only kernel (hwy_observe).
 template <int WPE, bool GRID = false>
 __global__ void __launch_bounds__(64, WPE) hwy_net_observe_kernel(const NetParams np) {

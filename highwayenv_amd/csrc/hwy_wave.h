@@ -1088,6 +1088,57 @@ __global__ void __launch_bounds__(64, WPE) hwy_rollout_wave_direct_kernel(const 
   }
 }
 
+// Re-spawn kernels (hwy_step_same_step_device; hwy_device.h: respawn_env has the contract) for the launches whose step runs on the
+// one-wavefront kernel: the auto-reset branch of wave_policy_step without its writes of reward / terminated / truncated, for the
+// environments whose done[e] the step launch before it set.  The first observation is observe_wave's, like that branch's: the
+// same episodes under SameStep and NextStep means the same bits, and observe_wave maps a feature with the host-computed reciprocal
+// of its range (lmap_inv) where the workgroup kernel's observe_env divides -- the two differ in the last bit of a double, which a
+// float keeps next to zero.  A wavefront whose environment did not end leaves after one load of its flag.
+template <typename TM = IdmTraffic>
+__device__ __forceinline__ void wave_respawn(const StepParams &p, WaveShared &sh, const LinearArgs &la = LinearArgs{},
+                                             const DirectArgs *da = nullptr) {
+  const int e = blockIdx.x, i = threadIdx.x;
+  if (!p.st.done[e]) return;  // wave-uniform
+  const bool active = i < p.N;
+  Veh me = Veh{};
+  const uint64_t seed = p.rp.base_seed + (uint64_t)e;
+  const uint32_t episode = p.st.episode[e] + 1u;  // the next episode's stream
+  spawn_env<1>(p, sh.x, sh.v, e, seed, episode, me);
+  if constexpr (TM::LINEAR) {
+    if (active) spawn_behavior(p, la, e, i, seed, episode, (me.flags & HWY_F_CONTROLLED) != 0);
+  }
+  observe_wave<false, MetaEgo, RuntimeShape>(p, e, e, me, false);
+  store_vehicle<1>(p, e, me);
+  if (active && (me.flags & HWY_F_CONTROLLED)) {
+    for (int a = 0; a < p.A; ++a)
+      if (p.agent_index[a] == i) {  // (p.reward stays the ending step's)
+        if (p.info_speed) p.info_speed[(size_t)e * p.A + a] = me.v;
+        if (p.info_crashed) p.info_crashed[(size_t)e * p.A + a] = 0;
+        if (da) da->ctl_accel[(size_t)e * p.A + a] = da->ctl_steer[(size_t)e * p.A + a] = 0.0;  // Vehicle.__init__
+      }
+  }
+  if (i == 0) {
+    p.st.time[e] = 0.0;
+    p.st.done[e] = 0;
+    p.st.episode[e] = episode;
+  }
+}
+template <int WPE>
+__global__ void __launch_bounds__(64, WPE) hwy_respawn_wave_kernel(const StepParams p) {
+  __shared__ WaveShared sh;
+  wave_respawn<IdmTraffic>(p, sh);
+}
+template <int WPE>
+__global__ void __launch_bounds__(64, WPE) hwy_respawn_wave_linear_kernel(const LinearParams lp) {
+  __shared__ WaveShared sh;
+  wave_respawn<LinearTraffic>(lp.s, sh, lp.la);
+}
+template <int WPE>
+__global__ void __launch_bounds__(64, WPE) hwy_respawn_wave_direct_kernel(const DirectParams dp) {
+  __shared__ WaveShared sh;
+  wave_respawn<IdmTraffic>(dp.s, sh, LinearArgs{}, &dp.da);
+}
+
 // Reset / observe kernels for N <= 64 reuse the generic ones (not on the per-step path).
 
 }  // namespace hwy

@@ -280,6 +280,21 @@ class Engine:
         """Enqueue hwy_action_mask_device on a raw device pointer (uint8 [E, A, n_ids]); does not synchronise."""
         self._check_scope(self._lib.hwy_action_mask_device(self._h, C.c_void_p(d_mask or None)))
 
+    # -- SameStep autoreset on the device (csrc/hwy_same_step.h) --------------------------------------
+    def step_same_step_device(self, d_actions: int, d_obs: int, d_reward: int, d_terminated: int, d_truncated: int,
+                              d_info_speed: int = 0, d_info_crashed: int = 0, d_final_obs: int = 0, d_final_info_speed: int = 0,
+                              d_final_info_crashed: int = 0, d_final_mask: int = 0, d_action_mask: int = 0,
+                              d_final_action_mask: int = 0):
+        """Enqueue hwy_step_same_step_device on raw device pointers: one policy step, the terminal rows of the environments that
+        ended stashed into the ``final`` planes (read them under ``d_final_mask``), their next episode started in the same call;
+        does not synchronise.  Needs ``set_autoreset(True, ...)``.  NotImplementedError on the intersection scenario, and for a
+        mask pointer on a DiscreteAction engine."""
+        vp = C.c_void_p
+        self._check_scope(self._lib.hwy_step_same_step_device(
+            self._h, vp(d_actions or None), vp(d_obs or None), vp(d_reward or None), vp(d_terminated or None), vp(d_truncated or None),
+            vp(d_info_speed or None), vp(d_info_crashed or None), vp(d_final_obs or None), vp(d_final_info_speed or None),
+            vp(d_final_info_crashed or None), vp(d_final_mask or None), vp(d_action_mask or None), vp(d_final_action_mask or None)))
+
     # -- reset --------------------------------------------------------------------------------
     def reset(self, seeds=None, mask=None, ego_spacing=2.0, vehicles_density=1.0, initial_lane_id=-1, base_seed=0):
         """Device-side spawn (counter-based RNG; NOT numpy's stream -- see spawn.py for that)."""

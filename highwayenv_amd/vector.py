@@ -17,13 +17,18 @@ environments are ONE engine (one kernel launch per step), and this class gives t
   - ``"SameStep"`` (what the reference's vectorisation test asks for): the step that ends an episode already returns the
     first observation of the next one; the terminal observation and info travel in ``infos["final_obs"]`` / ``infos["final_info"]``
     (object arrays, ``None`` where the episode goes on) with the ``_final_obs`` / ``_final_info`` masks.  One masked device reset
-    per step in which some episode ended;
+    per step in which some episode ended.  With ``output="torch"`` the whole of it happens on the device in the same call
+    (``hwy_step_same_step_device``: step, stash of the terminal rows, re-spawn) and the extras are DENSE tensors and a mask instead
+    of object arrays: ``final_obs`` [E, ...] and ``final_info = {"speed", "crashed"(, "action_mask")}`` hold the terminal values in
+    the rows where the bool mask ``_final_obs`` (== ``_final_info`` == ``terminated | truncated``) is set and are NOT written in the
+    other rows (zeros, or an earlier episode's end: read them under the mask); the episodes are those of ``"NextStep"`` on the
+    same seed, bit for bit.  Highway and merge ids; the intersection ids raise ``ValueError`` in this combination;
   - ``"Disabled"``: finished environments keep stepping until the caller resets.
 
 * ``output="torch"``: observations, rewards and flags are ``torch`` tensors that ALIAS the buffers the kernel writes (no host
   round trip), actions may be a device tensor, and everything is ordered on torch's current stream -- a policy network can read
-  ``obs`` and write ``actions`` without leaving the GPU ("keeping the policy on-GPU").  ``NextStep`` /
-  ``Disabled`` only.  ``rollout(actions[K])`` exposes ``hwy_rollout_device`` (K steps per launch) in this mode.
+  ``obs`` and write ``actions`` without leaving the GPU ("keeping the policy on-GPU").  Every autoreset
+  mode.  ``rollout(actions[K])`` exposes ``hwy_rollout_device`` (K steps per launch, NextStep between them) in this mode.
 
 With gymnasium installed the class IS a ``gymnasium.vector.VectorEnv``; without it (this image) the same attributes exist on a
 plain object.
@@ -74,9 +79,13 @@ class HighwayVectorEnv(_Base):
             raise ValueError(f"autoreset_mode must be one of {AUTORESET_MODES}")
         if output not in ("numpy", "torch"):
             raise ValueError("output must be 'numpy' or 'torch'")
-        if output == "torch" and mode == "SameStep":
-            raise ValueError("output='torch' supports the NextStep and Disabled autoreset modes (SameStep merges a masked reset on the host)")
         self.autoreset_mode = mode
+        # output="torch" with SameStep: the engine runs with auto-reset enabled and every step is one hwy_step_same_step_device
+        self._device_same_step = output == "torch" and mode == "SameStep"
+        scenario = getattr(_envs.batched_class(env) if isinstance(env, str) else env, "SCENARIO", None)
+        if self._device_same_step and scenario == "intersection":
+            raise ValueError("output='torch' with autoreset_mode='SameStep' is not available for the intersection scenario (its next "
+                             "episodes are pre-warmed on the device, keyed to the episode counter); use NextStep, or output='numpy'")
         self.output = output
         # action_masks: reset() and step() put info["action_mask"] (gymnasium's convention) into the info dict: bool [E, n_ids]
         # ([E, A, n_ids] for several agents), the mask of the state whose observation is returned (csrc/hwy_mask.h).  With
@@ -101,13 +110,14 @@ class HighwayVectorEnv(_Base):
             raise ValueError("stream= needs output='torch'")
         if isinstance(env, str):
             env = _envs.batched_class(env)
+        engine_autoreset = mode == "NextStep" or self._device_same_step
         if isinstance(env, type):
-            env = env(config, num_envs=num_envs, device=device, spawn_mode=spawn_mode, autoreset=(mode == "NextStep"),
+            env = env(config, num_envs=num_envs, device=device, spawn_mode=spawn_mode, autoreset=engine_autoreset,
                       stream=stream, **kwargs)
         elif config:
             env.configure(config)
         self.env = env
-        env.autoreset = mode == "NextStep"
+        env.autoreset = engine_autoreset
         self.num_envs = env.num_envs
         self.single_observation_space, self.single_action_space = env.single_observation_space, env.single_action_space
         if _gym is not None:
@@ -189,6 +199,11 @@ class HighwayVectorEnv(_Base):
             if self.env._hcfg.ego_control != _abi.EGO_META:
                 raise NotImplementedError("action_masks needs a DiscreteMetaAction ego")
             d["action_mask"] = t.empty((E, A, _abi.num_actions(self.env._hcfg)), dtype=t.uint8, device=dev)
+        if self._device_same_step:  # the planes of the terminal rows (hwy_step_same_step_device writes the rows of ended episodes)
+            d["final_obs"], d["final_speed"] = t.zeros_like(d["obs"]), t.zeros_like(d["speed"])
+            d["final_crashed"], d["final_mask"] = t.zeros_like(d["crashed"]), t.zeros(E, dtype=t.uint8, device=dev)
+            if self.action_masks:
+                d["final_action_mask"] = t.zeros_like(d["action_mask"])
         self._n_actions = E * A
         self._out_ptrs = tuple(d[k].data_ptr() for k in ("obs", "reward", "terminated", "truncated", "speed", "crashed"))
         # what step() hands out: views of the planes the kernel writes (bool views of the 0 / 1 flag bytes; the intersection's
@@ -199,6 +214,15 @@ class HighwayVectorEnv(_Base):
                        "speed": d["speed"][:, 0], "crashed": d["crashed"][:, 0].view(t.bool) if plain_crashed else None}
         if self.action_masks:  # the 0 / 1 bytes the mask kernel writes, as a zero-copy bool view
             self._views["action_mask"] = (d["action_mask"][:, 0] if A == 1 else d["action_mask"]).view(t.bool)
+        if self._device_same_step:
+            self._final_ptrs = tuple(d[k].data_ptr() if k in d else 0 for k in (
+                "final_obs", "final_speed", "final_crashed", "final_mask", "action_mask", "final_action_mask"))
+            v = self._views
+            v["final_obs"] = d["final_obs"][:, 0] if A == 1 else d["final_obs"]
+            v["final_mask"] = d["final_mask"].view(t.bool)
+            v["final_info"] = {"speed": d["final_speed"][:, 0], "crashed": d["final_crashed"][:, 0].view(t.bool)}
+            if self.action_masks:
+                v["final_info"]["action_mask"] = (d["final_action_mask"][:, 0] if A == 1 else d["final_action_mask"]).view(t.bool)
 
     def _mask_into(self, out):
         """Enqueue the mask kernel into the uint8 device tensor ``out`` on the engine's stream, ordered after the caller's current
@@ -233,9 +257,12 @@ class HighwayVectorEnv(_Base):
         same = cur.cuda_stream == self._stream.cuda_stream
         if not same:
             self._stream.wait_stream(cur)      # the actions (and the consumer of the previous outputs) come first
-        self.env._engine.step_device(actions.data_ptr(), *self._out_ptrs)
-        if self.action_masks:                  # of the state this step left, behind it on the engine's stream
-            self.env._engine.action_mask_device(d["action_mask"].data_ptr())
+        if self._device_same_step:             # step, stash of the terminal rows, re-spawn (and both masks) in one call
+            self.env._engine.step_same_step_device(actions.data_ptr(), *self._out_ptrs, *self._final_ptrs)
+        else:
+            self.env._engine.step_device(actions.data_ptr(), *self._out_ptrs)
+            if self.action_masks:              # of the state this step left, behind it on the engine's stream
+                self.env._engine.action_mask_device(d["action_mask"].data_ptr())
         if not same:
             cur.wait_stream(self._stream)      # whatever the caller enqueues next sees this step's outputs
             actions.record_stream(self._stream)
@@ -243,6 +270,9 @@ class HighwayVectorEnv(_Base):
         infos = {"speed": v["speed"], "crashed": v["crashed"] if v["crashed"] is not None else (d["crashed"][:, 0] & 1).bool()}
         if self.action_masks:
             infos["action_mask"] = v["action_mask"]
+        if self._device_same_step:             # dense tensors under a mask (the numpy path hands out object arrays)
+            infos.update({"final_obs": v["final_obs"], "_final_obs": v["final_mask"], "final_info": v["final_info"],
+                          "_final_info": v["final_mask"]})
         return v["obs"], v["reward"], v["terminated"], v["truncated"], infos
 
     def rollout(self, actions):

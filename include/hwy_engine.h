@@ -753,6 +753,40 @@ int hwy_comm_init(hwy_engine *eng, const uint8_t *id, int32_t rank, int32_t worl
 int hwy_gather(hwy_engine *eng, const void *d_send, void *d_recv, size_t bytes, int32_t root);
 int hwy_comm_destroy(hwy_engine *eng);
 
+/*
+ * SameStep autoreset on the device (additive to ABI v8: hwy_config keeps its layout).  gymnasium's vector autoreset mode "SameStep"
+ * (gymnasium/vector/vector_env.py: AutoresetMode.SAME_STEP; the reference's vectorisation test asks for it, tests/envs/test_gym.py):
+ * the step that ends an episode returns the FIRST observation of the next one, and the terminal observation and info on the side.
+ * hwy_step_device's arguments, then
+ *   d_final_obs           f32 the observation's own shape [E][A]...   rows of the environments that ended: the terminal observation
+ *   d_final_info_speed    f64 [E][A]   (may be NULL)                  likewise the terminal info
+ *   d_final_info_crashed  u8  [E][A]   (may be NULL)
+ *   d_final_mask          u8  [E]      1 = the environment ended in this call (terminated | truncated), 0 = it did not
+ *   d_action_mask         u8  [E][A][n_ids]  (may be NULL)  hwy_action_mask_device of the state the call leaves
+ *   d_final_action_mask   u8  [E][A][n_ids]  (may be NULL)  ... of the state the step left, before any re-spawn: the terminal state's
+ *                                                           mask in the rows of the environments that ended
+ * One call enqueues, in order on the engine's stream: the family's ordinary step launch, exactly as hwy_step_device issues it with
+ * auto-reset on (a Lidar engine: + the trace); the mask kernel into d_final_action_mask; the stash kernel (csrc/hwy_same_step.h) --
+ * d_final_mask[e] = done[e] for every e, and for the ones that ended their rows of d_obs, d_info_speed, d_info_crashed copied to
+ * the final planes, the rows of the others NOT written at all (the caller reads them under the mask); the family's re-spawn kernel,
+ * which starts the next episode of every environment that ended exactly as the next-step auto-reset would at the following call
+ * (seed base_seed + e, episode counter + 1, the same spawn rule, the Linear family's parameter draws, a direct-control ego's stored
+ * controls zeroed), observes it into d_obs, writes the new ego's d_info_speed and d_info_crashed = 0 and clears the "ended" mark --
+ * d_reward, d_terminated and d_truncated of the row are NOT touched, they stay the ending step's; a Lidar engine: the trace again;
+ * the mask kernel into d_action_mask.  Episode k of environment e is therefore the same episode, bit for bit, under this call and
+ * under hwy_step_device's next-step auto-reset.  No environment is ever "ended, awaiting its re-spawn" between two calls.
+ * hwy_set_autoreset must have enabled auto-reset (it supplies base_seed and the spawn arguments): HWY_ERR_INVALID_ARG otherwise, and
+ * for a NULL d_final_obs / d_final_mask or a final info plane without its info plane.  Either mask pointer on an engine without a
+ * DiscreteMetaAction ego: what hwy_action_mask_device returns.  HWY_SCENARIO_HIGHWAY (every traffic model, ego control, observation
+ * type, agent count and N) and the merge scenarios; HWY_ERR_UNSUPPORTED for HWY_SCENARIO_INTERSECTION, whose next episodes are
+ * pre-warmed in shadow planes keyed to the episode counter.
+ * DEVICE pointers; only enqueues and does not synchronise (like hwy_step_device); action ids are not validated (see there).
+ */
+int hwy_step_same_step_device(hwy_engine *eng, const int32_t *d_actions, float *d_obs, double *d_reward, uint8_t *d_terminated,
+                              uint8_t *d_truncated, double *d_info_speed, uint8_t *d_info_crashed, float *d_final_obs,
+                              double *d_final_info_speed, uint8_t *d_final_info_crashed, uint8_t *d_final_mask,
+                              uint8_t *d_action_mask, uint8_t *d_final_action_mask);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,53 @@
+"""Load-bearing checks of the SameStep sequence and its re-spawn kernels, by the method of tests/test_mask_mutations.py: a rule is
+broken in a COPY of the kernel source (one text replacement), the CPU emulation (tests/emu/emu_same_step.cpp) is built from the copy,
+and the comparison of one same-step call against two next-step calls (tests/same_step_util.py: one_call_against_two) must FAIL on
+it -- while it passes on the unmutated source (tests/test_same_step_device.py):
+
+* `same_episode`   -- the re-spawn draws from the stream of `episode` instead of `episode + 1` (and stores that number): in the
+  one-wavefront kernel (`fast`), the wide kernel (`n65`), the workgroup kernel (`n129`) and the road-network kernel (`merge`);
+* `stash_late`     -- the stash runs after the re-spawn instead of before it: the terminal rows are gone, the mark is cleared;
+* `clears_reward`  -- the re-spawn zeroes the reward of the row, as the next-step branch of the step kernels does.
+Only engine Y runs the mutant; X, the yardstick, is the unmutated next-step emulation."""
+import pytest
+
+from tests import mutation_util, same_step_util as ssu
+from tests.emu import emu
+
+NEXT = "const uint32_t episode = p.st.episode[e] + 1u;  // the next episode's stream"
+SAME = "const uint32_t episode = p.st.episode[e];  // the next episode's stream"
+MUTANTS = {
+    "same_episode_wave": [("hwy_wave.h", NEXT, SAME)],
+    "same_episode_wide": [("hwy_wave2.h", NEXT, SAME)],
+    "same_episode_block": [("hwy_device.h", NEXT, SAME)],
+    "same_episode_net": [("hwy_net.h", NEXT, SAME)],
+    "stash_late": [("hwy_same_step.h", "  if (int rc = ops.stash()) return rc;\n  if (int rc = ops.respawn()) return rc;\n",
+                    "  if (int rc = ops.respawn()) return rc;\n  if (int rc = ops.stash()) return rc;\n")],
+    "clears_reward": [("hwy_wave.h", "if (p.agent_index[a] == i) {  // (p.reward stays the ending step's)",
+                       "if (p.agent_index[a] == i) { p.reward[(size_t)e * p.A + a] = 0.0;")],
+}
+CASES = [("same_episode_wave", "fast"), ("same_episode_wide", "n65"), ("same_episode_block", "n129"), ("same_episode_net", "merge"),
+         ("stash_late", "fast"), ("clears_reward", "fast")]
+_libs = {}
+
+
+def mutant(name: str):
+    if name not in _libs:
+        import tests.emu.emu_same_step  # noqa: F401  (registers the unit)
+        _libs[name] = emu.load("same_step", mutation_util.build_mutant(MUTANTS[name], "emu_same_step.cpp", f"libhwy_emu_same_step_mut_{name}.so"))
+    return _libs[name]
+
+
+def _mutated_engine(name):
+    def make(cfg):
+        eng = ssu.make_engine("emu", cfg)
+        eng.same_step_lib = mutant(name)
+        return eng
+    return make
+
+
+@pytest.mark.parametrize("name,config", CASES, ids=[f"{m}-{c}" for m, c in CASES])
+def test_seeded_bug_fails_the_one_call_comparison(name, config):
+    seed, warmup, action, stagger = ssu.ENTRIES[config][0]
+    ssu.one_call_against_two("emu", config, seed, warmup, action, stagger)  # must pass on the unmutated source
+    with pytest.raises(AssertionError):  # ("DID NOT RAISE": the mutant survived)
+        ssu.one_call_against_two("emu", config, seed, warmup, action, stagger, make_y=_mutated_engine(name))
