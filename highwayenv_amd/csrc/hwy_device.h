@@ -1161,31 +1161,85 @@ __device__ inline void publish(typename EnvBlock<NW>::Shared &sh, const Veh &me,
 }
 
 // =============================================================================================
-// Reset kernel: AbstractEnv.reset for the masked environments + first observation.
-// (the body of both reset kernels: TM = the traffic model, whose Linear family also draws the per-vehicle parameters)
-// (da: the stored controls of a DirectEgo engine, zeroed like Vehicle.__init__ does -- the spawn itself is the one of MetaEgo)
-template <int NW, typename TM>
-__device__ __forceinline__ void reset_env(const StepParams &p, typename EnvBlock<NW>::Shared &sh, const LinearArgs &la,
-                                          const DirectArgs *da = nullptr) {
-  const int e = blockIdx.x, i = threadIdx.x;
-  if (p.reset_mask && !p.reset_mask[e]) return;  // block-uniform
+// Starting an episode of environment e: spawn on the Philox stream of (seed, episode), the Linear family's parameters, the first
+// observation, the planes, the agent rows, time / done / episode.  One function per kernel form does it for every caller --
+// block_begin_episode below, hwy_wave.h: wave_begin_episode, hwy_wave2.h: wide_begin_episode, hwy_net.h: net_begin_episode -- so
+// that an episode starts with the same bits whichever launch starts it.  The caller keeps the gate; the mode says the rest:
+//
+//   mode       caller (gate)                                  seed                           episode      row  reward, terminated, truncated
+//   Reset      the reset kernels (reset_mask)                 reset_seeds[e], else as below  0            e    untouched
+//   NextStep   top of the step kernels (autoreset && done)    base_seed + e                  episode + 1  eo   zeroed
+//   SameStep   the re-spawn kernels (done), behind the step   base_seed + e                  episode + 1  e    untouched: the ending step's
+//              launch of hwy_step_same_step_device
+//
+// Every mode stores time = 0, done = 0 and the episode number, zeroes the stored controls of a direct-control ego (Vehicle.__init__)
+// and writes the new ego's info_speed and info_crashed = 0 where those planes are bound -- a reset launch binds neither.
+enum class Begin { Reset, NextStep, SameStep };
+struct EpisodeStream {
+  uint64_t seed;
+  uint32_t episode;
+};
+template <Begin M>
+__device__ __forceinline__ EpisodeStream episode_stream(const StepParams &p, int e) {
+  EpisodeStream s;
+  s.episode = M == Begin::Reset ? 0u : p.st.episode[e] + 1u;  // the next episode's stream
+  s.seed = (M == Begin::Reset && p.reset_seeds) ? p.reset_seeds[e] : p.rp.base_seed + (uint64_t)e;
+  return s;
+}
+// The rows of the agents whose vehicle is vi (the straight-road forms; the road network keeps agent a in slot a), by vi's thread.
+template <Begin M, typename EG>
+__device__ __forceinline__ void begin_agent_rows(const StepParams &p, const DirectArgs *da, int e, int eo, int vi, bool active,
+                                                 const Veh &o) {
+  if (active && (o.flags & HWY_F_CONTROLLED)) {
+    for (int a = 0; a < p.A; ++a)
+      if (p.agent_index[a] == vi) {
+        if (M == Begin::NextStep) p.reward[(size_t)eo * p.A + a] = 0.0;  // (SameStep: p.reward stays the ending step's)
+        if (p.info_speed) p.info_speed[(size_t)eo * p.A + a] = o.v;
+        if (p.info_crashed) p.info_crashed[(size_t)eo * p.A + a] = 0;
+        if constexpr (EG::DIRECT) da->ctl_accel[(size_t)e * p.A + a] = da->ctl_steer[(size_t)e * p.A + a] = 0.0;  // Vehicle.__init__
+      }
+  }
+}
+// The environment's own words, by one thread (every form).
+template <Begin M>
+__device__ __forceinline__ void begin_env_row(const StepParams &p, int e, int eo, uint32_t episode) {
+  p.st.time[e] = 0.0;
+  p.st.done[e] = 0;
+  p.st.episode[e] = episode;
+  if (M == Begin::NextStep) {
+    p.terminated[eo] = 0;
+    p.truncated[eo] = 0;
+  }
+}
+
+// The workgroup form.  TM: the traffic model, whose Linear family also draws the per-vehicle parameters; EG / da: the ego control,
+// whose stored controls a direct-control engine zeroes (the spawn itself is the one of MetaEgo).  Called by the reset and the re-spawn
+// kernels; block_policy_step keeps its NextStep branch written out and says why.
+template <Begin M, int NW, typename TM, typename EG>
+__device__ __forceinline__ void block_begin_episode(const StepParams &p, typename EnvBlock<NW>::Shared &sh, int e, int eo,
+                                                    const LinearArgs &la, const DirectArgs *da) {
+  const int i = threadIdx.x;
   const bool active = i < p.N;
   Veh me = Veh{};
-  const uint64_t seed = p.reset_seeds ? p.reset_seeds[e] : p.rp.base_seed + (uint64_t)e;
-  spawn_env<NW>(p, sh.aux0, sh.aux1, e, seed, 0u, me);
+  const EpisodeStream s = episode_stream<M>(p, e);
+  spawn_env<NW>(p, sh.aux0, sh.aux1, e, s.seed, s.episode, me);
   if constexpr (TM::LINEAR) {
-    if (active) spawn_behavior(p, la, e, i, seed, 0u, (me.flags & HWY_F_CONTROLLED) != 0);
+    if (active) spawn_behavior(p, la, e, i, s.seed, s.episode, (me.flags & HWY_F_CONTROLLED) != 0);
   }
   publish<NW>(sh, me, active);
-  __syncthreads();
-  observe_env<NW>(p, sh, e, me, false);
+  __syncthreads();  // (also: every thread has read done[e] before thread 0 clears it below)
+  observe_env<NW>(p, sh, e, me, false, eo);
   store_vehicle<NW>(p, e, me);
-  if (da && i < p.A) da->ctl_accel[(size_t)e * p.A + i] = da->ctl_steer[(size_t)e * p.A + i] = 0.0;
-  if (i == 0) {
-    p.st.time[e] = 0.0;
-    p.st.done[e] = 0;
-    p.st.episode[e] = 0;
-  }
+  begin_agent_rows<M, EG>(p, da, e, eo, i, active, me);
+  if (i == 0) begin_env_row<M>(p, e, eo, s.episode);
+}
+
+// Reset kernels: AbstractEnv.reset for the masked environments + first observation.
+template <int NW, typename TM, typename EG = MetaEgo>
+__device__ __forceinline__ void reset_env(const StepParams &p, typename EnvBlock<NW>::Shared &sh, const LinearArgs &la,
+                                          const DirectArgs *da = nullptr) {
+  if (p.reset_mask && !p.reset_mask[blockIdx.x]) return;  // block-uniform
+  block_begin_episode<Begin::Reset, NW, TM, EG>(p, sh, blockIdx.x, blockIdx.x, la, da);
 }
 
 template <int NW>
@@ -1204,48 +1258,16 @@ __global__ void __launch_bounds__(NW * 64) hwy_reset_linear_kernel(const LinearP
 template <int NW>
 __global__ void __launch_bounds__(NW * 64) hwy_reset_direct_kernel(const DirectParams dp) {
   __shared__ typename EnvBlock<NW>::Shared sh;
-  reset_env<NW, IdmTraffic>(dp.s, sh, LinearArgs{}, &dp.da);
+  reset_env<NW, IdmTraffic, DirectEgo>(dp.s, sh, LinearArgs{}, &dp.da);
 }
 
-// =============================================================================================
-// Re-spawn kernels (hwy_step_same_step_device), the workgroup form (the launches whose step runs on the workgroup kernel; hwy_wave.h
-// and hwy_wave2.h have the forms of the one-wavefront and the wide kernel): the step launch before them wrote done[e]; every environment that ended starts its
-// next episode HERE, in the same call, exactly as the auto-reset branch of the step kernels would at the following call -- seed
-// base_seed + e, episode + 1, the same spawn rule and draws, the stored controls of a direct-control ego zeroed -- and then:
-// first observation, the new ego's info_speed, info_crashed 0, time 0, done 0, the episode number stored.  What differs from that
-// branch: reward / terminated / truncated of the row are NOT touched (they stay the ending step's: gymnasium's SameStep).  What
-// differs from reset_env: the mask is st.done, the episode number is episode + 1 and is stored.
-// A workgroup whose environment did not end leaves after one (scalar) load of its flag.
-template <int NW, typename TM>
+// Re-spawn kernels (hwy_step_same_step_device; Begin::SameStep above), the workgroup form: for the launches whose step runs on the
+// workgroup kernel.  A workgroup whose environment did not end leaves after one (scalar) load of its flag.
+template <int NW, typename TM, typename EG = MetaEgo>
 __device__ __forceinline__ void respawn_env(const StepParams &p, typename EnvBlock<NW>::Shared &sh, const LinearArgs &la,
                                             const DirectArgs *da = nullptr) {
-  const int e = blockIdx.x, i = threadIdx.x;
-  if (!p.st.done[e]) return;  // block-uniform
-  const bool active = i < p.N;
-  Veh me = Veh{};
-  const uint64_t seed = p.rp.base_seed + (uint64_t)e;
-  const uint32_t episode = p.st.episode[e] + 1u;  // the next episode's stream
-  spawn_env<NW>(p, sh.aux0, sh.aux1, e, seed, episode, me);
-  if constexpr (TM::LINEAR) {
-    if (active) spawn_behavior(p, la, e, i, seed, episode, (me.flags & HWY_F_CONTROLLED) != 0);
-  }
-  publish<NW>(sh, me, active);
-  __syncthreads();  // (also: every thread has read done[e] before thread 0 clears it below)
-  observe_env<NW>(p, sh, e, me, false);
-  store_vehicle<NW>(p, e, me);
-  if (active && (me.flags & HWY_F_CONTROLLED)) {
-    for (int a = 0; a < p.A; ++a)
-      if (p.agent_index[a] == i) {  // (p.reward stays the ending step's)
-        if (p.info_speed) p.info_speed[(size_t)e * p.A + a] = me.v;
-        if (p.info_crashed) p.info_crashed[(size_t)e * p.A + a] = 0;
-        if (da) da->ctl_accel[(size_t)e * p.A + a] = da->ctl_steer[(size_t)e * p.A + a] = 0.0;  // Vehicle.__init__
-      }
-  }
-  if (i == 0) {
-    p.st.time[e] = 0.0;
-    p.st.done[e] = 0;
-    p.st.episode[e] = episode;
-  }
+  if (!p.st.done[blockIdx.x]) return;  // block-uniform
+  block_begin_episode<Begin::SameStep, NW, TM, EG>(p, sh, blockIdx.x, blockIdx.x, la, da);
 }
 
 template <int NW>
@@ -1261,7 +1283,7 @@ __global__ void __launch_bounds__(NW * 64) hwy_respawn_linear_kernel(const Linea
 template <int NW>
 __global__ void __launch_bounds__(NW * 64) hwy_respawn_direct_kernel(const DirectParams dp) {
   __shared__ typename EnvBlock<NW>::Shared sh;
-  respawn_env<NW, IdmTraffic>(dp.s, sh, LinearArgs{}, &dp.da);
+  respawn_env<NW, IdmTraffic, DirectEgo>(dp.s, sh, LinearArgs{}, &dp.da);
 }
 
 // Observation-only kernel (hwy_observe).
@@ -1346,6 +1368,8 @@ __device__ __forceinline__ void block_policy_step(const StepParams &p, typename 
   const int lane_id = i & 63, wave = i >> 6;
 
   // ---- auto-reset (gymnasium vector "next-step" mode): re-spawn instead of stepping ------------
+  // block_begin_episode<Begin::NextStep>, written out: called as a function, the same text moves every register allocation of this
+  // kernel (profiles/episode_start_refactor.md has the figures).  tests/test_same_step_device.py holds the two to the same bits.
   if (p.autoreset && p.st.done[e]) {  // block-uniform
     Veh me = Veh{};
     const uint32_t episode = p.st.episode[e] + 1u;

@@ -667,6 +667,23 @@ __device__ inline void net_spawn_env(const NetParams &np, NetShared &sh, uint64_
 #ifndef HWY_NET_WALK_STEPS
 #define HWY_NET_WALK_STEPS 2  // partners asked per trip of the collision walk
 #endif
+// Starting an episode, the road-network form (hwy_device.h: Begin has the rule table); the lane table is in LDS.
+template <Begin M, bool GRID>
+__device__ __forceinline__ void net_begin_episode(const NetParams &np, NetShared &sh, int e, int eo, Veh &me) {
+  const StepParams &p = np.s;
+  const int i = threadIdx.x;
+  const EpisodeStream s = episode_stream<M>(p, e);
+  net_spawn_env(np, sh, s.seed, s.episode, me);
+  net_observe<GRID>(np, sh, e, eo, me, false);
+  store_vehicle<1>(p, e, me);
+  if (i < p.A) {  // agent a == slot a
+    if (M == Begin::NextStep) p.reward[(size_t)eo * p.A + i] = 0.0;  // (SameStep: the row's reward stays the ending step's)
+    if (p.info_speed) p.info_speed[(size_t)eo * p.A + i] = me.v;
+    if (p.info_crashed) p.info_crashed[(size_t)eo * p.A + i] = 0;
+  }
+  if (i == 0) begin_env_row<M>(p, e, eo, s.episode);
+}
+
 // One policy step of environment e by its wavefront (the lane table is in LDS); eo = row of the action / output planes.
 template <bool GRID>
 __device__ __forceinline__ void net_policy_step(const NetParams &np, NetShared &sh, const int e, const int eo) {
@@ -677,22 +694,7 @@ __device__ __forceinline__ void net_policy_step(const NetParams &np, NetShared &
   // ---- auto-reset --------------------------------------------------------------------------------------------
   if (p.autoreset && p.st.done[e]) {
     Veh me;
-    const uint32_t episode = p.st.episode[e] + 1u;
-    net_spawn_env(np, sh, p.rp.base_seed + (uint64_t)e, episode, me);
-    net_observe<GRID>(np, sh, e, eo, me, false);
-    store_vehicle<1>(p, e, me);
-    if (i < p.A) {  // agent a == slot a
-      p.reward[(size_t)eo * p.A + i] = 0.0;
-      if (p.info_speed) p.info_speed[(size_t)eo * p.A + i] = me.v;
-      if (p.info_crashed) p.info_crashed[(size_t)eo * p.A + i] = 0;
-    }
-    if (i == 0) {
-      p.st.time[e] = 0.0;
-      p.st.done[e] = 0;
-      p.st.episode[e] = episode;
-      p.terminated[eo] = 0;
-      p.truncated[eo] = 0;
-    }
+    net_begin_episode<Begin::NextStep, GRID>(np, sh, e, eo, me);
     return;
   }
 
@@ -1097,48 +1099,22 @@ __global__ void __launch_bounds__(64, WPE) hwy_net_rollout_kernel(const NetParam
 // Reset kernel: AbstractEnv.reset for the masked environments + first observation.
 template <int WPE, bool GRID = false>
 __global__ void __launch_bounds__(64, WPE) hwy_net_reset_kernel(const NetParams np) {
-  const StepParams &p = np.s;
   __shared__ NetShared sh;
-  const int e = blockIdx.x, i = threadIdx.x;
   net_load_table(np, sh);
-  if (p.reset_mask && !p.reset_mask[e]) return;  // block-uniform
+  if (np.s.reset_mask && !np.s.reset_mask[blockIdx.x]) return;  // block-uniform
   Veh me;
-  const uint64_t seed = p.reset_seeds ? p.reset_seeds[e] : p.rp.base_seed + (uint64_t)e;
-  net_spawn_env(np, sh, seed, 0u, me);
-  net_observe<GRID>(np, sh, e, e, me, false);
-  store_vehicle<1>(p, e, me);
-  if (i == 0) {
-    p.st.time[e] = 0.0;
-    p.st.done[e] = 0;
-    p.st.episode[e] = 0;
-  }
+  net_begin_episode<Begin::Reset, GRID>(np, sh, blockIdx.x, blockIdx.x, me);
 }
 
-// Re-spawn kernel (hwy_step_same_step_device; hwy_device.h: respawn_env has the contract): the environments whose done[e] the step
-// launch before it set start their next episode -- seed base_seed + e, episode + 1, as the auto-reset branch of net_policy_step
-// would at the following call -- and reward / terminated / truncated stay the ending step's.  A wavefront whose environment did
-// not end leaves after one load of its flag, before the lane table is copied.
+// Re-spawn kernel (hwy_step_same_step_device; hwy_device.h: Begin::SameStep).  A wavefront whose environment did not end leaves
+// after one load of its flag, before the lane table is copied.
 template <int WPE, bool GRID = false>
 __global__ void __launch_bounds__(64, WPE) hwy_net_respawn_kernel(const NetParams np) {
-  const StepParams &p = np.s;
   __shared__ NetShared sh;
-  const int e = blockIdx.x, i = threadIdx.x;
-  if (!p.st.done[e]) return;  // block-uniform
+  if (!np.s.st.done[blockIdx.x]) return;  // block-uniform
   net_load_table(np, sh);
   Veh me;
-  const uint32_t episode = p.st.episode[e] + 1u;  // the next episode's stream
-  net_spawn_env(np, sh, p.rp.base_seed + (uint64_t)e, episode, me);
-  net_observe<GRID>(np, sh, e, e, me, false);
-  store_vehicle<1>(p, e, me);
-  if (i < p.A) {  // agent a == slot a (p.reward stays the ending step's)
-    if (p.info_speed) p.info_speed[(size_t)e * p.A + i] = me.v;
-    if (p.info_crashed) p.info_crashed[(size_t)e * p.A + i] = 0;
-  }
-  if (i == 0) {
-    p.st.time[e] = 0.0;
-    p.st.done[e] = 0;
-    p.st.episode[e] = episode;
-  }
+  net_begin_episode<Begin::SameStep, GRID>(np, sh, blockIdx.x, blockIdx.x, me);
 }
 
 // Observation-only kernel (hwy_observe).

@@ -7,7 +7,7 @@
 //   2  the mask kernel (hwy_mask.h) on that state into final_action_mask                          (if asked for)
 //   3  the stash, hwy_final_kernel below: final_mask[e] = done[e]; for the environments that ended, their rows of obs, info_speed
 //      and info_crashed are copied to the final planes; the rows of the others are not written at all
-//   4  the family's re-spawn kernel (hwy_device.h: respawn_env has the contract; hwy_wave.h, hwy_wave2.h and hwy_net.h hold the
+//   4  the family's re-spawn kernel (hwy_device.h: Begin::SameStep has the contract; hwy_wave.h, hwy_wave2.h and hwy_net.h hold the
 //      forms of their step kernels, hwy_launch_family.h / hwy_launch_rules.h: select_respawn picks one by the step's rule), which
 //      starts the next episode of the environments that ended, observes it into obs and clears done[e]; reward / terminated /
 //      truncated stay the ending step's

@@ -358,6 +358,28 @@ __device__ inline void observe_wave(const StepParams &p, int e, int eo, const Ve
 }
 
 // =============================================================================================
+// Starting an episode, the one-wavefront form (hwy_device.h: Begin has the rule table).  `me` is the caller's record: the step
+// kernel has its registers live already.  The first observation is observe_wave's in every mode, through the caller's shape SH: it
+// maps a feature with the host-computed reciprocal of its range (lmap_inv) where the workgroup form's observe_env divides, and the
+// two differ in the last bit of a double, which a float keeps next to zero.
+template <Begin M, typename TM, typename EG, typename SH>
+__device__ __forceinline__ void wave_begin_episode(const StepParams &p, WaveShared &sh, int e, int eo, const LinearArgs &la,
+                                                   const DirectArgs *da, Veh &me) {
+  const int i = threadIdx.x;
+  const bool active = i < p.N;
+  me = Veh{};
+  const EpisodeStream s = episode_stream<M>(p, e);
+  spawn_env<1>(p, sh.x, sh.v, e, s.seed, s.episode, me);
+  if constexpr (TM::LINEAR) {
+    if (active) spawn_behavior(p, la, e, i, s.seed, s.episode, (me.flags & HWY_F_CONTROLLED) != 0);
+  }
+  observe_wave<false, MetaEgo, SH>(p, e, eo, me, false);
+  store_vehicle<1>(p, e, me);
+  begin_agent_rows<M, EG>(p, da, e, eo, i, active, me);
+  if (i == 0) begin_env_row<M>(p, e, eo, s.episode);
+}
+
+// =============================================================================================
 // FULL_SCAN = false builds the kernel without the full-pairwise window scan (every checker is handled by
 // the checker loop, which is correct for any set of checkers but O(#checkers)); the engine launches it for
 // highway-fast-v0 style configs (HWY_C_EGO_ONLY_COLLISIONS), where it keeps the frame loop at 173 VGPRs.
@@ -400,30 +422,7 @@ __device__ __forceinline__ void wave_policy_step(const StepParams &p, WaveShared
   HWY_ISSUED_TOGETHER(done_flag, env_time, act_lane, me.x, me.timer);  // (keeps the requests above the branch)
   // ---- auto-reset: re-spawn instead of stepping (rare; shares the generic helpers) -------------
   if (done_flag) {
-    me = Veh{};
-    const uint32_t episode = p.st.episode[e] + 1u;
-    spawn_env<1>(p, sh.x, sh.v, e, p.rp.base_seed + (uint64_t)e, episode, me);
-    if constexpr (TM::LINEAR) {
-      if (active) spawn_behavior(p, la, e, i, p.rp.base_seed + (uint64_t)e, episode, (me.flags & HWY_F_CONTROLLED) != 0);
-    }
-    observe_wave<false, MetaEgo, SH>(p, e, eo, me, false);
-    store_vehicle<1>(p, e, me);
-    if (active && (me.flags & HWY_F_CONTROLLED)) {
-      for (int a = 0; a < p.A; ++a)
-        if (p.agent_index[a] == i) {
-          p.reward[(size_t)eo * p.A + a] = 0.0;
-          if (p.info_speed) p.info_speed[(size_t)eo * p.A + a] = me.v;
-          if (p.info_crashed) p.info_crashed[(size_t)eo * p.A + a] = 0;
-          if constexpr (EG::DIRECT) da->ctl_accel[(size_t)e * p.A + a] = da->ctl_steer[(size_t)e * p.A + a] = 0.0;  // Vehicle.__init__
-        }
-    }
-    if (i == 0) {
-      p.st.time[e] = 0.0;
-      p.st.done[e] = 0;
-      p.st.episode[e] = episode;
-      p.terminated[eo] = 0;
-      p.truncated[eo] = 0;
-    }
+    wave_begin_episode<Begin::NextStep, TM, EG, SH>(p, sh, e, eo, la, da, me);  // (the old state was fetched for nothing)
     return;
   }
 
@@ -1088,40 +1087,14 @@ __global__ void __launch_bounds__(64, WPE) hwy_rollout_wave_direct_kernel(const 
   }
 }
 
-// Re-spawn kernels (hwy_step_same_step_device; hwy_device.h: respawn_env has the contract) for the launches whose step runs on the
-// one-wavefront kernel: the auto-reset branch of wave_policy_step without its writes of reward / terminated / truncated, for the
-// environments whose done[e] the step launch before it set.  The first observation is observe_wave's, like that branch's: the
-// same episodes under SameStep and NextStep means the same bits, and observe_wave maps a feature with the host-computed reciprocal
-// of its range (lmap_inv) where the workgroup kernel's observe_env divides -- the two differ in the last bit of a double, which a
-// float keeps next to zero.  A wavefront whose environment did not end leaves after one load of its flag.
-template <typename TM = IdmTraffic>
+// Re-spawn kernels (hwy_step_same_step_device; hwy_device.h: Begin::SameStep) for the launches whose step runs on the one-wavefront
+// kernel.  A wavefront whose environment did not end leaves after one load of its flag.
+template <typename TM = IdmTraffic, typename EG = MetaEgo>
 __device__ __forceinline__ void wave_respawn(const StepParams &p, WaveShared &sh, const LinearArgs &la = LinearArgs{},
                                              const DirectArgs *da = nullptr) {
-  const int e = blockIdx.x, i = threadIdx.x;
-  if (!p.st.done[e]) return;  // wave-uniform
-  const bool active = i < p.N;
-  Veh me = Veh{};
-  const uint64_t seed = p.rp.base_seed + (uint64_t)e;
-  const uint32_t episode = p.st.episode[e] + 1u;  // the next episode's stream
-  spawn_env<1>(p, sh.x, sh.v, e, seed, episode, me);
-  if constexpr (TM::LINEAR) {
-    if (active) spawn_behavior(p, la, e, i, seed, episode, (me.flags & HWY_F_CONTROLLED) != 0);
-  }
-  observe_wave<false, MetaEgo, RuntimeShape>(p, e, e, me, false);
-  store_vehicle<1>(p, e, me);
-  if (active && (me.flags & HWY_F_CONTROLLED)) {
-    for (int a = 0; a < p.A; ++a)
-      if (p.agent_index[a] == i) {  // (p.reward stays the ending step's)
-        if (p.info_speed) p.info_speed[(size_t)e * p.A + a] = me.v;
-        if (p.info_crashed) p.info_crashed[(size_t)e * p.A + a] = 0;
-        if (da) da->ctl_accel[(size_t)e * p.A + a] = da->ctl_steer[(size_t)e * p.A + a] = 0.0;  // Vehicle.__init__
-      }
-  }
-  if (i == 0) {
-    p.st.time[e] = 0.0;
-    p.st.done[e] = 0;
-    p.st.episode[e] = episode;
-  }
+  if (!p.st.done[blockIdx.x]) return;  // wave-uniform
+  Veh me;
+  wave_begin_episode<Begin::SameStep, TM, EG, RuntimeShape>(p, sh, blockIdx.x, blockIdx.x, la, da, me);
 }
 template <int WPE>
 __global__ void __launch_bounds__(64, WPE) hwy_respawn_wave_kernel(const StepParams p) {
@@ -1136,7 +1109,7 @@ __global__ void __launch_bounds__(64, WPE) hwy_respawn_wave_linear_kernel(const 
 template <int WPE>
 __global__ void __launch_bounds__(64, WPE) hwy_respawn_wave_direct_kernel(const DirectParams dp) {
   __shared__ WaveShared sh;
-  wave_respawn<IdmTraffic>(dp.s, sh, LinearArgs{}, &dp.da);
+  wave_respawn<IdmTraffic, DirectEgo>(dp.s, sh, LinearArgs{}, &dp.da);
 }
 
 // Reset / observe kernels for N <= 64 reuse the generic ones (not on the per-step path).

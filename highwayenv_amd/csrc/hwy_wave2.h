@@ -433,6 +433,43 @@ __device__ inline void observe_wide(const StepParams &p, WideShared<K> &sh, int 
 }
 
 // =============================================================================================
+// Starting an episode, the wide form (hwy_device.h: Begin has the rule table; IDM traffic with meta-actions only).  `me` are the
+// caller's records (hwy_wave.h: wave_begin_episode); the first observation is observe_wide's in every mode.
+template <Begin M, int K>
+__device__ __forceinline__ void wide_begin_episode(const StepParams &p, WideShared<K> &sh, int e, int eo, Veh (&me)[K]) {
+  const int l = threadIdx.x;
+  const int N = p.N;
+  const EpisodeStream s = episode_stream<M>(p, e);
+  bool active[K];
+  int vi[K];
+  SpawnDraw d[K];
+#pragma unroll
+  for (int h = 0; h < K; ++h) {
+    vi[h] = h * 64 + l; active[h] = vi[h] < N;
+    me[h] = Veh{};
+    d[h] = spawn_draw(p, vi[h], s.seed, s.episode);
+    if (active[h]) sh.x[vi[h]] = d[h].step;
+    if (active[h] && vi[h] == 0) sh.scratch_base[0] = 3 * d[h].offset;  // first vehicle starts from 3*offset
+  }
+  HWY_WAVE_LDS_FENCE();
+  // x_k = running sum of the steps in creation order (spawn_env)
+#pragma unroll
+  for (int h = 0; h < K; ++h) {
+    double x = sh.scratch_base[0];
+    for (int k = 0; k <= vi[h] && k < N; ++k) x += sh.x[k];
+    spawn_fill(p, d[h], x, vi[h], me[h]);
+  }
+  HWY_WAVE_LDS_FENCE();
+  observe_wide<K, false>(p, sh, e, eo, me, false, vi);  // (rank == creation index: spawn_fill)
+#pragma unroll
+  for (int h = 0; h < K; ++h) {
+    store_vehicle_at(p, e, vi[h], me[h]);
+    begin_agent_rows<M, MetaEgo>(p, nullptr, e, eo, vi[h], active[h], me[h]);
+  }
+  if (l == 0) begin_env_row<M>(p, e, eo, s.episode);
+}
+
+// =============================================================================================
 // One policy step of environment e by its wavefront, K vehicles per thread; eo = row of the action / output planes.
 template <int K>
 __device__ __forceinline__ void wide_policy_step(const StepParams &p, WideShared<K> &sh, const int e, const int eo) {
@@ -454,48 +491,7 @@ __device__ __forceinline__ void wide_policy_step(const StepParams &p, WideShared
   HWY_ISSUED_TOGETHER(done_flag, env_time, act_lane, me[0].x, me[K - 1].timer);
   // ---- auto-reset: re-spawn instead of stepping ---------------------------------------------------------------
   if (done_flag) {
-    const uint32_t episode = p.st.episode[e] + 1u;
-    const uint64_t seed = p.rp.base_seed + (uint64_t)e;
-    SpawnDraw d[K];
-#pragma unroll
-    for (int h = 0; h < K; ++h) {
-      me[h] = Veh{};  // (the old state was fetched for nothing)
-      d[h] = spawn_draw(p, vi[h], seed, episode);
-      if (active[h]) sh.x[vi[h]] = d[h].step;
-      if (active[h] && vi[h] == 0) sh.scratch_base[0] = 3 * d[h].offset;  // first vehicle starts from 3*offset
-    }
-    HWY_WAVE_LDS_FENCE();
-    // x_k = running sum of the steps in creation order (spawn_env)
-#pragma unroll
-    for (int h = 0; h < K; ++h) {
-      double x = sh.scratch_base[0];
-      for (int k = 0; k <= vi[h] && k < N; ++k) x += sh.x[k];
-      spawn_fill(p, d[h], x, vi[h], me[h]);
-    }
-    HWY_WAVE_LDS_FENCE();
-    int rank0[K];
-#pragma unroll
-    for (int h = 0; h < K; ++h) rank0[h] = vi[h];
-    observe_wide<K, false>(p, sh, e, eo, me, false, rank0);
-#pragma unroll
-    for (int h = 0; h < K; ++h) {
-      store_vehicle_at(p, e, vi[h], me[h]);
-      if (active[h] && (me[h].flags & HWY_F_CONTROLLED)) {
-        for (int a = 0; a < p.A; ++a)
-          if (p.agent_index[a] == vi[h]) {
-            p.reward[(size_t)eo * p.A + a] = 0.0;
-            if (p.info_speed) p.info_speed[(size_t)eo * p.A + a] = me[h].v;
-            if (p.info_crashed) p.info_crashed[(size_t)eo * p.A + a] = 0;
-          }
-      }
-    }
-    if (l == 0) {
-      p.st.time[e] = 0.0;
-      p.st.done[e] = 0;
-      p.st.episode[e] = episode;
-      p.terminated[eo] = 0;
-      p.truncated[eo] = 0;
-    }
+    wide_begin_episode<Begin::NextStep, K>(p, sh, e, eo, me);  // (the old state was fetched for nothing)
     return;
   }
 
@@ -1249,56 +1245,14 @@ __global__ void __launch_bounds__(64, WPE) hwy_rollout_wide_kernel(const StepPar
   }
 }
 
-// Re-spawn kernel (hwy_step_same_step_device; hwy_device.h: respawn_env has the contract) for the launches whose step runs on the
-// wide kernel: the auto-reset branch of wide_policy_step without its writes of reward / terminated / truncated, for the environments
-// whose done[e] the step launch before it set -- the first observation is observe_wide's, like that branch's (hwy_wave.h:
-// wave_respawn says why).  A wavefront whose environment did not end leaves after one load of its flag.
+// Re-spawn kernel (hwy_step_same_step_device; hwy_device.h: Begin::SameStep) for the launches whose step runs on the wide kernel.
+// A wavefront whose environment did not end leaves after one load of its flag.
 template <int K, int WPE>
 __global__ void __launch_bounds__(64, WPE) hwy_respawn_wide_kernel(const StepParams p) {
   __shared__ WideShared<K> sh;
-  const int e = blockIdx.x, l = threadIdx.x;
-  if (!p.st.done[e]) return;  // wave-uniform
-  const int N = p.N;
-  const uint32_t episode = p.st.episode[e] + 1u;  // the next episode's stream
-  const uint64_t seed = p.rp.base_seed + (uint64_t)e;
-  bool active[K];
-  int vi[K], rank0[K];
+  if (!p.st.done[blockIdx.x]) return;  // wave-uniform
   Veh me[K];
-  SpawnDraw d[K];
-#pragma unroll
-  for (int h = 0; h < K; ++h) {
-    vi[h] = h * 64 + l; active[h] = vi[h] < N; rank0[h] = vi[h];
-    me[h] = Veh{};
-    d[h] = spawn_draw(p, vi[h], seed, episode);
-    if (active[h]) sh.x[vi[h]] = d[h].step;
-    if (active[h] && vi[h] == 0) sh.scratch_base[0] = 3 * d[h].offset;  // first vehicle starts from 3*offset
-  }
-  HWY_WAVE_LDS_FENCE();
-  // x_k = running sum of the steps in creation order (spawn_env)
-#pragma unroll
-  for (int h = 0; h < K; ++h) {
-    double x = sh.scratch_base[0];
-    for (int j = 0; j < N && j <= vi[h]; ++j) x += sh.x[j];  // (the same sum in the same order as wide_policy_step's)
-    spawn_fill(p, d[h], x, vi[h], me[h]);
-  }
-  HWY_WAVE_LDS_FENCE();
-  observe_wide<K, false>(p, sh, e, e, me, false, rank0);
-#pragma unroll
-  for (int h = 0; h < K; ++h) {
-    store_vehicle_at(p, e, vi[h], me[h]);
-    if (active[h] && (me[h].flags & HWY_F_CONTROLLED)) {
-      for (int a = 0; a < p.A; ++a)
-        if (p.agent_index[a] == vi[h]) {  // (p.reward stays the ending step's)
-          if (p.info_speed) p.info_speed[(size_t)e * p.A + a] = me[h].v;
-          if (p.info_crashed) p.info_crashed[(size_t)e * p.A + a] = 0;
-        }
-    }
-  }
-  if (l == 0) {
-    p.st.time[e] = 0.0;
-    p.st.done[e] = 0;
-    p.st.episode[e] = episode;
-  }
+  wide_begin_episode<Begin::SameStep, K>(p, sh, blockIdx.x, blockIdx.x, me);
 }
 
 }  // namespace hwy

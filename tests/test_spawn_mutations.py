@@ -5,16 +5,19 @@ the unmutated source.
 * `draw_index_wraps_at_64` -- spawn_draw keys the lane / speed draw with `vi & 63`: vehicle 64 + k repeats the draws of vehicle k.
   Every spawn beyond one wavefront is wrong, and consistently so in every kernel built from spawn_draw.
 * `workgroup_linear_respawn_draws_episode_0` -- the workgroup kernel's re-spawn draws the Linear parameters on episode 0's stream
-  instead of the new episode's (the one-wavefront kernel's re-spawn and the reset kernel are right).
-* `wide_respawn_sum_stops_short` -- the wide kernel's re-spawn sums the steps of the vehicles BEFORE vehicle vi only (`k < vi[h]`):
-  every x lacks its own step (the reset kernel and the workgroup kernel's re-spawn are right).  Named row: N = 192 under
-  `block_kernel` 2, three vehicles per thread -- the `block_kernel` 0 and 1 rows of that size run the workgroup kernel and pass on
-  this mutant.
-* `wide_respawn_speed_in_the_step_row` -- the wide kernel's re-spawn writes info["speed"] to row e instead of row eo of the output
-  planes.  The two are the same row in a step launch; only the rollout build (row k * E + e) shows it, in entry point (c).  Named
-  row: N = 256 under `block_kernel` 2, four vehicles per thread.  The
-  re-spawn SOURCE of the rollout builds is the step builds' (one function, called in a loop), so this is the one mutant of a
-  re-spawn that only a rollout can see.
+  instead of the new episode's (the one-wavefront kernel's re-spawn and the reset kernel are right).  The site is the auto-reset
+  branch block_policy_step keeps for itself (profiles/episode_start_refactor.md says why); the reset and the SameStep re-spawn
+  kernel run block_begin_episode and stay right.
+* `wide_respawn_sum_stops_short` -- the wide kernel's re-spawn (wide_begin_episode: the step's branch and the SameStep kernel) sums
+  the steps of the vehicles BEFORE vehicle vi only (`k < vi[h]`): every x lacks its own step (the reset kernel and the workgroup
+  kernel's re-spawn are right).  Named row: N = 192 under `block_kernel` 2, three vehicles per thread -- the `block_kernel` 0 and 1
+  rows of that size run the workgroup kernel and pass on this mutant.
+* `wide_respawn_speed_in_the_step_row` -- the re-spawn writes info["speed"] to row e instead of row eo of the output planes.  The
+  two are the same row in a step launch; only the rollout build (row k * E + e) shows it, in entry point (c).  Named row: N = 256
+  under `block_kernel` 2, four vehicles per thread.  The site is the agent rows the straight-road forms share (hwy_device.h:
+  begin_agent_rows), so the one-wavefront and the workgroup kernel carry the mutant too; the named row is still the wide
+  kernel's.  The re-spawn SOURCE of the rollout builds is the step builds' (one function, called in a loop), so this is the one
+  mutant of a re-spawn that only a rollout can see.
 
 What the suite did with these mutants before tests/test_spawn_paths.py existed was established by running the CPU tests of
 tests/test_device_reset.py, test_wide_kernel.py, test_rollout.py, test_kernel_variants.py, test_schedule_independence.py,
@@ -48,8 +51,8 @@ MUTANTS = {
     "wide_respawn_sum_stops_short": ("emu_engine.cpp", "HWY_EMU_LIB", ROW_WIDE_K3, [
         ("hwy_wave2.h", "for (int k = 0; k <= vi[h] && k < N; ++k) x += sh.x[k];", "for (int k = 0; k < vi[h] && k < N; ++k) x += sh.x[k];")]),
     "wide_respawn_speed_in_the_step_row": ("emu_engine.cpp", "HWY_EMU_LIB", ROW_WIDE_K4, [
-        ("hwy_wave2.h", "if (p.info_speed) p.info_speed[(size_t)eo * p.A + a] = me[h].v;",
-         "if (p.info_speed) p.info_speed[(size_t)e * p.A + a] = me[h].v;")]),
+        ("hwy_device.h", "if (p.info_speed) p.info_speed[(size_t)eo * p.A + a] = o.v;",
+         "if (p.info_speed) p.info_speed[(size_t)e * p.A + a] = o.v;")]),
 }
 # what each mutant's row must say when it dies (a regular expression: the plane that differs, or the entry point)
 DIES_WITH = {"draw_index_wraps_at_64": r"^E\s+lane$", "workgroup_linear_respawn_draws_episode_0": "behaviour parameters",
