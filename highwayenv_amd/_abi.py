@@ -118,6 +118,43 @@ def direct_action_axes(act: dict) -> tuple:
     return accel, steer
 
 
+class HwyContinuousParams(C.Structure):
+    """hwy_continuous_params (include/hwy_engine.h): the ranges and axes of a ``ContinuousAction`` (action.py:89-121)."""
+    _fields_ = [("acceleration_range", C.c_double * 2), ("steering_range", C.c_double * 2), ("longitudinal", C.c_int32),
+                ("lateral", C.c_int32)]
+
+    @property
+    def size(self) -> int:
+        """Components of one action (action.py:117): 2 with both axes (throttle, steering), 1 with one."""
+        return int(bool(self.longitudinal)) + int(bool(self.lateral))
+
+
+def continuous_params(act: dict) -> HwyContinuousParams:
+    """The ``ContinuousAction`` behind an action config: ``DiscreteAction`` inherits ``acceleration_range`` / ``steering_range`` /
+    ``longitudinal`` / ``lateral`` / ``clip`` from it (action.py:165-188), so a ``DiscreteAction`` dict names one.  The range ends
+    stay the Python floats the config holds -- the act kernel rounds them to float32 where the reference does (csrc/hwy_act.h).
+    ``ValueError`` for what ``hwy_continuous_params`` rejects, ``NotImplementedError`` for ``clip: False`` (an unclipped steering
+    angle can leave the +-pi/3 the kernels' tan covers), ``speed_range`` and ``dynamical``."""
+    longi, lat = bool(act.get("longitudinal", True)), bool(act.get("lateral", True))
+    if not (longi or lat):
+        raise ValueError("Either longitudinal and/or lateral control must be enabled")  # action.py:108-111
+    if not act.get("clip", True):
+        raise NotImplementedError("continuous control with clip=False is outside the MI355X hot-path scope")
+    if act.get("dynamical", False) or act.get("speed_range") is not None:
+        raise NotImplementedError("continuous control with dynamical=True / speed_range is outside the MI355X hot-path scope")
+    acc_range = act.get("acceleration_range") or (-5, 5.0)                  # ContinuousAction.ACCELERATION_RANGE
+    steer_range = act.get("steering_range") or (-np.pi / 4, np.pi / 4)      # ContinuousAction.STEERING_RANGE
+    p = HwyContinuousParams()
+    p.acceleration_range[0], p.acceleration_range[1] = float(acc_range[0]), float(acc_range[1])
+    p.steering_range[0], p.steering_range[1] = float(steer_range[0]), float(steer_range[1])
+    p.longitudinal, p.lateral = int(longi), int(lat)
+    if not all(np.isfinite(v) for v in (*p.acceleration_range, *p.steering_range)):
+        raise ValueError("acceleration_range and steering_range must be finite")
+    if max(abs(v) for v in p.steering_range) > np.pi / 3:
+        raise ValueError("steering_range must lie within +-pi/3 (the kernels' tan covers Vehicle.MAX_STEERING_ANGLE)")
+    return p
+
+
 class HwyLane(C.Structure):
     """hwy_lane: one x-aligned lane of a RoadNetwork (include/hwy_engine.h)."""
     _fields_ = [

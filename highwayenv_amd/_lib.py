@@ -23,6 +23,8 @@ EXPORTS = [
     "hwy_set_controls", "hwy_get_controls", "hwy_ttc_grid_device", "hwy_ttc_grid", "hwy_mdp_plan_device", "hwy_mdp_plan",
     "hwy_fork_device", "hwy_fork", "hwy_score_device", "hwy_score_rollout", "hwy_opd_plan_device", "hwy_opd_plan",
     "hwy_action_mask_device", "hwy_action_mask", "hwy_step_same_step_device",
+    "hwy_act_continuous_device", "hwy_act_continuous", "hwy_step_continuous_device", "hwy_step_continuous",
+    "hwy_step_same_step_continuous_device", "hwy_rollout_continuous_device", "hwy_rollout_continuous",
     "hwy_step_shapes", "hwy_last_step_shape",
 ]
 
@@ -105,6 +107,14 @@ def load() -> C.CDLL:
     lib.hwy_action_mask_device.argtypes = [vp, vp]
     lib.hwy_action_mask.argtypes = [vp, vp]
     lib.hwy_step_same_step_device.argtypes = [vp] + [vp] * 13
+    cont = C.POINTER(_abi.HwyContinuousParams)
+    lib.hwy_act_continuous_device.argtypes = [vp, cont, vp]
+    lib.hwy_act_continuous.argtypes = [vp, cont, vp]
+    lib.hwy_step_continuous_device.argtypes = [vp, cont] + [vp] * 7
+    lib.hwy_step_continuous.argtypes = [vp, cont] + [vp] * 7
+    lib.hwy_step_same_step_continuous_device.argtypes = [vp, cont] + [vp] * 13
+    lib.hwy_rollout_continuous_device.argtypes = [vp, cont, i32] + [vp] * 7
+    lib.hwy_rollout_continuous.argtypes = [vp, cont, i32] + [vp] * 7
     lib.hwy_step_shapes.argtypes = [i32]
     lib.hwy_last_step_shape.argtypes = []
     lib.hwy_profile_enable.argtypes = [vp, i32]
@@ -115,7 +125,7 @@ def load() -> C.CDLL:
         fn = getattr(lib, name)
         if fn.restype is C.c_int or name.startswith(("hwy_create", "hwy_destroy", "hwy_set", "hwy_get", "hwy_reset",
                                                       "hwy_step", "hwy_rollout", "hwy_observe", "hwy_sync", "hwy_profile", "hwy_debug", "hwy_comm", "hwy_gather",
-                                                      "hwy_ttc", "hwy_mdp", "hwy_fork", "hwy_score", "hwy_opd", "hwy_action")):
+                                                      "hwy_ttc", "hwy_mdp", "hwy_fork", "hwy_score", "hwy_opd", "hwy_action", "hwy_act_")):
             if name not in ("hwy_status_string", "hwy_last_error", "hwy_config_size"):
                 fn.restype = C.c_int
     if lib.hwy_abi_version() != _abi.HWY_ABI_VERSION:

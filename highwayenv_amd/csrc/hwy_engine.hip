@@ -18,6 +18,7 @@
 #include "../../include/hwy_engine.h"
 #include "hwy_comm.h"
 #include "hwy_launch.h"
+#include "hwy_act.h"
 #include "hwy_mask.h"
 #include "hwy_params.h"
 
@@ -795,6 +796,17 @@ static void bind_full_step(const hwy_engine *eng, StepParams &p, const int32_t *
   p.actions = d_actions; p.obs = d_obs; p.reward = d_reward; p.terminated = d_terminated; p.truncated = d_truncated;
   p.info_speed = d_info_speed; p.info_crashed = d_info_crashed;
 }
+// The one full-step launch behind hwy_step_device and hwy_step_continuous_device: the family's step kernel around the caller's
+// planes, timed when the tuner or hwy_profile_* wants it.  d_actions: the action ids, or NULL -- the direct kernels then drive on
+// with the stored controls (the continuous door wrote them just before on this stream).  The device is set, the planes are checked.
+static int enqueue_full_step(hwy_engine *eng, const int32_t *d_actions, float *d_obs, double *d_reward, uint8_t *d_terminated,
+                             uint8_t *d_truncated, double *d_info_speed, uint8_t *d_info_crashed) {
+  StepParams p;
+  bind_full_step(eng, p, d_actions, d_obs, d_reward, d_terminated, d_truncated, d_info_speed, d_info_crashed);
+  if (eng->profiling && eng->events_used >= 65536)
+    if (int rc = drain_events(eng)) return rc;
+  return timed_launch(eng, p);
+}
 
 extern "C" int hwy_step_device(hwy_engine *eng, const int32_t *d_actions, float *d_obs, double *d_reward,
                                uint8_t *d_terminated, uint8_t *d_truncated, double *d_info_speed,
@@ -803,11 +815,7 @@ extern "C" int hwy_step_device(hwy_engine *eng, const int32_t *d_actions, float 
   if (!d_actions || !d_obs || !d_reward || !d_terminated || !d_truncated)
     return fail(eng, HWY_ERR_INVALID_ARG, "hwy_step_device: actions/obs/reward/terminated/truncated must be non-NULL");
   HWY_HIP(eng, hipSetDevice(eng->device));
-  StepParams p;
-  bind_full_step(eng, p, d_actions, d_obs, d_reward, d_terminated, d_truncated, d_info_speed, d_info_crashed);
-  if (eng->profiling && eng->events_used >= 65536)
-    if (int rc = drain_events(eng)) return rc;
-  return timed_launch(eng, p);
+  return enqueue_full_step(eng, d_actions, d_obs, d_reward, d_terminated, d_truncated, d_info_speed, d_info_crashed);
 }
 
 extern "C" int hwy_rollout_device(hwy_engine *eng, int32_t k_steps, const int32_t *d_actions, float *d_obs, double *d_reward,
@@ -841,22 +849,14 @@ extern "C" int hwy_rollout_device(hwy_engine *eng, int32_t k_steps, const int32_
   return HWY_OK;
 }
 
-extern "C" int hwy_rollout(hwy_engine *eng, int32_t k_steps, const int32_t *actions, float *obs, double *reward,
-                           uint8_t *terminated, uint8_t *truncated, double *info_speed, uint8_t *info_crashed) {
-  if (!eng) return HWY_ERR_INVALID_ARG;
-  if (k_steps < 1) return fail(eng, HWY_ERR_INVALID_ARG, "hwy_rollout: k_steps must be >= 1");
-  if (!actions || !obs || !reward || !terminated || !truncated)
-    return fail(eng, HWY_ERR_INVALID_ARG, "hwy_rollout: actions/obs/reward/terminated/truncated must be non-NULL");
-  if (k_steps > 1 && is_ix(eng) && (eng->cfg.flags & HWY_C_HOST_TRAFFIC))
-    return fail(eng, HWY_ERR_INVALID_ARG, "hwy_rollout: k_steps > 1 needs device traffic (HWY_C_HOST_TRAFFIC is set)");
-  const size_t n_act = num_agent_rows(eng->cfg), n_obs = num_obs_floats(eng->cfg);
-  const size_t E = eng->cfg.num_envs, K = (size_t)k_steps;
-  const int max_action = num_action_ids(eng) - 1;
-  for (size_t k = 0; k < K * n_act; ++k)  // the reference's KeyError / IndexError, before anything is simulated (action.py:260,195)
-    if (actions[k] < 0 || actions[k] > max_action) return fail(eng, HWY_ERR_ACTION, "action id out of range");
-  HWY_HIP(eng, hipSetDevice(eng->device));
+// The host-pointer form of a K-step call (hwy_rollout, hwy_rollout_continuous): the validated actions (`act_bytes` per step) up into
+// the engine's rollout block, `run` on the device pointers of that block, the outputs down; synchronises.  The device is set.
+template <typename Run>
+static int rollout_through_host(hwy_engine *eng, size_t K, const void *actions, size_t act_bytes, float *obs, double *reward,
+                                uint8_t *terminated, uint8_t *truncated, double *info_speed, uint8_t *info_crashed, Run &&run) {
+  const size_t n_act = num_agent_rows(eng->cfg), n_obs = num_obs_floats(eng->cfg), E = eng->cfg.num_envs;
   auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_act = 0, o_rew = up(K * n_act * 4), o_spd = o_rew + up(K * n_act * 8), o_obs = o_spd + up(K * n_act * 8),
+  const size_t o_act = 0, o_rew = up(K * act_bytes), o_spd = o_rew + up(K * n_act * 8), o_obs = o_spd + up(K * n_act * 8),
                o_term = o_obs + up(K * n_obs * 4), o_trunc = o_term + up(K * E), o_crash = o_trunc + up(K * E),
                total = o_crash + up(K * n_act);
   if (total > eng->roll_bytes) {
@@ -868,9 +868,9 @@ extern "C" int hwy_rollout(hwy_engine *eng, int32_t k_steps, const int32_t *acti
     eng->roll_bytes = total;
   }
   char *d = eng->d_roll;
-  HWY_HIP(eng, hipMemcpyAsync(d + o_act, actions, K * n_act * 4, hipMemcpyHostToDevice, eng->stream));
-  if (int rc = hwy_rollout_device(eng, k_steps, (const int32_t *)(d + o_act), (float *)(d + o_obs), (double *)(d + o_rew),
-                                  (uint8_t *)(d + o_term), (uint8_t *)(d + o_trunc), (double *)(d + o_spd), (uint8_t *)(d + o_crash)))
+  HWY_HIP(eng, hipMemcpyAsync(d + o_act, actions, K * act_bytes, hipMemcpyHostToDevice, eng->stream));
+  if (int rc = run((const void *)(d + o_act), (float *)(d + o_obs), (double *)(d + o_rew), (uint8_t *)(d + o_term), (uint8_t *)(d + o_trunc),
+                   (double *)(d + o_spd), (uint8_t *)(d + o_crash)))
     return rc;
   HWY_HIP(eng, hipMemcpyAsync(obs, d + o_obs, K * n_obs * 4, hipMemcpyDeviceToHost, eng->stream));
   HWY_HIP(eng, hipMemcpyAsync(reward, d + o_rew, K * n_act * 8, hipMemcpyDeviceToHost, eng->stream));
@@ -880,6 +880,25 @@ extern "C" int hwy_rollout(hwy_engine *eng, int32_t k_steps, const int32_t *acti
   if (info_crashed) HWY_HIP(eng, hipMemcpyAsync(info_crashed, d + o_crash, K * n_act, hipMemcpyDeviceToHost, eng->stream));
   HWY_HIP(eng, hipStreamSynchronize(eng->stream));
   return HWY_OK;
+}
+
+extern "C" int hwy_rollout(hwy_engine *eng, int32_t k_steps, const int32_t *actions, float *obs, double *reward,
+                           uint8_t *terminated, uint8_t *truncated, double *info_speed, uint8_t *info_crashed) {
+  if (!eng) return HWY_ERR_INVALID_ARG;
+  if (k_steps < 1) return fail(eng, HWY_ERR_INVALID_ARG, "hwy_rollout: k_steps must be >= 1");
+  if (!actions || !obs || !reward || !terminated || !truncated)
+    return fail(eng, HWY_ERR_INVALID_ARG, "hwy_rollout: actions/obs/reward/terminated/truncated must be non-NULL");
+  if (k_steps > 1 && is_ix(eng) && (eng->cfg.flags & HWY_C_HOST_TRAFFIC))
+    return fail(eng, HWY_ERR_INVALID_ARG, "hwy_rollout: k_steps > 1 needs device traffic (HWY_C_HOST_TRAFFIC is set)");
+  const size_t n_act = num_agent_rows(eng->cfg), K = (size_t)k_steps;
+  const int max_action = num_action_ids(eng) - 1;
+  for (size_t k = 0; k < K * n_act; ++k)  // the reference's KeyError / IndexError, before anything is simulated (action.py:260,195)
+    if (actions[k] < 0 || actions[k] > max_action) return fail(eng, HWY_ERR_ACTION, "action id out of range");
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  return rollout_through_host(eng, K, actions, n_act * 4, obs, reward, terminated, truncated, info_speed, info_crashed,
+                              [&](const void *d_act, float *d_obs, double *d_rew, uint8_t *d_term, uint8_t *d_trunc, double *d_spd, uint8_t *d_crash) {
+                                return hwy_rollout_device(eng, k_steps, (const int32_t *)d_act, d_obs, d_rew, d_term, d_trunc, d_spd, d_crash);
+                              });
 }
 
 extern "C" int hwy_step(hwy_engine *eng, const int32_t *actions, float *obs, double *reward, uint8_t *terminated,
@@ -1430,16 +1449,20 @@ extern "C" int hwy_action_mask(hwy_engine *eng, uint8_t *mask) {
 }
 
 // ---- SameStep autoreset on the device (hwy_same_step.h) -----------------------------------------------------------------------------
-extern "C" int hwy_step_same_step_device(hwy_engine *eng, const int32_t *d_actions, float *d_obs, double *d_reward, uint8_t *d_terminated,
-                                         uint8_t *d_truncated, double *d_info_speed, uint8_t *d_info_crashed, float *d_final_obs,
-                                         double *d_final_info_speed, uint8_t *d_final_info_crashed, uint8_t *d_final_mask,
-                                         uint8_t *d_action_mask, uint8_t *d_final_action_mask) {
-  static const char *who = "hwy_step_same_step_device";
+// The body of hwy_step_same_step_device and hwy_step_same_step_continuous_device.  The ids door: d_actions, cp NULL.  The continuous
+// door: cp and d_continuous, d_actions NULL -- the act launch goes first, and the step launch runs with no ids on the pair it stored.
+static int same_step_enqueue(hwy_engine *eng, const char *who, const int32_t *d_actions, const hwy_continuous_params *cp,
+                             const float *d_continuous, float *d_obs, double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated,
+                             double *d_info_speed, uint8_t *d_info_crashed, float *d_final_obs, double *d_final_info_speed,
+                             uint8_t *d_final_info_crashed, uint8_t *d_final_mask, uint8_t *d_action_mask, uint8_t *d_final_action_mask,
+                             bool continuous) {
   if (!eng) return HWY_ERR_INVALID_ARG;
   const char *why = "";
+  if (continuous)
+    if (const int rc = hwy::act_validate(eng->cfg, cp, &why)) return fail(eng, rc, std::string(who) + ": " + why);
   if (const int rc = hwy::same_step_validate(eng->cfg, eng->autoreset != 0, d_final_obs != nullptr, d_final_mask != nullptr, &why))
     return fail(eng, rc, std::string(who) + ": " + why);
-  if (!d_actions || !d_obs || !d_reward || !d_terminated || !d_truncated)
+  if ((continuous ? !d_continuous : !d_actions) || !d_obs || !d_reward || !d_terminated || !d_truncated)
     return fail(eng, HWY_ERR_INVALID_ARG, std::string(who) + ": actions/obs/reward/terminated/truncated must be non-NULL");
   if ((d_final_info_speed && !d_info_speed) || (d_final_info_crashed && !d_info_crashed))
     return fail(eng, HWY_ERR_INVALID_ARG, std::string(who) + ": a final info plane needs the info plane it is copied from");
@@ -1448,6 +1471,7 @@ extern "C" int hwy_step_same_step_device(hwy_engine *eng, const int32_t *d_actio
   HWY_HIP(eng, hipSetDevice(eng->device));
   if (eng->profiling && eng->events_used >= 65536)
     if (int rc = drain_events(eng)) return rc;
+  if (continuous) HWY_HIP(eng, hwy::launch_act_continuous(hwy::act_params(eng->cfg, *cp, d_continuous, eng->d_controls), eng->stream));
   struct Ops {
     hwy_engine *eng;
     StepParams p;  // the full step around the caller's planes: the step launch's and the re-spawn's arguments
@@ -1468,6 +1492,136 @@ extern "C" int hwy_step_same_step_device(hwy_engine *eng, const int32_t *d_actio
   ops.fp = hwy::final_params(eng->cfg, hwy::obs_len(eng->cfg), eng->d_done, d_final_mask, d_obs, d_final_obs, d_info_speed,
                              d_final_info_speed, d_info_crashed, d_final_info_crashed);
   return hwy::same_step_sequence(ops, d_final_action_mask != nullptr, d_action_mask != nullptr);
+}
+extern "C" int hwy_step_same_step_device(hwy_engine *eng, const int32_t *d_actions, float *d_obs, double *d_reward, uint8_t *d_terminated,
+                                         uint8_t *d_truncated, double *d_info_speed, uint8_t *d_info_crashed, float *d_final_obs,
+                                         double *d_final_info_speed, uint8_t *d_final_info_crashed, uint8_t *d_final_mask,
+                                         uint8_t *d_action_mask, uint8_t *d_final_action_mask) {
+  return same_step_enqueue(eng, "hwy_step_same_step_device", d_actions, nullptr, nullptr, d_obs, d_reward, d_terminated, d_truncated,
+                           d_info_speed, d_info_crashed, d_final_obs, d_final_info_speed, d_final_info_crashed, d_final_mask, d_action_mask,
+                           d_final_action_mask, false);
+}
+
+// ---- continuous throttle and steering of a direct-control engine (hwy_act.h) -------------------------------------------------------
+// what every continuous entry point checks first: the engine, the params (hwy_act.h: act_validate) and the action pointer
+static int act_check(hwy_engine *eng, const hwy_continuous_params *cp, const void *actions, const char *who) {
+  if (!eng) return HWY_ERR_INVALID_ARG;
+  const char *why = "";
+  if (const int rc = hwy::act_validate(eng->cfg, cp, &why)) return fail(eng, rc, std::string(who) + ": " + why);
+  if (!actions) return fail(eng, HWY_ERR_INVALID_ARG, std::string(who) + ": actions must be non-NULL");
+  return HWY_OK;
+}
+// the host-pointer doors: a NaN or an infinity is no action of the Box (the device forms leave such a row's stored pair as it is)
+static int act_check_finite(hwy_engine *eng, const hwy_continuous_params *cp, const float *actions, size_t steps, const char *who) {
+  if (!hwy::act_all_finite(actions, steps * num_agent_rows(eng->cfg) * (size_t)hwy::act_size(*cp)))
+    return fail(eng, HWY_ERR_ACTION, std::string(who) + ": a continuous action must be finite");
+  return HWY_OK;
+}
+static size_t act_floats(const hwy_engine *eng, const hwy_continuous_params &cp) { return num_agent_rows(eng->cfg) * (size_t)hwy::act_size(cp); }
+
+extern "C" int hwy_act_continuous_device(hwy_engine *eng, const hwy_continuous_params *params, const float *d_actions) {
+  if (int rc = act_check(eng, params, d_actions, "hwy_act_continuous_device")) return rc;
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  HWY_HIP(eng, hwy::launch_act_continuous(hwy::act_params(eng->cfg, *params, d_actions, eng->d_controls), eng->stream));
+  return HWY_OK;
+}
+
+// the device block the host-pointer doors stage their actions in: the head of the rollout block (grown on demand)
+static int act_stage(hwy_engine *eng, const float *actions, size_t bytes, const float **d_out) {
+  if (bytes > eng->roll_bytes) {
+    HWY_HIP(eng, hipStreamSynchronize(eng->stream));
+    if (eng->d_roll) (void)hipFree(eng->d_roll);
+    eng->d_roll = nullptr;
+    eng->roll_bytes = 0;
+    HWY_HIP(eng, hipMalloc((void **)&eng->d_roll, bytes));
+    eng->roll_bytes = bytes;
+  }
+  HWY_HIP(eng, hipMemcpyAsync(eng->d_roll, actions, bytes, hipMemcpyHostToDevice, eng->stream));
+  *d_out = (const float *)eng->d_roll;
+  return HWY_OK;
+}
+
+extern "C" int hwy_act_continuous(hwy_engine *eng, const hwy_continuous_params *params, const float *actions) {
+  static const char *who = "hwy_act_continuous";
+  if (int rc = act_check(eng, params, actions, who)) return rc;
+  if (int rc = act_check_finite(eng, params, actions, 1, who)) return rc;
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  const float *d_actions = nullptr;
+  if (int rc = act_stage(eng, actions, act_floats(eng, *params) * sizeof(float), &d_actions)) return rc;
+  if (int rc = hwy_act_continuous_device(eng, params, d_actions)) return rc;
+  HWY_HIP(eng, hipStreamSynchronize(eng->stream));
+  return HWY_OK;
+}
+
+extern "C" int hwy_step_continuous_device(hwy_engine *eng, const hwy_continuous_params *params, const float *d_actions, float *d_obs,
+                                          double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, double *d_info_speed,
+                                          uint8_t *d_info_crashed) {
+  if (int rc = act_check(eng, params, d_actions, "hwy_step_continuous_device")) return rc;
+  if (!d_obs || !d_reward || !d_terminated || !d_truncated)
+    return fail(eng, HWY_ERR_INVALID_ARG, "hwy_step_continuous_device: obs/reward/terminated/truncated must be non-NULL");
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  HWY_HIP(eng, hwy::launch_act_continuous(hwy::act_params(eng->cfg, *params, d_actions, eng->d_controls), eng->stream));
+  return enqueue_full_step(eng, nullptr, d_obs, d_reward, d_terminated, d_truncated, d_info_speed, d_info_crashed);
+}
+
+extern "C" int hwy_step_same_step_continuous_device(hwy_engine *eng, const hwy_continuous_params *params, const float *d_actions,
+                                                    float *d_obs, double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated,
+                                                    double *d_info_speed, uint8_t *d_info_crashed, float *d_final_obs,
+                                                    double *d_final_info_speed, uint8_t *d_final_info_crashed, uint8_t *d_final_mask,
+                                                    uint8_t *d_action_mask, uint8_t *d_final_action_mask) {
+  return same_step_enqueue(eng, "hwy_step_same_step_continuous_device", nullptr, params, d_actions, d_obs, d_reward, d_terminated,
+                           d_truncated, d_info_speed, d_info_crashed, d_final_obs, d_final_info_speed, d_final_info_crashed, d_final_mask,
+                           d_action_mask, d_final_action_mask, true);
+}
+
+extern "C" int hwy_rollout_continuous_device(hwy_engine *eng, const hwy_continuous_params *params, int32_t k_steps, const float *d_actions,
+                                             float *d_obs, double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated,
+                                             double *d_info_speed, uint8_t *d_info_crashed) {
+  static const char *who = "hwy_rollout_continuous_device";
+  if (int rc = act_check(eng, params, d_actions, who)) return rc;
+  if (k_steps < 1) return fail(eng, HWY_ERR_INVALID_ARG, std::string(who) + ": k_steps must be >= 1");
+  if (!d_obs || !d_reward || !d_terminated || !d_truncated)
+    return fail(eng, HWY_ERR_INVALID_ARG, std::string(who) + ": obs/reward/terminated/truncated must be non-NULL");
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  // k_steps x (act launch + step launch) on block k of every plane: step k's stored pair comes from action k, so the steps cannot
+  // share a launch without a rollout kernel that reads the float buffer.  The launches are those of k_steps
+  // hwy_step_continuous_device calls: the same results by construction.
+  const size_t E = eng->cfg.num_envs, EA = num_agent_rows(eng->cfg), n_obs = num_obs_floats(eng->cfg), n_a = act_floats(eng, *params);
+  for (size_t k = 0; k < (size_t)k_steps; ++k) {
+    HWY_HIP(eng, hwy::launch_act_continuous(hwy::act_params(eng->cfg, *params, d_actions + k * n_a, eng->d_controls), eng->stream));
+    if (int rc = enqueue_full_step(eng, nullptr, d_obs + k * n_obs, d_reward + k * EA, d_terminated + k * E, d_truncated + k * E,
+                                   d_info_speed ? d_info_speed + k * EA : nullptr, d_info_crashed ? d_info_crashed + k * EA : nullptr))
+      return rc;
+  }
+  return HWY_OK;
+}
+
+// the host-pointer doors (hwy_step_continuous: one step): the validated actions up, hwy_rollout_continuous_device, the outputs down
+static int rollout_continuous_host(hwy_engine *eng, const char *who, const hwy_continuous_params *params, int32_t k_steps,
+                                   const float *actions, float *obs, double *reward, uint8_t *terminated, uint8_t *truncated,
+                                   double *info_speed, uint8_t *info_crashed) {
+  if (int rc = act_check(eng, params, actions, who)) return rc;
+  if (k_steps < 1) return fail(eng, HWY_ERR_INVALID_ARG, std::string(who) + ": k_steps must be >= 1");
+  if (!obs || !reward || !terminated || !truncated)
+    return fail(eng, HWY_ERR_INVALID_ARG, std::string(who) + ": obs/reward/terminated/truncated must be non-NULL");
+  if (int rc = act_check_finite(eng, params, actions, (size_t)k_steps, who)) return rc;
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  return rollout_through_host(eng, (size_t)k_steps, actions, act_floats(eng, *params) * sizeof(float), obs, reward, terminated, truncated,
+                              info_speed, info_crashed,
+                              [&](const void *d_act, float *d_obs, double *d_rew, uint8_t *d_term, uint8_t *d_trunc, double *d_spd, uint8_t *d_crash) {
+                                return hwy_rollout_continuous_device(eng, params, k_steps, (const float *)d_act, d_obs, d_rew, d_term, d_trunc,
+                                                                     d_spd, d_crash);
+                              });
+}
+extern "C" int hwy_rollout_continuous(hwy_engine *eng, const hwy_continuous_params *params, int32_t k_steps, const float *actions,
+                                      float *obs, double *reward, uint8_t *terminated, uint8_t *truncated, double *info_speed,
+                                      uint8_t *info_crashed) {
+  return rollout_continuous_host(eng, "hwy_rollout_continuous", params, k_steps, actions, obs, reward, terminated, truncated, info_speed,
+                                 info_crashed);
+}
+extern "C" int hwy_step_continuous(hwy_engine *eng, const hwy_continuous_params *params, const float *actions, float *obs, double *reward,
+                                   uint8_t *terminated, uint8_t *truncated, double *info_speed, uint8_t *info_crashed) {
+  return rollout_continuous_host(eng, "hwy_step_continuous", params, 1, actions, obs, reward, terminated, truncated, info_speed, info_crashed);
 }
 
 extern "C" int hwy_sync(hwy_engine *eng) {

@@ -1,7 +1,7 @@
 // hwy_launch_units.h -- arguments -> (precondition check, kernel instantiation, grid, block, LDS) of the add-on kernel units beside
 // the step kernels -- the Lidar trace (hwy_lidar.h), the TTC grid and planner (hwy_ttc.h), fork and score (hwy_lookahead.h), the OPD
-// tree (hwy_opd.h) and the action mask (hwy_mask.h) -- written ONCE for the product and for the CPU emulation of tests/emu, like
-// hwy_launch_family.h for the step families.  Host code only, generic over the thing that launches: a backend B with one member
+// tree (hwy_opd.h), the action mask (hwy_mask.h) and the continuous action (hwy_act.h) -- written ONCE for the product and for the
+// CPU emulation of tests/emu, like hwy_launch_family.h for the step families.  Host code only, generic over the thing that launches: a backend B with one member
 //   B::launch_plain(kernel, grid, block, lds, stream, args)   enqueue / run the kernel; no dispatch timestamps (those of
 //                                                             hwy_profile_* belong to the step kernel)
 // hwy_launch.h: HipBackend (hipLaunchKernelGGL); tests/emu/hip_emu.h: emu::PlainBackend (emu::launch).  Nothing here needs
@@ -91,6 +91,20 @@ template <typename B> hipError_t select_mask(const MaskParams &mp, hipStream_t s
     return hipErrorInvalidValue;
   const int blocks = (mp.rows + HWY_MASK_BLOCK - 1) / HWY_MASK_BLOCK;
   return B::launch_plain(hwy_mask_kernel<HWY_MASK_BLOCK>, blocks, HWY_MASK_BLOCK, 0, stream, mp);
+}
+}  // namespace hwy
+#endif
+
+// ---- continuous action (hwy_act.h): ap.rows (environment, agent) rows, one thread each, row r -> ap.ctl_accel[r], ap.ctl_steer[r] ------
+#if defined(HWY_ACT_BLOCK) && !defined(HWY_LAUNCH_ACT_UNIT)
+#define HWY_LAUNCH_ACT_UNIT
+namespace hwy {
+template <typename B> hipError_t select_act_continuous(const ActParams &ap, hipStream_t stream) {
+  if (ap.rows < 1 || ap.A < 1 || ap.rows % ap.A != 0 || !ap.actions || !ap.ctl_accel || !ap.ctl_steer || (!ap.longitudinal && !ap.lateral) ||
+      ap.size != (ap.longitudinal ? 1 : 0) + (ap.lateral ? 1 : 0))
+    return hipErrorInvalidValue;
+  const int blocks = (ap.rows + HWY_ACT_BLOCK - 1) / HWY_ACT_BLOCK;
+  return B::launch_plain(hwy_act_continuous_kernel<HWY_ACT_BLOCK>, blocks, HWY_ACT_BLOCK, 0, stream, ap);
 }
 }  // namespace hwy
 #endif

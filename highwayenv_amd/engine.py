@@ -295,6 +295,87 @@ class Engine:
             vp(d_info_speed or None), vp(d_info_crashed or None), vp(d_final_obs or None), vp(d_final_info_speed or None),
             vp(d_final_info_crashed or None), vp(d_final_mask or None), vp(d_action_mask or None), vp(d_final_action_mask or None)))
 
+    # -- continuous throttle and steering of a direct-control engine (csrc/hwy_act.h) -------------------
+    def _check_continuous(self, rc: int):
+        if rc == _abi.HWY_ERR_ACTION:  # a NaN or an infinity: no member of Box(-1, 1, (size,), float32)
+            raise ValueError(self._lib.hwy_last_error(self._h).decode())
+        self._check_scope(rc)
+
+    def _continuous_actions(self, params: _abi.HwyContinuousParams, actions, lead=()) -> np.ndarray:
+        """``actions`` as the contiguous float32 [*lead, E, A, size] the entry points read.  A float64 array is ROUNDED to float32
+        here: the reference's ``Box(-1, 1, (size,), float32)`` does not contain it either, and its mapping is defined on float32."""
+        return np.ascontiguousarray(np.asarray(actions, np.float32).reshape(*lead, self.E, self.A, params.size))
+
+    def act_continuous(self, params: _abi.HwyContinuousParams, actions):
+        """hwy_act_continuous: the act kernel alone.  ``actions`` [E, A, size] are clipped to [-1, 1], mapped onto the ranges of
+        ``params`` as the reference's ``ContinuousAction.get_action`` maps a float32 action, and stored as the (acceleration,
+        steering) pairs ``get_controls`` reads.  ValueError for a non-finite component."""
+        a = self._continuous_actions(params, actions)
+        self._check_continuous(self._lib.hwy_act_continuous(self._h, C.byref(params), _ptr(a)))
+
+    def act_continuous_device(self, params: _abi.HwyContinuousParams, d_actions: int):
+        """Enqueue hwy_act_continuous_device on a raw device pointer (float32 [E, A, size]); does not synchronise.  A row with a
+        non-finite component leaves its stored pair as it is."""
+        self._check_continuous(self._lib.hwy_act_continuous_device(self._h, C.byref(params), C.c_void_p(d_actions or None)))
+
+    def step_continuous(self, params: _abi.HwyContinuousParams, actions):
+        """hwy_step_continuous (host arrays): ``step`` with float actions [E, A, size] in place of ids -- the act kernel, then the
+        engine's own step launch on the pair it stored.  A float64 array is rounded to float32 first.  ValueError for a
+        non-finite component, before anything runs."""
+        E, A = self.E, self.A
+        a = self._continuous_actions(params, actions)
+        obs = np.empty((E, A, *_abi.obs_shape(self.cfg)), np.float32)
+        reward = np.empty((E, A), np.float64)
+        term, trunc = np.empty(E, np.uint8), np.empty(E, np.uint8)
+        speed, crashed = np.empty((E, A), np.float64), np.empty((E, A), np.uint8)
+        self._check_continuous(self._lib.hwy_step_continuous(self._h, C.byref(params), _ptr(a), _ptr(obs), _ptr(reward), _ptr(term),
+                                                             _ptr(trunc), _ptr(speed), _ptr(crashed)))
+        return obs, reward, term.astype(bool), trunc.astype(bool), {"speed": speed, "crashed": (crashed & 1).astype(bool),
+                                                                    "arrived": (crashed & 2).astype(bool)}
+
+    def rollout_continuous(self, params: _abi.HwyContinuousParams, actions):
+        """hwy_rollout_continuous (host arrays): actions [K, E, A, size] -> the tuple of ``rollout``.  K (act, step) launch pairs
+        enqueued by one call; the results of K ``step_continuous`` calls, bit for bit."""
+        a = self._continuous_actions(params, actions, lead=(-1,))
+        K, E, A = a.shape[0], self.E, self.A
+        obs = np.empty((K, E, A, *_abi.obs_shape(self.cfg)), np.float32)
+        reward = np.empty((K, E, A), np.float64)
+        term, trunc = np.empty((K, E), np.uint8), np.empty((K, E), np.uint8)
+        speed, crashed = np.empty((K, E, A), np.float64), np.empty((K, E, A), np.uint8)
+        self._check_continuous(self._lib.hwy_rollout_continuous(self._h, C.byref(params), K, _ptr(a), _ptr(obs), _ptr(reward),
+                                                                _ptr(term), _ptr(trunc), _ptr(speed), _ptr(crashed)))
+        return obs, reward, term.astype(bool), trunc.astype(bool), {"speed": speed, "crashed": (crashed & 1).astype(bool),
+                                                                    "arrived": (crashed & 2).astype(bool)}
+
+    def step_continuous_device(self, params: _abi.HwyContinuousParams, d_actions: int, d_obs: int, d_reward: int, d_terminated: int,
+                               d_truncated: int, d_info_speed: int = 0, d_info_crashed: int = 0):
+        """Enqueue hwy_step_continuous_device on raw device pointers (``d_actions``: float32 [E, A, size]); does not synchronise."""
+        vp = C.c_void_p
+        self._check_continuous(self._lib.hwy_step_continuous_device(
+            self._h, C.byref(params), vp(d_actions or None), vp(d_obs or None), vp(d_reward or None), vp(d_terminated or None),
+            vp(d_truncated or None), vp(d_info_speed or None), vp(d_info_crashed or None)))
+
+    def rollout_continuous_device(self, params: _abi.HwyContinuousParams, k_steps: int, d_actions: int, d_obs: int, d_reward: int,
+                                  d_terminated: int, d_truncated: int, d_info_speed: int = 0, d_info_crashed: int = 0):
+        """Enqueue hwy_rollout_continuous_device (``d_actions``: float32 [K, E, A, size], block k of every plane belongs to step k):
+        ``k_steps`` (act, step) launch pairs, no host round trip; does not synchronise."""
+        vp = C.c_void_p
+        self._check_continuous(self._lib.hwy_rollout_continuous_device(
+            self._h, C.byref(params), int(k_steps), vp(d_actions or None), vp(d_obs or None), vp(d_reward or None),
+            vp(d_terminated or None), vp(d_truncated or None), vp(d_info_speed or None), vp(d_info_crashed or None)))
+
+    def step_same_step_continuous_device(self, params: _abi.HwyContinuousParams, d_actions: int, d_obs: int, d_reward: int,
+                                         d_terminated: int, d_truncated: int, d_info_speed: int = 0, d_info_crashed: int = 0,
+                                         d_final_obs: int = 0, d_final_info_speed: int = 0, d_final_info_crashed: int = 0,
+                                         d_final_mask: int = 0, d_action_mask: int = 0, d_final_action_mask: int = 0):
+        """Enqueue hwy_step_same_step_continuous_device: ``step_same_step_device`` with float actions [E, A, size] in place of ids."""
+        vp = C.c_void_p
+        self._check_continuous(self._lib.hwy_step_same_step_continuous_device(
+            self._h, C.byref(params), vp(d_actions or None), vp(d_obs or None), vp(d_reward or None), vp(d_terminated or None),
+            vp(d_truncated or None), vp(d_info_speed or None), vp(d_info_crashed or None), vp(d_final_obs or None),
+            vp(d_final_info_speed or None), vp(d_final_info_crashed or None), vp(d_final_mask or None), vp(d_action_mask or None),
+            vp(d_final_action_mask or None)))
+
     # -- reset --------------------------------------------------------------------------------
     def reset(self, seeds=None, mask=None, ego_spacing=2.0, vehicles_density=1.0, initial_lane_id=-1, base_seed=0):
         """Device-side spawn (counter-based RNG; NOT numpy's stream -- see spawn.py for that)."""

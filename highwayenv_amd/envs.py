@@ -295,6 +295,64 @@ class BatchedHighwayEnv:
             out_info["agents_speed"], out_info["agents_crashed"] = info["speed"], info["crashed"]
         return self._shape_obs(obs), reward[:, 0], term, trunc, out_info
 
+    # ---- continuous throttle and steering (ContinuousAction.act, action.py:136-163) ----------------------------------------------
+    def continuous_params(self) -> "_abi.HwyContinuousParams":
+        """The ``ContinuousAction`` behind this env's ``DiscreteAction`` config (same vehicle class, same ``acceleration_range`` /
+        ``steering_range`` / ``longitudinal`` / ``lateral`` / ``clip`` keys: ``DiscreteAction`` inherits them, action.py:165-188).
+        NotImplementedError on a ``DiscreteMetaAction`` ego (an MDPVehicle follows lanes and speeds, not a throttle) and for
+        ``clip: False``."""
+        if self._hcfg.ego_control != _abi.EGO_DIRECT:
+            raise NotImplementedError("step_continuous needs a plain-Vehicle ego: configure the env with {'type': 'DiscreteAction'} "
+                                      "(a DiscreteMetaAction ego is an MDPVehicle)")
+        act = self.config["action"]
+        return _abi.continuous_params(act["action_config"] if act["type"] == "MultiAgentAction" else act)
+
+    def continuous_action_space(self):
+        """``ContinuousAction.space()`` (action.py:113-118): ``Box(-1, 1, (size,), float32)``, size 2 with both axes (throttle,
+        steering), 1 with one; its stand-in without gymnasium."""
+        size = self.continuous_params().size
+        if _gym is not None:
+            return _gym.spaces.Box(-1.0, 1.0, (size,), np.float32)
+        box = _Box((size,), np.float32)
+        box.low, box.high = -1.0, 1.0
+        return box
+
+    def _continuous_actions(self, action, size: int) -> np.ndarray:
+        """``action`` as float32 [E, A, size]: shape (size,) drives every agent of every env, (E, size) every agent of env e,
+        (E, A, size) is taken as is.  Cast to float32: a float64 array is ROUNDED first."""
+        E, A = self.num_envs, self._hcfg.num_agents
+        a = np.asarray(action, np.float32)
+        if a.shape == (size,):
+            a = np.broadcast_to(a, (E, A, size))
+        elif a.shape == (E, size):
+            a = np.broadcast_to(a[:, None, :], (E, A, size))
+        elif a.shape != (E, A, size):
+            raise ValueError(f"a continuous action must have shape ({size},), ({E}, {size}) or ({E}, {A}, {size}); got {a.shape}")
+        return np.ascontiguousarray(a)
+
+    def step_continuous(self, action):
+        """``step`` with the reference's ``ContinuousAction`` in place of the action ids: ``action`` in [-1, 1]^size per agent
+        (size 2: throttle, steering; 1 with ``longitudinal`` or ``lateral`` off; shapes (size,), (E, size), (E, A, size)) is
+        clipped and mapped onto ``acceleration_range`` / ``steering_range`` on the device (csrc/hwy_act.h) exactly as
+        ``ContinuousAction.get_action`` maps a float32 action, then the engine's own step runs on the stored pair.  The action
+        is cast to float32; a float64 array is rounded to float32 FIRST -- the reference's ``Box(-1, 1, (size,), float32)``
+        would not contain it either.  ``info["action"]`` echoes the float32 array.  ValueError for a NaN or an infinity,
+        NotImplementedError on a ``DiscreteMetaAction`` ego and for ``clip: False``."""
+        params = self.continuous_params()
+        if self._engine is None:
+            raise NotImplementedError("The road and vehicle must be initialized in the environment implementation")
+        A = self._hcfg.num_agents
+        acts = self._continuous_actions(action, params.size)
+        obs, reward, term, trunc, info = self._engine.step_continuous(params, acts)
+        self.time += 1 / self.config["policy_frequency"]
+        self.steps += self._hcfg.frames_per_step
+        out_info = {"speed": info["speed"][:, 0], "crashed": info["crashed"][:, 0], "action": acts if A > 1 else acts[:, 0]}
+        self._agents_step = (reward, info)
+        if A > 1:
+            out_info["agents_rewards"] = reward
+            out_info["agents_speed"], out_info["agents_crashed"] = info["speed"], info["crashed"]
+        return self._shape_obs(obs), reward[:, 0], term, trunc, out_info
+
     def _shape_obs(self, obs):
         # KinematicObservation(order="shuffled") (observation.py:273-274): `self.env.np_random.shuffle(obs[1:])` after every
         # observe(), agent by agent -- the engine returned the rows in list order (HWY_C_OBS_UNSORTED), the shuffle draws
@@ -808,6 +866,13 @@ class _SingleEnvMixin:
         return (obs[0], float(reward[0]), bool(term[0]), bool(trunc[0]),
                 {"speed": float(info["speed"][0]), "crashed": bool(info["crashed"][0]), "action": action,
                  "rewards": self.rewards(0)})
+
+    def step_continuous(self, action):
+        """``step`` with a ``ContinuousAction`` array of shape (size,) -- (A, size) under ``MultiAgentAction`` -- in place of the id."""
+        a = np.asarray(action, np.float32)
+        obs, reward, term, trunc, info = super().step_continuous(a.reshape(1, self._hcfg.num_agents, -1))
+        return (obs[0], float(reward[0]), bool(term[0]), bool(trunc[0]),
+                {"speed": float(info["speed"][0]), "crashed": bool(info["crashed"][0]), "action": a, "rewards": self.rewards(0)})
 
     def to_finite_mdp(self):
         """``AbstractEnv.to_finite_mdp()`` (abstract.py:452-453): horizon 10 s, time step ``1 / policy_frequency``."""

@@ -29,6 +29,10 @@ environments are ONE engine (one kernel launch per step), and this class gives t
   round trip), actions may be a device tensor, and everything is ordered on torch's current stream -- a policy network can read
   ``obs`` and write ``actions`` without leaving the GPU ("keeping the policy on-GPU").  Every autoreset
   mode.  ``rollout(actions[K])`` exposes ``hwy_rollout_device`` (K steps per launch, NextStep between them) in this mode.
+* ``continuous=True`` (an env configured with ``DiscreteAction``): the reference's ``ContinuousAction`` -- ``single_action_space`` is
+  ``Box(-1, 1, (size,), float32)`` and ``step`` / ``step_async`` / ``rollout`` take float actions [E(, A), size] (throttle, steering),
+  mapped onto the configured ranges by a kernel of its own (csrc/hwy_act.h) in front of the engine's step; every output and every
+  autoreset mode as with ids.  A policy network's float32 device tensor goes to the kernel as it is.
 
 With gymnasium installed the class IS a ``gymnasium.vector.VectorEnv``; without it (this image) the same attributes exist on a
 plain object.
@@ -72,7 +76,7 @@ class HighwayVectorEnv(_Base):
 
     def __init__(self, env="highway-fast-v0", num_envs: int = 1, config: dict | None = None, autoreset_mode: str = "NextStep",
                  output: str = "numpy", device: int = 0, spawn_mode: str = "device", stream=None, action_masks: bool = False,
-                 **kwargs):
+                 continuous: bool = False, **kwargs):
         mode = getattr(autoreset_mode, "value", autoreset_mode)  # gymnasium.vector.AutoresetMode or its string
         mode = {"next_step": "NextStep", "same_step": "SameStep", "disabled": "Disabled"}.get(str(mode).lower(), str(mode))
         if mode not in AUTORESET_MODES:
@@ -120,6 +124,16 @@ class HighwayVectorEnv(_Base):
         env.autoreset = engine_autoreset
         self.num_envs = env.num_envs
         self.single_observation_space, self.single_action_space = env.single_observation_space, env.single_action_space
+        # continuous: the actions of step / step_async / rollout are the reference's ContinuousAction arrays -- float32 [E(, A), size]
+        # in [-1, 1], size 2 (throttle, steering) or 1 -- in place of DiscreteAction ids; the env is configured with a DiscreteAction
+        # (same vehicle class, same ranges and axes) and every call goes through the engine's continuous entry points (csrc/hwy_act.h).
+        self.continuous = bool(continuous)
+        self._cparams = None
+        if self.continuous:
+            if env._hcfg.ego_control != _abi.EGO_DIRECT:
+                raise ValueError("continuous=True needs an env configured with {'type': 'DiscreteAction'} (a plain-Vehicle ego)")
+            self._cparams = env.continuous_params()
+            self.single_action_space = env.continuous_action_space()  # Box(-1, 1, (size,), float32); several agents: as for Discrete
         if _gym is not None:
             self.observation_space = _gym.vector.utils.batch_space(self.single_observation_space, self.num_envs)
             self.action_space = _gym.vector.utils.batch_space(self.single_action_space, self.num_envs)
@@ -163,7 +177,7 @@ class HighwayVectorEnv(_Base):
     def step(self, actions):
         if self.output == "torch":
             return self._step_torch(actions)
-        obs, reward, term, trunc, info = self.env.step(actions)
+        obs, reward, term, trunc, info = self.env.step_continuous(actions) if self.continuous else self.env.step(actions)
         infos = {"speed": np.asarray(info["speed"], np.float64), "crashed": np.asarray(info["crashed"], bool)}
         for k in ("agents_rewards", "agents_terminated", "rewards"):
             if k in info:
@@ -204,7 +218,8 @@ class HighwayVectorEnv(_Base):
             d["final_crashed"], d["final_mask"] = t.zeros_like(d["crashed"]), t.zeros(E, dtype=t.uint8, device=dev)
             if self.action_masks:
                 d["final_action_mask"] = t.zeros_like(d["action_mask"])
-        self._n_actions = E * A
+        self._n_actions = E * A * (self._cparams.size if self.continuous else 1)
+        self._action_dtype = t.float32 if self.continuous else t.int32
         self._out_ptrs = tuple(d[k].data_ptr() for k in ("obs", "reward", "terminated", "truncated", "speed", "crashed"))
         # what step() hands out: views of the planes the kernel writes (bool views of the 0 / 1 flag bytes; the intersection's
         # info_crashed carries has_arrived in bit 1, include/hwy_engine.h, so its `crashed` is computed per step)
@@ -238,6 +253,12 @@ class HighwayVectorEnv(_Base):
     def _device_actions(self, actions, lead=()):
         t, E, A = self._torch, self.num_envs, self.env._hcfg.num_agents
         a = actions if isinstance(actions, t.Tensor) else t.as_tensor(np.asarray(actions))
+        if self.continuous:  # float32 [*lead, E(, A), size] (a float64 tensor is rounded to float32, like the numpy path)
+            size = self._cparams.size
+            a = a.to(device=self._dev["obs"].device, dtype=t.float32)
+            if a.dim() == len(lead) + 2 and A > 1:
+                a = a.unsqueeze(-2).expand(*lead, E, A, size)
+            return a.reshape(*lead, E, A, size).contiguous()
         a = a.to(device=self._dev["obs"].device, dtype=t.int32)
         if a.dim() == len(lead) + 1 and A > 1:
             a = a.unsqueeze(-1).expand(*lead, E, A)
@@ -248,16 +269,21 @@ class HighwayVectorEnv(_Base):
         Action ids are NOT validated on this path (include/hwy_engine.h: hwy_step_device); ids outside the table act as IDLE.
         The host side of a step is kept to the launch and two stream waits: no elementwise kernel is launched for the outputs
         (the flag planes hold 0 / 1 bytes and are returned as zero-copy bool VIEWS), and an int32 device tensor of the right
-        shape goes to the kernel as it is."""
+        shape goes to the kernel as it is.  ``continuous=True``: the same with a float32 device tensor [E(, A), size] and the
+        continuous entry points (the act kernel, then the step launch, on the same stream; a NaN row keeps its stored controls)."""
         t, d = self._torch, self._dev
-        if not (isinstance(actions, t.Tensor) and actions.dtype == t.int32 and actions.is_cuda and actions.is_contiguous()
+        if not (isinstance(actions, t.Tensor) and actions.dtype == self._action_dtype and actions.is_cuda and actions.is_contiguous()
                 and actions.numel() == self._n_actions):
             actions = self._device_actions(actions)
         cur = t.cuda.current_stream()
         same = cur.cuda_stream == self._stream.cuda_stream
         if not same:
             self._stream.wait_stream(cur)      # the actions (and the consumer of the previous outputs) come first
-        if self._device_same_step:             # step, stash of the terminal rows, re-spawn (and both masks) in one call
+        if self.continuous and self._device_same_step:
+            self.env._engine.step_same_step_continuous_device(self._cparams, actions.data_ptr(), *self._out_ptrs, *self._final_ptrs)
+        elif self.continuous:
+            self.env._engine.step_continuous_device(self._cparams, actions.data_ptr(), *self._out_ptrs)
+        elif self._device_same_step:           # step, stash of the terminal rows, re-spawn (and both masks) in one call
             self.env._engine.step_same_step_device(actions.data_ptr(), *self._out_ptrs, *self._final_ptrs)
         else:
             self.env._engine.step_device(actions.data_ptr(), *self._out_ptrs)
@@ -290,7 +316,11 @@ class HighwayVectorEnv(_Base):
         term, trunc = t.empty((K, E), dtype=t.uint8, device=dev), t.empty((K, E), dtype=t.uint8, device=dev)
         cur = t.cuda.current_stream()
         self._stream.wait_stream(cur)
-        self.env._engine.rollout_device(K, a.data_ptr(), obs.data_ptr(), rew.data_ptr(), term.data_ptr(), trunc.data_ptr())
+        if self.continuous:  # K (act, step) launch pairs enqueued by one call (hwy_rollout_continuous_device)
+            self.env._engine.rollout_continuous_device(self._cparams, K, a.data_ptr(), obs.data_ptr(), rew.data_ptr(), term.data_ptr(),
+                                                       trunc.data_ptr())
+        else:
+            self.env._engine.rollout_device(K, a.data_ptr(), obs.data_ptr(), rew.data_ptr(), term.data_ptr(), trunc.data_ptr())
         cur.wait_stream(self._stream)
         for x in (a, obs, rew, term, trunc):
             x.record_stream(self._stream)

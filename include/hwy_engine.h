@@ -787,6 +787,68 @@ int hwy_step_same_step_device(hwy_engine *eng, const int32_t *d_actions, float *
                               double *d_final_info_speed, uint8_t *d_final_info_crashed, uint8_t *d_final_mask,
                               uint8_t *d_action_mask, uint8_t *d_final_action_mask);
 
+/*
+ * Continuous throttle and steering for the plain-Vehicle egos of a HWY_EGO_DIRECT engine (additive to ABI v8: hwy_config keeps its
+ * layout).  ContinuousAction.act (envs/common/action.py:136-163): a float action in [-1, 1]^size per (environment, agent) -- size 2
+ * with both axes (throttle first, then steering), 1 with one -- is clipped, mapped onto the configured ranges and stored as the
+ * vehicle's (acceleration, steering) pair, the planes of hwy_set_controls.  DiscreteAction is nothing but this on a grid
+ * (action.py:189-196), so the simulation is the engine's own: every entry point below is the act kernel (csrc/hwy_act.h:
+ * hwy_act_continuous_kernel, one thread per row) followed on the engine's stream by the EXISTING step launch with no action ids,
+ * which then drives on with the stored pair.  No step kernel reads a float buffer.
+ * The mapping is the reference's for a FLOAT32 action, the dtype of its Box(-1, 1, (size,), float32): np.clip and every operation of
+ * utils.lmap in float32, the range ends rounded to float32 where they meet the value, the result widened to double
+ * (csrc/hwy_act.h states the steps); an axis that is not controlled stores 0.0.  Bit for bit the reference's stored action.
+ */
+typedef struct hwy_continuous_params {
+  double acceleration_range[2]; /* ContinuousAction.acceleration_range (default (-5, 5.0)), as configured: not float32-rounded */
+  double steering_range[2];     /* ContinuousAction.steering_range (default (-pi/4, pi/4)); both ends within +-pi/3 */
+  int32_t longitudinal;         /* 0 / 1: the throttle axis is controlled */
+  int32_t lateral;              /* 0 / 1: the steering axis is controlled; at least one of the two */
+} hwy_continuous_params;
+/*
+ * Every entry point validates `params` the same way: HWY_ERR_INVALID_ARG on a HWY_EGO_META engine (its vehicles store no controls),
+ * for a NULL pointer, non-finite ranges, a steering end beyond +-pi/3 or no controlled axis.
+ *
+ * hwy_act_continuous_device: the act launch alone.  d_actions f32 [E][A][size], DEVICE pointer; enqueues and does not synchronise.
+ * A row with a non-finite component (NaN, +-inf) leaves BOTH stored values of that row as they are -- the rule hwy_step_device
+ * has for an id outside the table; the DEVICE forms do not validate the values.  Nothing is skipped for an environment that awaits its
+ * next-step re-spawn: the episode start that follows zeroes its controls, as after a DiscreteAction step.
+ * hwy_act_continuous: the same from a HOST pointer (HWY_ERR_ACTION for a non-finite component, before anything runs); synchronises.
+ */
+int hwy_act_continuous_device(hwy_engine *eng, const hwy_continuous_params *params, const float *d_actions);
+int hwy_act_continuous(hwy_engine *eng, const hwy_continuous_params *params, const float *actions);
+/*
+ * One policy step: the act launch, then exactly hwy_step_device's launch with no ids (the same kernel, timing and auto-reset).  The
+ * remaining arguments are hwy_step_device's.  Enqueues on the engine's stream and does not synchronise.
+ */
+int hwy_step_continuous_device(hwy_engine *eng, const hwy_continuous_params *params, const float *d_actions, float *d_obs,
+                               double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, double *d_info_speed,
+                               uint8_t *d_info_crashed);
+/* The same through HOST pointers, like hwy_step (HWY_ERR_ACTION for a non-finite component; H2D, launches, D2H, synchronises). */
+int hwy_step_continuous(hwy_engine *eng, const hwy_continuous_params *params, const float *actions, float *obs, double *reward,
+                        uint8_t *terminated, uint8_t *truncated, double *info_speed, uint8_t *info_crashed);
+/*
+ * SameStep autoreset: the act launch, then hwy_step_same_step_device's sequence with no ids (step, stash, re-spawn).  The remaining
+ * arguments and errors are that entry point's; either mask pointer: what hwy_action_mask_device returns (a direct ego has no mask).
+ */
+int hwy_step_same_step_continuous_device(hwy_engine *eng, const hwy_continuous_params *params, const float *d_actions, float *d_obs,
+                                         double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, double *d_info_speed,
+                                         uint8_t *d_info_crashed, float *d_final_obs, double *d_final_info_speed,
+                                         uint8_t *d_final_info_crashed, uint8_t *d_final_mask, uint8_t *d_action_mask,
+                                         uint8_t *d_final_action_mask);
+/*
+ * k_steps policy steps with pre-staged actions: d_actions f32 [K][E][A][size], block k of every output plane belongs to step k as in
+ * hwy_rollout_device.  ONE call enqueues k_steps (act, step) pairs with no host round trip; the results are those of k_steps calls of
+ * hwy_step_continuous_device, bit for bit, next-step auto-reset included.  The one-launch K-step form of hwy_rollout_device would
+ * need a rollout kernel that reads the float buffer -- a new kernel of the step family; out of scope here.
+ * hwy_rollout_continuous: the same through HOST pointers (HWY_ERR_ACTION for a non-finite component; synchronises).
+ */
+int hwy_rollout_continuous_device(hwy_engine *eng, const hwy_continuous_params *params, int32_t k_steps, const float *d_actions,
+                                  float *d_obs, double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, double *d_info_speed,
+                                  uint8_t *d_info_crashed);
+int hwy_rollout_continuous(hwy_engine *eng, const hwy_continuous_params *params, int32_t k_steps, const float *actions, float *obs,
+                           double *reward, uint8_t *terminated, uint8_t *truncated, double *info_speed, uint8_t *info_crashed);
+
 #ifdef __cplusplus
 }
 #endif
