@@ -331,6 +331,50 @@ def opd_params(cfg: "HwyConfig", budget: int, gamma: float, masked: bool = False
     return p
 
 
+class HwyCemParams(C.Structure):
+    """hwy_cem_params (include/hwy_engine.h): the shape and the smoothing of a cross-entropy-method search."""
+    _fields_ = [("population", C.c_int32), ("elites", C.c_int32), ("iterations", C.c_int32), ("horizon", C.c_int32),
+                ("gamma", C.c_double), ("init_std", C.c_double), ("min_std", C.c_double), ("alpha", C.c_double), ("seed", C.c_uint64)]
+
+
+HWY_CEM_MAX_POP = 1024          # include/hwy_engine.h
+HWY_CEM_MAX_HORIZON = 64
+HWY_CEM_MAX_ITERATIONS = 1024
+HWY_CEM_STREAM_TAG = 0x4857434D  # "HWCM": counter word 3 of the sample kernel's Philox draws (csrc/hwy_cem.h)
+
+
+def cem_params(population: int, elites: int, iterations: int, horizon: int, gamma: float, init_std: float, min_std: float,
+               alpha: float, seed: int) -> HwyCemParams:
+    """``hwy_cem_params`` of ``plan_cem``.  ValueError for what hwy_cem_plan_device rejects as HWY_ERR_INVALID_ARG."""
+    B, M, I, K = int(population), int(elites), int(iterations), int(horizon)
+    if not 1 <= B <= HWY_CEM_MAX_POP:
+        raise ValueError(f"population ({B}) must be in [1, HWY_CEM_MAX_POP = {HWY_CEM_MAX_POP}]")
+    if not 1 <= M <= B:
+        raise ValueError(f"elites ({M}) must be in [1, population = {B}]")
+    if not 1 <= I <= HWY_CEM_MAX_ITERATIONS:
+        raise ValueError(f"iterations ({I}) must be in [1, HWY_CEM_MAX_ITERATIONS = {HWY_CEM_MAX_ITERATIONS}]")
+    if not 1 <= K <= HWY_CEM_MAX_HORIZON:
+        raise ValueError(f"horizon ({K}) must be in [1, HWY_CEM_MAX_HORIZON = {HWY_CEM_MAX_HORIZON}]")
+    if not np.isfinite(gamma):
+        raise ValueError("gamma must be finite")
+    if not (np.isfinite(init_std) and init_std >= 0 and np.isfinite(min_std) and min_std >= 0):
+        raise ValueError("init_std and min_std must be finite and >= 0")
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError("alpha must be in [0, 1]")
+    p = HwyCemParams()
+    p.population, p.elites, p.iterations, p.horizon = B, M, I, K
+    p.gamma, p.init_std, p.min_std, p.alpha = float(gamma), float(init_std), float(min_std), float(alpha)
+    p.seed = int(seed) & (2 ** 64 - 1)
+    return p
+
+
+def cem_bytes(cfg: "HwyConfig", num_envs: int, params: HwyCemParams, size: int, debug: bool = False) -> int:
+    """Device bytes ``plan_cem`` holds beside the parent: the work engine, the planes of its K-step rollout and the search's arrays."""
+    E, B, K, I = int(num_envs), params.population, params.horizon, params.iterations
+    own = K * E * B * size * 4 + E * (K * size * 28 + 8 + size * 4) + (I * E * (B * K * size * 12 + params.elites * 4) if debug else 0)
+    return fork_bytes(cfg, E * B, K) + own
+
+
 def opd_bytes(cfg: "HwyConfig", num_envs: int, params: HwyOpdParams) -> int:
     """Device bytes ``plan_opd`` holds beside the parent: the tree engine, the work engine and the trees' bookkeeping."""
     E, n, M = int(num_envs), params.n_ids, params.nodes

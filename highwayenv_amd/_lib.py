@@ -25,6 +25,7 @@ EXPORTS = [
     "hwy_action_mask_device", "hwy_action_mask", "hwy_step_same_step_device",
     "hwy_act_continuous_device", "hwy_act_continuous", "hwy_step_continuous_device", "hwy_step_continuous",
     "hwy_step_same_step_continuous_device", "hwy_rollout_continuous_device", "hwy_rollout_continuous",
+    "hwy_score_rollout_continuous", "hwy_cem_plan_device", "hwy_cem_plan",
     "hwy_step_shapes", "hwy_last_step_shape",
 ]
 
@@ -115,6 +116,10 @@ def load() -> C.CDLL:
     lib.hwy_step_same_step_continuous_device.argtypes = [vp, cont] + [vp] * 13
     lib.hwy_rollout_continuous_device.argtypes = [vp, cont, i32] + [vp] * 7
     lib.hwy_rollout_continuous.argtypes = [vp, cont, i32] + [vp] * 7
+    lib.hwy_score_rollout_continuous.argtypes = [vp, cont, i32, i32, f64] + [vp] * 6
+    cem = C.POINTER(_abi.HwyCemParams)
+    lib.hwy_cem_plan_device.argtypes = [vp, vp, cont, cem] + [vp] * 9
+    lib.hwy_cem_plan.argtypes = [vp, vp, cont, cem] + [vp] * 9
     lib.hwy_step_shapes.argtypes = [i32]
     lib.hwy_last_step_shape.argtypes = []
     lib.hwy_profile_enable.argtypes = [vp, i32]
@@ -125,7 +130,7 @@ def load() -> C.CDLL:
         fn = getattr(lib, name)
         if fn.restype is C.c_int or name.startswith(("hwy_create", "hwy_destroy", "hwy_set", "hwy_get", "hwy_reset",
                                                       "hwy_step", "hwy_rollout", "hwy_observe", "hwy_sync", "hwy_profile", "hwy_debug", "hwy_comm", "hwy_gather",
-                                                      "hwy_ttc", "hwy_mdp", "hwy_fork", "hwy_score", "hwy_opd", "hwy_action", "hwy_act_")):
+                                                      "hwy_ttc", "hwy_mdp", "hwy_fork", "hwy_score", "hwy_opd", "hwy_action", "hwy_act_", "hwy_cem")):
             if name not in ("hwy_status_string", "hwy_last_error", "hwy_config_size"):
                 fn.restype = C.c_int
     if lib.hwy_abi_version() != _abi.HWY_ABI_VERSION:

@@ -11,9 +11,9 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libhwy_engine.so")
-SOURCES = ["hwy_kernels.hip", "hwy_kernels_shapes.hip", "hwy_kernels_linear.hip", "hwy_kernels_direct.hip", "hwy_kernels_lidar.hip", "hwy_kernels_ttc.hip", "hwy_kernels_lookahead.hip", "hwy_kernels_opd.hip", "hwy_kernels_mask.hip", "hwy_kernels_act.hip", "hwy_kernels_final.hip", "hwy_kernels_respawn.hip", "hwy_engine.hip", "hwy_comm.hip"]
+SOURCES = ["hwy_kernels.hip", "hwy_kernels_shapes.hip", "hwy_kernels_linear.hip", "hwy_kernels_direct.hip", "hwy_kernels_lidar.hip", "hwy_kernels_ttc.hip", "hwy_kernels_lookahead.hip", "hwy_kernels_opd.hip", "hwy_kernels_mask.hip", "hwy_kernels_act.hip", "hwy_kernels_cem.hip", "hwy_kernels_final.hip", "hwy_kernels_respawn.hip", "hwy_engine.hip", "hwy_comm.hip"]
 KERNEL_SOURCES = ("hwy_kernels.hip", "hwy_kernels_shapes.hip", "hwy_kernels_linear.hip", "hwy_kernels_direct.hip", "hwy_kernels_lidar.hip", "hwy_kernels_ttc.hip",
-                  "hwy_kernels_lookahead.hip", "hwy_kernels_opd.hip", "hwy_kernels_mask.hip", "hwy_kernels_act.hip", "hwy_kernels_final.hip",
+                  "hwy_kernels_lookahead.hip", "hwy_kernels_opd.hip", "hwy_kernels_mask.hip", "hwy_kernels_act.hip", "hwy_kernels_cem.hip", "hwy_kernels_final.hip",
                   "hwy_kernels_respawn.hip")  # the translation units that hold device code
 import glob
 

@@ -79,6 +79,10 @@ struct hwy_engine {
   // plane and the host form's outputs, in one block allocated on first use
   char *d_opd = nullptr;
   size_t opd_bytes = 0;
+  // hwy_cem_plan_device (this engine as `work`): the action block the sample kernel writes, the rollout's outputs, the returns, the
+  // search's mean / std / best sequence and the host form's outputs, in one block allocated on first use
+  char *d_cem = nullptr;
+  size_t cem_bytes = 0;
   // pinned host staging
   void *h_pinned = nullptr;
   size_t h_pinned_bytes = 0;
@@ -532,7 +536,7 @@ extern "C" int hwy_destroy(hwy_engine *eng) {
   void *ptrs[] = {eng->d_f64, eng->d_packed, eng->d_time, eng->d_done, eng->d_episode, eng->d_actions, eng->d_out, eng->d_roll,
                   eng->d_mask, eng->d_seeds, eng->d_grid_ws, eng->d_route, eng->d_road_steps, eng->d_gnet,
                   eng->d_shadow_f64, eng->d_shadow_packed, eng->d_shadow_route, eng->d_shadow_meta, eng->d_counters, eng->d_block_env,
-                  eng->d_behavior, eng->d_controls, eng->d_ttc_grid, eng->d_plan_action, eng->d_plan_q, eng->d_fork_src, eng->d_opd, eng->d_action_mask};
+                  eng->d_behavior, eng->d_controls, eng->d_ttc_grid, eng->d_plan_action, eng->d_plan_q, eng->d_fork_src, eng->d_opd, eng->d_cem, eng->d_action_mask};
   for (void *q : ptrs) if (q) (void)hipFree(q);
   if (eng->fork_event) (void)hipEventDestroy(eng->fork_event);
   if (eng->h_pinned) (void)hipHostFree(eng->h_pinned);
@@ -1622,6 +1626,166 @@ extern "C" int hwy_rollout_continuous(hwy_engine *eng, const hwy_continuous_para
 extern "C" int hwy_step_continuous(hwy_engine *eng, const hwy_continuous_params *params, const float *actions, float *obs, double *reward,
                                    uint8_t *terminated, uint8_t *truncated, double *info_speed, uint8_t *info_crashed) {
   return rollout_continuous_host(eng, "hwy_step_continuous", params, 1, actions, obs, reward, terminated, truncated, info_speed, info_crashed);
+}
+
+// ---- the float door into fork / rollout / score, and the CEM planner on top of it (hwy_cem.h) --------------------------------------
+extern "C" int hwy_score_rollout_continuous(hwy_engine *eng, const hwy_continuous_params *params, int32_t k_steps, int32_t branches,
+                                            double gamma, const float *actions, double *reward, uint8_t *terminated, uint8_t *truncated,
+                                            double *ret, int32_t *best_branch) {
+  static const char *who = "hwy_score_rollout_continuous";
+  if (int rc = act_check(eng, params, actions, who)) return rc;
+  const char *why = "";
+  if (const int rc = hwy::score_validate(eng->cfg, k_steps, branches, gamma, false, true, false, false, &why))
+    return fail(eng, rc, std::string(who) + ": " + why);
+  if (int rc = act_check_finite(eng, params, actions, (size_t)k_steps, who)) return rc;  // before anything is simulated
+  const size_t n_row = num_agent_rows(eng->cfg), n_obs = num_obs_floats(eng->cfg), n_a = act_floats(eng, *params);
+  const size_t EB = eng->cfg.num_envs, K = (size_t)k_steps, E = EB / branches, A = eng->cfg.num_agents;
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t o_act = 0, o_rew = up(K * n_a * 4), o_obs = o_rew + up(K * n_row * 8), o_term = o_obs + up(K * n_obs * 4),
+               o_trunc = o_term + up(K * EB), o_ret = o_trunc + up(K * EB), o_bb = o_ret + up(n_row * 8), total = o_bb + up(E * A * 4);
+  if (total > eng->roll_bytes) {
+    HWY_HIP(eng, hipStreamSynchronize(eng->stream));
+    if (eng->d_roll) (void)hipFree(eng->d_roll);
+    eng->d_roll = nullptr;
+    eng->roll_bytes = 0;
+    HWY_HIP(eng, hipMalloc((void **)&eng->d_roll, total));
+    eng->roll_bytes = total;
+  }
+  char *d = eng->d_roll;
+  HWY_HIP(eng, hipMemcpyAsync(d + o_act, actions, K * n_a * 4, hipMemcpyHostToDevice, eng->stream));
+  if (int rc = hwy_rollout_continuous_device(eng, params, k_steps, (const float *)(d + o_act), (float *)(d + o_obs), (double *)(d + o_rew),
+                                             (uint8_t *)(d + o_term), (uint8_t *)(d + o_trunc), nullptr, nullptr))
+    return rc;
+  if (int rc = hwy_score_device(eng, k_steps, branches, gamma, nullptr, (const double *)(d + o_rew), (const uint8_t *)(d + o_term),
+                                (const uint8_t *)(d + o_trunc), (double *)(d + o_ret), nullptr, nullptr, (int32_t *)(d + o_bb)))
+    return rc;
+  if (reward) HWY_HIP(eng, hipMemcpyAsync(reward, d + o_rew, K * n_row * 8, hipMemcpyDeviceToHost, eng->stream));
+  if (terminated) HWY_HIP(eng, hipMemcpyAsync(terminated, d + o_term, K * EB, hipMemcpyDeviceToHost, eng->stream));
+  if (truncated) HWY_HIP(eng, hipMemcpyAsync(truncated, d + o_trunc, K * EB, hipMemcpyDeviceToHost, eng->stream));
+  if (ret) HWY_HIP(eng, hipMemcpyAsync(ret, d + o_ret, n_row * 8, hipMemcpyDeviceToHost, eng->stream));
+  if (best_branch) HWY_HIP(eng, hipMemcpyAsync(best_branch, d + o_bb, E * A * 4, hipMemcpyDeviceToHost, eng->stream));
+  HWY_HIP(eng, hipStreamSynchronize(eng->stream));
+  return HWY_OK;
+}
+
+static int cem_check(hwy_engine *src, hwy_engine *work, const hwy_continuous_params *cp, const hwy_cem_params *params, bool has_action,
+                     const char *who) {
+  if (!src) return HWY_ERR_INVALID_ARG;
+  if (!work) return fail(src, HWY_ERR_INVALID_ARG, std::string(who) + ": work is NULL");
+  if (src == work) return fail(src, HWY_ERR_INVALID_ARG, std::string(who) + ": src and work must be two engines");
+  const char *why = "";
+  if (const int rc = hwy::cem_validate(src->cfg, work->cfg, cp, params, has_action, &why)) return fail(src, rc, std::string(who) + ": " + why);
+  if (work->autoreset) return fail(src, HWY_ERR_INVALID_ARG, std::string(who) + ": work must run with auto-reset off");
+  if (work->device != src->device) return fail(src, HWY_ERR_INVALID_ARG, std::string(who) + ": the two engines are on different devices");
+  return HWY_OK;
+}
+
+// the block of `work` that holds the planner's arrays: actions f32 [K][EB][size], the rollout's reward f64 [K][EB] | obs | terminated |
+// truncated [K][EB], ret f64 [EB], mean | std f64 [E][K][size], best_return f64 [E], best_sequence f32 [E][K][size], then the host
+// form's: init_mean f64 [E][K][size], action f32 [E][size], noise f64 | samples f32 [I][E][B][K][size] | elites i32 [I][E][M] (when
+// asked for)
+struct CemLayout {
+  size_t act, rew, obs, term, trunc, ret, mean, sd, best_ret, best_seq, init_mean, action, noise, samples, elites, total;
+};
+static CemLayout cem_layout(const hwy_engine *work, size_t E, size_t B, size_t K, size_t size, size_t I, size_t M, bool debug) {
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t EB = E * B, cols = E * K * size, dbg = debug ? I * EB * K * size : 0;
+  CemLayout l;
+  l.act = 0; l.rew = up(K * EB * size * 4); l.obs = l.rew + up(K * EB * 8); l.term = l.obs + up(K * num_obs_floats(work->cfg) * 4);
+  l.trunc = l.term + up(K * EB); l.ret = l.trunc + up(K * EB); l.mean = l.ret + up(EB * 8); l.sd = l.mean + up(cols * 8);
+  l.best_ret = l.sd + up(cols * 8); l.best_seq = l.best_ret + up(E * 8); l.init_mean = l.best_seq + up(cols * 4);
+  l.action = l.init_mean + up(cols * 8); l.noise = l.action + up(E * size * 4); l.samples = l.noise + up(dbg * 8);
+  l.elites = l.samples + up(dbg * 4);
+  l.total = l.elites + up(debug ? I * E * M * 4 : 0);
+  return l;
+}
+static int cem_block(hwy_engine *src, hwy_engine *work, const CemLayout &l) {
+  if (l.total <= work->cem_bytes) return HWY_OK;
+  HWY_HIP(src, hipStreamSynchronize(work->stream));  // (a smaller block may still be in use)
+  if (work->d_cem) (void)hipFree(work->d_cem);
+  work->d_cem = nullptr;
+  work->cem_bytes = 0;
+  HWY_HIP(src, hipMalloc((void **)&work->d_cem, l.total));
+  work->cem_bytes = l.total;
+  return HWY_OK;
+}
+
+extern "C" int hwy_cem_plan_device(hwy_engine *src, hwy_engine *work, const hwy_continuous_params *params, const hwy_cem_params *cem,
+                                   const double *d_init_mean, float *d_action, double *d_best_return, double *d_mean, double *d_std,
+                                   float *d_best_sequence, double *d_noise, float *d_samples, int32_t *d_elites) {
+  if (int rc = cem_check(src, work, params, cem, d_action != nullptr, "hwy_cem_plan_device")) return rc;
+  HWY_HIP(src, hipSetDevice(src->device));
+  const size_t E = src->cfg.num_envs, B = cem->population, K = cem->horizon, size = hwy::act_size(*params), I = cem->iterations;
+  // (a block laid out for the host form's debug arrays stays valid: the planner's own arrays come first in either layout)
+  const CemLayout l = cem_layout(work, E, B, K, size, I, (size_t)cem->elites, false);
+  if (int rc = cem_block(src, work, l)) return rc;
+  char *d = work->d_cem;
+  const hwy::CemArrays a = {(float *)(d + l.act), d_init_mean, d_mean ? d_mean : (double *)(d + l.mean), d_std ? d_std : (double *)(d + l.sd),
+                            d_noise, d_samples, d_best_return ? d_best_return : (double *)(d + l.best_ret),
+                            d_best_sequence ? d_best_sequence : (float *)(d + l.best_seq), d_action, d_elites};
+  const hwy::CemParams p = hwy::cem_params(*cem, *params, (int32_t)E, a, (const double *)(d + l.ret));
+  // the operations of hwy_cem.h's sequence, all on work's stream (the fork orders it behind src's); a failure of a call on `work` is
+  // reported on `src`, the engine the caller asks
+  struct Ops {
+    hwy_engine *src, *work;
+    const hwy_continuous_params *cp;
+    double gamma;
+    char *d;
+    CemLayout l;
+    int sample(const hwy::CemParams &p) {
+      HWY_HIP(src, hwy::launch_cem_sample(p, work->stream));
+      return HWY_OK;
+    }
+    int fork(int32_t branches) { return opd_forward(src, work, hwy_fork_device(work, src, branches, nullptr)); }
+    int rollout(int32_t k_steps) {
+      return opd_forward(src, work, hwy_rollout_continuous_device(work, cp, k_steps, (const float *)(d + l.act), (float *)(d + l.obs),
+                                                                  (double *)(d + l.rew), (uint8_t *)(d + l.term), (uint8_t *)(d + l.trunc),
+                                                                  nullptr, nullptr));
+    }
+    int score(int32_t k_steps, int32_t branches) {
+      return opd_forward(src, work, hwy_score_device(work, k_steps, branches, gamma, nullptr, (const double *)(d + l.rew),
+                                                     (const uint8_t *)(d + l.term), (const uint8_t *)(d + l.trunc), (double *)(d + l.ret),
+                                                     nullptr, nullptr, nullptr));
+    }
+    int refit(const hwy::CemParams &p) {
+      HWY_HIP(src, hwy::launch_cem_refit(p, work->stream));
+      return HWY_OK;
+    }
+  };
+  if (int rc = opd_forward(src, work, stream_after(work, src))) return rc;  // (d_init_mean may come from src's stream)
+  if (int rc = hwy::cem_iterate(p, Ops{src, work, params, cem->gamma, d, l})) return rc;
+  return stream_after(src, work);  // the parent is not stepped before the last fork has read it, nor the action read before it is written
+}
+
+extern "C" int hwy_cem_plan(hwy_engine *src, hwy_engine *work, const hwy_continuous_params *params, const hwy_cem_params *cem,
+                            const double *init_mean, float *action, double *best_return, double *mean, double *stddev,
+                            float *best_sequence, double *noise, float *samples, int32_t *elites) {
+  static const char *who = "hwy_cem_plan";
+  if (int rc = cem_check(src, work, params, cem, action != nullptr, who)) return rc;
+  const size_t E = src->cfg.num_envs, B = cem->population, K = cem->horizon, size = hwy::act_size(*params), I = cem->iterations;
+  const size_t cols = E * K * size, dbg = I * E * B * K * size;
+  if (init_mean && !hwy::cem_all_finite(init_mean, cols)) return fail(src, HWY_ERR_ACTION, std::string(who) + ": init_mean must be finite");
+  HWY_HIP(src, hipSetDevice(src->device));
+  const CemLayout l = cem_layout(work, E, B, K, size, I, (size_t)cem->elites, noise || samples || elites);
+  if (int rc = cem_block(src, work, l)) return rc;
+  char *d = work->d_cem;
+  if (init_mean) HWY_HIP(src, hipMemcpyAsync(d + l.init_mean, init_mean, cols * 8, hipMemcpyHostToDevice, work->stream));
+  if (int rc = hwy_cem_plan_device(src, work, params, cem, init_mean ? (const double *)(d + l.init_mean) : nullptr, (float *)(d + l.action),
+                                   (double *)(d + l.best_ret), (double *)(d + l.mean), (double *)(d + l.sd), (float *)(d + l.best_seq),
+                                   noise ? (double *)(d + l.noise) : nullptr, samples ? (float *)(d + l.samples) : nullptr,
+                                   elites ? (int32_t *)(d + l.elites) : nullptr))
+    return rc;
+  HWY_HIP(src, hipMemcpyAsync(action, d + l.action, E * size * 4, hipMemcpyDeviceToHost, work->stream));
+  if (best_return) HWY_HIP(src, hipMemcpyAsync(best_return, d + l.best_ret, E * 8, hipMemcpyDeviceToHost, work->stream));
+  if (mean) HWY_HIP(src, hipMemcpyAsync(mean, d + l.mean, cols * 8, hipMemcpyDeviceToHost, work->stream));
+  if (stddev) HWY_HIP(src, hipMemcpyAsync(stddev, d + l.sd, cols * 8, hipMemcpyDeviceToHost, work->stream));
+  if (best_sequence) HWY_HIP(src, hipMemcpyAsync(best_sequence, d + l.best_seq, cols * 4, hipMemcpyDeviceToHost, work->stream));
+  if (noise) HWY_HIP(src, hipMemcpyAsync(noise, d + l.noise, dbg * 8, hipMemcpyDeviceToHost, work->stream));
+  if (samples) HWY_HIP(src, hipMemcpyAsync(samples, d + l.samples, dbg * 4, hipMemcpyDeviceToHost, work->stream));
+  if (elites) HWY_HIP(src, hipMemcpyAsync(elites, d + l.elites, I * E * (size_t)cem->elites * 4, hipMemcpyDeviceToHost, work->stream));
+  HWY_HIP(src, hipStreamSynchronize(work->stream));
+  return HWY_OK;
 }
 
 extern "C" int hwy_sync(hwy_engine *eng) {

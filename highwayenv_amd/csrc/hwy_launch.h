@@ -1,6 +1,6 @@
 // hwy_launch.h -- host-visible launch functions of the kernels in hwy_kernels.hip, hwy_kernels_linear.hip and
 // hwy_kernels_direct.hip: one overload per kernel family, chosen by the type of its parameter struct; and of the add-on units
-// (hwy_kernels_lidar.hip, _ttc.hip, _lookahead.hip, _opd.hip, _mask.hip, _act.hip).  Each is the shared selection layer (hwy_launch_family.h,
+// (hwy_kernels_lidar.hip, _ttc.hip, _lookahead.hip, _opd.hip, _mask.hip, _act.hip, _cem.hip).  Each is the shared selection layer (hwy_launch_family.h,
 // hwy_launch_rules.h; the add-on units: hwy_launch_units.h) with the HIP backend below.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -15,6 +15,7 @@
 #include "hwy_opd.h"
 #include "hwy_mask.h"
 #include "hwy_act.h"
+#include "hwy_cem.h"
 #include "hwy_same_step.h"
 #include "hwy_launch_units.h"
 
@@ -110,6 +111,10 @@ hipError_t launch_mask(const MaskParams &mp, hipStream_t stream);
 // ContinuousAction.act into the stored controls of a direct-control engine (hwy_act.h, hwy_kernels_act.hip: one thread per (environment,
 // agent), row r of ap.actions -> ap.ctl_accel[r], ap.ctl_steer[r])
 hipError_t launch_act_continuous(const ActParams &ap, hipStream_t stream);
+// The CEM planner's two kernels (hwy_cem.h, hwy_kernels_cem.hip): the samples of iteration cp.iter (one thread per (environment, branch,
+// step)) and the refit behind the score kernel (cp.E wavefronts)
+hipError_t launch_cem_sample(const CemParams &cp, hipStream_t stream);
+hipError_t launch_cem_refit(const CemParams &cp, hipStream_t stream);
 // SameStep stash (hwy_same_step.h, hwy_kernels_final.hip: one workgroup per environment, the rows of those that ended -> the final planes)
 hipError_t launch_final(const FinalParams &fp, hipStream_t stream);
 hipError_t launch_math_probe(int op, const double *in, double *out, long long n, hipStream_t stream);

@@ -1,6 +1,6 @@
 // hwy_launch_units.h -- arguments -> (precondition check, kernel instantiation, grid, block, LDS) of the add-on kernel units beside
 // the step kernels -- the Lidar trace (hwy_lidar.h), the TTC grid and planner (hwy_ttc.h), fork and score (hwy_lookahead.h), the OPD
-// tree (hwy_opd.h), the action mask (hwy_mask.h) and the continuous action (hwy_act.h) -- written ONCE for the product and for the
+// tree (hwy_opd.h), the action mask (hwy_mask.h), the continuous action (hwy_act.h) and the CEM planner (hwy_cem.h) -- written ONCE for the product and for the
 // CPU emulation of tests/emu, like hwy_launch_family.h for the step families.  Host code only, generic over the thing that launches: a backend B with one member
 //   B::launch_plain(kernel, grid, block, lds, stream, args)   enqueue / run the kernel; no dispatch timestamps (those of
 //                                                             hwy_profile_* belong to the step kernel)
@@ -105,6 +105,30 @@ template <typename B> hipError_t select_act_continuous(const ActParams &ap, hipS
     return hipErrorInvalidValue;
   const int blocks = (ap.rows + HWY_ACT_BLOCK - 1) / HWY_ACT_BLOCK;
   return B::launch_plain(hwy_act_continuous_kernel<HWY_ACT_BLOCK>, blocks, HWY_ACT_BLOCK, 0, stream, ap);
+}
+}  // namespace hwy
+#endif
+
+// ---- CEM planner (hwy_cem.h): the sample kernel, one thread per (environment, branch, step) of iteration cp.iter, and the refit, one
+// wavefront per environment behind the score kernel that wrote cp.ret -------------------------------------------------------------------
+#if defined(HWY_CEM_BLOCK) && !defined(HWY_LAUNCH_CEM_UNIT)
+#define HWY_LAUNCH_CEM_UNIT
+namespace hwy {
+inline bool cem_shape_ok(const CemParams &cp) {
+  return cp.E >= 1 && cp.B >= 1 && cp.B <= HWY_CEM_MAX_POP && cp.K >= 1 && cp.K <= HWY_CEM_MAX_HORIZON && (cp.size == 1 || cp.size == 2) &&
+         cp.M >= 1 && cp.M <= cp.B && cp.I >= 1 && cp.I <= HWY_CEM_MAX_ITERATIONS && cp.iter >= 0 && cp.iter < cp.I &&
+         (long long)cp.E * cp.B <= 0x7fffffffll && cp.actions && cp.mean && cp.stddev;
+}
+template <typename B> hipError_t select_cem_sample(const CemParams &cp, hipStream_t stream) {
+  if (!cem_shape_ok(cp)) return hipErrorInvalidValue;
+  const long long threads = (long long)cp.E * cp.B * cp.K;
+  const long long blocks = (threads + HWY_CEM_BLOCK - 1) / HWY_CEM_BLOCK;
+  if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
+  return B::launch_plain(hwy_cem_sample_kernel<HWY_CEM_BLOCK>, (unsigned)blocks, HWY_CEM_BLOCK, 0, stream, cp);
+}
+template <typename B> hipError_t select_cem_refit(const CemParams &cp, hipStream_t stream) {
+  if (!cem_shape_ok(cp) || !cp.ret || !cp.best_return || !cp.best_sequence || !cp.action) return hipErrorInvalidValue;
+  return B::launch_plain(hwy_cem_refit_kernel<HWY_CEM_MAX_POP>, cp.E, 64, 0, stream, cp);
 }
 }  // namespace hwy
 #endif

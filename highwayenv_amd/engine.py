@@ -376,6 +376,54 @@ class Engine:
             vp(d_final_info_speed or None), vp(d_final_info_crashed or None), vp(d_final_mask or None), vp(d_action_mask or None),
             vp(d_final_action_mask or None)))
 
+    # -- the float door into fork / rollout / score, and the CEM planner on it (csrc/hwy_cem.h) ----------
+    def score_rollout_continuous(self, params: _abi.HwyContinuousParams, actions, branches: int, gamma: float = 1.0) -> dict:
+        """hwy_score_rollout_continuous (host arrays): float actions [K, E*branches, A, size] are rolled out from the current state
+        (K act + step launch pairs) and folded.  Returns ``reward`` [K, E*branches, A], ``terminated`` / ``truncated``
+        [K, E*branches], ``returns`` [E, branches, A] and ``best_branch`` [E, A].  ValueError for a non-finite component."""
+        a = self._continuous_actions(params, actions, lead=(-1,))
+        K, EB, A, B = a.shape[0], self.E, self.A, int(branches)
+        if B < 1 or EB % B:
+            raise ValueError(f"score_rollout_continuous: branches={B} does not divide the engine's {EB} environments")
+        E = EB // B
+        out = {"reward": np.empty((K, EB, A), np.float64), "terminated": np.empty((K, EB), np.uint8),
+               "truncated": np.empty((K, EB), np.uint8), "returns": np.empty((E, B, A), np.float64),
+               "best_branch": np.empty((E, A), np.int32)}
+        self._check_continuous(self._lib.hwy_score_rollout_continuous(self._h, C.byref(params), K, B, float(gamma), _ptr(a), *(
+            _ptr(out[k]) for k in ("reward", "terminated", "truncated", "returns", "best_branch"))))
+        out["terminated"], out["truncated"] = out["terminated"].astype(bool), out["truncated"].astype(bool)
+        return out
+
+    def cem_plan(self, work: "Engine", params: _abi.HwyContinuousParams, cem: _abi.HwyCemParams, init_mean=None, debug: bool = False) -> dict:
+        """hwy_cem_plan (host arrays): ``action`` f32 [E, size], ``best_return`` f64 [E], ``mean`` / ``std`` f64 [E, K, size],
+        ``best_sequence`` f32 [E, K, size] and, with ``debug``, ``noise`` f64 / ``samples`` f32 [I, E, B, K, size] and ``elites`` int32 [I, E, M].  ``work``: an
+        engine of E * population environments, auto-reset off.  ``init_mean``: f64 [E, K, size] or None (zeros); ValueError for a
+        non-finite entry."""
+        E, B, K, I, size = self.E, cem.population, cem.horizon, cem.iterations, params.size
+        im = None
+        if init_mean is not None:
+            im = np.ascontiguousarray(init_mean, dtype=np.float64)
+            if im.shape != (E, K, size):
+                raise ValueError(f"cem_plan: init_mean has shape {im.shape}, this search needs {(E, K, size)}")
+        out = {"action": np.empty((E, size), np.float32), "best_return": np.empty(E, np.float64), "mean": np.empty((E, K, size), np.float64),
+               "std": np.empty((E, K, size), np.float64), "best_sequence": np.empty((E, K, size), np.float32),
+               "noise": np.empty((I, E, B, K, size), np.float64) if debug else None,
+               "samples": np.empty((I, E, B, K, size), np.float32) if debug else None,
+               "elites": np.empty((I, E, cem.elites), np.int32) if debug else None}
+        self._check_continuous(self._lib.hwy_cem_plan(self._h, work._h, C.byref(params), C.byref(cem), _ptr(im), *(
+            _ptr(out[k]) for k in ("action", "best_return", "mean", "std", "best_sequence", "noise", "samples", "elites"))))
+        return out
+
+    def cem_plan_device(self, work: "Engine", params: _abi.HwyContinuousParams, cem: _abi.HwyCemParams, d_action: int,
+                        d_init_mean: int = 0, d_best_return: int = 0, d_mean: int = 0, d_std: int = 0, d_best_sequence: int = 0,
+                        d_noise: int = 0, d_samples: int = 0, d_elites: int = 0):
+        """Enqueue hwy_cem_plan_device on raw device pointers; does not synchronise."""
+        vp = C.c_void_p
+        self._check_continuous(self._lib.hwy_cem_plan_device(
+            self._h, work._h, C.byref(params), C.byref(cem), vp(d_init_mean or None), vp(d_action or None), vp(d_best_return or None),
+            vp(d_mean or None), vp(d_std or None), vp(d_best_sequence or None), vp(d_noise or None), vp(d_samples or None),
+            vp(d_elites or None)))
+
     # -- reset --------------------------------------------------------------------------------
     def reset(self, seeds=None, mask=None, ego_spacing=2.0, vehicles_density=1.0, initial_lane_id=-1, base_seed=0):
         """Device-side spawn (counter-based RNG; NOT numpy's stream -- see spawn.py for that)."""

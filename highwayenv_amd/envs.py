@@ -129,6 +129,7 @@ class BatchedHighwayEnv:
         self._np_randoms = [None] * self.num_envs  # per-env Generator == reference env.np_random
         self.time = np.zeros(self.num_envs)
         self.steps = 0
+        self._cem_decisions = 0  # plan_cem(seed=None) calls since reset()
         self._define_spaces()
 
     @property
@@ -224,6 +225,7 @@ class BatchedHighwayEnv:
         self._episodes = np.zeros(E, np.uint64)
         self.time[:] = 0
         self.steps = 0
+        self._cem_decisions = 0
         st = eng.get_state()
         rows, ego = np.arange(E), self._ego_slots(st)
         info = {"speed": st["speed"][rows, ego].copy(), "crashed": (st["flags"][rows, ego] & _abi.F_CRASHED) != 0,
@@ -647,6 +649,110 @@ class BatchedHighwayEnv:
             return out["action"]
         return out["action"], {k: out[k] for k in ("value", "upper", "sequence", "expanded")}
 
+    # ---- score_sequences_continuous / plan_cem: the planning seam for continuous control (csrc/hwy_cem.h) -------------------------
+    def _continuous_sequences(self, actions, size: int) -> np.ndarray:
+        """``actions`` [B, K(, A), size] or [E, B, K(, A), size] -> float32 [E, B, K, A, size] (a float64 array is ROUNDED first)."""
+        E, A = self.num_envs, self._hcfg.num_agents
+        a = np.asarray(actions, np.float32)
+        want = f"[B, K{', A' if A > 1 else ''}, {size}] or [E, B, K{', A' if A > 1 else ''}, {size}]"
+        if a.ndim < 3 or a.shape[-1] != size:
+            raise ValueError(f"continuous action sequences must have shape {want}; got {a.shape}")
+        if A == 1 and a.ndim in (3, 4):
+            a = a[..., None, :]
+        elif not (a.ndim in (4, 5) and a.shape[-2] == A):
+            raise ValueError(f"continuous action sequences must have shape {want}; got {a.shape}")
+        if a.ndim == 4:
+            a = np.broadcast_to(a, (E, *a.shape))
+        if a.ndim != 5 or a.shape[0] != E or a.shape[1] < 1 or a.shape[2] < 1:
+            raise ValueError(f"continuous action sequences for {E} environments needed (with at least one branch and one step); got {np.shape(actions)}")
+        return a
+
+    def score_sequences_continuous(self, actions, gamma: float = 1.0, return_details: bool = False):
+        """``score_sequences`` for the reference's ``ContinuousAction``: B candidate sequences of K float actions (throttle,
+        steering in [-1, 1]; float32 ``[B, K, size]`` or ``[E, B, K, size]``, an agent axis before ``size`` for several agents,
+        validated like ``step_continuous``) are stepped from the CURRENT state with the true simulator -- fork ->
+        ``hwy_rollout_continuous_device`` -> ``hwy_score_device`` -- and their discounted returns f64 [E, B] ([E, B, A]) come
+        back.  An episode that ends within a sequence is absorbing.  This environment is left exactly as it was.
+        ``return_details``: also ``reward`` [E, B, K(, A)], ``terminated`` / ``truncated`` [E, B, K] and ``best_branch`` [E(, A)]
+        (a float sequence has no first action id: no ``q``, no ``best_action``).  NotImplementedError outside the highway ids
+        and on a ``DiscreteMetaAction`` ego."""
+        params = self.continuous_params()
+        self._lookahead_scope("score_sequences_continuous")
+        if not np.isfinite(gamma):
+            raise ValueError("gamma must be finite")
+        a = self._continuous_sequences(actions, params.size)
+        E, B, K, A, size = a.shape
+        self._lookahead_fits(E * B, K)
+        child = self.fork(B)
+        out = child._engine.score_rollout_continuous(params, np.ascontiguousarray(a.transpose(2, 0, 1, 3, 4)).reshape(K, E * B, A, size), B, gamma)
+        returns = out["returns"] if A > 1 else out["returns"][:, :, 0]
+        if not return_details:
+            return returns
+        reward = out["reward"].reshape(K, E, B, A).transpose(1, 2, 0, 3)
+        return returns, {"reward": reward if A > 1 else reward[..., 0],
+                         "terminated": out["terminated"].reshape(K, E, B).transpose(1, 2, 0),
+                         "truncated": out["truncated"].reshape(K, E, B).transpose(1, 2, 0),
+                         "best_branch": out["best_branch"] if A > 1 else out["best_branch"][:, 0]}
+
+    def _cem_setup(self, population, elites, iterations, horizon, gamma, init_std, min_std, alpha, seed, debug=False):
+        """(continuous params, cem params, work) of ``plan_cem``: the checks, then the cached child of E * population environments."""
+        cp = self.continuous_params()
+        self._lookahead_scope("plan_cem")
+        if self._hcfg.num_agents > 1:
+            raise NotImplementedError("plan_cem plans for a single agent (joint searches are outside the MI355X hot-path scope): "
+                                      "score_sequences_continuous serves several agents")
+        if seed is None:  # successive decisions draw different noise; an explicit seed is used as given
+            seed = self._cem_default_seed()
+        cem = _abi.cem_params(population, elites, iterations, horizon, gamma, init_std, min_std, alpha, seed)
+        E = self.num_envs
+        n = E * cem.population
+        need, limit = _abi.cem_bytes(self._hcfg, E, cem, cp.size, debug), getattr(self, "max_fork_bytes", None)
+        if n > 2 ** 31 - 1 or (limit is not None and need > limit):
+            raise ValueError(f"{n} branch environments need {need} bytes of device memory"
+                             + (f" (max_fork_bytes = {limit})" if limit is not None else " and more than 2^31 - 1 environments"))
+        return cp, cem, self._fork_child(("cem", n), n, "plan_cem")
+
+    def _cem_default_seed(self) -> int:
+        """The Philox key of a ``plan_cem(seed=None)``: hashed from the seed of ``reset()``, the env's step count and the number of
+        default-seed decisions since ``reset()`` -- the last because the device-pointer fronts (``HighwayVectorEnv`` with
+        ``output="torch"``) step the engine without passing through ``step`` here, so the step count alone would stand still."""
+        key = (int(getattr(self, "_same_step_entropy", 0)) & (2 ** 64 - 1), int(self.steps), self._cem_decisions)
+        self._cem_decisions += 1
+        return int(np.random.SeedSequence(key).generate_state(1, np.uint64)[0])
+
+    def _cem_init_mean(self, init_mean, K: int, size: int):
+        if init_mean is None:
+            return None
+        m = np.asarray(init_mean, np.float64)
+        if m.shape == (K, size):
+            m = np.broadcast_to(m, (self.num_envs, K, size))
+        if m.shape != (self.num_envs, K, size):
+            raise ValueError(f"init_mean must have shape ({K}, {size}) or ({self.num_envs}, {K}, {size}); got {m.shape}")
+        if not np.isfinite(m).all():
+            raise ValueError("init_mean must be finite")
+        return np.ascontiguousarray(m)
+
+    def plan_cem(self, population: int = 64, elites: int = 8, iterations: int = 3, horizon: int = 8, gamma: float = 0.9,
+                 init_std: float = 0.5, min_std: float = 0.05, alpha: float = 1.0, seed: int | None = None, init_mean=None,
+                 return_details: bool = False, debug: bool = False):
+        """Sampling MPC for a continuous ego: the first action float32 [E, size] of a cross-entropy-method search of every
+        environment, entirely on the device (``hwy_cem_plan``; DESIGN.md "CEM on the device" states the rules).  Per iteration
+        ``population`` sequences of ``horizon`` actions are drawn around the current mean (branch 0 IS the mean), stepped from the
+        current state with the TRUE simulator, and mean and std are refitted to the ``elites`` best; the best sequence seen over
+        all iterations gives the action.  ``seed=None``: derived from the seed of ``reset()``, the env's step count and the number
+        of default-seed decisions since ``reset()``, so that successive decisions do not reuse noise on any front end; an explicit ``seed`` is used as given (same seed, same plan).  ``init_mean``:
+        f64 [K, size] or [E, K, size] -- shift the returned ``mean`` by one step and pass it back to warm-start.  This environment
+        is left exactly as it was.  ``return_details``: also a dict with ``best_return`` f64 [E], ``best_sequence`` f32
+        [E, K, size], ``mean`` / ``std`` f64 [E, K, size]; with ``debug`` also ``noise`` f64 / ``samples`` f32 [I, E, B, K, size] and
+        ``elites`` int32 [I, E, M] (every iteration's elite branches, ascending).
+        Single agent, ``DiscreteAction`` config, highway ids; NotImplementedError otherwise."""
+        cp, cem, work = self._cem_setup(population, elites, iterations, horizon, gamma, init_std, min_std, alpha, seed, debug)
+        out = self._engine.cem_plan(work._engine, cp, cem, self._cem_init_mean(init_mean, cem.horizon, cp.size), debug=debug)
+        if not return_details:
+            return out["action"]
+        keys = ("best_return", "best_sequence", "mean", "std") + (("noise", "samples", "elites") if debug else ())
+        return out["action"], {k: out[k] for k in keys}
+
     def close(self) -> None:
         for child in self.__dict__.pop("_forks", {}).values():
             child.close()
@@ -873,6 +979,14 @@ class _SingleEnvMixin:
         obs, reward, term, trunc, info = super().step_continuous(a.reshape(1, self._hcfg.num_agents, -1))
         return (obs[0], float(reward[0]), bool(term[0]), bool(trunc[0]),
                 {"speed": float(info["speed"][0]), "crashed": bool(info["crashed"][0]), "action": a, "rewards": self.rewards(0)})
+
+    def plan_cem(self, *args, **kwargs):
+        """``BatchedHighwayEnv.plan_cem`` of the one environment: the action float32 (size,) -- what ``step_continuous`` takes -- and,
+        with ``return_details``, the details without their environment axis (``noise`` / ``samples``: [I, B, K, size], ``elites``: [I, M])."""
+        out = super().plan_cem(*args, **kwargs)
+        if not isinstance(out, tuple):
+            return out[0]
+        return out[0][0], {k: (v[:, 0] if k in ("noise", "samples", "elites") else v[0]) for k, v in out[1].items()}
 
     def to_finite_mdp(self):
         """``AbstractEnv.to_finite_mdp()`` (abstract.py:452-453): horizon 10 s, time step ``1 / policy_frequency``."""

@@ -32,7 +32,9 @@ environments are ONE engine (one kernel launch per step), and this class gives t
 * ``continuous=True`` (an env configured with ``DiscreteAction``): the reference's ``ContinuousAction`` -- ``single_action_space`` is
   ``Box(-1, 1, (size,), float32)`` and ``step`` / ``step_async`` / ``rollout`` take float actions [E(, A), size] (throttle, steering),
   mapped onto the configured ranges by a kernel of its own (csrc/hwy_act.h) in front of the engine's step; every output and every
-  autoreset mode as with ids.  A policy network's float32 device tensor goes to the kernel as it is.
+  autoreset mode as with ids.  A policy network's float32 device tensor goes to the kernel as it is.  ``plan_cem(...)`` plans such
+  actions by the cross-entropy method on the device (csrc/hwy_cem.h); with ``output="torch"`` ``env.step(env.plan_cem())`` never
+  leaves the GPU.
 
 With gymnasium installed the class IS a ``gymnasium.vector.VectorEnv``; without it (this image) the same attributes exist on a
 plain object.
@@ -477,6 +479,60 @@ class HighwayVectorEnv(_Base):
         if not return_details:
             return d["action"]
         return d["action"], {k: d[k] for k in ("value", "upper", "sequence", "expanded")}
+
+    def plan_cem(self, population: int = 64, elites: int = 8, iterations: int = 3, horizon: int = 8, gamma: float = 0.9,
+                 init_std: float = 0.5, min_std: float = 0.05, alpha: float = 1.0, seed: int | None = None, init_mean=None,
+                 return_details: bool = False, debug: bool = False):
+        """``BatchedHighwayEnv.plan_cem``: the first action float32 [E, size] of a cross-entropy-method search of every environment
+        (``continuous=True``).  ``output="torch"``: the device tensor the refit kernel wrote (and, with ``return_details``, device
+        tensors ``best_return``, ``best_sequence``, ``mean``, ``std``; all valid until the next call of that shape), ordered on the
+        current stream like ``plan()`` -- the whole search is enqueued by one ``hwy_cem_plan_device`` call and
+        ``env.step(env.plan_cem())`` never leaves the GPU.  ``init_mean``: a float64 array or device tensor [K, size] or
+        [E, K, size]; a device tensor is not validated.  ``debug``: the details also hold ``noise`` f64 / ``samples`` f32
+        [I, E, B, K, size] and ``elites`` int32 [I, E, M].  ``seed=None`` draws a new Philox key per decision (the env counts them),
+        although this path steps the engine without advancing the env's step count."""
+        if not self.continuous:
+            raise ValueError("plan_cem needs continuous=True (an env configured with {'type': 'DiscreteAction'})")
+        if self.output != "torch":
+            return self.env.plan_cem(population, elites, iterations, horizon, gamma, init_std, min_std, alpha, seed, init_mean,
+                                     return_details=return_details, debug=debug)
+        t, E, env = self._torch, self.num_envs, self.env
+        cp, cem, work = env._cem_setup(population, elites, iterations, horizon, gamma, init_std, min_std, alpha, seed, debug)
+        if self._dev is None:
+            raise RuntimeError("plan_cem() before reset()")
+        K, size, dev = cem.horizon, cp.size, self._dev["obs"].device
+        key = ("cem", K)
+        if key not in self._dev:
+            self._dev[key] = {"action": t.empty((E, size), dtype=t.float32, device=dev), "best_return": t.empty(E, dtype=t.float64, device=dev),
+                              "mean": t.empty((E, K, size), dtype=t.float64, device=dev), "std": t.empty((E, K, size), dtype=t.float64, device=dev),
+                              "best_sequence": t.empty((E, K, size), dtype=t.float32, device=dev)}
+        d = self._dev[key]
+        dbg = {}
+        if debug:  # (allocated per call: a test's door, not the hot path)
+            shape = (cem.iterations, E, cem.population, K, size)
+            dbg = {"noise": t.empty(shape, dtype=t.float64, device=dev), "samples": t.empty(shape, dtype=t.float32, device=dev),
+                   "elites": t.empty((cem.iterations, E, cem.elites), dtype=t.int32, device=dev)}
+        im = None
+        if init_mean is not None:
+            if isinstance(init_mean, t.Tensor):
+                im = init_mean.to(device=dev, dtype=t.float64)
+                im = (im.unsqueeze(0).expand(E, K, size) if im.dim() == 2 else im).reshape(E, K, size).contiguous()
+            else:
+                im = t.from_numpy(env._cem_init_mean(init_mean, K, size)).to(dev)
+        cur = t.cuda.current_stream()
+        same = cur.cuda_stream == self._stream.cuda_stream
+        if not same:
+            self._stream.wait_stream(cur)      # the consumer of the previous plan (and init_mean) comes first
+        env._engine.cem_plan_device(work._engine, cp, cem, d["action"].data_ptr(), 0 if im is None else im.data_ptr(),
+                                    *(d[k].data_ptr() for k in ("best_return", "mean", "std", "best_sequence")),
+                                    *(dbg[k].data_ptr() for k in ("noise", "samples", "elites") if debug))
+        if not same:
+            cur.wait_stream(self._stream)
+            for x in ([im] if im is not None else []) + list(dbg.values()):
+                x.record_stream(self._stream)
+        if not return_details:
+            return d["action"]
+        return d["action"], dict({k: d[k] for k in ("best_return", "best_sequence", "mean", "std")}, **dbg)
 
     # ---- the rest of the interface ----------------------------------------------------------------------------------------------
     @property

@@ -849,6 +849,59 @@ int hwy_rollout_continuous_device(hwy_engine *eng, const hwy_continuous_params *
 int hwy_rollout_continuous(hwy_engine *eng, const hwy_continuous_params *params, int32_t k_steps, const float *actions, float *obs,
                            double *reward, uint8_t *terminated, uint8_t *truncated, double *info_speed, uint8_t *info_crashed);
 
+/*
+ * The float door into fork / rollout / score (additive to ABI v8).  hwy_score_rollout_continuous is the host-pointer twin of
+ * hwy_score_rollout for a HWY_EGO_DIRECT engine: `eng` holds E * branches environments (environment e * branches + b == branch b of
+ * group e, already forked), actions f32 [K][E * branches][A][size] are validated like hwy_rollout_continuous (HWY_ERR_ACTION for a
+ * non-finite component, before anything runs), uploaded, rolled out by hwy_rollout_continuous_device into the engine's rollout block
+ * and folded by hwy_score_device with d_first_action == NULL (a float sequence has no first action id: no q, no best_action).
+ * Outputs (HOST pointers, each may be NULL): reward f64 [K][E * branches][A], terminated / truncated u8 [K][E * branches],
+ * ret f64 [E][branches][A], best_branch i32 [E][A].  Synchronises.  No kernel of its own.
+ */
+int hwy_score_rollout_continuous(hwy_engine *eng, const hwy_continuous_params *params, int32_t k_steps, int32_t branches, double gamma,
+                                 const float *actions, double *reward, uint8_t *terminated, uint8_t *truncated, double *ret,
+                                 int32_t *best_branch);
+
+/*
+ * Sampling MPC by the cross-entropy method, one search per environment, on the device (csrc/hwy_cem.h; DESIGN.md "CEM on the
+ * device").  Per iteration i: hwy_cem_sample_kernel draws `population` sequences of `horizon` float actions around the current mean
+ * (branch 0 IS the mean) into the action block of `work`; hwy_fork_device(work, src, population); hwy_rollout_continuous_device(work,
+ * horizon); hwy_score_device(work, ..., first_action NULL) folds the returns; hwy_cem_refit_kernel refits mean and std to the
+ * `elites` best sequences and keeps the best sequence seen.  Everything is enqueued on work's stream with no host round trip; src's
+ * stream continues behind it.  `work`: an engine of src.num_envs * population environments, same config, same device, auto-reset
+ * off; its planner arrays live in a block of its own, grown on demand.  src is left as it was.
+ * Scope: HWY_SCENARIO_HIGHWAY, HWY_EGO_DIRECT, a single agent (hwy_score_rollout_continuous serves several), every observation type;
+ * HWY_ERR_UNSUPPORTED otherwise, HWY_ERR_INVALID_ARG for parameters outside the caps below, each with a reason in hwy_last_error(src).
+ */
+#define HWY_CEM_MAX_POP 1024    /* population: the keys of one environment's returns in LDS (8 KB) */
+#define HWY_CEM_MAX_HORIZON 64  /* horizon; also the stride of the iteration in the Philox counter */
+#define HWY_CEM_MAX_ITERATIONS 1024
+typedef struct hwy_cem_params {
+  int32_t population; /* B: sequences per iteration, 1 .. HWY_CEM_MAX_POP */
+  int32_t elites;     /* M: 1 .. population */
+  int32_t iterations; /* I: 1 .. HWY_CEM_MAX_ITERATIONS */
+  int32_t horizon;    /* K: 1 .. HWY_CEM_MAX_HORIZON */
+  double gamma;       /* discount of the return, finite */
+  double init_std;    /* std of every component before the first refit, >= 0 */
+  double min_std;     /* floor of the refitted std, >= 0 */
+  double alpha;       /* smoothing: new = alpha * fitted + (1 - alpha) * old, in [0, 1] */
+  uint64_t seed;      /* Philox key */
+} hwy_cem_params;
+/*
+ * hwy_cem_plan_device: DEVICE pointers.  d_init_mean f64 [E][K][size] or NULL (zeros; not validated here).  d_action f32 [E][size]:
+ * step 0 of the best sequence.  Optional (NULL: not written / kept in work's block): d_best_return f64 [E], d_mean / d_std f64
+ * [E][K][size] (after the last refit), d_best_sequence f32 [E][K][size], d_noise f64 / d_samples f32 [I][E][B][K][size] (what the
+ * sample kernel drew and wrote), d_elites i32 [I][E][M] (every iteration's elite branches, ascending).  d_init_mean may be produced
+ * on src's stream: work's stream waits for what src's stream holds before the first sample.  Enqueues and does not synchronise.
+ * hwy_cem_plan: the same through HOST pointers (HWY_ERR_ACTION for a non-finite init_mean, before anything runs); synchronises.
+ */
+int hwy_cem_plan_device(hwy_engine *src, hwy_engine *work, const hwy_continuous_params *params, const hwy_cem_params *cem,
+                        const double *d_init_mean, float *d_action, double *d_best_return, double *d_mean, double *d_std,
+                        float *d_best_sequence, double *d_noise, float *d_samples, int32_t *d_elites);
+int hwy_cem_plan(hwy_engine *src, hwy_engine *work, const hwy_continuous_params *params, const hwy_cem_params *cem,
+                 const double *init_mean, float *action, double *best_return, double *mean, double *stddev, float *best_sequence,
+                 double *noise, float *samples, int32_t *elites);
+
 #ifdef __cplusplus
 }
 #endif
