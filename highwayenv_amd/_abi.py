@@ -302,6 +302,26 @@ def check_finite_mdp_scope(cfg: "HwyConfig") -> None:
                                   "(the reference builds a 5-column reward next to a 3-column transition there)")
 
 
+TTC_OBS_SIDE = 3  # csrc/hwy_collision_obs.h: obs_speeds == obs_lanes == 3 (observation.py:139,147)
+
+
+def ttc_obs_shape(params: HwyTtcParams) -> tuple:
+    """Shape of one agent's TimeToCollision observation: (3, 3, T)."""
+    return (TTC_OBS_SIDE, TTC_OBS_SIDE, int(params.time_steps))
+
+
+def check_ttc_observation_scope(cfg: "HwyConfig") -> None:
+    """What the TimeToCollision observation runs on (csrc/hwy_collision_obs.h: ttc_obs_validate, the same rules)."""
+    if cfg.scenario != SCENARIO_HIGHWAY:
+        raise NotImplementedError("the TimeToCollision observation is in the MI355X hot-path scope on the highway scenario only")
+    if cfg.ego_control != EGO_META:
+        raise NotImplementedError("the TimeToCollision observation needs a DiscreteMetaAction ego (a plain Vehicle has no speed_index: "
+                                  "the reference raises there too)")
+    if cfg.num_target_speeds < 2:
+        raise NotImplementedError("the TimeToCollision observation needs at least 2 target speeds (with one, the reference's own "
+                                  "slicing returns shape (2, 3, T))")
+
+
 class HwyOpdParams(C.Structure):
     """hwy_opd_params (include/hwy_engine.h): the budget and discount of the optimistic planner and what follows from them."""
     _fields_ = [("budget", C.c_int32), ("n_ids", C.c_int32), ("nodes", C.c_int32), ("flags", C.c_int32),

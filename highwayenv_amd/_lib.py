@@ -26,6 +26,7 @@ EXPORTS = [
     "hwy_act_continuous_device", "hwy_act_continuous", "hwy_step_continuous_device", "hwy_step_continuous",
     "hwy_step_same_step_continuous_device", "hwy_rollout_continuous_device", "hwy_rollout_continuous",
     "hwy_score_rollout_continuous", "hwy_cem_plan_device", "hwy_cem_plan",
+    "hwy_ttc_observe_device", "hwy_ttc_observe", "hwy_step_same_step_ttc_device", "hwy_rollout_ttc_device",
     "hwy_step_shapes", "hwy_last_step_shape",
 ]
 
@@ -120,6 +121,10 @@ def load() -> C.CDLL:
     cem = C.POINTER(_abi.HwyCemParams)
     lib.hwy_cem_plan_device.argtypes = [vp, vp, cont, cem] + [vp] * 9
     lib.hwy_cem_plan.argtypes = [vp, vp, cont, cem] + [vp] * 9
+    lib.hwy_ttc_observe_device.argtypes = [vp, ttc, vp]
+    lib.hwy_ttc_observe.argtypes = [vp, ttc, vp]
+    lib.hwy_step_same_step_ttc_device.argtypes = [vp, ttc] + [vp] * 13
+    lib.hwy_rollout_ttc_device.argtypes = [vp, ttc, i32] + [vp] * 7
     lib.hwy_step_shapes.argtypes = [i32]
     lib.hwy_last_step_shape.argtypes = []
     lib.hwy_profile_enable.argtypes = [vp, i32]

@@ -11,9 +11,9 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libhwy_engine.so")
-SOURCES = ["hwy_kernels.hip", "hwy_kernels_shapes.hip", "hwy_kernels_linear.hip", "hwy_kernels_direct.hip", "hwy_kernels_lidar.hip", "hwy_kernels_ttc.hip", "hwy_kernels_lookahead.hip", "hwy_kernels_opd.hip", "hwy_kernels_mask.hip", "hwy_kernels_act.hip", "hwy_kernels_cem.hip", "hwy_kernels_final.hip", "hwy_kernels_respawn.hip", "hwy_engine.hip", "hwy_comm.hip"]
+SOURCES = ["hwy_kernels.hip", "hwy_kernels_shapes.hip", "hwy_kernels_linear.hip", "hwy_kernels_direct.hip", "hwy_kernels_lidar.hip", "hwy_kernels_ttc.hip", "hwy_kernels_lookahead.hip", "hwy_kernels_opd.hip", "hwy_kernels_mask.hip", "hwy_kernels_act.hip", "hwy_kernels_cem.hip", "hwy_kernels_collision_obs.hip", "hwy_kernels_final.hip", "hwy_kernels_respawn.hip", "hwy_engine.hip", "hwy_comm.hip"]
 KERNEL_SOURCES = ("hwy_kernels.hip", "hwy_kernels_shapes.hip", "hwy_kernels_linear.hip", "hwy_kernels_direct.hip", "hwy_kernels_lidar.hip", "hwy_kernels_ttc.hip",
-                  "hwy_kernels_lookahead.hip", "hwy_kernels_opd.hip", "hwy_kernels_mask.hip", "hwy_kernels_act.hip", "hwy_kernels_cem.hip", "hwy_kernels_final.hip",
+                  "hwy_kernels_lookahead.hip", "hwy_kernels_opd.hip", "hwy_kernels_mask.hip", "hwy_kernels_act.hip", "hwy_kernels_cem.hip", "hwy_kernels_collision_obs.hip", "hwy_kernels_final.hip",
                   "hwy_kernels_respawn.hip")  # the translation units that hold device code
 import glob
 
@@ -221,8 +221,16 @@ def gfx950_code_objects(blob: bytes) -> list:
 
 
 def kernel_resources(lib_path: str = LIB_PATH) -> dict:
-    """What the compiler allocated to every kernel of the gfx950 code objects inside the built library, read from the code
-    objects' own metadata (NT_AMDGPU_METADATA note: the numbers the hardware dispatcher uses), keyed by demangled kernel name
+    """``kernel_resources_by_unit`` over all code objects (a kernel that several units emit has the same allocation in each)."""
+    out = {}
+    for unit in kernel_resources_by_unit(lib_path):
+        out.update(unit)
+    return out
+
+
+def kernel_resources_by_unit(lib_path: str = LIB_PATH) -> list:
+    """One dict per gfx950 code object of the built library that holds kernels (one per kernel translation unit): what the
+    compiler allocated to every kernel of that code object, read from the code objects' own metadata (NT_AMDGPU_METADATA note: the numbers the hardware dispatcher uses), keyed by demangled kernel name
     without the argument list: ``{"hwy::hwy_step_wave_kernel<3, false>": {"vgpr": 102, "vgpr_spill": 0, "sgpr": 106,
     "sgpr_spill": 76, "lds": 8080, "scratch": 36, "workgroup": 64}, ...}``.  Needs no GPU.  Used by tests/test_kernel_resources.py
     (the occupancy DESIGN.md quotes for each step kernel is a property of the build, checked where the build is checked) and
@@ -234,8 +242,9 @@ def kernel_resources(lib_path: str = LIB_PATH) -> dict:
     objects = gfx950_code_objects(blob)
     if not objects:
         raise RuntimeError(f"{lib_path}: no gfx950 code object in the offload bundle")
-    out = {}
+    units = []
     for co in objects:
+        out = {}
         shoff = struct.unpack_from("<Q", co, 0x28)[0]
         shentsize, shnum = struct.unpack_from("<HH", co, 0x3A)
         meta = None
@@ -261,7 +270,8 @@ def kernel_resources(lib_path: str = LIB_PATH) -> dict:
                 "vgpr": k[".vgpr_count"], "vgpr_spill": k[".vgpr_spill_count"], "sgpr": k[".sgpr_count"],
                 "sgpr_spill": k[".sgpr_spill_count"], "lds": k[".group_segment_fixed_size"],
                 "scratch": k[".private_segment_fixed_size"], "workgroup": k[".max_flat_workgroup_size"]}
-    return out
+        units.append(out)
+    return units
 
 
 if __name__ == "__main__":

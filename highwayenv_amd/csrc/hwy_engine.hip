@@ -71,6 +71,10 @@ struct hwy_engine {
   double *d_plan_q = nullptr;        // [E][A][5]
   // output of the host-pointer form of the action mask (hwy_action_mask), allocated on first use
   uint8_t *d_action_mask = nullptr;  // [E][A][n_ids]
+  // the TimeToCollision entry points (hwy_collision_obs.h), allocated on first use: the step's own observation (the step kernels
+  // keep writing the engine's obs_type, so the shape kernels stay the launch; nobody reads it) and the host form's output
+  float *d_ttc_step_obs = nullptr;  // [E][A][obs_len]
+  float *d_ttc_obs = nullptr;       // [E][A][9 * HWY_MAX_TTC_STEPS]
   // hwy_fork / hwy_fork_device: the uploaded source indices [E] (host form) and the event that orders this engine's stream behind
   // the source engine's, both created on first use
   int32_t *d_fork_src = nullptr;
@@ -536,7 +540,8 @@ extern "C" int hwy_destroy(hwy_engine *eng) {
   void *ptrs[] = {eng->d_f64, eng->d_packed, eng->d_time, eng->d_done, eng->d_episode, eng->d_actions, eng->d_out, eng->d_roll,
                   eng->d_mask, eng->d_seeds, eng->d_grid_ws, eng->d_route, eng->d_road_steps, eng->d_gnet,
                   eng->d_shadow_f64, eng->d_shadow_packed, eng->d_shadow_route, eng->d_shadow_meta, eng->d_counters, eng->d_block_env,
-                  eng->d_behavior, eng->d_controls, eng->d_ttc_grid, eng->d_plan_action, eng->d_plan_q, eng->d_fork_src, eng->d_opd, eng->d_cem, eng->d_action_mask};
+                  eng->d_behavior, eng->d_controls, eng->d_ttc_grid, eng->d_plan_action, eng->d_plan_q, eng->d_fork_src, eng->d_opd, eng->d_cem, eng->d_action_mask,
+                  eng->d_ttc_step_obs, eng->d_ttc_obs};
   for (void *q : ptrs) if (q) (void)hipFree(q);
   if (eng->fork_event) (void)hipEventDestroy(eng->fork_event);
   if (eng->h_pinned) (void)hipHostFree(eng->h_pinned);
@@ -1455,6 +1460,27 @@ extern "C" int hwy_action_mask(hwy_engine *eng, uint8_t *mask) {
 // ---- SameStep autoreset on the device (hwy_same_step.h) -----------------------------------------------------------------------------
 // The body of hwy_step_same_step_device and hwy_step_same_step_continuous_device.  The ids door: d_actions, cp NULL.  The continuous
 // door: cp and d_continuous, d_actions NULL -- the act launch goes first, and the step launch runs with no ids on the pair it stored.
+// What every SameStep door does once its own arguments (the continuous params, the TimeToCollision params) are accepted and before
+// its first launch: hwy_same_step.h's validation, the planes, the mask pointers (what hwy_action_mask_device answers for this
+// engine), the device, room for the timing events.
+static int same_step_begin(hwy_engine *eng, const char *who, const void *d_actions, const float *d_obs, const double *d_reward,
+                           const uint8_t *d_terminated, const uint8_t *d_truncated, const double *d_info_speed, const uint8_t *d_info_crashed,
+                           const float *d_final_obs, const double *d_final_info_speed, const uint8_t *d_final_info_crashed,
+                           const uint8_t *d_final_mask, uint8_t *d_action_mask, uint8_t *d_final_action_mask) {
+  const char *why = "";
+  if (const int rc = hwy::same_step_validate(eng->cfg, eng->autoreset != 0, d_final_obs != nullptr, d_final_mask != nullptr, &why))
+    return fail(eng, rc, std::string(who) + ": " + why);
+  if (!d_actions || !d_obs || !d_reward || !d_terminated || !d_truncated)
+    return fail(eng, HWY_ERR_INVALID_ARG, std::string(who) + ": actions/obs/reward/terminated/truncated must be non-NULL");
+  if ((d_final_info_speed && !d_info_speed) || (d_final_info_crashed && !d_info_crashed))
+    return fail(eng, HWY_ERR_INVALID_ARG, std::string(who) + ": a final info plane needs the info plane it is copied from");
+  if (d_action_mask || d_final_action_mask)
+    if (int rc = mask_check(eng, d_action_mask ? d_action_mask : d_final_action_mask, who)) return rc;
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  if (eng->profiling && eng->events_used >= 65536)
+    if (int rc = drain_events(eng)) return rc;
+  return HWY_OK;
+}
 static int same_step_enqueue(hwy_engine *eng, const char *who, const int32_t *d_actions, const hwy_continuous_params *cp,
                              const float *d_continuous, float *d_obs, double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated,
                              double *d_info_speed, uint8_t *d_info_crashed, float *d_final_obs, double *d_final_info_speed,
@@ -1464,17 +1490,10 @@ static int same_step_enqueue(hwy_engine *eng, const char *who, const int32_t *d_
   const char *why = "";
   if (continuous)
     if (const int rc = hwy::act_validate(eng->cfg, cp, &why)) return fail(eng, rc, std::string(who) + ": " + why);
-  if (const int rc = hwy::same_step_validate(eng->cfg, eng->autoreset != 0, d_final_obs != nullptr, d_final_mask != nullptr, &why))
-    return fail(eng, rc, std::string(who) + ": " + why);
-  if ((continuous ? !d_continuous : !d_actions) || !d_obs || !d_reward || !d_terminated || !d_truncated)
-    return fail(eng, HWY_ERR_INVALID_ARG, std::string(who) + ": actions/obs/reward/terminated/truncated must be non-NULL");
-  if ((d_final_info_speed && !d_info_speed) || (d_final_info_crashed && !d_info_crashed))
-    return fail(eng, HWY_ERR_INVALID_ARG, std::string(who) + ": a final info plane needs the info plane it is copied from");
-  if (d_action_mask || d_final_action_mask)  // what hwy_action_mask_device answers for this engine
-    if (int rc = mask_check(eng, d_action_mask ? d_action_mask : d_final_action_mask, who)) return rc;
-  HWY_HIP(eng, hipSetDevice(eng->device));
-  if (eng->profiling && eng->events_used >= 65536)
-    if (int rc = drain_events(eng)) return rc;
+  if (int rc = same_step_begin(eng, who, continuous ? (const void *)d_continuous : (const void *)d_actions, d_obs, d_reward, d_terminated,
+                               d_truncated, d_info_speed, d_info_crashed, d_final_obs, d_final_info_speed, d_final_info_crashed, d_final_mask,
+                               d_action_mask, d_final_action_mask))
+    return rc;
   if (continuous) HWY_HIP(eng, hwy::launch_act_continuous(hwy::act_params(eng->cfg, *cp, d_continuous, eng->d_controls), eng->stream));
   struct Ops {
     hwy_engine *eng;
@@ -1504,6 +1523,117 @@ extern "C" int hwy_step_same_step_device(hwy_engine *eng, const int32_t *d_actio
   return same_step_enqueue(eng, "hwy_step_same_step_device", d_actions, nullptr, nullptr, d_obs, d_reward, d_terminated, d_truncated,
                            d_info_speed, d_info_crashed, d_final_obs, d_final_info_speed, d_final_info_crashed, d_final_mask, d_action_mask,
                            d_final_action_mask, false);
+}
+
+// ---- TimeToCollision observation (hwy_collision_obs.h) ---------------------------------------------------------------------------------
+static int ttc_obs_check(hwy_engine *eng, const hwy_ttc_params *params, const void *out, const char *who) {
+  if (!eng) return HWY_ERR_INVALID_ARG;
+  const char *why = "";
+  if (const int rc = hwy::ttc_obs_validate(eng->cfg, params, &why)) return fail(eng, rc, std::string(who) + ": " + why);
+  if (!out) return fail(eng, HWY_ERR_INVALID_ARG, std::string(who) + ": obs must be non-NULL");
+  return HWY_OK;
+}
+static hipError_t ttc_obs_launch(const hwy_engine *eng, const hwy_ttc_params &tp, float *d_obs) {
+  const size_t plane = (size_t)eng->cfg.num_envs * eng->pitch;
+  const double *f = eng->d_f64;  // planes: x | y | heading | speed | ...
+  const hwy::CollisionObsParams p = hwy::collision_obs_params(eng->cfg, tp, f, f + 2 * plane, f + 3 * plane, eng->d_packed, eng->pitch, d_obs);
+  return hwy::launch_collision_obs(p, (int)num_agent_rows(eng->cfg), eng->stream);
+}
+// the buffer the step's own observation goes to (a null `obs` would take the step off its shape kernel)
+static int ttc_step_obs(hwy_engine *eng) {
+  if (!eng->d_ttc_step_obs) HWY_HIP(eng, hipMalloc((void **)&eng->d_ttc_step_obs, num_obs_floats(eng->cfg) * sizeof(float)));
+  return HWY_OK;
+}
+
+extern "C" int hwy_ttc_observe_device(hwy_engine *eng, const hwy_ttc_params *params, float *d_obs) {
+  if (int rc = ttc_obs_check(eng, params, d_obs, "hwy_ttc_observe_device")) return rc;
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  HWY_HIP(eng, ttc_obs_launch(eng, *params, d_obs));
+  return HWY_OK;
+}
+
+extern "C" int hwy_ttc_observe(hwy_engine *eng, const hwy_ttc_params *params, float *obs) {
+  if (int rc = ttc_obs_check(eng, params, obs, "hwy_ttc_observe")) return rc;
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  const size_t rows = num_agent_rows(eng->cfg);
+  if (!eng->d_ttc_obs) HWY_HIP(eng, hipMalloc((void **)&eng->d_ttc_obs, rows * HWY_COLLISION_OBS_CELLS * sizeof(float)));
+  HWY_HIP(eng, ttc_obs_launch(eng, *params, eng->d_ttc_obs));
+  HWY_HIP(eng, hipMemcpyAsync(obs, eng->d_ttc_obs, rows * hwy::collision_obs_len(*params) * sizeof(float), hipMemcpyDeviceToHost, eng->stream));
+  HWY_HIP(eng, hipStreamSynchronize(eng->stream));
+  return HWY_OK;
+}
+
+extern "C" int hwy_rollout_ttc_device(hwy_engine *eng, const hwy_ttc_params *params, int32_t k_steps, const int32_t *d_actions, float *d_obs,
+                                      double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, double *d_info_speed,
+                                      uint8_t *d_info_crashed) {
+  static const char *who = "hwy_rollout_ttc_device";
+  if (int rc = ttc_obs_check(eng, params, d_obs, who)) return rc;
+  if (k_steps < 1) return fail(eng, HWY_ERR_INVALID_ARG, std::string(who) + ": k_steps must be >= 1");
+  if (!d_actions || !d_reward || !d_terminated || !d_truncated)
+    return fail(eng, HWY_ERR_INVALID_ARG, std::string(who) + ": actions/reward/terminated/truncated must be non-NULL");
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  if (int rc = ttc_step_obs(eng)) return rc;
+  struct Ops {
+    hwy_engine *eng;
+    const hwy_ttc_params *tp;
+    const int32_t *actions;
+    float *obs;
+    double *reward;
+    uint8_t *term, *trunc;
+    double *speed;
+    uint8_t *crashed;
+    int step(int32_t k) {  // exactly hwy_step_device's launch on block k
+      const size_t E = eng->cfg.num_envs, EA = num_agent_rows(eng->cfg);
+      return enqueue_full_step(eng, actions + k * EA, eng->d_ttc_step_obs, reward + k * EA, term + k * E, trunc + k * E,
+                               speed ? speed + k * EA : nullptr, crashed ? crashed + k * EA : nullptr);
+    }
+    int observe(int32_t k) {
+      HWY_HIP(eng, ttc_obs_launch(eng, *tp, obs + (size_t)k * num_agent_rows(eng->cfg) * hwy::collision_obs_len(*tp)));
+      return HWY_OK;
+    }
+  } ops{eng, params, d_actions, d_obs, d_reward, d_terminated, d_truncated, d_info_speed, d_info_crashed};
+  return hwy::ttc_obs_rollout_sequence(ops, k_steps);
+}
+
+extern "C" int hwy_step_same_step_ttc_device(hwy_engine *eng, const hwy_ttc_params *params, const int32_t *d_actions, float *d_obs,
+                                             double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, double *d_info_speed,
+                                             uint8_t *d_info_crashed, float *d_final_obs, double *d_final_info_speed,
+                                             uint8_t *d_final_info_crashed, uint8_t *d_final_mask, uint8_t *d_action_mask,
+                                             uint8_t *d_final_action_mask) {
+  static const char *who = "hwy_step_same_step_ttc_device";
+  if (!eng) return HWY_ERR_INVALID_ARG;
+  const char *why = "";
+  if (const int rc = hwy::ttc_obs_validate(eng->cfg, params, &why)) return fail(eng, rc, std::string(who) + ": " + why);
+  if (int rc = same_step_begin(eng, who, d_actions, d_obs, d_reward, d_terminated, d_truncated, d_info_speed, d_info_crashed, d_final_obs,
+                               d_final_info_speed, d_final_info_crashed, d_final_mask, d_action_mask, d_final_action_mask))
+    return rc;
+  if (int rc = ttc_step_obs(eng)) return rc;
+  struct Ops {
+    hwy_engine *eng;
+    const hwy_ttc_params *tp;
+    float *obs;
+    StepParams p;  // the full step around the caller's planes, its own observation into the engine's buffer
+    hwy::FinalParams fp;
+    uint8_t *action_mask, *final_action_mask;
+    int step() { return timed_launch(eng, p); }
+    int mask(bool final) { return hwy_action_mask_device(eng, final ? final_action_mask : action_mask); }
+    int observe() {
+      HWY_HIP(eng, ttc_obs_launch(eng, *tp, obs));
+      return HWY_OK;
+    }
+    int stash() {
+      HWY_HIP(eng, hwy::launch_final(fp, eng->stream));
+      return HWY_OK;
+    }
+    int respawn() {
+      HWY_HIP(eng, launch_stage(eng, RESPAWN, p));
+      return HWY_OK;
+    }
+  } ops{eng, params, d_obs, {}, {}, d_action_mask, d_final_action_mask};
+  bind_full_step(eng, ops.p, d_actions, eng->d_ttc_step_obs, d_reward, d_terminated, d_truncated, d_info_speed, d_info_crashed);
+  ops.fp = hwy::final_params(eng->cfg, hwy::collision_obs_len(*params), eng->d_done, d_final_mask, d_obs, d_final_obs, d_info_speed,
+                             d_final_info_speed, d_info_crashed, d_final_info_crashed);
+  return hwy::ttc_obs_same_step_sequence(ops, d_final_action_mask != nullptr, d_action_mask != nullptr);
 }
 
 // ---- continuous throttle and steering of a direct-control engine (hwy_act.h) -------------------------------------------------------

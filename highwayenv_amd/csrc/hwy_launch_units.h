@@ -1,6 +1,6 @@
 // hwy_launch_units.h -- arguments -> (precondition check, kernel instantiation, grid, block, LDS) of the add-on kernel units beside
 // the step kernels -- the Lidar trace (hwy_lidar.h), the TTC grid and planner (hwy_ttc.h), fork and score (hwy_lookahead.h), the OPD
-// tree (hwy_opd.h), the action mask (hwy_mask.h), the continuous action (hwy_act.h) and the CEM planner (hwy_cem.h) -- written ONCE for the product and for the
+// tree (hwy_opd.h), the action mask (hwy_mask.h), the continuous action (hwy_act.h), the CEM planner (hwy_cem.h) and the TimeToCollision observation (hwy_collision_obs.h) -- written ONCE for the product and for the
 // CPU emulation of tests/emu, like hwy_launch_family.h for the step families.  Host code only, generic over the thing that launches: a backend B with one member
 //   B::launch_plain(kernel, grid, block, lds, stream, args)   enqueue / run the kernel; no dispatch timestamps (those of
 //                                                             hwy_profile_* belong to the step kernel)
@@ -129,6 +129,21 @@ template <typename B> hipError_t select_cem_sample(const CemParams &cp, hipStrea
 template <typename B> hipError_t select_cem_refit(const CemParams &cp, hipStream_t stream) {
   if (!cem_shape_ok(cp) || !cp.ret || !cp.best_return || !cp.best_sequence || !cp.action) return hipErrorInvalidValue;
   return B::launch_plain(hwy_cem_refit_kernel<HWY_CEM_MAX_POP>, cp.E, 64, 0, stream, cp);
+}
+}  // namespace hwy
+#endif
+
+// ---- TimeToCollision observation (hwy_collision_obs.h): `rows` (environment, agent) pairs, one wavefront each, row r ->
+// cp.obs + r * 9 * T.  The window's nine rows live in LDS at one dword per cell (static, 576 dwords): one class for every V and L.
+#if defined(HWY_COLLISION_OBS_CELLS) && !defined(HWY_LAUNCH_COLLISION_OBS_UNIT)
+#define HWY_LAUNCH_COLLISION_OBS_UNIT
+namespace hwy {
+template <typename B> hipError_t select_collision_obs(const CollisionObsParams &cp, int rows, hipStream_t stream) {
+  if (rows < 1 || cp.A < 1 || rows % cp.A != 0 || cp.V < 2 || cp.V > HWY_MAX_TARGET_SPEEDS || cp.L < 1 || cp.L > HWY_MAX_LANES || cp.T < 1 ||
+      cp.T > HWY_MAX_TTC_STEPS || cp.N < 1 || cp.N > HWY_MAX_VEHICLES || cp.N > cp.pitch || !cp.x || !cp.heading || !cp.speed || !cp.packed ||
+      !cp.obs)
+    return hipErrorInvalidValue;
+  return B::launch_plain(hwy_collision_obs_kernel<HWY_COLLISION_OBS_CELLS>, rows, 64, 0, stream, cp);
 }
 }  // namespace hwy
 #endif

@@ -205,6 +205,42 @@ class Engine:
         vp = C.c_void_p
         self._check_ttc(self._lib.hwy_mdp_plan_device(self._h, C.byref(params), vp(d_action), vp(d_q or None), vp(d_grid or None)))
 
+    # -- TimeToCollision observation (csrc/hwy_collision_obs.h) --------------------------------------
+    def ttc_observe(self, params: _abi.HwyTtcParams) -> np.ndarray:
+        """hwy_ttc_observe: TimeToCollisionObservation.observe for every controlled vehicle, f32 [E, A, 3, 3, T] (values 0, 0.5,
+        1).  ``gamma`` and ``lane_change_reward`` of ``params`` are not read."""
+        steps = params.time_steps if 1 <= params.time_steps <= _abi.HWY_MAX_TTC_STEPS else 1  # (the entry point refuses the rest)
+        obs = np.empty((self.E, self.A, _abi.TTC_OBS_SIDE, _abi.TTC_OBS_SIDE, steps), np.float32)
+        self._check_scope(self._lib.hwy_ttc_observe(self._h, C.byref(params), _ptr(obs)))
+        return obs
+
+    def ttc_observe_device(self, params: _abi.HwyTtcParams, d_obs: int):
+        """Enqueue hwy_ttc_observe_device on a raw device pointer (float32 [E, A, 3, 3, T]); does not synchronise."""
+        self._check_scope(self._lib.hwy_ttc_observe_device(self._h, C.byref(params), C.c_void_p(d_obs or None)))
+
+    def step_same_step_ttc_device(self, params: _abi.HwyTtcParams, d_actions: int, d_obs: int, d_reward: int, d_terminated: int,
+                                  d_truncated: int, d_info_speed: int = 0, d_info_crashed: int = 0, d_final_obs: int = 0,
+                                  d_final_info_speed: int = 0, d_final_info_crashed: int = 0, d_final_mask: int = 0,
+                                  d_action_mask: int = 0, d_final_action_mask: int = 0):
+        """Enqueue hwy_step_same_step_ttc_device: ``step_same_step_device`` with the TimeToCollision window as ``d_obs`` and
+        ``d_final_obs`` [E, A, 3, 3, T]; does not synchronise."""
+        vp = C.c_void_p
+        self._check_scope(self._lib.hwy_step_same_step_ttc_device(
+            self._h, C.byref(params), vp(d_actions or None), vp(d_obs or None), vp(d_reward or None), vp(d_terminated or None),
+            vp(d_truncated or None), vp(d_info_speed or None), vp(d_info_crashed or None), vp(d_final_obs or None),
+            vp(d_final_info_speed or None), vp(d_final_info_crashed or None), vp(d_final_mask or None), vp(d_action_mask or None),
+            vp(d_final_action_mask or None)))
+
+    def rollout_ttc_device(self, params: _abi.HwyTtcParams, k_steps: int, d_actions: int, d_obs: int, d_reward: int, d_terminated: int,
+                           d_truncated: int, d_info_speed: int = 0, d_info_crashed: int = 0):
+        """Enqueue hwy_rollout_ttc_device: ``k_steps`` (step, observe) launch pairs on block k of every plane (d_obs
+        [K, E, A, 3, 3, T]); does not synchronise.  ``k_steps`` 1: one step with the window as its observation; K steps give the
+        results of K such calls, bit for bit."""
+        vp = C.c_void_p
+        self._check_scope(self._lib.hwy_rollout_ttc_device(self._h, C.byref(params), int(k_steps), vp(d_actions or None), vp(d_obs or None),
+                                                           vp(d_reward or None), vp(d_terminated or None), vp(d_truncated or None),
+                                                           vp(d_info_speed or None), vp(d_info_crashed or None)))
+
     # -- environment fork and scoring of action sequences (csrc/hwy_lookahead.h) -------------------
     def fork_from(self, src: "Engine", branches: int = 1, source=None):
         """hwy_fork / hwy_fork_device: environment j of this engine becomes a copy of environment ``source[j]`` of ``src``

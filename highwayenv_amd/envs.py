@@ -445,6 +445,40 @@ class BatchedHighwayEnv:
             action, q = action[:, 0], (q[:, 0] if q is not None else None)
         return (action, q) if return_q else action
 
+    # ---- TimeToCollisionObservation (envs/common/observation.py:115-152), through a door of its own ------------------------------
+    def _ttc_obs_params(self, horizon, need_engine: bool = True):
+        _abi.check_ttc_observation_scope(self._hcfg)  # NotImplementedError off the highway / with a DiscreteAction ego
+        params = _abi.ttc_params(self.config, horizon, None)  # time step 1 / policy_frequency (observation.py:131)
+        if need_engine and self._engine is None:
+            raise NotImplementedError("The road and vehicle must be initialized in the environment implementation")
+        return params
+
+    def ttc_observation(self, horizon: float = 10.0) -> np.ndarray:
+        """``TimeToCollisionObservation(env, horizon).observe()`` of every controlled vehicle of every environment, computed on the
+        device by a kernel of its own (csrc/hwy_collision_obs.h): float32 [E, 3, 3, T] ([E, A, 3, 3, T] for several agents), axes
+        speeds ``speed_index - 1 .. + 1`` (clamped) x lanes ``lane - 1 .. + 1`` (1.0 off the road) x ``T = int(horizon *
+        policy_frequency)`` time steps; values 0, 0.5 or 1.  The config type ``{"type": "TimeToCollision"}`` stays rejected: the
+        env keeps its configured observation and hands this one out next to it."""
+        params = self._ttc_obs_params(horizon)
+        obs = self._engine.ttc_observe(params)
+        return obs[:, 0] if self._hcfg.num_agents == 1 else obs
+
+    def ttc_observation_space(self, horizon: float = 10.0):
+        """``TimeToCollisionObservation.space()``: ``Box(0, 1, (3, 3, T), float32)``; several agents: a tuple of them
+        (MultiAgentObservation.space, observation.py:598-601)."""
+        shape = _abi.ttc_obs_shape(self._ttc_obs_params(horizon, need_engine=False))
+        if _gym is not None:
+            one = lambda: _gym.spaces.Box(0, 1, shape, np.float32)  # noqa: E731
+            tup = _gym.spaces.Tuple
+        else:
+            def one():
+                box = _Box(shape, np.float32)
+                box.low, box.high = 0, 1
+                return box
+            tup = _Tuple
+        A = self._hcfg.num_agents
+        return one() if A == 1 else tup([one() for _ in range(A)])
+
     # ---- fork / score_sequences / plan_lookahead: AbstractEnv.__deepcopy__ + step on the copy (abstract.py:455) ------------------
     def _lookahead_scope(self, what: str):
         if self._hcfg.scenario != _abi.SCENARIO_HIGHWAY:
@@ -987,6 +1021,12 @@ class _SingleEnvMixin:
         if not isinstance(out, tuple):
             return out[0]
         return out[0][0], {k: (v[:, 0] if k in ("noise", "samples", "elites") else v[0]) for k, v in out[1].items()}
+
+    def ttc_observation(self, horizon: float = 10.0):
+        """``TimeToCollisionObservation(env, horizon).observe()``: float32 (3, 3, T); under ``MultiAgentAction`` a tuple with one such
+        array per controlled vehicle (MultiAgentObservation.observe, observation.py:603-604)."""
+        obs = super().ttc_observation(horizon)[0]
+        return obs if self._hcfg.num_agents == 1 else tuple(obs)
 
     def to_finite_mdp(self):
         """``AbstractEnv.to_finite_mdp()`` (abstract.py:452-453): horizon 10 s, time step ``1 / policy_frequency``."""

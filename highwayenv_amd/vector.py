@@ -35,6 +35,12 @@ environments are ONE engine (one kernel launch per step), and this class gives t
   autoreset mode as with ids.  A policy network's float32 device tensor goes to the kernel as it is.  ``plan_cem(...)`` plans such
   actions by the cross-entropy method on the device (csrc/hwy_cem.h); with ``output="torch"`` ``env.step(env.plan_cem())`` never
   leaves the GPU.
+* ``ttc_observation=True`` (or ``{"horizon": h}``; highway ids with ``DiscreteMetaAction``): the observation is the reference's
+  ``TimeToCollisionObservation`` -- ``single_observation_space`` is ``Box(0, 1, (3, 3, T), float32)`` and ``reset`` / ``step`` /
+  ``rollout`` / ``final_obs`` hand out that window, computed by a kernel of its own (csrc/hwy_collision_obs.h) behind the engine's
+  step; the env's configured observation type is still computed and not returned.  NumPy output: step, observe, masked reset,
+  observe.  ``output="torch"``: the device entry points (``hwy_rollout_ttc_device`` with K = 1; SameStep: the one call
+  ``hwy_step_same_step_ttc_device``), no host copy anywhere.  Not together with ``continuous=True`` (the egos differ).
 
 With gymnasium installed the class IS a ``gymnasium.vector.VectorEnv``; without it (this image) the same attributes exist on a
 plain object.
@@ -78,7 +84,7 @@ class HighwayVectorEnv(_Base):
 
     def __init__(self, env="highway-fast-v0", num_envs: int = 1, config: dict | None = None, autoreset_mode: str = "NextStep",
                  output: str = "numpy", device: int = 0, spawn_mode: str = "device", stream=None, action_masks: bool = False,
-                 continuous: bool = False, **kwargs):
+                 continuous: bool = False, ttc_observation=False, **kwargs):
         mode = getattr(autoreset_mode, "value", autoreset_mode)  # gymnasium.vector.AutoresetMode or its string
         mode = {"next_step": "NextStep", "same_step": "SameStep", "disabled": "Disabled"}.get(str(mode).lower(), str(mode))
         if mode not in AUTORESET_MODES:
@@ -136,6 +142,16 @@ class HighwayVectorEnv(_Base):
                 raise ValueError("continuous=True needs an env configured with {'type': 'DiscreteAction'} (a plain-Vehicle ego)")
             self._cparams = env.continuous_params()
             self.single_action_space = env.continuous_action_space()  # Box(-1, 1, (size,), float32); several agents: as for Discrete
+        # ttc_observation: the observations of reset / step / rollout / final_obs are the reference's TimeToCollisionObservation
+        # windows, float32 [E(, A), 3, 3, T] (csrc/hwy_collision_obs.h), in place of the env's configured observation type.
+        self._ttc_horizon = None
+        if ttc_observation is not False and ttc_observation is not None:  # ({}: the default horizon)
+            if self.continuous:
+                raise ValueError("ttc_observation needs a DiscreteMetaAction ego and continuous=True a DiscreteAction ego: not together")
+            h = ttc_observation.get("horizon", 10.0) if isinstance(ttc_observation, dict) else 10.0
+            self._ttc_horizon = float(h)
+            self.single_observation_space = env.ttc_observation_space(self._ttc_horizon)  # NotImplementedError outside the scope
+            self._ttc_params = env._ttc_obs_params(self._ttc_horizon, need_engine=False)
         if _gym is not None:
             self.observation_space = _gym.vector.utils.batch_space(self.single_observation_space, self.num_envs)
             self.action_space = _gym.vector.utils.batch_space(self.single_action_space, self.num_envs)
@@ -154,6 +170,9 @@ class HighwayVectorEnv(_Base):
     # ---- reset / step ------------------------------------------------------------------------------------------------------
     def reset(self, *, seed=None, options=None):
         obs, info = self.env.reset(seed=seed, options=options)
+        if self._ttc_horizon is not None:
+            self._ttc_params = self.env._ttc_obs_params(self._ttc_horizon)
+            obs = None if self.output == "torch" else self.env.ttc_observation(self._ttc_horizon)
         self._needs_reset[:] = False
         infos = {"speed": np.asarray(info["speed"], np.float64), "crashed": np.asarray(info["crashed"], bool)}
         if self.output == "torch":
@@ -162,6 +181,10 @@ class HighwayVectorEnv(_Base):
             if self.action_masks:
                 self._mask_into(self._dev["action_mask"])
                 infos["action_mask"] = self._views["action_mask"]
+            if self._ttc_horizon is not None:  # observed on the device into a tensor of its own (the next step overwrites the view)
+                first = t.empty_like(self._dev["obs"])
+                self._ordered(lambda: self.env._engine.ttc_observe_device(self._ttc_params, first.data_ptr()), first)
+                return (first[:, 0] if first.shape[1] == 1 else first), infos
             return t.from_numpy(np.ascontiguousarray(obs)).to(self._dev["obs"].device), infos
         if self.action_masks:
             infos["action_mask"] = self.env.get_available_actions()
@@ -185,6 +208,8 @@ class HighwayVectorEnv(_Base):
             if k in info:
                 infos[k] = info[k]
         done = term | trunc
+        if self._ttc_horizon is not None:  # of the state the step left: the terminal window where an episode ended
+            obs = self.env.ttc_observation(self._ttc_horizon)
         if self.action_masks:
             infos["action_mask"] = self.env.get_available_actions()
         if self.autoreset_mode == "SameStep" and done.any():
@@ -196,7 +221,11 @@ class HighwayVectorEnv(_Base):
                 final_info[e] = {"speed": float(infos["speed"][e]), "crashed": bool(infos["crashed"][e])}
                 if self.action_masks:  # the ended episode's mask
                     final_info[e]["action_mask"] = infos["action_mask"][e].copy()
-            obs[done] = self.env.reset_done(done)
+            if self._ttc_horizon is None:
+                obs[done] = self.env.reset_done(done)
+            else:  # the new episodes' windows (the other rows: the same state, the same values)
+                self.env.reset_done(done)
+                obs = self.env.ttc_observation(self._ttc_horizon)
             if self.action_masks:      # ... and the new episode's, next to its observation
                 infos["action_mask"] = self.env.get_available_actions()
             infos.update({"final_obs": final_obs, "_final_obs": done.copy(), "final_info": final_info, "_final_info": done.copy()})
@@ -206,7 +235,7 @@ class HighwayVectorEnv(_Base):
     def _bind_device_buffers(self):
         t, E, A = self._torch, self.num_envs, self.env._hcfg.num_agents
         dev = t.device("cuda", self.env.device)
-        shape = _abi.obs_shape(self.env._hcfg)
+        shape = self._obs_shape()
         self._dev = {"obs": t.empty((E, A, *shape), dtype=t.float32, device=dev), "reward": t.empty((E, A), dtype=t.float64, device=dev),
                      "terminated": t.empty(E, dtype=t.uint8, device=dev), "truncated": t.empty(E, dtype=t.uint8, device=dev),
                      "speed": t.empty((E, A), dtype=t.float64, device=dev), "crashed": t.empty((E, A), dtype=t.uint8, device=dev)}
@@ -240,6 +269,22 @@ class HighwayVectorEnv(_Base):
             v["final_info"] = {"speed": d["final_speed"][:, 0], "crashed": d["final_crashed"][:, 0].view(t.bool)}
             if self.action_masks:
                 v["final_info"]["action_mask"] = (d["final_action_mask"][:, 0] if A == 1 else d["final_action_mask"]).view(t.bool)
+
+    def _obs_shape(self) -> tuple:
+        """Shape of one agent's observation as this front end hands it out."""
+        return _abi.obs_shape(self.env._hcfg) if self._ttc_horizon is None else _abi.ttc_obs_shape(self._ttc_params)
+
+    def _ordered(self, enqueue, *tensors):
+        """``enqueue()`` on the engine's stream, ordered after the caller's current stream and the caller's stream after it."""
+        cur = self._torch.cuda.current_stream()
+        same = cur.cuda_stream == self._stream.cuda_stream
+        if not same:
+            self._stream.wait_stream(cur)
+        enqueue()
+        if not same:
+            cur.wait_stream(self._stream)
+            for x in tensors:
+                x.record_stream(self._stream)
 
     def _mask_into(self, out):
         """Enqueue the mask kernel into the uint8 device tensor ``out`` on the engine's stream, ordered after the caller's current
@@ -281,7 +326,13 @@ class HighwayVectorEnv(_Base):
         same = cur.cuda_stream == self._stream.cuda_stream
         if not same:
             self._stream.wait_stream(cur)      # the actions (and the consumer of the previous outputs) come first
-        if self.continuous and self._device_same_step:
+        if self._ttc_horizon is not None and self._device_same_step:  # step, observe, stash, re-spawn, observe in one call
+            self.env._engine.step_same_step_ttc_device(self._ttc_params, actions.data_ptr(), *self._out_ptrs, *self._final_ptrs)
+        elif self._ttc_horizon is not None:    # the step launch, then the window of the state it left
+            self.env._engine.rollout_ttc_device(self._ttc_params, 1, actions.data_ptr(), *self._out_ptrs)
+            if self.action_masks:
+                self.env._engine.action_mask_device(d["action_mask"].data_ptr())
+        elif self.continuous and self._device_same_step:
             self.env._engine.step_same_step_continuous_device(self._cparams, actions.data_ptr(), *self._out_ptrs, *self._final_ptrs)
         elif self.continuous:
             self.env._engine.step_continuous_device(self._cparams, actions.data_ptr(), *self._out_ptrs)
@@ -313,12 +364,15 @@ class HighwayVectorEnv(_Base):
         K = int(actions.shape[0])
         a = self._device_actions(actions, lead=(K,))
         dev = self._dev["obs"].device
-        obs = t.empty((K, E, A, *_abi.obs_shape(self.env._hcfg)), dtype=t.float32, device=dev)
+        obs = t.empty((K, E, A, *self._obs_shape()), dtype=t.float32, device=dev)
         rew = t.empty((K, E, A), dtype=t.float64, device=dev)
         term, trunc = t.empty((K, E), dtype=t.uint8, device=dev), t.empty((K, E), dtype=t.uint8, device=dev)
         cur = t.cuda.current_stream()
         self._stream.wait_stream(cur)
-        if self.continuous:  # K (act, step) launch pairs enqueued by one call (hwy_rollout_continuous_device)
+        if self._ttc_horizon is not None:  # K (step, observe) launch pairs enqueued by one call (hwy_rollout_ttc_device)
+            self.env._engine.rollout_ttc_device(self._ttc_params, K, a.data_ptr(), obs.data_ptr(), rew.data_ptr(), term.data_ptr(),
+                                                trunc.data_ptr())
+        elif self.continuous:  # K (act, step) launch pairs enqueued by one call (hwy_rollout_continuous_device)
             self.env._engine.rollout_continuous_device(self._cparams, K, a.data_ptr(), obs.data_ptr(), rew.data_ptr(), term.data_ptr(),
                                                        trunc.data_ptr())
         else:

@@ -539,6 +539,47 @@ int hwy_mdp_plan_device(hwy_engine *eng, const hwy_ttc_params *params, int32_t *
 int hwy_mdp_plan(hwy_engine *eng, const hwy_ttc_params *params, int32_t *action, double *q, float *grid);
 
 /*
+ * TimeToCollision observation (additive to ABI v8: hwy_config keeps its layout and hwy_config.obs_type gains no value -- the
+ * observation comes through these entry points, next to whatever obs_type the engine was created with).  Replaces
+ * TimeToCollisionObservation.observe (envs/common/observation.py:115-152) for every (environment, agent) at once, in a kernel of its
+ * own (csrc/hwy_collision_obs.h) that computes only the window the reference slices out of compute_ttc_grid: float32 [3][3][T],
+ *   obs[a][b][t] = 1.0                                                          where lane + b - 1 is outside [0, lanes_count)
+ *                = grid[clamp(speed_index + a - 1, 0, V - 1)][lane + b - 1][t]  otherwise
+ * with values exactly 0, 0.5 or 1.  `params` is the planner's hwy_ttc_params: horizon, time_quantization (the observation uses
+ * 1 / policy_frequency) and time_steps = int(horizon / time_quantization) are read and checked as there; gamma and
+ * lane_change_reward are IGNORED by these entry points (any value, NaN included).
+ * HWY_SCENARIO_HIGHWAY with a HWY_EGO_META ego only; any action_set, traffic model, obs_type and N.  HWY_ERR_UNSUPPORTED for the
+ * other scenarios, for a HWY_EGO_DIRECT ego (a plain Vehicle has no speed_index: the reference raises there too) and for
+ * num_target_speeds < 2 (numpy's duplicate fancy index makes the reference return shape (2, 3, T) there); HWY_ERR_INVALID_ARG for a
+ * NULL params or output and for the horizon / time_quantization / time_steps the planner rejects.  hwy_last_error has the reason.
+ *
+ * hwy_ttc_observe_device: the state as it stands, d_obs f32 [E][A][3][3][T], DEVICE pointer; enqueues on the engine's stream and
+ * does not synchronise.  hwy_ttc_observe: the same into a HOST pointer; synchronises.
+ */
+int hwy_ttc_observe_device(hwy_engine *eng, const hwy_ttc_params *params, float *d_obs);
+int hwy_ttc_observe(hwy_engine *eng, const hwy_ttc_params *params, float *obs);
+/*
+ * SameStep autoreset with the window as the observation.  The planes are those of hwy_step_same_step_device, except that d_obs and
+ * d_final_obs are [E][A][3][3][T].  In order, on the engine's stream: the step launch; the mask of the terminal state (if
+ * d_final_action_mask); the observe launch (the terminal window goes into d_obs); the stash (rows of the environments that ended go
+ * to the final planes, the others are not written); the re-spawn; the observe launch again; the mask (if d_action_mask).  Refuses
+ * what hwy_step_same_step_device and hwy_ttc_observe_device refuse.
+ */
+int hwy_step_same_step_ttc_device(hwy_engine *eng, const hwy_ttc_params *params, const int32_t *d_actions, float *d_obs, double *d_reward,
+                                  uint8_t *d_terminated, uint8_t *d_truncated, double *d_info_speed, uint8_t *d_info_crashed,
+                                  float *d_final_obs, double *d_final_info_speed, uint8_t *d_final_info_crashed, uint8_t *d_final_mask,
+                                  uint8_t *d_action_mask, uint8_t *d_final_action_mask);
+/*
+ * k_steps (step launch, observe launch) pairs in one call, block k of every plane belonging to step k: d_actions [K][E][A],
+ * d_obs [K][E][A][3][3][T], d_reward [K][E][A], d_terminated / d_truncated [K][E], the info planes [K][E][A] or NULL.  NextStep
+ * auto-reset between the steps when hwy_set_autoreset enabled it.  k_steps == 1 is the single step whose observation is
+ * the window; bit for bit the results of k_steps such calls.  The step's own Kinematics / Lidar / OccupancyGrid observation goes to a
+ * buffer the engine owns (allocated on first use).
+ */
+int hwy_rollout_ttc_device(hwy_engine *eng, const hwy_ttc_params *params, int32_t k_steps, const int32_t *d_actions, float *d_obs,
+                           double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, double *d_info_speed, uint8_t *d_info_crashed);
+
+/*
  * Environment fork and scoring of action sequences (additive to ABI v8: hwy_config keeps its layout).  The device form of the
  * reference's simulator-based planning seam: copy.deepcopy(env) (AbstractEnv.__deepcopy__, envs/common/abstract.py:455) and
  * env.step on the copy (scripts/highway_planning.ipynb).  HWY_SCENARIO_HIGHWAY only -- every traffic model, ego control, observation
