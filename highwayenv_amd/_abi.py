@@ -23,6 +23,7 @@ HWY_MAX_GLANES = 24
 HWY_MAX_ROUTE = 11
 HWY_MAX_ACTIONS_PER_AXIS = 16
 HWY_MAX_LIDAR_CELLS = 64
+HWY_MAX_LIDAR_DOOR_CELLS = 256
 HWY_MAX_TTC_STEPS = 64
 
 # hwy_status
@@ -320,6 +321,29 @@ def check_ttc_observation_scope(cfg: "HwyConfig") -> None:
     if cfg.num_target_speeds < 2:
         raise NotImplementedError("the TimeToCollision observation needs at least 2 target speeds (with one, the reference's own "
                                   "slicing returns shape (2, 3, T))")
+
+
+class HwyLidarParams(C.Structure):
+    """hwy_lidar_params (include/hwy_engine.h): LidarObservation's arguments for the door of its own (csrc/hwy_lidar_door.h)."""
+    _fields_ = [("cells", C.c_int32), ("normalize", C.c_int32), ("maximum_range", C.c_double)]
+
+
+def lidar_door_params(cells: int = 16, maximum_range: float = 60.0, normalize: bool = True) -> HwyLidarParams:
+    """``LidarObservation(cells, maximum_range, normalize)`` (observation.py:682-696) for ``hwy_lidar_observe*``: up to
+    ``HWY_MAX_LIDAR_DOOR_CELLS`` cells on every scenario (csrc/hwy_lidar_door.h: lidar_door_validate, the same rules)."""
+    p = HwyLidarParams()
+    cells, maximum_range = int(cells), float(maximum_range)
+    if not (1 <= cells <= HWY_MAX_LIDAR_DOOR_CELLS):
+        raise ValueError(f"cells = {cells}: the Lidar door traces 1..{HWY_MAX_LIDAR_DOOR_CELLS} cells")
+    if not (0 < maximum_range <= float(np.finfo(np.float32).max)):  # (the grid holds it as a float32: the engine's rule)
+        raise ValueError("maximum_range must be positive and finite as a float32 (at most FLT_MAX)")
+    p.cells, p.maximum_range, p.normalize = cells, maximum_range, int(bool(normalize))
+    return p
+
+
+def lidar_door_shape(params: HwyLidarParams) -> tuple:
+    """Shape of one agent's observation through the Lidar door: (cells, 2)."""
+    return (int(params.cells), 2)
 
 
 class HwyOpdParams(C.Structure):

@@ -27,6 +27,7 @@ EXPORTS = [
     "hwy_step_same_step_continuous_device", "hwy_rollout_continuous_device", "hwy_rollout_continuous",
     "hwy_score_rollout_continuous", "hwy_cem_plan_device", "hwy_cem_plan",
     "hwy_ttc_observe_device", "hwy_ttc_observe", "hwy_step_same_step_ttc_device", "hwy_rollout_ttc_device",
+    "hwy_lidar_observe_device", "hwy_lidar_observe", "hwy_rollout_lidar_device",
     "hwy_step_shapes", "hwy_last_step_shape",
 ]
 
@@ -125,6 +126,10 @@ def load() -> C.CDLL:
     lib.hwy_ttc_observe.argtypes = [vp, ttc, vp]
     lib.hwy_step_same_step_ttc_device.argtypes = [vp, ttc] + [vp] * 13
     lib.hwy_rollout_ttc_device.argtypes = [vp, ttc, i32] + [vp] * 7
+    lidar = C.POINTER(_abi.HwyLidarParams)
+    lib.hwy_lidar_observe_device.argtypes = [vp, lidar, vp]
+    lib.hwy_lidar_observe.argtypes = [vp, lidar, vp]
+    lib.hwy_rollout_lidar_device.argtypes = [vp, lidar, i32] + [vp] * 7
     lib.hwy_step_shapes.argtypes = [i32]
     lib.hwy_last_step_shape.argtypes = []
     lib.hwy_profile_enable.argtypes = [vp, i32]

@@ -11,9 +11,9 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libhwy_engine.so")
-SOURCES = ["hwy_kernels.hip", "hwy_kernels_shapes.hip", "hwy_kernels_linear.hip", "hwy_kernels_direct.hip", "hwy_kernels_lidar.hip", "hwy_kernels_ttc.hip", "hwy_kernels_lookahead.hip", "hwy_kernels_opd.hip", "hwy_kernels_mask.hip", "hwy_kernels_act.hip", "hwy_kernels_cem.hip", "hwy_kernels_collision_obs.hip", "hwy_kernels_final.hip", "hwy_kernels_respawn.hip", "hwy_engine.hip", "hwy_comm.hip"]
+SOURCES = ["hwy_kernels.hip", "hwy_kernels_shapes.hip", "hwy_kernels_linear.hip", "hwy_kernels_direct.hip", "hwy_kernels_lidar.hip", "hwy_kernels_ttc.hip", "hwy_kernels_lookahead.hip", "hwy_kernels_opd.hip", "hwy_kernels_mask.hip", "hwy_kernels_act.hip", "hwy_kernels_cem.hip", "hwy_kernels_collision_obs.hip", "hwy_kernels_lidar_door.hip", "hwy_kernels_final.hip", "hwy_kernels_respawn.hip", "hwy_engine.hip", "hwy_comm.hip"]
 KERNEL_SOURCES = ("hwy_kernels.hip", "hwy_kernels_shapes.hip", "hwy_kernels_linear.hip", "hwy_kernels_direct.hip", "hwy_kernels_lidar.hip", "hwy_kernels_ttc.hip",
-                  "hwy_kernels_lookahead.hip", "hwy_kernels_opd.hip", "hwy_kernels_mask.hip", "hwy_kernels_act.hip", "hwy_kernels_cem.hip", "hwy_kernels_collision_obs.hip", "hwy_kernels_final.hip",
+                  "hwy_kernels_lookahead.hip", "hwy_kernels_opd.hip", "hwy_kernels_mask.hip", "hwy_kernels_act.hip", "hwy_kernels_cem.hip", "hwy_kernels_collision_obs.hip", "hwy_kernels_lidar_door.hip", "hwy_kernels_final.hip",
                   "hwy_kernels_respawn.hip")  # the translation units that hold device code
 import glob
 
@@ -78,9 +78,10 @@ def kernel_source_hash() -> str:
 
 def flags_for(src: str) -> list:
     """hipcc flags of one translation unit: HIPCC_FLAGS, except that the Linear traffic family's kernels
-    (hwy_kernels_linear.hip) and the direct-ego-control kernels (hwy_kernels_direct.hip) are scheduled by the default strategy --
-    ROCm 7.2's register allocator crashes on them after the iterative-ilp scheduler."""
-    if src in ("hwy_kernels_linear.hip", "hwy_kernels_direct.hip"):
+    (hwy_kernels_linear.hip), the direct-ego-control kernels (hwy_kernels_direct.hip) and the Lidar door's kernel
+    (hwy_kernels_lidar_door.hip: its four-cells-per-lane instantiation) are scheduled by the default strategy -- ROCm 7.2's
+    register allocator crashes on them after the iterative-ilp scheduler."""
+    if src in ("hwy_kernels_linear.hip", "hwy_kernels_direct.hip", "hwy_kernels_lidar_door.hip"):
         out = list(HIPCC_FLAGS)
         k = out.index("-amdgpu-sched-strategy=iterative-ilp")
         del out[k - 1:k + 1]

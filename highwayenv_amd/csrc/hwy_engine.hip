@@ -71,10 +71,15 @@ struct hwy_engine {
   double *d_plan_q = nullptr;        // [E][A][5]
   // output of the host-pointer form of the action mask (hwy_action_mask), allocated on first use
   uint8_t *d_action_mask = nullptr;  // [E][A][n_ids]
-  // the TimeToCollision entry points (hwy_collision_obs.h), allocated on first use: the step's own observation (the step kernels
-  // keep writing the engine's obs_type, so the shape kernels stay the launch; nobody reads it) and the host form's output
-  float *d_ttc_step_obs = nullptr;  // [E][A][obs_len]
+  // the observation doors (hwy_collision_obs.h, hwy_lidar_door.h), allocated on first use: the step's own observation (the step
+  // kernels keep writing the engine's obs_type, so the shape kernels stay the launch; nobody reads it) and the TimeToCollision host
+  // form's output
+  float *d_door_step_obs = nullptr;  // [E][A][obs_len]
   float *d_ttc_obs = nullptr;       // [E][A][9 * HWY_MAX_TTC_STEPS]
+  // the Lidar door (hwy_lidar_door.h): the host form's output, allocated on first use; whether the planes hold a state at all
+  // (hwy_reset, hwy_set_state or a fork into this engine has run)
+  float *d_lidar_door_obs = nullptr;  // [E][A][HWY_MAX_LIDAR_DOOR_CELLS][2]
+  bool has_state = false;
   // hwy_fork / hwy_fork_device: the uploaded source indices [E] (host form) and the event that orders this engine's stream behind
   // the source engine's, both created on first use
   int32_t *d_fork_src = nullptr;
@@ -541,7 +546,7 @@ extern "C" int hwy_destroy(hwy_engine *eng) {
                   eng->d_mask, eng->d_seeds, eng->d_grid_ws, eng->d_route, eng->d_road_steps, eng->d_gnet,
                   eng->d_shadow_f64, eng->d_shadow_packed, eng->d_shadow_route, eng->d_shadow_meta, eng->d_counters, eng->d_block_env,
                   eng->d_behavior, eng->d_controls, eng->d_ttc_grid, eng->d_plan_action, eng->d_plan_q, eng->d_fork_src, eng->d_opd, eng->d_cem, eng->d_action_mask,
-                  eng->d_ttc_step_obs, eng->d_ttc_obs};
+                  eng->d_door_step_obs, eng->d_ttc_obs, eng->d_lidar_door_obs};
   for (void *q : ptrs) if (q) (void)hipFree(q);
   if (eng->fork_event) (void)hipEventDestroy(eng->fork_event);
   if (eng->h_pinned) (void)hipHostFree(eng->h_pinned);
@@ -606,6 +611,7 @@ extern "C" int hwy_set_state(hwy_engine *eng, const hwy_state *h) {
   HWY_HIP(eng, hipMemcpyAsync(eng->d_time, tm, E * sizeof(double), hipMemcpyHostToDevice, eng->stream));
   HWY_HIP(eng, hipMemsetAsync(eng->d_done, 0, E, eng->stream));
   HWY_HIP(eng, hipStreamSynchronize(eng->stream));
+  eng->has_state = true;
   return HWY_OK;
 }
 
@@ -1011,6 +1017,7 @@ extern "C" int hwy_reset(hwy_engine *eng, const uint8_t *mask, const uint64_t *s
   p.reward = eng->d_reward; p.terminated = eng->d_term; p.truncated = eng->d_trunc;
   HWY_HIP(eng, launch_stage(eng, RESET, p));
   HWY_HIP(eng, hipStreamSynchronize(eng->stream));
+  eng->has_state = true;
   if (obs) {
     HWY_HIP(eng, hipMemcpyAsync(eng->h_pinned, eng->d_obs, n_obs * 4, hipMemcpyDeviceToHost, eng->stream));
     HWY_HIP(eng, hipStreamSynchronize(eng->stream));
@@ -1235,6 +1242,7 @@ extern "C" int hwy_fork_device(hwy_engine *dst, hwy_engine *src, int32_t branche
   }
   const hwy::ForkParams p = hwy::fork_params(fork_view(dst), fork_view(src), branches, d_src_env);
   HWY_HIP(dst, hwy::launch_fork(p, dst->stream));
+  dst->has_state = dst->has_state || src->has_state;
   return HWY_OK;
 }
 
@@ -1540,8 +1548,8 @@ static hipError_t ttc_obs_launch(const hwy_engine *eng, const hwy_ttc_params &tp
   return hwy::launch_collision_obs(p, (int)num_agent_rows(eng->cfg), eng->stream);
 }
 // the buffer the step's own observation goes to (a null `obs` would take the step off its shape kernel)
-static int ttc_step_obs(hwy_engine *eng) {
-  if (!eng->d_ttc_step_obs) HWY_HIP(eng, hipMalloc((void **)&eng->d_ttc_step_obs, num_obs_floats(eng->cfg) * sizeof(float)));
+static int door_step_obs(hwy_engine *eng) {
+  if (!eng->d_door_step_obs) HWY_HIP(eng, hipMalloc((void **)&eng->d_door_step_obs, num_obs_floats(eng->cfg) * sizeof(float)));
   return HWY_OK;
 }
 
@@ -1572,7 +1580,7 @@ extern "C" int hwy_rollout_ttc_device(hwy_engine *eng, const hwy_ttc_params *par
   if (!d_actions || !d_reward || !d_terminated || !d_truncated)
     return fail(eng, HWY_ERR_INVALID_ARG, std::string(who) + ": actions/reward/terminated/truncated must be non-NULL");
   HWY_HIP(eng, hipSetDevice(eng->device));
-  if (int rc = ttc_step_obs(eng)) return rc;
+  if (int rc = door_step_obs(eng)) return rc;
   struct Ops {
     hwy_engine *eng;
     const hwy_ttc_params *tp;
@@ -1584,7 +1592,7 @@ extern "C" int hwy_rollout_ttc_device(hwy_engine *eng, const hwy_ttc_params *par
     uint8_t *crashed;
     int step(int32_t k) {  // exactly hwy_step_device's launch on block k
       const size_t E = eng->cfg.num_envs, EA = num_agent_rows(eng->cfg);
-      return enqueue_full_step(eng, actions + k * EA, eng->d_ttc_step_obs, reward + k * EA, term + k * E, trunc + k * E,
+      return enqueue_full_step(eng, actions + k * EA, eng->d_door_step_obs, reward + k * EA, term + k * E, trunc + k * E,
                                speed ? speed + k * EA : nullptr, crashed ? crashed + k * EA : nullptr);
     }
     int observe(int32_t k) {
@@ -1607,7 +1615,7 @@ extern "C" int hwy_step_same_step_ttc_device(hwy_engine *eng, const hwy_ttc_para
   if (int rc = same_step_begin(eng, who, d_actions, d_obs, d_reward, d_terminated, d_truncated, d_info_speed, d_info_crashed, d_final_obs,
                                d_final_info_speed, d_final_info_crashed, d_final_mask, d_action_mask, d_final_action_mask))
     return rc;
-  if (int rc = ttc_step_obs(eng)) return rc;
+  if (int rc = door_step_obs(eng)) return rc;
   struct Ops {
     hwy_engine *eng;
     const hwy_ttc_params *tp;
@@ -1630,10 +1638,75 @@ extern "C" int hwy_step_same_step_ttc_device(hwy_engine *eng, const hwy_ttc_para
       return HWY_OK;
     }
   } ops{eng, params, d_obs, {}, {}, d_action_mask, d_final_action_mask};
-  bind_full_step(eng, ops.p, d_actions, eng->d_ttc_step_obs, d_reward, d_terminated, d_truncated, d_info_speed, d_info_crashed);
+  bind_full_step(eng, ops.p, d_actions, eng->d_door_step_obs, d_reward, d_terminated, d_truncated, d_info_speed, d_info_crashed);
   ops.fp = hwy::final_params(eng->cfg, hwy::collision_obs_len(*params), eng->d_done, d_final_mask, d_obs, d_final_obs, d_info_speed,
                              d_final_info_speed, d_info_crashed, d_final_info_crashed);
   return hwy::ttc_obs_same_step_sequence(ops, d_final_action_mask != nullptr, d_action_mask != nullptr);
+}
+
+// ---- Lidar through a door of its own (hwy_lidar_door.h) -----------------------------------------------------------------------------
+static int lidar_door_check(hwy_engine *eng, const hwy_lidar_params *params, const void *out, bool rollout, const char *who) {
+  if (!eng) return HWY_ERR_INVALID_ARG;
+  const char *why = "";
+  if (const int rc = hwy::lidar_door_validate(eng->cfg, params, eng->has_state, rollout, &why)) return fail(eng, rc, std::string(who) + ": " + why);
+  if (!out) return fail(eng, HWY_ERR_INVALID_ARG, std::string(who) + ": obs must be non-NULL");
+  return HWY_OK;
+}
+static hipError_t lidar_door_launch(const hwy_engine *eng, const hwy_lidar_params &lp, float *d_obs) {
+  const size_t plane = (size_t)eng->cfg.num_envs * eng->pitch;
+  const double *f = eng->d_f64;  // planes: x | y | heading | speed | ...
+  const hwy::LidarDoorParams p = hwy::lidar_door_params(eng->cfg, lp, f, f + plane, f + 2 * plane, f + 3 * plane, eng->d_packed, eng->pitch, d_obs);
+  return hwy::launch_lidar_door(p, lp.normalize != 0, (int)num_agent_rows(eng->cfg), eng->stream);
+}
+
+extern "C" int hwy_lidar_observe_device(hwy_engine *eng, const hwy_lidar_params *params, float *d_obs) {
+  if (int rc = lidar_door_check(eng, params, d_obs, false, "hwy_lidar_observe_device")) return rc;
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  HWY_HIP(eng, lidar_door_launch(eng, *params, d_obs));
+  return HWY_OK;
+}
+
+extern "C" int hwy_lidar_observe(hwy_engine *eng, const hwy_lidar_params *params, float *obs) {
+  if (int rc = lidar_door_check(eng, params, obs, false, "hwy_lidar_observe")) return rc;
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  const size_t rows = num_agent_rows(eng->cfg);
+  if (!eng->d_lidar_door_obs) HWY_HIP(eng, hipMalloc((void **)&eng->d_lidar_door_obs, rows * HWY_LIDAR_DOOR_MAX_CELLS * 2 * sizeof(float)));
+  HWY_HIP(eng, lidar_door_launch(eng, *params, eng->d_lidar_door_obs));
+  HWY_HIP(eng, hipMemcpyAsync(obs, eng->d_lidar_door_obs, rows * hwy::lidar_door_len(*params) * sizeof(float), hipMemcpyDeviceToHost, eng->stream));
+  HWY_HIP(eng, hipStreamSynchronize(eng->stream));
+  return HWY_OK;
+}
+
+extern "C" int hwy_rollout_lidar_device(hwy_engine *eng, const hwy_lidar_params *params, int32_t k_steps, const int32_t *d_actions, float *d_obs,
+                                        double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, double *d_info_speed,
+                                        uint8_t *d_info_crashed) {
+  static const char *who = "hwy_rollout_lidar_device";
+  if (int rc = lidar_door_check(eng, params, d_obs, true, who)) return rc;
+  if (k_steps < 1) return fail(eng, HWY_ERR_INVALID_ARG, std::string(who) + ": k_steps must be >= 1");
+  if (!d_actions || !d_reward || !d_terminated || !d_truncated)
+    return fail(eng, HWY_ERR_INVALID_ARG, std::string(who) + ": actions/reward/terminated/truncated must be non-NULL");
+  HWY_HIP(eng, hipSetDevice(eng->device));
+  if (int rc = door_step_obs(eng)) return rc;
+  struct Ops {
+    hwy_engine *eng;
+    const hwy_lidar_params *lp;
+    const int32_t *actions;
+    float *obs;
+    double *reward;
+    uint8_t *term, *trunc;
+    double *speed;
+    uint8_t *crashed;
+    int step(int32_t k) {  // exactly hwy_step_device's launch on block k
+      const size_t E = eng->cfg.num_envs, EA = num_agent_rows(eng->cfg);
+      return enqueue_full_step(eng, actions + k * EA, eng->d_door_step_obs, reward + k * EA, term + k * E, trunc + k * E,
+                               speed ? speed + k * EA : nullptr, crashed ? crashed + k * EA : nullptr);
+    }
+    int observe(int32_t k) {
+      HWY_HIP(eng, lidar_door_launch(eng, *lp, obs + (size_t)k * num_agent_rows(eng->cfg) * hwy::lidar_door_len(*lp)));
+      return HWY_OK;
+    }
+  } ops{eng, params, d_actions, d_obs, d_reward, d_terminated, d_truncated, d_info_speed, d_info_crashed};
+  return hwy::lidar_door_rollout_sequence(ops, k_steps);
 }
 
 // ---- continuous throttle and steering of a direct-control engine (hwy_act.h) -------------------------------------------------------

@@ -1,6 +1,6 @@
 // hwy_launch.h -- host-visible launch functions of the kernels in hwy_kernels.hip, hwy_kernels_linear.hip and
 // hwy_kernels_direct.hip: one overload per kernel family, chosen by the type of its parameter struct; and of the add-on units
-// (hwy_kernels_lidar.hip, _ttc.hip, _lookahead.hip, _opd.hip, _mask.hip, _act.hip, _cem.hip, _collision_obs.hip).  Each is the shared selection layer (hwy_launch_family.h,
+// (hwy_kernels_lidar.hip, _ttc.hip, _lookahead.hip, _opd.hip, _mask.hip, _act.hip, _cem.hip, _collision_obs.hip, _lidar_door.hip).  Each is the shared selection layer (hwy_launch_family.h,
 // hwy_launch_rules.h; the add-on units: hwy_launch_units.h) with the HIP backend below.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -17,6 +17,7 @@
 #include "hwy_act.h"
 #include "hwy_cem.h"
 #include "hwy_collision_obs.h"
+#include "hwy_lidar_door.h"
 #include "hwy_same_step.h"
 #include "hwy_launch_units.h"
 
@@ -119,6 +120,9 @@ hipError_t launch_cem_refit(const CemParams &cp, hipStream_t stream);
 // TimeToCollision observation of the current state (hwy_collision_obs.h, hwy_kernels_collision_obs.hip): `rows` = environments x agents
 // wavefronts, row r -> cp.obs + r * 9 * T
 hipError_t launch_collision_obs(const CollisionObsParams &cp, int rows, hipStream_t stream);
+// Lidar through a door of its own (hwy_lidar_door.h, hwy_kernels_lidar_door.hip): `rows` = environments x agents wavefronts, row r ->
+// lp.obs + r * cells * 2
+hipError_t launch_lidar_door(const LidarDoorParams &lp, bool normalize, int rows, hipStream_t stream);
 // SameStep stash (hwy_same_step.h, hwy_kernels_final.hip: one workgroup per environment, the rows of those that ended -> the final planes)
 hipError_t launch_final(const FinalParams &fp, hipStream_t stream);
 hipError_t launch_math_probe(int op, const double *in, double *out, long long n, hipStream_t stream);

@@ -1,6 +1,6 @@
 // hwy_launch_units.h -- arguments -> (precondition check, kernel instantiation, grid, block, LDS) of the add-on kernel units beside
 // the step kernels -- the Lidar trace (hwy_lidar.h), the TTC grid and planner (hwy_ttc.h), fork and score (hwy_lookahead.h), the OPD
-// tree (hwy_opd.h), the action mask (hwy_mask.h), the continuous action (hwy_act.h), the CEM planner (hwy_cem.h) and the TimeToCollision observation (hwy_collision_obs.h) -- written ONCE for the product and for the
+// tree (hwy_opd.h), the action mask (hwy_mask.h), the continuous action (hwy_act.h), the CEM planner (hwy_cem.h) the TimeToCollision observation (hwy_collision_obs.h) and the Lidar door (hwy_lidar_door.h) -- written ONCE for the product and for the
 // CPU emulation of tests/emu, like hwy_launch_family.h for the step families.  Host code only, generic over the thing that launches: a backend B with one member
 //   B::launch_plain(kernel, grid, block, lds, stream, args)   enqueue / run the kernel; no dispatch timestamps (those of
 //                                                             hwy_profile_* belong to the step kernel)
@@ -144,6 +144,26 @@ template <typename B> hipError_t select_collision_obs(const CollisionObsParams &
       !cp.obs)
     return hipErrorInvalidValue;
   return B::launch_plain(hwy_collision_obs_kernel<HWY_COLLISION_OBS_CELLS>, rows, 64, 0, stream, cp);
+}
+}  // namespace hwy
+#endif
+
+// ---- Lidar through a door of its own (hwy_lidar_door.h): `rows` (environment, agent) pairs, one wavefront each, row r ->
+// lp.obs + r * cells * 2.  Cells per lane: 1 up to 64 cells (hwy_lidar_kernel's arrangement), 4 up to 256.  The observer of an
+// intersection state is found by one ballot: N <= 64 there.
+#if defined(HWY_LIDAR_DOOR_UNIT) && !defined(HWY_LAUNCH_LIDAR_DOOR_UNIT)
+#define HWY_LAUNCH_LIDAR_DOOR_UNIT
+namespace hwy {
+template <typename B> hipError_t select_lidar_door(const LidarDoorParams &lp, bool normalize, int rows, hipStream_t stream) {
+  if (rows < 1 || lp.A < 1 || lp.A > HWY_MAX_AGENTS || rows % lp.A != 0 || lp.cells < 1 || lp.cells > HWY_LIDAR_DOOR_MAX_CELLS || lp.N < 1 ||
+      lp.N > HWY_MAX_VEHICLES || lp.N > lp.pitch || (lp.scenario == HWY_SCENARIO_INTERSECTION && lp.N > 64) || !(lp.max_range > 0) || !lp.x ||
+      !lp.y || !lp.heading || !lp.speed || !lp.packed || !lp.obs)
+    return hipErrorInvalidValue;
+  if (lp.cells <= 64)
+    return normalize ? B::launch_plain(hwy_lidar_any_kernel<true, 1>, rows, 64, 0, stream, lp)
+                     : B::launch_plain(hwy_lidar_any_kernel<false, 1>, rows, 64, 0, stream, lp);
+  return normalize ? B::launch_plain(hwy_lidar_any_kernel<true, 4>, rows, 64, 0, stream, lp)
+                   : B::launch_plain(hwy_lidar_any_kernel<false, 4>, rows, 64, 0, stream, lp);
 }
 }  // namespace hwy
 #endif

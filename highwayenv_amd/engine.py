@@ -241,6 +241,28 @@ class Engine:
                                                            vp(d_reward or None), vp(d_terminated or None), vp(d_truncated or None),
                                                            vp(d_info_speed or None), vp(d_info_crashed or None)))
 
+    # -- Lidar through a door of its own (csrc/hwy_lidar_door.h) --------------------------------------
+    def lidar_observe(self, params: _abi.HwyLidarParams) -> np.ndarray:
+        """hwy_lidar_observe: LidarObservation.observe of the current state for every controlled vehicle, f32 [E, A, cells, 2], on
+        every scenario and next to whatever observation type the engine was created with."""
+        cells = params.cells if 1 <= params.cells <= _abi.HWY_MAX_LIDAR_DOOR_CELLS else 1  # (the entry point refuses the rest)
+        obs = np.empty((self.E, self.A, cells, 2), np.float32)
+        self._check_scope(self._lib.hwy_lidar_observe(self._h, C.byref(params), _ptr(obs)))
+        return obs
+
+    def lidar_observe_device(self, params: _abi.HwyLidarParams, d_obs: int):
+        """Enqueue hwy_lidar_observe_device on a raw device pointer (float32 [E, A, cells, 2]); does not synchronise."""
+        self._check_scope(self._lib.hwy_lidar_observe_device(self._h, C.byref(params), C.c_void_p(d_obs or None)))
+
+    def rollout_lidar_device(self, params: _abi.HwyLidarParams, k_steps: int, d_actions: int, d_obs: int, d_reward: int,
+                             d_terminated: int, d_truncated: int, d_info_speed: int = 0, d_info_crashed: int = 0):
+        """Enqueue hwy_rollout_lidar_device: ``k_steps`` (step, observe) launch pairs on block k of every plane (d_obs
+        [K, E, A, cells, 2]); does not synchronise.  NotImplementedError on the intersection."""
+        vp = C.c_void_p
+        self._check_scope(self._lib.hwy_rollout_lidar_device(self._h, C.byref(params), int(k_steps), vp(d_actions or None), vp(d_obs or None),
+                                                             vp(d_reward or None), vp(d_terminated or None), vp(d_truncated or None),
+                                                             vp(d_info_speed or None), vp(d_info_crashed or None)))
+
     # -- environment fork and scoring of action sequences (csrc/hwy_lookahead.h) -------------------
     def fork_from(self, src: "Engine", branches: int = 1, source=None):
         """hwy_fork / hwy_fork_device: environment j of this engine becomes a copy of environment ``source[j]`` of ``src``

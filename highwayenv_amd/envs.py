@@ -479,6 +479,40 @@ class BatchedHighwayEnv:
         A = self._hcfg.num_agents
         return one() if A == 1 else tup([one() for _ in range(A)])
 
+    # ---- LidarObservation (envs/common/observation.py:678-769), through a door of its own -------------------------------------------
+    def lidar_observation(self, cells: int = 16, maximum_range: float = 60.0, normalize: bool = True) -> np.ndarray:
+        """``LidarObservation(env, cells, maximum_range, normalize).observe()`` of every controlled vehicle of every environment,
+        traced on the device by a kernel of its own (csrc/hwy_lidar_door.h) on EVERY scenario family, next to the configured
+        observation type: float32 [E, cells, 2] ([E, A, cells, 2] for several agents), (distance, relative radial speed) per cell,
+        up to 256 cells; a merge scenario's ``Obstacle`` is traced as the 2 m x 2 m object it is.  The config type
+        ``{"type": "LidarObservation"}`` stays what it was (highway ids, up to 64 cells).
+
+        Intersection: the reference's ``step()`` observes BEFORE ``_clear_vehicles()`` / ``_spawn_vehicle()``
+        (intersection_env.py:136-140); this call sees the vehicle list AFTER them.  It is what
+        ``env.unwrapped.observation_type.observe()`` returns when called after ``step()`` -- not the value ``step()`` returned."""
+        params = _abi.lidar_door_params(cells, maximum_range, normalize)
+        if self._engine is None:
+            raise NotImplementedError("The road and vehicle must be initialized in the environment implementation")
+        obs = self._engine.lidar_observe(params)
+        return obs[:, 0] if self._hcfg.num_agents == 1 else obs
+
+    def lidar_observation_space(self, cells: int = 16, maximum_range: float = 60.0, normalize: bool = True):
+        """``LidarObservation.space()``: ``Box(-high, high, (cells, 2), float32)`` with ``high`` 1 if normalised, else
+        ``maximum_range``; several agents: a tuple of them (MultiAgentObservation.space, observation.py:598-601)."""
+        params = _abi.lidar_door_params(cells, maximum_range, normalize)
+        shape, high = _abi.lidar_door_shape(params), (1 if params.normalize else params.maximum_range)
+        if _gym is not None:
+            one = lambda: _gym.spaces.Box(-high, high, shape, np.float32)  # noqa: E731
+            tup = _gym.spaces.Tuple
+        else:
+            def one():
+                box = _Box(shape, np.float32)
+                box.low, box.high = -high, high
+                return box
+            tup = _Tuple
+        A = self._hcfg.num_agents
+        return one() if A == 1 else tup([one() for _ in range(A)])
+
     # ---- fork / score_sequences / plan_lookahead: AbstractEnv.__deepcopy__ + step on the copy (abstract.py:455) ------------------
     def _lookahead_scope(self, what: str):
         if self._hcfg.scenario != _abi.SCENARIO_HIGHWAY:
@@ -1026,6 +1060,12 @@ class _SingleEnvMixin:
         """``TimeToCollisionObservation(env, horizon).observe()``: float32 (3, 3, T); under ``MultiAgentAction`` a tuple with one such
         array per controlled vehicle (MultiAgentObservation.observe, observation.py:603-604)."""
         obs = super().ttc_observation(horizon)[0]
+        return obs if self._hcfg.num_agents == 1 else tuple(obs)
+
+    def lidar_observation(self, cells: int = 16, maximum_range: float = 60.0, normalize: bool = True):
+        """``LidarObservation(env, cells, maximum_range, normalize).observe()``: float32 (cells, 2); under ``MultiAgentAction`` a
+        tuple with one such array per controlled vehicle, as ``step`` returns its observations."""
+        obs = super().lidar_observation(cells, maximum_range, normalize)[0]
         return obs if self._hcfg.num_agents == 1 else tuple(obs)
 
     def to_finite_mdp(self):

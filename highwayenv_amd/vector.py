@@ -41,6 +41,16 @@ environments are ONE engine (one kernel launch per step), and this class gives t
   step; the env's configured observation type is still computed and not returned.  NumPy output: step, observe, masked reset,
   observe.  ``output="torch"``: the device entry points (``hwy_rollout_ttc_device`` with K = 1; SameStep: the one call
   ``hwy_step_same_step_ttc_device``), no host copy anywhere.  Not together with ``continuous=True`` (the egos differ).
+* ``lidar_observation=True`` (or ``{"cells": c, "maximum_range": r, "normalize": n}``; highway AND merge ids, any ego, up to 256
+  cells): the observation is the reference's ``LidarObservation`` -- ``single_observation_space`` is ``Box(-high, high, (cells, 2),
+  float32)`` and ``reset`` / ``step`` / ``rollout`` / ``final_obs`` hand out that trace, computed by a kernel of its own
+  (csrc/hwy_lidar_door.h) behind the engine's step; the env's configured observation type is still computed and not returned.
+  NumPy output, every autoreset mode: step, observe, masked reset, observe.  ``output="torch"`` (NextStep, Disabled): the step's
+  device call -- ids or, with ``continuous=True``, the continuous door -- then ``hwy_lidar_observe_device`` into the tensor handed
+  out, on the same stream; ``rollout``: ``hwy_rollout_lidar_device`` (ids only).  ``ValueError``: on the intersection ids (the
+  reference observes there BEFORE it clears and spawns vehicles, a kernel behind the step AFTER: ``env.lidar_observation()`` is
+  ``observe()`` called after ``step()``, not the observation ``step()`` returns); with ``output="torch"`` and SameStep; together
+  with ``ttc_observation``.
 
 With gymnasium installed the class IS a ``gymnasium.vector.VectorEnv``; without it (this image) the same attributes exist on a
 plain object.
@@ -84,7 +94,7 @@ class HighwayVectorEnv(_Base):
 
     def __init__(self, env="highway-fast-v0", num_envs: int = 1, config: dict | None = None, autoreset_mode: str = "NextStep",
                  output: str = "numpy", device: int = 0, spawn_mode: str = "device", stream=None, action_masks: bool = False,
-                 continuous: bool = False, ttc_observation=False, **kwargs):
+                 continuous: bool = False, ttc_observation=False, lidar_observation=False, **kwargs):
         mode = getattr(autoreset_mode, "value", autoreset_mode)  # gymnasium.vector.AutoresetMode or its string
         mode = {"next_step": "NextStep", "same_step": "SameStep", "disabled": "Disabled"}.get(str(mode).lower(), str(mode))
         if mode not in AUTORESET_MODES:
@@ -99,6 +109,25 @@ class HighwayVectorEnv(_Base):
             raise ValueError("output='torch' with autoreset_mode='SameStep' is not available for the intersection scenario (its next "
                              "episodes are pre-warmed on the device, keyed to the episode counter); use NextStep, or output='numpy'")
         self.output = output
+        # lidar_observation: the observations of reset / step / rollout / final_obs are the reference's LidarObservation traces,
+        # float32 [E(, A), cells, 2] (csrc/hwy_lidar_door.h), in place of the env's configured observation type.
+        self._lidar_params = None
+        if lidar_observation is not False and lidar_observation is not None:  # ({}: the defaults)
+            if ttc_observation is not False and ttc_observation is not None:
+                raise ValueError("lidar_observation and ttc_observation both replace the observation: not together")
+            if scenario == "intersection":
+                raise ValueError("lidar_observation is not available for the intersection scenario: the reference's step() observes "
+                                 "BEFORE it clears and spawns vehicles, a kernel behind the step sees the list AFTER them, so the trace "
+                                 "is observe() called after step(), not the observation step() returns (env.lidar_observation() "
+                                 "hands out exactly that)")
+            if self._device_same_step:
+                raise ValueError("lidar_observation with output='torch' and autoreset_mode='SameStep' is not available (it takes a "
+                                 "SameStep sequence of its own on the device); use NextStep, or output='numpy'")
+            opts = dict(lidar_observation) if isinstance(lidar_observation, dict) else {}
+            unknown = set(opts) - {"cells", "maximum_range", "normalize"}
+            if unknown:
+                raise ValueError(f"lidar_observation: unknown keys {sorted(unknown)}")
+            self._lidar_params = _abi.lidar_door_params(opts.get("cells", 16), opts.get("maximum_range", 60.0), opts.get("normalize", True))
         # action_masks: reset() and step() put info["action_mask"] (gymnasium's convention) into the info dict: bool [E, n_ids]
         # ([E, A, n_ids] for several agents), the mask of the state whose observation is returned (csrc/hwy_mask.h).  With
         # output="torch" it is the device tensor the kernel wrote.  False: nothing more is launched.
@@ -152,6 +181,10 @@ class HighwayVectorEnv(_Base):
             self._ttc_horizon = float(h)
             self.single_observation_space = env.ttc_observation_space(self._ttc_horizon)  # NotImplementedError outside the scope
             self._ttc_params = env._ttc_obs_params(self._ttc_horizon, need_engine=False)
+        if self._lidar_params is not None:
+            self._lidar_kw = {"cells": self._lidar_params.cells, "maximum_range": self._lidar_params.maximum_range,
+                              "normalize": bool(self._lidar_params.normalize)}
+            self.single_observation_space = env.lidar_observation_space(**self._lidar_kw)
         if _gym is not None:
             self.observation_space = _gym.vector.utils.batch_space(self.single_observation_space, self.num_envs)
             self.action_space = _gym.vector.utils.batch_space(self.single_action_space, self.num_envs)
@@ -173,6 +206,8 @@ class HighwayVectorEnv(_Base):
         if self._ttc_horizon is not None:
             self._ttc_params = self.env._ttc_obs_params(self._ttc_horizon)
             obs = None if self.output == "torch" else self.env.ttc_observation(self._ttc_horizon)
+        if self._lidar_params is not None:
+            obs = None if self.output == "torch" else self.env.lidar_observation(**self._lidar_kw)
         self._needs_reset[:] = False
         infos = {"speed": np.asarray(info["speed"], np.float64), "crashed": np.asarray(info["crashed"], bool)}
         if self.output == "torch":
@@ -184,6 +219,10 @@ class HighwayVectorEnv(_Base):
             if self._ttc_horizon is not None:  # observed on the device into a tensor of its own (the next step overwrites the view)
                 first = t.empty_like(self._dev["obs"])
                 self._ordered(lambda: self.env._engine.ttc_observe_device(self._ttc_params, first.data_ptr()), first)
+                return (first[:, 0] if first.shape[1] == 1 else first), infos
+            if self._lidar_params is not None:
+                first = t.empty_like(self._dev["obs"])
+                self._ordered(lambda: self.env._engine.lidar_observe_device(self._lidar_params, first.data_ptr()), first)
                 return (first[:, 0] if first.shape[1] == 1 else first), infos
             return t.from_numpy(np.ascontiguousarray(obs)).to(self._dev["obs"].device), infos
         if self.action_masks:
@@ -210,6 +249,8 @@ class HighwayVectorEnv(_Base):
         done = term | trunc
         if self._ttc_horizon is not None:  # of the state the step left: the terminal window where an episode ended
             obs = self.env.ttc_observation(self._ttc_horizon)
+        if self._lidar_params is not None:  # the trace of the state the step left: the terminal one where an episode ended
+            obs = self.env.lidar_observation(**self._lidar_kw)
         if self.action_masks:
             infos["action_mask"] = self.env.get_available_actions()
         if self.autoreset_mode == "SameStep" and done.any():
@@ -221,7 +262,10 @@ class HighwayVectorEnv(_Base):
                 final_info[e] = {"speed": float(infos["speed"][e]), "crashed": bool(infos["crashed"][e])}
                 if self.action_masks:  # the ended episode's mask
                     final_info[e]["action_mask"] = infos["action_mask"][e].copy()
-            if self._ttc_horizon is None:
+            if self._lidar_params is not None:  # the new episodes' traces (the other rows: the same state, the same values)
+                self.env.reset_done(done)
+                obs = self.env.lidar_observation(**self._lidar_kw)
+            elif self._ttc_horizon is None:
                 obs[done] = self.env.reset_done(done)
             else:  # the new episodes' windows (the other rows: the same state, the same values)
                 self.env.reset_done(done)
@@ -252,6 +296,9 @@ class HighwayVectorEnv(_Base):
         self._n_actions = E * A * (self._cparams.size if self.continuous else 1)
         self._action_dtype = t.float32 if self.continuous else t.int32
         self._out_ptrs = tuple(d[k].data_ptr() for k in ("obs", "reward", "terminated", "truncated", "speed", "crashed"))
+        if self._lidar_params is not None:  # the step's own observation goes to a tensor nobody reads; d["obs"] takes the trace
+            d["step_obs"] = t.empty((E, A, *_abi.obs_shape(self.env._hcfg)), dtype=t.float32, device=dev)
+            self._out_ptrs = (d["step_obs"].data_ptr(),) + self._out_ptrs[1:]
         # what step() hands out: views of the planes the kernel writes (bool views of the 0 / 1 flag bytes; the intersection's
         # info_crashed carries has_arrived in bit 1, include/hwy_engine.h, so its `crashed` is computed per step)
         plain_crashed = self.env._hcfg.scenario != _abi.SCENARIO_INTERSECTION
@@ -272,6 +319,8 @@ class HighwayVectorEnv(_Base):
 
     def _obs_shape(self) -> tuple:
         """Shape of one agent's observation as this front end hands it out."""
+        if self._lidar_params is not None:
+            return _abi.lidar_door_shape(self._lidar_params)
         return _abi.obs_shape(self.env._hcfg) if self._ttc_horizon is None else _abi.ttc_obs_shape(self._ttc_params)
 
     def _ordered(self, enqueue, *tensors):
@@ -342,6 +391,8 @@ class HighwayVectorEnv(_Base):
             self.env._engine.step_device(actions.data_ptr(), *self._out_ptrs)
             if self.action_masks:              # of the state this step left, behind it on the engine's stream
                 self.env._engine.action_mask_device(d["action_mask"].data_ptr())
+        if self._lidar_params is not None:     # the trace of the state the step left, behind it on the engine's stream
+            self.env._engine.lidar_observe_device(self._lidar_params, d["obs"].data_ptr())
         if not same:
             cur.wait_stream(self._stream)      # whatever the caller enqueues next sees this step's outputs
             actions.record_stream(self._stream)
@@ -358,6 +409,8 @@ class HighwayVectorEnv(_Base):
         """``actions`` [K, E(, A)] -> (obs [K, E, ...], rewards [K, E], terminations [K, E], truncations [K, E]) as device tensors:
         K policy steps in one call of ``hwy_rollout_device`` (one LAUNCH on the one-wavefront kernel), NextStep autoreset between
         the steps.  ``output="torch"`` only."""
+        if self._lidar_params is not None and self.continuous:
+            raise ValueError("rollout() with lidar_observation and continuous=True is not available (hwy_rollout_lidar_device takes ids)")
         if self.output != "torch":
             raise ValueError("rollout() needs output='torch'")
         t, E, A = self._torch, self.num_envs, self.env._hcfg.num_agents
@@ -369,7 +422,10 @@ class HighwayVectorEnv(_Base):
         term, trunc = t.empty((K, E), dtype=t.uint8, device=dev), t.empty((K, E), dtype=t.uint8, device=dev)
         cur = t.cuda.current_stream()
         self._stream.wait_stream(cur)
-        if self._ttc_horizon is not None:  # K (step, observe) launch pairs enqueued by one call (hwy_rollout_ttc_device)
+        if self._lidar_params is not None:  # K (step, observe) launch pairs enqueued by one call (hwy_rollout_lidar_device)
+            self.env._engine.rollout_lidar_device(self._lidar_params, K, a.data_ptr(), obs.data_ptr(), rew.data_ptr(), term.data_ptr(),
+                                                  trunc.data_ptr())
+        elif self._ttc_horizon is not None:  # K (step, observe) launch pairs enqueued by one call (hwy_rollout_ttc_device)
             self.env._engine.rollout_ttc_device(self._ttc_params, K, a.data_ptr(), obs.data_ptr(), rew.data_ptr(), term.data_ptr(),
                                                 trunc.data_ptr())
         elif self.continuous:  # K (act, step) launch pairs enqueued by one call (hwy_rollout_continuous_device)

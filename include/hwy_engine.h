@@ -48,6 +48,7 @@ extern "C" {
 #define HWY_MAX_GLANES 24  /* lanes of a general (any direction / circular) road network: HWY_SCENARIO_INTERSECTION */
 #define HWY_MAX_ACTIONS_PER_AXIS 16 /* DiscreteAction(actions_per_axis): points per axis of the throttle x steering table */
 #define HWY_MAX_LIDAR_CELLS 64 /* LidarObservation(cells): one lane of a wavefront per cell */
+#define HWY_MAX_LIDAR_DOOR_CELLS 256 /* hwy_lidar_params.cells: up to four cells per lane of a wavefront */
 #define HWY_MAX_TTC_STEPS 64 /* time cells of the time-to-collision grid (hwy_ttc_params.time_steps) */
 #define HWY_MAX_ROUTE 11   /* remaining roads of a planned route kept per vehicle (64-bit route word, 5 bits per road) */
 
@@ -578,6 +579,38 @@ int hwy_step_same_step_ttc_device(hwy_engine *eng, const hwy_ttc_params *params,
  */
 int hwy_rollout_ttc_device(hwy_engine *eng, const hwy_ttc_params *params, int32_t k_steps, const int32_t *d_actions, float *d_obs,
                            double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, double *d_info_speed, uint8_t *d_info_crashed);
+
+/*
+ * Lidar through a door of its own (additive to ABI v8: hwy_config keeps its layout; obs_type HWY_OBS_LIDAR stays what it was, on the
+ * highway scenario and up to HWY_MAX_LIDAR_CELLS cells).  Replaces LidarObservation.trace + observe (envs/common/observation.py:
+ * 702-769) of the state as it stands for every (environment, agent) at once, in a kernel of its own (csrc/hwy_lidar_door.h), next to
+ * whatever obs_type the engine was created with: float32 [cells][2] = (distance, relative radial speed) per cell, divided by
+ * maximum_range when `normalize`.  Every scenario, ego control, traffic model and obs_type.  Every slot that is not HWY_F_ABSENT and
+ * is not the observer is traced, in slot order (the reference's road.vehicles + road.objects); a slot with HWY_F_OBSTACLE is 2 m x 2 m.
+ * HWY_SCENARIO_INTERSECTION: agent a observes from the a-th present slot that carries HWY_F_CONTROLLED.  The reference's
+ * IntersectionEnv.step observes BEFORE it clears and spawns vehicles (intersection_env.py:136-140); this call sees the list AFTER
+ * them, so behind a step it is what observation_type.observe() returns when called after step(), NOT the observation step() returned.
+ * HWY_ERR_INVALID_ARG: NULL params or output, cells outside 1..HWY_MAX_LIDAR_DOOR_CELLS, maximum_range not positive or above FLT_MAX (the grid holds it as a float32),
+ * normalize not 0 or 1, an engine that was never reset (hwy_reset / hwy_set_state / a fork into it).  hwy_last_error has the reason.
+ */
+typedef struct hwy_lidar_params {
+  int32_t cells;        /* 1..HWY_MAX_LIDAR_DOOR_CELLS: cell k looks along k * 2 pi / cells */
+  int32_t normalize;    /* 0 / 1: divide by maximum_range */
+  double maximum_range; /* metres; positive, at most FLT_MAX */
+} hwy_lidar_params;
+/* d_obs f32 [E][A][cells][2], DEVICE pointer; one launch on the engine's stream; does not synchronise. */
+int hwy_lidar_observe_device(hwy_engine *eng, const hwy_lidar_params *params, float *d_obs);
+/* The same into a HOST pointer; synchronises. */
+int hwy_lidar_observe(hwy_engine *eng, const hwy_lidar_params *params, float *obs);
+/*
+ * k_steps (step launch, observe launch) pairs in one call, block k of every plane belonging to step k: d_actions [K][E][A],
+ * d_obs [K][E][A][cells][2], d_reward [K][E][A], d_terminated / d_truncated [K][E], the info planes [K][E][A] or NULL.  NextStep
+ * auto-reset between the steps when hwy_set_autoreset enabled it.  k_steps == 1 is the single step whose observation is the trace;
+ * bit for bit the results of k_steps such calls.  The step's own configured observation goes to a buffer the engine owns (allocated
+ * on first use).  HWY_ERR_UNSUPPORTED on HWY_SCENARIO_INTERSECTION (see above: the trace behind a step is not step()'s observation).
+ */
+int hwy_rollout_lidar_device(hwy_engine *eng, const hwy_lidar_params *params, int32_t k_steps, const int32_t *d_actions, float *d_obs,
+                             double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, double *d_info_speed, uint8_t *d_info_crashed);
 
 /*
  * Environment fork and scoring of action sequences (additive to ABI v8: hwy_config keeps its layout).  The device form of the

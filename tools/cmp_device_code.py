@@ -5,7 +5,10 @@
 
 Every gfx950 code object of every offload bundle is disassembled; required are the same set of function symbols and, for every
 symbol, the same instruction listing (addresses and encodings left out, so the order of the functions inside a code object does
-not count), and equal build.kernel_resources() -- registers, spills, LDS, scratch of every kernel.  Needs no GPU."""
+not count), and equal build.kernel_resources() -- registers, spills, LDS, scratch of every kernel.  A kernel that several translation
+units emit (the re-spawn kernels, through hwy_launch.h) has one listing per code object: the SET of its distinct listings is what is
+compared, so such a symbol is "the same" in two libraries exactly when every listing it has in one also occurs in the other --
+two differing listings of one symbol inside a library are never folded into one, they make a set of two.  Needs no GPU."""
 import hashlib
 import os
 import re
@@ -21,7 +24,7 @@ OBJDUMP = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", 
 
 
 def functions(path: str) -> dict:
-    """symbol -> sha256 of its instruction listing"""
+    """symbol -> the sha256 of its instruction listing in every code object that defines it (sorted, duplicates folded)"""
     fns = {}
     for co in build.gfx950_code_objects(open(path, "rb").read()):
         with tempfile.NamedTemporaryFile(suffix=".co") as f:
@@ -33,9 +36,8 @@ def functions(path: str) -> dict:
         for line in txt.splitlines() + ["<end>:"]:
             m = re.match(r"^[0-9a-f]* ?<(.+)>:$", line)
             if m:
-                if name:
-                    assert name not in fns, f"{path}: {name} is defined in two code objects"
-                    fns[name] = hashlib.sha256("\n".join(body).encode()).hexdigest()
+                if name:  # (a kernel that several translation units emit: the set of its listings, one entry when they agree)
+                    fns[name] = tuple(sorted(set(fns.get(name, ())) | {hashlib.sha256("\n".join(body).encode()).hexdigest()}))
                 name, body = m.group(1), []
             elif name and line.strip() not in ("", "...") and not line.startswith("Disassembly of section"):  # ("...": padding)
                 body.append(re.sub(r"\s*//.*$", "", line).strip())
