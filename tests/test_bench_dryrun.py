@@ -96,6 +96,17 @@ class CpuPlatform:
         return Ev()
 
 
+class StepClock:
+    """bench.py's `time` for the settling test: 0.1 ms per step the stand-in engine has taken, so that how many steps fit into
+    --settle-ms, and into its 20 x bound, is the same on every host, however fast its cores and however busy they are."""
+
+    def __init__(self, plat):
+        self.plat = plat
+
+    def perf_counter(self):
+        return 1e-4 * getattr(getattr(self.plat, "engine", None), "steps", 0)
+
+
 def _rank_main(rank, world, port, argv, out_path):
     os.environ.update({"RANK": str(rank), "LOCAL_RANK": str(rank), "WORLD_SIZE": str(world), "MASTER_ADDR": "127.0.0.1",
                        "MASTER_PORT": str(port)})
@@ -103,6 +114,8 @@ def _rank_main(rank, world, port, argv, out_path):
     import bench
     lines = []
     plat = CpuPlatform(rank)
+    if os.environ.get("HWY_FAKE_SAMPLING"):
+        bench.time = StepClock(plat)
     outs = bench.main(argv, platform=plat, emit=lines.append)
     json.dump({"lines": lines, "steps": plat.engine.steps, "envs": plat.engine.E, "resets_at_step": plat.engine.resets_at_step,
                "profiled": plat.engine.profiled,
@@ -135,9 +148,9 @@ def test_settling_goes_on_until_the_engine_has_chosen_its_turn(tmp_path, monkeyp
     settle = line["settle_steps"]
     assert settle > 0 and settle % warmup == 0
     turn = line["config"]["issue_priority_turn"]
-    if chosen:  # the slower rank needed 90 steps: the settling covered them although 2 ms of the fake engine are a handful of steps
+    if chosen:  # the slower rank needed 90 steps: the settling covered them although 2 ms of the stand-in engine are 20 steps
         assert warmup + settle >= 90 and turn["chosen_by"] == "engine (timed its first launches)", (settle, turn)
-    else:       # rank 1 never finishes: the bound (20 x 2 ms) ends the settling and the line says so (rank 0 reports its own state)
+    else:       # rank 1 never finishes: the bound (20 x 2 ms = 400 steps) ends the settling and the line says so (rank 0 reports its own state)
         assert turn["chosen_by"] in ("engine (timed its first launches)", "engine, still sampling")
 
 
