@@ -11,16 +11,16 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libhwy_engine.so")
-SOURCES = ["hwy_kernels.hip", "hwy_kernels_shapes.hip", "hwy_kernels_linear.hip", "hwy_kernels_direct.hip", "hwy_kernels_lidar.hip", "hwy_kernels_ttc.hip", "hwy_kernels_lookahead.hip", "hwy_kernels_opd.hip", "hwy_kernels_mask.hip", "hwy_kernels_act.hip", "hwy_kernels_cem.hip", "hwy_kernels_collision_obs.hip", "hwy_kernels_lidar_door.hip", "hwy_kernels_final.hip", "hwy_kernels_respawn.hip", "hwy_engine.hip", "hwy_comm.hip"]
+SOURCES = ["hwy_kernels.hip", "hwy_kernels_shapes.hip", "hwy_kernels_linear.hip", "hwy_kernels_direct.hip", "hwy_kernels_lidar.hip", "hwy_kernels_ttc.hip", "hwy_kernels_lookahead.hip", "hwy_kernels_opd.hip", "hwy_kernels_mask.hip", "hwy_kernels_act.hip", "hwy_kernels_cem.hip", "hwy_kernels_collision_obs.hip", "hwy_kernels_lidar_door.hip", "hwy_kernels_final.hip", "hwy_kernels_respawn.hip", "hwy_kernels_park.hip", "hwy_engine.hip", "hwy_comm.hip", "hwy_park.hip"]
 KERNEL_SOURCES = ("hwy_kernels.hip", "hwy_kernels_shapes.hip", "hwy_kernels_linear.hip", "hwy_kernels_direct.hip", "hwy_kernels_lidar.hip", "hwy_kernels_ttc.hip",
                   "hwy_kernels_lookahead.hip", "hwy_kernels_opd.hip", "hwy_kernels_mask.hip", "hwy_kernels_act.hip", "hwy_kernels_cem.hip", "hwy_kernels_collision_obs.hip", "hwy_kernels_lidar_door.hip", "hwy_kernels_final.hip",
-                  "hwy_kernels_respawn.hip")  # the translation units that hold device code
+                  "hwy_kernels_respawn.hip", "hwy_kernels_park.hip")  # the translation units that hold device code
 import glob
 
 # every header the two translation units can include: csrc/*.h (hwy_device.h, hwy_wave.h, hwy_net.h, hwy_ix.h, ...)
 # plus the public ABI header -- globbed so that a new kernel header can never be forgotten by is_stale()
 HEADERS = sorted(os.path.basename(h) for h in glob.glob(os.path.join(CSRC, "*.h"))) + [
-    os.path.join("..", "..", "include", "hwy_engine.h")]
+    os.path.join("..", "..", "include", "hwy_engine.h"), os.path.join("..", "..", "include", "hwy_park.h")]
 # -disable-machine-licm: MachineLICM hoists the materialisation of every f64 literal (two v_mov_b32 each) and of most LDS
 # offsets out of the frame loop, where they sit in ~50 VGPRs for the whole loop (tools/vgpr_pressure.py).  Without it the
 # road-network kernel fits 128 VGPRs with NO spills (181 natural / 64 spilled before), the one-wavefront kernel 102 (118),
@@ -79,9 +79,9 @@ def kernel_source_hash() -> str:
 def flags_for(src: str) -> list:
     """hipcc flags of one translation unit: HIPCC_FLAGS, except that the Linear traffic family's kernels
     (hwy_kernels_linear.hip), the direct-ego-control kernels (hwy_kernels_direct.hip) and the Lidar door's kernel
-    (hwy_kernels_lidar_door.hip: its four-cells-per-lane instantiation) are scheduled by the default strategy -- ROCm 7.2's
-    register allocator crashes on them after the iterative-ilp scheduler."""
-    if src in ("hwy_kernels_linear.hip", "hwy_kernels_direct.hip", "hwy_kernels_lidar_door.hip"):
+    (hwy_kernels_lidar_door.hip: its four-cells-per-lane instantiation) and the parking kernels (hwy_kernels_park.hip) are scheduled
+    by the default strategy -- ROCm 7.2's register allocator crashes on them after the iterative-ilp scheduler."""
+    if src in ("hwy_kernels_linear.hip", "hwy_kernels_direct.hip", "hwy_kernels_lidar_door.hip", "hwy_kernels_park.hip"):
         out = list(HIPCC_FLAGS)
         k = out.index("-amdgpu-sched-strategy=iterative-ilp")
         del out[k - 1:k + 1]

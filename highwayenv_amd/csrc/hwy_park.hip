@@ -1,0 +1,281 @@
+// hwy_park.hip -- C-ABI host side of the parking scenario (include/hwy_park.h): an opaque handle that owns the planes of E
+// environments and one HIP stream.  The device-pointer entry points enqueue on that stream and return; the host-pointer forms
+// stage through device buffers of the handle and synchronise.  No CPU implementation: without a GPU hwy_park_create fails.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "hwy_park.h"
+
+namespace hwy {
+hipError_t launch_park_advance(const ParkParams &p, hipStream_t stream);
+hipError_t launch_park_reset(const ParkParams &p, bool reset, hipStream_t stream);
+hipError_t launch_park_goal_reward(const ParkGoalParams &g, hipStream_t stream);
+}  // namespace hwy
+
+struct hwy_park {
+  hwy_park_config cfg{};
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  double *d_ego = nullptr, *d_parked = nullptr;
+  int32_t *d_ints = nullptr;
+  uint8_t *d_order = nullptr;
+  // outputs and inputs of the host-pointer forms
+  float *d_obs = nullptr;
+  double *d_reward = nullptr;
+  uint8_t *d_flags = nullptr, *d_mask = nullptr;
+  uint64_t *d_seeds = nullptr;
+  char *d_roll = nullptr;  // actions | step_reward | step_flags of k steps, grown on demand
+  size_t roll_bytes = 0;
+  double *d_goal = nullptr;  // achieved | desired | out of m rows, grown on demand
+  size_t goal_rows = 0;
+  std::string err;
+};
+
+static thread_local std::string g_park_create_error;
+
+#define PARK_HIP(p, call)                                              \
+  do {                                                                 \
+    hipError_t _e = (call);                                            \
+    if (_e != hipSuccess) {                                            \
+      (p)->err = std::string(#call) + ": " + hipGetErrorString(_e);    \
+      return HWY_PARK_ERR_HIP;                                         \
+    }                                                                  \
+  } while (0)
+
+static int park_fail(hwy_park *p, int code, const std::string &msg) {
+  if (p) p->err = msg; else g_park_create_error = msg;
+  return code;
+}
+static size_t ego_bytes(const hwy_park *p) { return sizeof(double) * HWY_PARK_EGO_F64 * p->cfg.num_envs; }
+static size_t ints_bytes(const hwy_park *p) { return sizeof(int32_t) * HWY_PARK_INTS * p->cfg.num_envs; }
+static size_t order_bytes(const hwy_park *p) { return (size_t)HWY_PARK_MAX_PARKED * p->cfg.num_envs; }
+static size_t parked_bytes(const hwy_park *p) { return sizeof(double) * HWY_PARK_PARKED_F64 * HWY_PARK_MAX_PARKED * p->cfg.num_envs; }
+
+static hwy::ParkParams params_of(const hwy_park *p) {
+  hwy::ParkParams q = hwy::park_params(p->cfg);
+  q.ego = p->d_ego; q.ints = p->d_ints; q.order = p->d_order; q.parked = p->d_parked;
+  return q;
+}
+
+extern "C" const char *hwy_park_last_error(const hwy_park *p) { return p ? p->err.c_str() : g_park_create_error.c_str(); }
+
+extern "C" int hwy_park_destroy(hwy_park *p) {
+  if (!p) return HWY_PARK_OK;
+  (void)hipSetDevice(p->device);
+  if (p->stream) (void)hipStreamSynchronize(p->stream);
+  void *blocks[] = {p->d_ego, p->d_parked, p->d_ints, p->d_order, p->d_obs, p->d_reward, p->d_flags, p->d_mask, p->d_seeds, p->d_roll, p->d_goal};
+  for (void *b : blocks)
+    if (b) (void)hipFree(b);
+  if (p->own_stream && p->stream) (void)hipStreamDestroy(p->stream);
+  delete p;
+  return HWY_PARK_OK;
+}
+
+extern "C" int hwy_park_create(const hwy_park_config *cfg, int device, void *stream, hwy_park **out) {
+  if (!out) return park_fail(nullptr, HWY_PARK_ERR_INVALID_ARG, "out is NULL");
+  *out = nullptr;
+  const char *why = "";
+  if (int rc = hwy::park_validate(cfg, &why)) return park_fail(nullptr, rc, why);
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n < 1)
+    return park_fail(nullptr, HWY_PARK_ERR_NO_DEVICE, "no MI355X / HIP device available (there is no CPU fallback)");
+  if (device < 0 || device >= n) return park_fail(nullptr, HWY_PARK_ERR_INVALID_ARG, "device index out of range");
+  hwy_park *p = new hwy_park();
+  p->cfg = *cfg;
+  p->device = device;
+#define PARK_CREATE(call)                                                                        \
+  do {                                                                                           \
+    hipError_t _e = (call);                                                                      \
+    if (_e != hipSuccess) {                                                                      \
+      g_park_create_error = std::string(#call) + ": " + hipGetErrorString(_e);                   \
+      hwy_park_destroy(p);                                                                       \
+      return HWY_PARK_ERR_HIP;                                                                   \
+    }                                                                                            \
+  } while (0)
+  PARK_CREATE(hipSetDevice(device));
+  if (stream) p->stream = (hipStream_t)stream;
+  else {
+    PARK_CREATE(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+    p->own_stream = true;
+  }
+  const size_t E = (size_t)cfg->num_envs;
+  PARK_CREATE(hipMalloc((void **)&p->d_ego, ego_bytes(p)));
+  PARK_CREATE(hipMalloc((void **)&p->d_ints, ints_bytes(p)));
+  PARK_CREATE(hipMalloc((void **)&p->d_order, order_bytes(p)));
+  PARK_CREATE(hipMalloc((void **)&p->d_parked, parked_bytes(p)));
+  PARK_CREATE(hipMalloc((void **)&p->d_obs, sizeof(float) * 18 * E));
+  PARK_CREATE(hipMalloc((void **)&p->d_reward, sizeof(double) * E));
+  PARK_CREATE(hipMalloc((void **)&p->d_flags, E));
+  PARK_CREATE(hipMalloc((void **)&p->d_mask, E));
+  PARK_CREATE(hipMalloc((void **)&p->d_seeds, sizeof(uint64_t) * E));
+  PARK_CREATE(hipMemset(p->d_ego, 0, ego_bytes(p)));
+  PARK_CREATE(hipMemset(p->d_ints, 0, ints_bytes(p)));
+  PARK_CREATE(hipMemset(p->d_order, 0, order_bytes(p)));
+  PARK_CREATE(hipMemset(p->d_parked, 0, parked_bytes(p)));
+  PARK_CREATE(hipDeviceSynchronize());
+#undef PARK_CREATE
+  *out = p;
+  return HWY_PARK_OK;
+}
+
+extern "C" int hwy_park_sync(hwy_park *p) {
+  if (!p) return HWY_PARK_ERR_INVALID_ARG;
+  PARK_HIP(p, hipSetDevice(p->device));
+  PARK_HIP(p, hipStreamSynchronize(p->stream));
+  return HWY_PARK_OK;
+}
+
+extern "C" int hwy_park_set_autoreset(hwy_park *p, int32_t enabled, uint64_t base_seed) {
+  if (!p) return HWY_PARK_ERR_INVALID_ARG;
+  p->cfg.autoreset = enabled ? 1 : 0;
+  p->cfg.base_seed = base_seed;
+  return HWY_PARK_OK;
+}
+
+extern "C" int hwy_park_set_state(hwy_park *p, const double *ego, const int32_t *ints, const uint8_t *order, const double *parked) {
+  if (!p || !ego || !ints || !order || !parked) return park_fail(p, HWY_PARK_ERR_INVALID_ARG, "hwy_park_set_state: NULL argument");
+  const size_t E = (size_t)p->cfg.num_envs;
+  for (size_t e = 0; e < E; ++e) {  // what the kernel indexes by: checked here, not on the device
+    const uint32_t occ = (uint32_t)ints[HWY_PARK_I_OCCUPIED * E + e];
+    const int n = __builtin_popcount(occ);
+    const int goal = ints[HWY_PARK_I_GOAL * E + e];
+    if ((occ >> HWY_PARK_SPOTS) || n > HWY_PARK_MAX_PARKED || goal < 0 || goal >= HWY_PARK_SPOTS)
+      return park_fail(p, HWY_PARK_ERR_INVALID_ARG, "hwy_park_set_state: occupancy mask or goal spot out of range");
+    for (int k = HWY_PARK_I_STRUCK; k <= HWY_PARK_I_PIMPACT; ++k)
+      if (n < 32 && ((uint32_t)ints[k * E + e] >> n))
+        return park_fail(p, HWY_PARK_ERR_INVALID_ARG, "hwy_park_set_state: a list mask has a bit beyond the parked vehicles");
+    for (int i = 0; i < n; ++i)
+      if (order[(size_t)i * E + e] >= HWY_PARK_SPOTS || !((occ >> order[(size_t)i * E + e]) & 1u))
+        return park_fail(p, HWY_PARK_ERR_INVALID_ARG, "hwy_park_set_state: order names a spot that is not occupied");
+  }
+  PARK_HIP(p, hipSetDevice(p->device));
+  PARK_HIP(p, hipMemcpyAsync(p->d_ego, ego, ego_bytes(p), hipMemcpyHostToDevice, p->stream));
+  PARK_HIP(p, hipMemcpyAsync(p->d_ints, ints, ints_bytes(p), hipMemcpyHostToDevice, p->stream));
+  PARK_HIP(p, hipMemcpyAsync(p->d_order, order, order_bytes(p), hipMemcpyHostToDevice, p->stream));
+  PARK_HIP(p, hipMemcpyAsync(p->d_parked, parked, parked_bytes(p), hipMemcpyHostToDevice, p->stream));
+  PARK_HIP(p, hipStreamSynchronize(p->stream));
+  return HWY_PARK_OK;
+}
+
+extern "C" int hwy_park_get_state(hwy_park *p, double *ego, int32_t *ints, uint8_t *order, double *parked) {
+  if (!p || !ego || !ints || !order || !parked) return park_fail(p, HWY_PARK_ERR_INVALID_ARG, "hwy_park_get_state: NULL argument");
+  PARK_HIP(p, hipSetDevice(p->device));
+  PARK_HIP(p, hipMemcpyAsync(ego, p->d_ego, ego_bytes(p), hipMemcpyDeviceToHost, p->stream));
+  PARK_HIP(p, hipMemcpyAsync(ints, p->d_ints, ints_bytes(p), hipMemcpyDeviceToHost, p->stream));
+  PARK_HIP(p, hipMemcpyAsync(order, p->d_order, order_bytes(p), hipMemcpyDeviceToHost, p->stream));
+  PARK_HIP(p, hipMemcpyAsync(parked, p->d_parked, parked_bytes(p), hipMemcpyDeviceToHost, p->stream));
+  PARK_HIP(p, hipStreamSynchronize(p->stream));
+  return HWY_PARK_OK;
+}
+
+static int observe_or_reset(hwy_park *p, bool reset, const uint8_t *mask, const uint64_t *seeds, float *obs) {
+  const size_t E = (size_t)p->cfg.num_envs;
+  PARK_HIP(p, hipSetDevice(p->device));
+  hwy::ParkParams q = params_of(p);
+  if (mask) {
+    PARK_HIP(p, hipMemcpyAsync(p->d_mask, mask, E, hipMemcpyHostToDevice, p->stream));
+    q.mask = p->d_mask;
+  }
+  if (seeds) {
+    PARK_HIP(p, hipMemcpyAsync(p->d_seeds, seeds, sizeof(uint64_t) * E, hipMemcpyHostToDevice, p->stream));
+    q.seeds = p->d_seeds;
+  }
+  q.obs = obs ? p->d_obs : nullptr;
+  PARK_HIP(p, hwy::launch_park_reset(q, reset, p->stream));
+  if (obs) PARK_HIP(p, hipMemcpyAsync(obs, p->d_obs, sizeof(float) * 18 * E, hipMemcpyDeviceToHost, p->stream));
+  PARK_HIP(p, hipStreamSynchronize(p->stream));
+  return HWY_PARK_OK;
+}
+
+extern "C" int hwy_park_reset(hwy_park *p, const uint8_t *mask, const uint64_t *seeds, float *obs) {
+  if (!p) return HWY_PARK_ERR_INVALID_ARG;
+  return observe_or_reset(p, true, mask, seeds, obs);
+}
+
+extern "C" int hwy_park_observe(hwy_park *p, float *obs) {
+  if (!p || !obs) return park_fail(p, HWY_PARK_ERR_INVALID_ARG, "hwy_park_observe: NULL argument");
+  return observe_or_reset(p, false, nullptr, nullptr, obs);
+}
+
+extern "C" int hwy_park_advance_device(hwy_park *p, int32_t k_steps, const float *d_actions, float *d_obs, double *d_reward,
+                                       uint8_t *d_flags, double *d_step_reward, uint8_t *d_step_flags) {
+  if (!p || !d_actions) return park_fail(p, HWY_PARK_ERR_INVALID_ARG, "hwy_park_advance_device: NULL argument");
+  if (k_steps < 1 || k_steps > (1 << 16)) return park_fail(p, HWY_PARK_ERR_INVALID_ARG, "hwy_park_advance_device: k_steps must be in [1, 65536]");
+  PARK_HIP(p, hipSetDevice(p->device));
+  hwy::ParkParams q = params_of(p);
+  q.k_steps = k_steps; q.actions = d_actions; q.obs = d_obs; q.reward = d_reward; q.flags = d_flags;
+  q.step_reward = d_step_reward; q.step_flags = d_step_flags;
+  PARK_HIP(p, hwy::launch_park_advance(q, p->stream));
+  return HWY_PARK_OK;
+}
+
+extern "C" int hwy_park_advance(hwy_park *p, int32_t k_steps, const float *actions, float *obs, double *reward, uint8_t *flags,
+                                double *step_reward, uint8_t *step_flags) {
+  if (!p || !actions) return park_fail(p, HWY_PARK_ERR_INVALID_ARG, "hwy_park_advance: NULL argument");
+  if (k_steps < 1 || k_steps > (1 << 16)) return park_fail(p, HWY_PARK_ERR_INVALID_ARG, "hwy_park_advance: k_steps must be in [1, 65536]");
+  const size_t E = (size_t)p->cfg.num_envs, rows = (size_t)k_steps * E;
+  if (!hwy::act_all_finite(actions, rows * 2)) return park_fail(p, HWY_PARK_ERR_ACTION, "hwy_park_advance: non-finite action");
+  PARK_HIP(p, hipSetDevice(p->device));
+  const size_t off_reward = rows * 2 * sizeof(float), off_flags = off_reward + rows * sizeof(double), need = off_flags + rows;
+  if (need > p->roll_bytes) {
+    PARK_HIP(p, hipStreamSynchronize(p->stream));
+    if (p->d_roll) PARK_HIP(p, hipFree(p->d_roll));
+    p->d_roll = nullptr;
+    p->roll_bytes = 0;
+    PARK_HIP(p, hipMalloc((void **)&p->d_roll, need));
+    p->roll_bytes = need;
+  }
+  float *d_actions = (float *)p->d_roll;
+  double *d_sr = (double *)(p->d_roll + off_reward);
+  uint8_t *d_sf = (uint8_t *)(p->d_roll + off_flags);
+  PARK_HIP(p, hipMemcpyAsync(d_actions, actions, rows * 2 * sizeof(float), hipMemcpyHostToDevice, p->stream));
+  if (int rc = hwy_park_advance_device(p, k_steps, d_actions, p->d_obs, p->d_reward, p->d_flags, step_reward ? d_sr : nullptr,
+                                       step_flags ? d_sf : nullptr))
+    return rc;
+  if (obs) PARK_HIP(p, hipMemcpyAsync(obs, p->d_obs, sizeof(float) * 18 * E, hipMemcpyDeviceToHost, p->stream));
+  if (reward) PARK_HIP(p, hipMemcpyAsync(reward, p->d_reward, sizeof(double) * E, hipMemcpyDeviceToHost, p->stream));
+  if (flags) PARK_HIP(p, hipMemcpyAsync(flags, p->d_flags, E, hipMemcpyDeviceToHost, p->stream));
+  if (step_reward) PARK_HIP(p, hipMemcpyAsync(step_reward, d_sr, rows * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+  if (step_flags) PARK_HIP(p, hipMemcpyAsync(step_flags, d_sf, rows, hipMemcpyDeviceToHost, p->stream));
+  PARK_HIP(p, hipStreamSynchronize(p->stream));
+  return HWY_PARK_OK;
+}
+
+extern "C" int hwy_park_goal_reward_device(hwy_park *p, int64_t m, const double *d_achieved, const double *d_desired, double *d_out) {
+  if (!p || !d_achieved || !d_desired || !d_out) return park_fail(p, HWY_PARK_ERR_INVALID_ARG, "hwy_park_goal_reward_device: NULL argument");
+  if (m < 0 || m > ((int64_t)1 << 36)) return park_fail(p, HWY_PARK_ERR_INVALID_ARG, "hwy_park_goal_reward_device: m out of range");
+  if (m == 0) return HWY_PARK_OK;
+  PARK_HIP(p, hipSetDevice(p->device));
+  hwy::ParkGoalParams g;
+  g.achieved = d_achieved; g.desired = d_desired; g.out = d_out; g.m = m;
+  for (int k = 0; k < 6; ++k) g.w[k] = p->cfg.reward_weights[k];
+  PARK_HIP(p, hwy::launch_park_goal_reward(g, p->stream));
+  return HWY_PARK_OK;
+}
+
+extern "C" int hwy_park_goal_reward(hwy_park *p, int64_t m, const double *achieved, const double *desired, double *out) {
+  if (!p || !achieved || !desired || !out) return park_fail(p, HWY_PARK_ERR_INVALID_ARG, "hwy_park_goal_reward: NULL argument");
+  if (m < 0 || m > ((int64_t)1 << 28)) return park_fail(p, HWY_PARK_ERR_INVALID_ARG, "hwy_park_goal_reward: m out of range");
+  if (m == 0) return HWY_PARK_OK;
+  PARK_HIP(p, hipSetDevice(p->device));
+  if ((size_t)m > p->goal_rows) {
+    PARK_HIP(p, hipStreamSynchronize(p->stream));
+    if (p->d_goal) PARK_HIP(p, hipFree(p->d_goal));
+    p->d_goal = nullptr;
+    p->goal_rows = 0;
+    PARK_HIP(p, hipMalloc((void **)&p->d_goal, sizeof(double) * 13 * (size_t)m));
+    p->goal_rows = (size_t)m;
+  }
+  double *d_a = p->d_goal, *d_d = d_a + 6 * (size_t)m, *d_o = d_d + 6 * (size_t)m;
+  PARK_HIP(p, hipMemcpyAsync(d_a, achieved, sizeof(double) * 6 * m, hipMemcpyHostToDevice, p->stream));
+  PARK_HIP(p, hipMemcpyAsync(d_d, desired, sizeof(double) * 6 * m, hipMemcpyHostToDevice, p->stream));
+  if (int rc = hwy_park_goal_reward_device(p, m, d_a, d_d, d_o)) return rc;
+  PARK_HIP(p, hipMemcpyAsync(out, d_o, sizeof(double) * m, hipMemcpyDeviceToHost, p->stream));
+  PARK_HIP(p, hipStreamSynchronize(p->stream));
+  return HWY_PARK_OK;
+}

@@ -90,7 +90,14 @@ class HighwayVectorEnv(_Base):
     """E environments of one scenario behind the vector-env interface (see the module docstring).
 
     ``env``: a ``Batched*Env`` class or instance, or an id of ``highwayenv_amd.envs.REGISTRY`` ("highway-fast-v0", "merge-v0",
-    "intersection-v0", ...)."""
+    "intersection-v0", ...).  An id of ``highwayenv_amd.parking.REGISTRY`` ("parking-v0", ...) gives that scenario's own front
+    end, ``parking.ParkingVectorEnv``, with the same arguments."""
+
+    def __new__(cls, env="highway-fast-v0", *args, **kwargs):
+        from . import parking
+        if parking.is_parking_id(env):  # (not an instance of cls: __init__ below is not run)
+            return parking.ParkingVectorEnv(env, *args, **kwargs)
+        return super().__new__(cls)
 
     def __init__(self, env="highway-fast-v0", num_envs: int = 1, config: dict | None = None, autoreset_mode: str = "NextStep",
                  output: str = "numpy", device: int = 0, spawn_mode: str = "device", stream=None, action_masks: bool = False,

@@ -1,0 +1,97 @@
+/* hwy_park.h -- C-ABI of the parking scenario (the reference's ParkingEnv, envs/parking_env.py): goal-conditioned continuous
+ * control, E environments of ONE moving rectangle (the ContinuousAction ego), up to 26 resting ones and four walls, advanced by
+ * a kernel of its own (csrc/hwy_park.h: one THREAD per environment).  A door next to the engine of hwy_engine.h: an opaque handle
+ * of its own, exported from the same shared library; hwy_config and the engine's ABI version are not involved.
+ *
+ * Scope (hwy_park_create returns HWY_PARK_ERR_INVALID_ARG outside it, before anything reaches the device): one controlled vehicle,
+ * vehicles_count 0 .. 26, walls or none, 1 .. 15 frames per policy step, the six default features in their default order, a
+ * ContinuousAction with both axes and clip, any acceleration_range, a steering_range within +-pi/3.
+ *
+ * State, struct-of-arrays over environments ([field][E]; the host forms below take and return exactly these planes):
+ *   ego     f64 [HWY_PARK_EGO_F64][E]   x, y, heading, speed, stored acceleration, stored steering, impact_x, impact_y, time
+ *   ints    i32 [HWY_PARK_INTS][E]      flags (HWY_PARK_F_*), policy steps, episode, goal spot, occupancy mask over the 28 spots,
+ *                                       and three masks over the LIST index of the parked vehicles: struck, crashed, has_impact
+ *   order   u8  [26][E]                 spot of the i-th parked vehicle of Road.vehicles (i < popcount(occupancy))
+ *   parked  f64 [HWY_PARK_PARKED_F64][26][E]   x, y, impact_x, impact_y of parked vehicle i; read and written only once its
+ *                                       struck bit is set (a vehicle that was never struck is fully described by its spot; heading and
+ *                                       speed of a parked vehicle never change: its action is (0, 0) and its speed 0)
+ * Spot k: k < 14 is lane ("a", "b", k) (y = +14, heading +pi/2), k >= 14 lane ("b", "c", k - 14) (y = -14, heading -pi/2);
+ * x = 4 (k mod 14) - 26: the order of RoadNetwork.lanes_dict().
+ */
+#ifndef HWY_PARK_H
+#define HWY_PARK_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define HWY_PARK_SPOTS 28
+#define HWY_PARK_MAX_PARKED 26
+#define HWY_PARK_MAX_FRAMES 15
+#define HWY_PARK_EGO_F64 9
+#define HWY_PARK_INTS 8
+#define HWY_PARK_PARKED_F64 4
+
+enum { HWY_PARK_OK = 0, HWY_PARK_ERR_INVALID_ARG = 1, HWY_PARK_ERR_HIP = 2, HWY_PARK_ERR_NO_DEVICE = 4, HWY_PARK_ERR_ACTION = 5 };
+/* ints plane 0 */
+enum { HWY_PARK_F_CRASHED = 1, HWY_PARK_F_HAS_IMPACT = 2, HWY_PARK_F_DONE = 4 };
+/* planes of `ego` and of `ints` */
+enum { HWY_PARK_X = 0, HWY_PARK_Y, HWY_PARK_HEADING, HWY_PARK_SPEED, HWY_PARK_ACCEL, HWY_PARK_STEER, HWY_PARK_IMPACT_X,
+       HWY_PARK_IMPACT_Y, HWY_PARK_TIME };
+enum { HWY_PARK_I_FLAGS = 0, HWY_PARK_I_STEPS, HWY_PARK_I_EPISODE, HWY_PARK_I_GOAL, HWY_PARK_I_OCCUPIED, HWY_PARK_I_STRUCK,
+       HWY_PARK_I_PCRASHED, HWY_PARK_I_PIMPACT };
+/* bits of the optional per-step flag bytes of hwy_park_advance */
+enum { HWY_PARK_S_TERMINATED = 1, HWY_PARK_S_TRUNCATED = 2, HWY_PARK_S_SUCCESS = 4, HWY_PARK_S_CRASHED = 8 };
+
+typedef struct hwy_park_config {
+  int32_t struct_size;   /* sizeof(hwy_park_config) */
+  int32_t num_envs;
+  int32_t vehicles_count; /* 0 .. 26 (the reference `continue`s once no spot is free: 26 is every spot) */
+  int32_t add_walls;
+  int32_t frames;        /* simulation_frequency // policy_frequency, 1 .. 15 */
+  int32_t autoreset;     /* NextStep: an environment that ended is re-spawned by the next advance call */
+  double dt;             /* 1 / simulation_frequency */
+  double policy_dt;      /* 1 / policy_frequency: what AbstractEnv.step adds to `time` */
+  double duration;
+  double reward_weights[6];
+  double scales[6];
+  double success_goal_reward, collision_reward;
+  double acceleration_range[2], steering_range[2]; /* of the ContinuousAction (NOT the config's top-level "steering_range") */
+  uint64_t base_seed;    /* device reset and auto-reset: environment e draws from (base_seed + e, episode) */
+} hwy_park_config;
+
+typedef struct hwy_park hwy_park;
+
+/* stream: a hipStream_t the handle enqueues on, or NULL (it creates one). */
+int hwy_park_create(const hwy_park_config *cfg, int device, void *stream, hwy_park **out);
+int hwy_park_destroy(hwy_park *p);
+const char *hwy_park_last_error(const hwy_park *p);
+/* Device reset of the environments with mask[e] != 0 (NULL: all): episode 0 of (seeds[e] or base_seed + e) on the Philox stream,
+ * the first observation into obs (host, float32 [E][3][6], may be NULL). */
+int hwy_park_reset(hwy_park *p, const uint8_t *mask, const uint64_t *seeds, float *obs);
+/* Auto-reset (NextStep) on or off and the seed its re-spawns draw from; replaces the config's two fields. */
+int hwy_park_set_autoreset(hwy_park *p, int32_t enabled, uint64_t base_seed);
+int hwy_park_set_state(hwy_park *p, const double *ego, const int32_t *ints, const uint8_t *order, const double *parked);
+int hwy_park_get_state(hwy_park *p, double *ego, int32_t *ints, uint8_t *order, double *parked);
+/* k_steps >= 1 policy steps in ONE launch, bit-identical to k_steps launches.  actions: float32 [k_steps][E][2].  Outputs of the
+ * last step: obs float32 [E][3][6] (observation, achieved_goal, desired_goal), reward f64 [E], flags u8 [E] (HWY_PARK_S_*);
+ * step_reward f64 [k_steps][E] and step_flags u8 [k_steps][E] may be NULL.  The host form rejects non-finite actions
+ * (HWY_PARK_ERR_ACTION); on the device form such a row keeps its stored controls.  The device form enqueues on the handle's stream
+ * and returns; no host round trip. */
+int hwy_park_advance(hwy_park *p, int32_t k_steps, const float *actions, float *obs, double *reward, uint8_t *flags,
+                     double *step_reward, uint8_t *step_flags);
+int hwy_park_advance_device(hwy_park *p, int32_t k_steps, const float *d_actions, float *d_obs, double *d_reward, uint8_t *d_flags,
+                            double *d_step_reward, uint8_t *d_step_flags);
+int hwy_park_observe(hwy_park *p, float *obs);
+/* ParkingEnv.compute_reward (p = 0.5) of m rows of six features: -sqrt(dot(|achieved - desired|, reward_weights)), f64 [m]. */
+int hwy_park_goal_reward_device(hwy_park *p, int64_t m, const double *d_achieved, const double *d_desired, double *d_out);
+int hwy_park_goal_reward(hwy_park *p, int64_t m, const double *achieved, const double *desired, double *out);
+int hwy_park_sync(hwy_park *p);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -1,0 +1,90 @@
+#!/usr/bin/env python3
+"""Time the parking advance kernel (csrc/hwy_park.h: hwy_park_advance_kernel) on the GPU: per policy step, for E environments,
+``vehicles_count`` parked vehicles and ``k_steps`` steps per launch; next to each time the bytes a launch moves and the HBM time
+they imply.  Needs a GPU (there is no fallback).  One JSON line per shape; ``--out`` also writes them to a file.
+
+    python tools/parking_bench.py [--envs 4096 65536] [--vehicles 0 10] [--k 1 16] [--launches 200] [--repeats 5] [--out FILE]
+
+Method: device tensors in and out (``hwy_park_advance_device``: no host round trip), a device reset, ``--warmup`` launches, then
+``--repeats`` windows of ``--launches`` back-to-back launches, each window closed by a stream synchronise and timed by the host
+clock around it; the median window is reported with the spread.  Actions are small random throttle and steering, so that episodes
+last; auto-reset is on, as in training.  Back-to-back launches on one stream: the figure is the launch-to-launch time, which at
+small E is the launch latency and not the kernel's own run time.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+HBM_BYTES_PER_S = 8.0e12  # MI355X: 8 TB/s peak
+
+
+def launch_bytes(E: int, k_steps: int) -> int:
+    """Bytes one launch moves on the common path (no struck vehicle: the parked planes and the list order are not touched): the ego
+    planes (9 f64) and the integer planes (8 i32) read and written, K float32 action pairs read, the last step's observation (18
+    float32), reward (f64) and flag byte written."""
+    return E * (2 * (9 * 8 + 8 * 4) + k_steps * 8 + 18 * 4 + 8 + 1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, nargs="+", default=[4096, 65536])
+    ap.add_argument("--vehicles", type=int, nargs="+", default=[0, 10])
+    ap.add_argument("--k", type=int, nargs="+", default=[1, 16])
+    ap.add_argument("--launches", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("parking_bench needs a GPU: nothing is measured without one")
+    from highwayenv_amd import build, parking
+    res = build.kernel_resources()["hwy::hwy_park_advance_kernel<256>"]
+    lines = []
+    for E in args.envs:
+        for vc in args.vehicles:
+            cfg = dict(parking.parking_default_config(), vehicles_count=vc)
+            eng = parking.ParkEngine(parking.make_park_config(cfg, E, autoreset=True, base_seed=1))
+            eng.reset()
+            for K in args.k:
+                g = torch.Generator(device="cuda").manual_seed(E + vc + K)
+                actions = (torch.rand((K, E, 2), device="cuda", generator=g) - 0.5) * 0.6
+                obs = torch.empty((E, 3, 6), dtype=torch.float32, device="cuda")
+                reward = torch.empty(E, dtype=torch.float64, device="cuda")
+                flags = torch.empty(E, dtype=torch.uint8, device="cuda")
+                torch.cuda.synchronize()
+                ptrs = (actions.data_ptr(), obs.data_ptr(), reward.data_ptr(), flags.data_ptr())
+                for _ in range(args.warmup):
+                    eng.advance_device(K, *ptrs)
+                eng.sync()
+                windows = []
+                for _ in range(args.repeats):
+                    t0 = time.perf_counter()
+                    for _ in range(args.launches):
+                        eng.advance_device(K, *ptrs)
+                    eng.sync()
+                    windows.append((time.perf_counter() - t0) / args.launches)
+                windows.sort()
+                per_launch = windows[len(windows) // 2]
+                nbytes = launch_bytes(E, K)
+                lines.append({"envs": E, "vehicles_count": vc, "k_steps": K, "us_per_launch": per_launch * 1e6,
+                              "us_per_policy_step": per_launch * 1e6 / K, "us_per_launch_min": windows[0] * 1e6,
+                              "us_per_launch_max": windows[-1] * 1e6, "env_steps_per_s": E * K / per_launch,
+                              "bytes_per_launch": nbytes, "hbm_us_per_launch": nbytes / HBM_BYTES_PER_S * 1e6,
+                              "vgpr": res["vgpr"], "vgpr_spill": res["vgpr_spill"], "scratch": res["scratch"]})
+                print(json.dumps(lines[-1]), flush=True)
+            eng.close()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write("\n".join(json.dumps(x) for x in lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
