@@ -187,43 +187,52 @@ __device__ inline void park_store(const ParkParams &p, int e, const ParkEnv &s) 
   p.ints[HWY_PARK_I_OCCUPIED * E + e] = (int32_t)s.occ; p.ints[HWY_PARK_I_STRUCK * E + e] = (int32_t)s.struck;
   p.ints[HWY_PARK_I_PCRASHED * E + e] = (int32_t)s.pcrashed; p.ints[HWY_PARK_I_PIMPACT * E + e] = (int32_t)s.pimpact;
 }
+// where a body of work keeps the planes of its struck bodies and the stored steering angle the direct-control functions write: the
+// advance kernel its environment's own column of ParkParams::parked ({p.parked, E, e, e}), a planner's candidate a private column
+// (hwy_park_cem.h), so that nothing it strikes reaches the environment it started from
+struct ParkSlot {
+  double *planes;  // [HWY_PARK_PARKED_F64][26][stride]
+  size_t stride, at;
+  size_t ctl;      // the entry of DirectArgs::ctl_steer
+};
 // plane f of parked vehicle i
-__device__ inline double &park_plane(const ParkParams &p, int e, int f, int i) {
-  return p.parked[((size_t)f * HWY_PARK_MAX_PARKED + i) * p.E + e];
+__device__ inline double &park_plane(const ParkSlot &q, int f, int i) {
+  return q.planes[((size_t)f * HWY_PARK_MAX_PARKED + i) * q.stride + q.at];
 }
 // parked vehicle i of the list as a body: from its spot, or from the planes once it has been struck
-__device__ inline ParkBody park_parked_body(const ParkParams &p, int e, const ParkEnv &s, int i) {
+__device__ inline ParkBody park_parked_body(const ParkParams &p, int e, const ParkSlot &q, const ParkEnv &s, int i) {
   const int k = p.order[(size_t)i * p.E + e];
   ParkBody b{park_spot_x(k), park_spot_y(k), 0.0, HWY_PARK_COS_HALF_PI, park_spot_sin(k), HWY_VEH_LENGTH / 2, HWY_VEH_WIDTH / 2,
              sqrt(HWY_VEH_LENGTH * HWY_VEH_LENGTH + HWY_VEH_WIDTH * HWY_VEH_WIDTH)};
   if ((s.struck >> i) & 1u) {
-    b.x = park_plane(p, e, 0, i);
-    b.y = park_plane(p, e, 1, i);
+    b.x = park_plane(q, 0, i);
+    b.y = park_plane(q, 1, i);
   }
   return b;
 }
 // a collision verdict r != 0 on parked vehicle i: from now on it is a general body (its position moves into the planes) ...
-__device__ inline void park_strike(const ParkParams &p, int e, ParkEnv &s, int i, const ParkBody &b, int r, double ix, double iy) {
+__device__ inline void park_strike(const ParkSlot &q, ParkEnv &s, int i, const ParkBody &b, int r, double ix, double iy) {
   const uint32_t bit = 1u << i;
   if (!(s.struck & bit)) {
-    park_plane(p, e, 0, i) = b.x;
-    park_plane(p, e, 1, i) = b.y;
+    park_plane(q, 0, i) = b.x;
+    park_plane(q, 1, i) = b.y;
     s.struck |= bit;
   }
   if (r & 2) {  // ... with a pending impact (applied by its next Vehicle.step)
-    park_plane(p, e, 2, i) = ix;
-    park_plane(p, e, 3, i) = iy;
+    park_plane(q, 2, i) = ix;
+    park_plane(q, 3, i) = iy;
     s.pimpact |= bit;
   }
   if (r & 1) s.pcrashed |= bit;
 }
 
 // ---- one frame: Road.step(dt) ---------------------------------------------------------------------------------------------------------
-__device__ inline void park_frame(const ParkParams &p, int e, ParkEnv &s, EgoControls &ctl, const DirectArgs &da) {
+// e: the environment whose list order is read; q: where its struck bodies live
+__device__ inline void park_frame(const ParkParams &p, int e, const ParkSlot &q, ParkEnv &s, EgoControls &ctl, const DirectArgs &da) {
   const double dt = p.dt;
   {  // Vehicle.step of the ego
     const bool crashed0 = (s.flags & HWY_PARK_F_CRASHED) != 0;
-    const EgoControls now = direct_clip_actions(da, (size_t)e, ctl, s.v, crashed0);
+    const EgoControls now = direct_clip_actions(da, q.ctl, ctl, s.v, crashed0);
     if (crashed0) s.steer = 0.0;
     const double tb = now.tb;
     const double cb = fast_rsqrt(1.0 + tb * tb), sb = tb * cb;
@@ -243,10 +252,10 @@ __device__ inline void park_frame(const ParkParams &p, int e, ParkEnv &s, EgoCon
   // Vehicle.step of the parked vehicles: only a pending impact moves one
   for (uint32_t m = s.pimpact; m; m &= m - 1) {
     const int i = __ffs((int)m) - 1;
-    park_plane(p, e, 0, i) += park_plane(p, e, 2, i);
-    park_plane(p, e, 1, i) += park_plane(p, e, 3, i);
-    park_plane(p, e, 2, i) = 0.0;
-    park_plane(p, e, 3, i) = 0.0;
+    park_plane(q, 0, i) += park_plane(q, 2, i);
+    park_plane(q, 1, i) += park_plane(q, 3, i);
+    park_plane(q, 2, i) = 0.0;
+    park_plane(q, 3, i) = 0.0;
     s.pcrashed |= 1u << i;
   }
   s.pimpact = 0;
@@ -266,7 +275,7 @@ __device__ inline void park_frame(const ParkParams &p, int e, ParkEnv &s, EgoCon
   }
   if (listed) {
     for (int i = 0; i < n; ++i) {
-      const ParkBody b = park_parked_body(p, e, s, i);
+      const ParkBody b = park_parked_body(p, e, q, s, i);
       const int r = park_pair_collide(ego, b, dt, &tx, &ty);
       if (!r) continue;
       if (r & 2) {  // two vehicles: a signed half each
@@ -275,7 +284,7 @@ __device__ inline void park_frame(const ParkParams &p, int e, ParkEnv &s, EgoCon
         s.flags |= HWY_PARK_F_HAS_IMPACT;
       }
       if (r & 1) s.flags |= HWY_PARK_F_CRASHED;
-      park_strike(p, e, s, i, b, r, -tx / 2, -ty / 2);
+      park_strike(q, s, i, b, r, -tx / 2, -ty / 2);
     }
   }
   // ego x walls: the whole translation goes to the vehicle
@@ -293,19 +302,19 @@ __device__ inline void park_frame(const ParkParams &p, int e, ParkEnv &s, EgoCon
   // pairs that contain a struck body (resting pairs: provably (False, False), see the head of the file)
   if (s.struck) {
     for (int i = 0; i < n; ++i) {
-      const ParkBody a = park_parked_body(p, e, s, i);
+      const ParkBody a = park_parked_body(p, e, q, s, i);
       for (int j = i + 1; j < n; ++j) {
         if (!(((s.struck >> i) | (s.struck >> j)) & 1u)) continue;
-        const ParkBody b = park_parked_body(p, e, s, j);
+        const ParkBody b = park_parked_body(p, e, q, s, j);
         const int r = park_pair_collide(a, b, dt, &tx, &ty);
         if (!r) continue;
-        park_strike(p, e, s, i, a, r, tx / 2, ty / 2);
-        park_strike(p, e, s, j, b, r, -tx / 2, -ty / 2);
+        park_strike(q, s, i, a, r, tx / 2, ty / 2);
+        park_strike(q, s, j, b, r, -tx / 2, -ty / 2);
       }
       if (p.add_walls && ((s.struck >> i) & 1u)) {
         for (int w = 0; w < 4; ++w) {
           const int r = park_pair_collide(a, park_wall(w), dt, &tx, &ty);
-          if (r) park_strike(p, e, s, i, a, r, tx, ty);
+          if (r) park_strike(q, s, i, a, r, tx, ty);
         }
       }
     }
@@ -329,6 +338,29 @@ __device__ inline double park_observe(const ParkParams &p, const ParkEnv &s, flo
     d += fabs(a - b) * p.w[k];
   }
   return d;
+}
+
+// ---- one policy step of an environment that is not re-spawned: AbstractEnv.step with the action pair (v0, v1) -----------------------
+// Returns the step's HWY_PARK_S_* bits, the reward in *reward and (obs non-null) the observation.  A non-finite pair keeps the stored
+// controls.  The one definition behind the advance kernel and the planner's candidates (hwy_park_cem.h).
+__device__ inline int park_policy_step(const ParkParams &p, int e, const ParkSlot &q, ParkEnv &s, const DirectArgs &da, float v0, float v1,
+                                       float *obs, double *reward) {
+  const bool acted = __builtin_isfinite(v0) && __builtin_isfinite(v1);
+  const double act_accel = act_map(v0, p.a0, p.a1), act_steer = act_map(v1, p.s0, p.s1);
+  EgoControls ctl = direct_begin_step(da, q.ctl, s.accel, s.steer, acted, act_accel, act_steer);
+  if (acted) s.steer = act_steer;
+  s.time += p.policy_dt;
+  for (int f = 0; f < p.frames; ++f) park_frame(p, e, q, s, ctl, da);
+  s.accel = ctl.accel;
+  s.steps += 1;
+  const double goal_reward = -sqrt(park_observe(p, s, obs));
+  const bool crashed = (s.flags & HWY_PARK_F_CRASHED) != 0;
+  const bool success = goal_reward > -p.success;
+  *reward = goal_reward + p.collision_reward * (crashed ? 1.0 : 0.0);
+  const int out = ((crashed || success) ? HWY_PARK_S_TERMINATED : 0) | (s.time >= p.duration ? HWY_PARK_S_TRUNCATED : 0) |
+                  (success ? HWY_PARK_S_SUCCESS : 0) | (crashed ? HWY_PARK_S_CRASHED : 0);
+  if (out & (HWY_PARK_S_TERMINATED | HWY_PARK_S_TRUNCATED)) s.flags |= HWY_PARK_F_DONE;
+  return out;
 }
 
 // ---- episode start: ParkingEnv._create_vehicles on the Philox stream of (seed, episode) ---------------------------------------------
@@ -378,6 +410,7 @@ __global__ void __launch_bounds__(BLOCK) hwy_park_advance_kernel(const ParkParam
   DirectArgs da;  // (only the two planes are read: the stored pair of this environment)
   da.ctl_accel = p.ego + (size_t)HWY_PARK_ACCEL * p.E;
   da.ctl_steer = p.ego + (size_t)HWY_PARK_STEER * p.E;
+  const ParkSlot slot{p.parked, (size_t)p.E, (size_t)e, (size_t)e};
   double reward = 0.0;
   int out = 0;
   for (int k = 0; k < p.k_steps; ++k) {
@@ -389,22 +422,7 @@ __global__ void __launch_bounds__(BLOCK) hwy_park_advance_kernel(const ParkParam
       out = 0;
     } else {
       const float *a = p.actions + ((size_t)k * p.E + e) * 2;
-      const float v0 = a[0], v1 = a[1];
-      const bool acted = __builtin_isfinite(v0) && __builtin_isfinite(v1);
-      const double act_accel = act_map(v0, p.a0, p.a1), act_steer = act_map(v1, p.s0, p.s1);
-      EgoControls ctl = direct_begin_step(da, (size_t)e, s.accel, s.steer, acted, act_accel, act_steer);
-      if (acted) s.steer = act_steer;
-      s.time += p.policy_dt;
-      for (int f = 0; f < p.frames; ++f) park_frame(p, e, s, ctl, da);
-      s.accel = ctl.accel;
-      s.steps += 1;
-      const double goal_reward = -sqrt(park_observe(p, s, obs));
-      const bool crashed = (s.flags & HWY_PARK_F_CRASHED) != 0;
-      const bool success = goal_reward > -p.success;
-      reward = goal_reward + p.collision_reward * (crashed ? 1.0 : 0.0);
-      out = ((crashed || success) ? HWY_PARK_S_TERMINATED : 0) | (s.time >= p.duration ? HWY_PARK_S_TRUNCATED : 0) |
-            (success ? HWY_PARK_S_SUCCESS : 0) | (crashed ? HWY_PARK_S_CRASHED : 0);
-      if (out & (HWY_PARK_S_TERMINATED | HWY_PARK_S_TRUNCATED)) s.flags |= HWY_PARK_F_DONE;
+      out = park_policy_step(p, e, slot, s, da, a[0], a[1], obs, &reward);
     }
     if (p.step_reward) p.step_reward[(size_t)k * p.E + e] = reward;
     if (p.step_flags) p.step_flags[(size_t)k * p.E + e] = (uint8_t)out;

@@ -9,8 +9,10 @@
 #include <vector>
 
 #include "hwy_park.h"
+#include "hwy_park_cem.h"
 
 namespace hwy {
+hipError_t launch_park_cem(const ParkCemParams &q, bool sample, hipStream_t stream);
 hipError_t launch_park_advance(const ParkParams &p, hipStream_t stream);
 hipError_t launch_park_reset(const ParkParams &p, bool reset, hipStream_t stream);
 hipError_t launch_park_goal_reward(const ParkGoalParams &g, hipStream_t stream);
@@ -33,6 +35,9 @@ struct hwy_park {
   size_t roll_bytes = 0;
   double *d_goal = nullptr;  // achieved | desired | out of m rows, grown on demand
   size_t goal_rows = 0;
+  double *d_plan = nullptr;  // the candidates' struck bodies of hwy_park_cem_plan / hwy_park_score, allocated by the first call
+  char *d_stage = nullptr;   // inputs and outputs of their host-pointer forms, grown on demand
+  size_t stage_bytes = 0;
   std::string err;
 };
 
@@ -68,7 +73,7 @@ extern "C" int hwy_park_destroy(hwy_park *p) {
   if (!p) return HWY_PARK_OK;
   (void)hipSetDevice(p->device);
   if (p->stream) (void)hipStreamSynchronize(p->stream);
-  void *blocks[] = {p->d_ego, p->d_parked, p->d_ints, p->d_order, p->d_obs, p->d_reward, p->d_flags, p->d_mask, p->d_seeds, p->d_roll, p->d_goal};
+  void *blocks[] = {p->d_ego, p->d_parked, p->d_ints, p->d_order, p->d_obs, p->d_reward, p->d_flags, p->d_mask, p->d_seeds, p->d_roll, p->d_goal, p->d_plan, p->d_stage};
   for (void *b : blocks)
     if (b) (void)hipFree(b);
   if (p->own_stream && p->stream) (void)hipStreamDestroy(p->stream);
@@ -276,6 +281,140 @@ extern "C" int hwy_park_goal_reward(hwy_park *p, int64_t m, const double *achiev
   PARK_HIP(p, hipMemcpyAsync(d_d, desired, sizeof(double) * 6 * m, hipMemcpyHostToDevice, p->stream));
   if (int rc = hwy_park_goal_reward_device(p, m, d_a, d_d, d_o)) return rc;
   PARK_HIP(p, hipMemcpyAsync(out, d_o, sizeof(double) * m, hipMemcpyDeviceToHost, p->stream));
+  PARK_HIP(p, hipStreamSynchronize(p->stream));
+  return HWY_PARK_OK;
+}
+
+// ---- sampling MPC (hwy_park_cem.h): one launch per search / per scoring pass ------------------------------------------------------------
+static int plan_block(hwy_park *p) {  // the candidates' struck bodies
+  if (!p->d_plan) PARK_HIP(p, hipMalloc((void **)&p->d_plan, hwy::park_cem_plane_bytes(p->cfg.num_envs)));
+  return HWY_PARK_OK;
+}
+static int stage_block(hwy_park *p, size_t need) {
+  if (need <= p->stage_bytes) return HWY_PARK_OK;
+  PARK_HIP(p, hipStreamSynchronize(p->stream));
+  if (p->d_stage) PARK_HIP(p, hipFree(p->d_stage));
+  p->d_stage = nullptr;
+  p->stage_bytes = 0;
+  PARK_HIP(p, hipMalloc((void **)&p->d_stage, need));
+  p->stage_bytes = need;
+  return HWY_PARK_OK;
+}
+// the layout of a staging block: 8-byte items first; take() returns an offset, or npos for an item that is not wanted
+struct ParkStage {
+  static constexpr size_t npos = ~(size_t)0;
+  size_t bytes = 0;
+  size_t take(size_t n, bool want) {
+    if (!want) return npos;
+    const size_t at = bytes;
+    bytes += (n + 7) & ~(size_t)7;
+    return at;
+  }
+};
+template <typename T>
+static T *staged(hwy_park *p, size_t off) { return off == ParkStage::npos ? nullptr : (T *)(p->d_stage + off); }
+
+static hwy::ParkCemParams cem_params_of(const hwy_park *p, const hwy_cem_params &c) {
+  hwy::ParkCemParams q;
+  memset(&q, 0, sizeof q);
+  q.park = params_of(p);
+  q.planes = p->d_plan;
+  q.gamma = c.gamma; q.init_std = c.init_std; q.min_std = c.min_std; q.alpha = c.alpha; q.seed = c.seed;
+  q.B = c.population; q.K = c.horizon; q.M = c.elites; q.I = c.iterations;
+  return q;
+}
+static hwy_cem_params score_shape(int32_t branches, int32_t k_steps, double gamma) {  // a scoring pass under the search's caps
+  hwy_cem_params c;
+  memset(&c, 0, sizeof c);
+  c.population = branches; c.elites = 1; c.iterations = 1; c.horizon = k_steps; c.gamma = gamma; c.alpha = 1.0;
+  return c;
+}
+
+extern "C" int hwy_park_cem_plan_device(hwy_park *p, const hwy_cem_params *cem, const double *d_init_mean, float *d_action,
+                                        double *d_best_return, double *d_mean, double *d_std, float *d_best_sequence, double *d_noise,
+                                        float *d_samples, double *d_returns, int32_t *d_elites) {
+  if (!p) return HWY_PARK_ERR_INVALID_ARG;
+  const char *why = "";
+  if (int rc = hwy::park_cem_validate(cem, &why)) return park_fail(p, rc, std::string("hwy_park_cem_plan: ") + why);
+  if (!d_action) return park_fail(p, HWY_PARK_ERR_INVALID_ARG, "hwy_park_cem_plan: action must be non-NULL");
+  PARK_HIP(p, hipSetDevice(p->device));
+  if (int rc = plan_block(p)) return rc;
+  hwy::ParkCemParams q = cem_params_of(p, *cem);
+  q.init_mean = d_init_mean; q.action = d_action; q.best_return = d_best_return; q.mean = d_mean; q.stddev = d_std;
+  q.best_sequence = d_best_sequence; q.noise = d_noise; q.samples = d_samples; q.returns = d_returns; q.elites = d_elites;
+  PARK_HIP(p, hwy::launch_park_cem(q, true, p->stream));
+  return HWY_PARK_OK;
+}
+
+extern "C" int hwy_park_cem_plan(hwy_park *p, const hwy_cem_params *cem, const double *init_mean, float *action, double *best_return,
+                                 double *mean, double *stddev, float *best_sequence, double *noise, float *samples, double *returns,
+                                 int32_t *elites) {
+  if (!p) return HWY_PARK_ERR_INVALID_ARG;
+  const char *why = "";
+  if (int rc = hwy::park_cem_validate(cem, &why)) return park_fail(p, rc, std::string("hwy_park_cem_plan: ") + why);
+  if (!action) return park_fail(p, HWY_PARK_ERR_INVALID_ARG, "hwy_park_cem_plan: action must be non-NULL");
+  const size_t E = (size_t)p->cfg.num_envs, cols = E * cem->horizon * 2, I = (size_t)cem->iterations;
+  const size_t draws = I * E * cem->population * cem->horizon * 2, rets = I * E * cem->population, el = I * E * cem->elites;
+  if (init_mean && !hwy::cem_all_finite(init_mean, cols)) return park_fail(p, HWY_PARK_ERR_ACTION, "hwy_park_cem_plan: non-finite init_mean");
+  PARK_HIP(p, hipSetDevice(p->device));
+  ParkStage st;
+  const size_t o_init = st.take(cols * 8, init_mean), o_best = st.take(E * 8, best_return), o_mean = st.take(cols * 8, mean);
+  const size_t o_std = st.take(cols * 8, stddev), o_noise = st.take(draws * 8, noise), o_rets = st.take(rets * 8, returns);
+  const size_t o_action = st.take(E * 2 * 4, true), o_seq = st.take(cols * 4, best_sequence), o_samples = st.take(draws * 4, samples);
+  const size_t o_elites = st.take(el * 4, elites);
+  if (int rc = stage_block(p, st.bytes)) return rc;
+  if (init_mean) PARK_HIP(p, hipMemcpyAsync(p->d_stage + o_init, init_mean, cols * 8, hipMemcpyHostToDevice, p->stream));
+  if (int rc = hwy_park_cem_plan_device(p, cem, staged<double>(p, o_init), staged<float>(p, o_action), staged<double>(p, o_best),
+                                        staged<double>(p, o_mean), staged<double>(p, o_std), staged<float>(p, o_seq),
+                                        staged<double>(p, o_noise), staged<float>(p, o_samples), staged<double>(p, o_rets),
+                                        staged<int32_t>(p, o_elites)))
+    return rc;
+  const struct { void *dst; size_t off, bytes; } back[] = {
+      {action, o_action, E * 2 * 4}, {best_return, o_best, E * 8}, {mean, o_mean, cols * 8}, {stddev, o_std, cols * 8},
+      {best_sequence, o_seq, cols * 4}, {noise, o_noise, draws * 8}, {samples, o_samples, draws * 4}, {returns, o_rets, rets * 8},
+      {elites, o_elites, el * 4}};
+  for (const auto &b : back)
+    if (b.dst) PARK_HIP(p, hipMemcpyAsync(b.dst, p->d_stage + b.off, b.bytes, hipMemcpyDeviceToHost, p->stream));
+  PARK_HIP(p, hipStreamSynchronize(p->stream));
+  return HWY_PARK_OK;
+}
+
+extern "C" int hwy_park_score_device(hwy_park *p, int32_t branches, int32_t k_steps, double gamma, const float *d_actions, double *d_ret,
+                                     double *d_step_reward, uint8_t *d_step_flags) {
+  if (!p) return HWY_PARK_ERR_INVALID_ARG;
+  const hwy_cem_params shape = score_shape(branches, k_steps, gamma);
+  const char *why = "";
+  if (int rc = hwy::park_cem_validate(&shape, &why)) return park_fail(p, rc, std::string("hwy_park_score (population = branches, horizon = k_steps): ") + why);
+  if (!d_actions || !d_ret) return park_fail(p, HWY_PARK_ERR_INVALID_ARG, "hwy_park_score: actions and ret must be non-NULL");
+  PARK_HIP(p, hipSetDevice(p->device));
+  if (int rc = plan_block(p)) return rc;
+  hwy::ParkCemParams q = cem_params_of(p, shape);
+  q.actions = d_actions; q.ret = d_ret; q.step_reward = d_step_reward; q.step_flags = d_step_flags;
+  PARK_HIP(p, hwy::launch_park_cem(q, false, p->stream));
+  return HWY_PARK_OK;
+}
+
+extern "C" int hwy_park_score(hwy_park *p, int32_t branches, int32_t k_steps, double gamma, const float *actions, double *ret,
+                              double *step_reward, uint8_t *step_flags) {
+  if (!p) return HWY_PARK_ERR_INVALID_ARG;
+  const hwy_cem_params shape = score_shape(branches, k_steps, gamma);
+  const char *why = "";
+  if (int rc = hwy::park_cem_validate(&shape, &why)) return park_fail(p, rc, std::string("hwy_park_score (population = branches, horizon = k_steps): ") + why);
+  if (!actions || !ret) return park_fail(p, HWY_PARK_ERR_INVALID_ARG, "hwy_park_score: actions and ret must be non-NULL");
+  const size_t rows = (size_t)p->cfg.num_envs * branches, steps = rows * k_steps;
+  if (!hwy::act_all_finite(actions, steps * 2)) return park_fail(p, HWY_PARK_ERR_ACTION, "hwy_park_score: non-finite action");
+  PARK_HIP(p, hipSetDevice(p->device));
+  ParkStage st;
+  const size_t o_ret = st.take(rows * 8, true), o_sr = st.take(steps * 8, step_reward), o_act = st.take(steps * 2 * 4, true);
+  const size_t o_sf = st.take(steps, step_flags);
+  if (int rc = stage_block(p, st.bytes)) return rc;
+  PARK_HIP(p, hipMemcpyAsync(p->d_stage + o_act, actions, steps * 2 * 4, hipMemcpyHostToDevice, p->stream));
+  if (int rc = hwy_park_score_device(p, branches, k_steps, gamma, staged<float>(p, o_act), staged<double>(p, o_ret),
+                                     staged<double>(p, o_sr), staged<uint8_t>(p, o_sf)))
+    return rc;
+  PARK_HIP(p, hipMemcpyAsync(ret, p->d_stage + o_ret, rows * 8, hipMemcpyDeviceToHost, p->stream));
+  if (step_reward) PARK_HIP(p, hipMemcpyAsync(step_reward, p->d_stage + o_sr, steps * 8, hipMemcpyDeviceToHost, p->stream));
+  if (step_flags) PARK_HIP(p, hipMemcpyAsync(step_flags, p->d_stage + o_sf, steps, hipMemcpyDeviceToHost, p->stream));
   PARK_HIP(p, hipStreamSynchronize(p->stream));
   return HWY_PARK_OK;
 }

@@ -4,7 +4,8 @@ E environments of one ``ContinuousAction`` ego, up to 26 parked vehicles and fou
 (``csrc/hwy_park.h``, one thread per environment) behind the C-ABI of ``include/hwy_park.h`` -- a door next to the step engine.
 
 * ``BatchedParkingEnv(config, num_envs)``: ``reset`` / ``step(actions)`` / ``rollout(actions[K])`` / ``compute_reward`` /
-  ``get_state`` / ``set_state``; observations are the reference's dict of ``observation`` / ``achieved_goal`` / ``desired_goal``,
+  ``get_state`` / ``set_state`` / ``plan_cem`` / ``score_sequences`` (sampling MPC, ``csrc/hwy_park_cem.h``: the whole search of
+  every environment in one launch, a wavefront per environment and a candidate per lane); observations are the reference's dict of ``observation`` / ``achieved_goal`` / ``desired_goal``,
   float32 ``[E, 6]`` each.
 * ``ParkingEnv``, ``ParkingEnvActionRepeat``, ``ParkingEnvParkedVehicles``: single-environment drop-ins with ``info["is_success"]``.
 * ``REGISTRY`` / ``register_envs``: the ids ``parking-v0``, ``parking-ActionRepeat-v0`` and ``parking-parked-v0``.  They live here
@@ -39,7 +40,10 @@ S_TERMINATED, S_TRUNCATED, S_SUCCESS, S_CRASHED = 1, 2, 4, 8
 FEATURES = ["x", "y", "vx", "vy", "cos_h", "sin_h"]
 EXPORTS = ["hwy_park_create", "hwy_park_destroy", "hwy_park_last_error", "hwy_park_reset", "hwy_park_set_autoreset",
            "hwy_park_set_state", "hwy_park_get_state", "hwy_park_advance", "hwy_park_advance_device", "hwy_park_observe",
-           "hwy_park_goal_reward_device", "hwy_park_goal_reward", "hwy_park_sync"]
+           "hwy_park_goal_reward_device", "hwy_park_goal_reward", "hwy_park_sync", "hwy_park_cem_plan_device", "hwy_park_cem_plan",
+           "hwy_park_score_device", "hwy_park_score"]
+CEM_MAX_POP, CEM_MAX_HORIZON, CEM_MAX_SAMPLES, CEM_MAX_ITERATIONS = 256, 32, 4096, 16  # include/hwy_park.h: HWY_PARK_CEM_*
+PLAN_BYTES_PER_ENV = 8 * 4 * MAX_PARKED * 64  # the candidates' struck bodies, f64 [4][26][64] per environment
 
 
 class HwyParkConfig(C.Structure):
@@ -105,6 +109,22 @@ def make_park_config(config: dict, num_envs: int, autoreset: bool = False, base_
     return c
 
 
+def park_cem_params(population, elites, iterations, horizon, gamma, init_std, min_std, alpha, seed):
+    """``hwy_cem_params`` of a search on parking: ``_abi.cem_params`` under parking's own caps.  ValueError for what
+    ``hwy_park_cem_plan`` rejects as HWY_PARK_ERR_INVALID_ARG."""
+    from . import _abi
+    cem = _abi.cem_params(population, elites, iterations, horizon, gamma, init_std, min_std, alpha, seed)
+    if cem.population > CEM_MAX_POP:
+        raise ValueError(f"parking: population ({cem.population}) must be at most {CEM_MAX_POP}")
+    if cem.horizon > CEM_MAX_HORIZON:
+        raise ValueError(f"parking: horizon ({cem.horizon}) must be at most {CEM_MAX_HORIZON}")
+    if cem.population * cem.horizon > CEM_MAX_SAMPLES:
+        raise ValueError(f"parking: population * horizon ({cem.population * cem.horizon}) must be at most {CEM_MAX_SAMPLES}")
+    if cem.iterations > CEM_MAX_ITERATIONS:
+        raise ValueError(f"parking: iterations ({cem.iterations}) must be at most {CEM_MAX_ITERATIONS}")
+    return cem
+
+
 _park_lib = None
 
 
@@ -125,6 +145,8 @@ def load():
         lib.hwy_park_observe.argtypes = [vp, vp]
         lib.hwy_park_goal_reward.argtypes = lib.hwy_park_goal_reward_device.argtypes = [vp, C.c_int64, vp, vp, vp]
         lib.hwy_park_sync.argtypes = [vp]
+        lib.hwy_park_cem_plan.argtypes = lib.hwy_park_cem_plan_device.argtypes = [vp] * 12
+        lib.hwy_park_score.argtypes = lib.hwy_park_score_device.argtypes = [vp, i32, i32, C.c_double] + [vp] * 4
         _park_lib = lib
     return _park_lib
 
@@ -214,6 +236,39 @@ class ParkEngine:
     def sync(self):
         self._check(self.lib.hwy_park_sync(self.h))
 
+    def score(self, actions, gamma: float = 1.0, per_step: bool = False):
+        """``actions`` float32 [E, B, K, 2] -> the returns f64 [E, B] of the sequences, each stepped from its environment's current
+        state (``hwy_park_score``), and with ``per_step`` the reward f64 and the flags u8 [E, B, K] of every step."""
+        a = np.ascontiguousarray(actions, np.float32)
+        if a.ndim != 4 or a.shape[0] != self.E or a.shape[3] != 2:
+            raise ValueError(f"actions must be [{self.E}, B, K, 2]")
+        B, K = a.shape[1:3]
+        ret = np.empty((self.E, B))
+        sr, sf = (np.empty((self.E, B, K)), np.empty((self.E, B, K), np.uint8)) if per_step else (None, None)
+        self._check(self.lib.hwy_park_score(self.h, B, K, float(gamma), _ptr(a), _ptr(ret), _ptr(sr), _ptr(sf)))
+        return (ret, sr, sf) if per_step else ret
+
+    def score_device(self, branches, k_steps, gamma, d_actions, d_ret, d_step_reward=None, d_step_flags=None):
+        self._check(self.lib.hwy_park_score_device(self.h, int(branches), int(k_steps), float(gamma), d_actions, d_ret, d_step_reward, d_step_flags))
+
+    def cem_plan(self, cem, init_mean=None, debug: bool = False) -> dict:
+        """One search per environment (``hwy_park_cem_plan``): ``action`` f32 [E, 2], ``best_return``, ``best_sequence``, ``mean``,
+        ``std``, and with ``debug`` every iteration's ``noise``, ``samples``, ``returns`` and ``elites``."""
+        E, B, K, M, I = self.E, cem.population, cem.horizon, cem.elites, cem.iterations
+        out = {"action": np.empty((E, 2), np.float32), "best_return": np.empty(E), "mean": np.empty((E, K, 2)), "std": np.empty((E, K, 2)),
+               "best_sequence": np.empty((E, K, 2), np.float32)}
+        dbg = {"noise": np.empty((I, E, B, K, 2)), "samples": np.empty((I, E, B, K, 2), np.float32), "returns": np.empty((I, E, B)),
+               "elites": np.empty((I, E, M), np.int32)} if debug else {}
+        im = None if init_mean is None else np.ascontiguousarray(init_mean, np.float64)
+        self._check(self.lib.hwy_park_cem_plan(self.h, C.addressof(cem), _ptr(im), *(_ptr(out[k]) for k in ("action", "best_return", "mean", "std", "best_sequence")),
+                                               *(_ptr(dbg.get(k)) for k in ("noise", "samples", "returns", "elites"))))
+        return dict(out, **dbg)
+
+    def cem_plan_device(self, cem, d_action, d_init_mean=None, d_best_return=None, d_mean=None, d_std=None, d_best_sequence=None,
+                        d_noise=None, d_samples=None, d_returns=None, d_elites=None):
+        self._check(self.lib.hwy_park_cem_plan_device(self.h, C.addressof(cem), d_init_mean, d_action, d_best_return, d_mean, d_std,
+                                                      d_best_sequence, d_noise, d_samples, d_returns, d_elites))
+
 
 # ---- the lot and the host spawn (ParkingEnv._create_road / _create_vehicles on NumPy's generator) ----------------------------------
 def spot_position(k):
@@ -282,7 +337,7 @@ class BatchedParkingEnv:
     CONFIG = {}
 
     def __init__(self, config: dict | None = None, num_envs: int = 1, device: int = 0, render_mode=None,
-                 spawn_mode: str = "reference", autoreset: bool = False, stream: int | None = None):
+                 spawn_mode: str = "reference", autoreset: bool = False, stream: int | None = None, max_plan_bytes: int = 1 << 30):
         if render_mode is not None:
             raise NotImplementedError("rendering is outside the MI355X hot-path scope")
         if spawn_mode not in ("reference", "device"):
@@ -292,6 +347,7 @@ class BatchedParkingEnv:
         self.configure(config)
         self._engine = self._engine_key = None
         self._np_randoms = [None] * self.num_envs
+        self.max_plan_bytes, self._plan_entropy, self._steps, self._cem_decisions = max_plan_bytes, 0, 0, 0
         self._define_spaces()
 
     @classmethod
@@ -343,6 +399,7 @@ class BatchedParkingEnv:
         base = (int(np.random.SeedSequence(None).generate_state(1, np.uint64)[0] >> np.uint64(1)) if seeds[0] is None
                 else int(seeds[0]) + 0x9E3779B9)
         eng.set_autoreset(self.autoreset, base)
+        self._plan_entropy, self._steps, self._cem_decisions = base & (2 ** 64 - 1), 0, 0
         return obs_dict(obs), self._info(obs, np.zeros(E, np.uint8))
 
     def _info(self, obs, flags):
@@ -352,12 +409,14 @@ class BatchedParkingEnv:
     def step(self, actions):
         """``actions`` float32 [E, 2] in [-1, 1] (throttle, steering; clipped) -> (obs dict, reward f64 [E], terminated, truncated, info)."""
         obs, reward, flags = self._ensure_engine().advance(np.asarray(actions, np.float32).reshape(1, self.num_envs, 2))
+        self._steps += 1
         return obs_dict(obs), reward, (flags & S_TERMINATED) != 0, (flags & S_TRUNCATED) != 0, self._info(obs, flags)
 
     def rollout(self, actions):
         """K policy steps in one launch (action repeat, open-loop rollouts): ``actions`` float32 [K, E, 2] -> the observation of the
         last step and reward / terminated / truncated / is_success [K, E] of every step."""
         obs, _, _, sr, sf = self._ensure_engine().advance(actions, per_step=True)
+        self._steps += len(sr)
         return obs_dict(obs), sr, (sf & S_TERMINATED) != 0, (sf & S_TRUNCATED) != 0, {"is_success": (sf & S_SUCCESS) != 0,
                                                                                         "crashed": (sf & S_CRASHED) != 0}
 
@@ -380,6 +439,76 @@ class BatchedParkingEnv:
         out = eng.goal_reward(a, np.broadcast_to(np.asarray(desired_goal, np.float64), a.shape))
         return out.reshape(a.shape[:-1]) if a.ndim > 1 else float(out[0])
 
+    # ---- sampling MPC: csrc/hwy_park_cem.h, one launch per call ---------------------------------------------------------------------
+    def _plan_fits(self):
+        need = PLAN_BYTES_PER_ENV * self.num_envs
+        if need > self.max_plan_bytes:
+            raise MemoryError(f"parking: the candidates of {self.num_envs} environments keep {need} bytes of struck bodies on the device "
+                              f"(max_plan_bytes = {self.max_plan_bytes})")
+
+    def _sequences(self, actions):
+        a, E = np.asarray(actions, np.float32), self.num_envs
+        if a.ndim == 3:
+            a = np.broadcast_to(a, (E, *a.shape))
+        if a.ndim != 4 or a.shape[0] != E or a.shape[3] != 2 or a.shape[1] < 1 or a.shape[2] < 1:
+            raise ValueError(f"action sequences must have shape [B, K, 2] or [{E}, B, K, 2]; got {np.shape(actions)}")
+        if not np.isfinite(a).all():
+            raise ValueError("action sequences must be finite")
+        return np.ascontiguousarray(a)
+
+    def _cem_setup(self, population, elites, iterations, horizon, gamma, init_std, min_std, alpha, seed):
+        """The checks of ``plan_cem`` -- all before the engine is created -- and its ``hwy_cem_params``."""
+        if seed is None:  # successive decisions draw different noise; an explicit seed is used as given
+            seed = int(np.random.SeedSequence((self._plan_entropy, self._steps, self._cem_decisions)).generate_state(1, np.uint64)[0])
+            self._cem_decisions += 1
+        cem = park_cem_params(population, elites, iterations, horizon, gamma, init_std, min_std, alpha, seed)
+        self._plan_fits()
+        return cem
+
+    def _cem_init_mean(self, init_mean, K: int):
+        if init_mean is None:
+            return None
+        m = np.asarray(init_mean, np.float64)
+        if m.shape == (K, 2):
+            m = np.broadcast_to(m, (self.num_envs, K, 2))
+        if m.shape != (self.num_envs, K, 2):
+            raise ValueError(f"init_mean must have shape ({K}, 2) or ({self.num_envs}, {K}, 2); got {m.shape}")
+        if not np.isfinite(m).all():
+            raise ValueError("init_mean must be finite")
+        return np.ascontiguousarray(m)
+
+    def score_sequences(self, actions, gamma: float = 1.0, return_details: bool = False):
+        """B candidate sequences of K action pairs (float32 ``[B, K, 2]``, or ``[E, B, K, 2]``) are stepped from the CURRENT state with
+        the true simulator, one candidate per lane of the environment's wavefront, and their discounted returns f64 [E, B] come
+        back.  An episode that ends within a sequence is absorbing.  This environment is left exactly as it was.
+        ``return_details``: also ``reward``, ``terminated``, ``truncated``, ``is_success``, ``crashed`` [E, B, K] of every step."""
+        a = self._sequences(actions)
+        park_cem_params(a.shape[1], 1, 1, a.shape[2], gamma, 0.0, 0.0, 1.0, 0)
+        self._plan_fits()
+        if not return_details:
+            return self._ensure_engine().score(a, gamma)
+        ret, sr, sf = self._ensure_engine().score(a, gamma, per_step=True)
+        return ret, {"reward": sr, "terminated": (sf & S_TERMINATED) != 0, "truncated": (sf & S_TRUNCATED) != 0,
+                     "is_success": (sf & S_SUCCESS) != 0, "crashed": (sf & S_CRASHED) != 0}
+
+    def plan_cem(self, population: int = 64, elites: int = 8, iterations: int = 3, horizon: int = 8, gamma: float = 0.9,
+                 init_std: float = 0.5, min_std: float = 0.05, alpha: float = 1.0, seed: int | None = None, init_mean=None,
+                 return_details: bool = False, debug: bool = False):
+        """Sampling MPC: the first action float32 [E, 2] of a cross-entropy-method search of every environment, the whole search in
+        ONE launch (``hwy_park_cem_plan``; DESIGN.md "CEM on parking: one launch").  The signature and the rules are
+        ``BatchedHighwayEnv.plan_cem``'s under parking's caps (population <= 256, horizon <= 32, population * horizon <= 4096,
+        iterations <= 16).  ``seed=None``: derived from the seed of ``reset()``, the step count and the number of default-seed
+        decisions since ``reset()``.  This environment is left exactly as it was.  ``return_details``: also ``best_return`` f64 [E],
+        ``best_sequence`` f32 [E, K, 2], ``mean`` / ``std`` f64 [E, K, 2]; with ``debug`` also ``noise`` f64 / ``samples`` f32
+        [I, E, B, K, 2], ``returns`` f64 [I, E, B] and ``elites`` int32 [I, E, M]."""
+        cem = self._cem_setup(population, elites, iterations, horizon, gamma, init_std, min_std, alpha, seed)
+        im = self._cem_init_mean(init_mean, cem.horizon)
+        out = self._ensure_engine().cem_plan(cem, im, debug=debug)
+        if not return_details:
+            return out["action"]
+        keys = ("best_return", "best_sequence", "mean", "std") + (("noise", "samples", "returns", "elites") if debug else ())
+        return out["action"], {k: out[k] for k in keys}
+
     def get_state(self) -> dict:
         return self._ensure_engine().get_state()
 
@@ -400,6 +529,16 @@ class _SingleParkingMixin:
     def step(self, action):
         obs, reward, term, trunc, info = super().step(np.asarray(action, np.float32).reshape(1, 2))
         return self._one(obs), float(reward[0]), bool(term[0]), bool(trunc[0]), dict(self._one_info(info), action=action)
+
+    def score_sequences(self, actions, gamma: float = 1.0, return_details: bool = False):
+        out = super().score_sequences(np.asarray(actions, np.float32)[None] if np.ndim(actions) == 3 else actions, gamma, return_details)
+        return (out[0][0], {k: v[0] for k, v in out[1].items()}) if return_details else out[0]
+
+    def plan_cem(self, *args, **kwargs):
+        out = super().plan_cem(*args, **kwargs)
+        if not isinstance(out, tuple):
+            return out[0]
+        return out[0][0], {k: (v[:, 0] if k in ("noise", "samples", "returns", "elites") else v[0]) for k, v in out[1].items()}
 
     @staticmethod
     def _one(obs):
@@ -471,7 +610,8 @@ class ParkingVectorEnv(_VecBase):
     the next step), one launch per step and no host round trip.  SameStep is not available on this front end."""
 
     def __init__(self, env="parking-v0", num_envs: int = 1, config: dict | None = None, autoreset_mode: str = "NextStep",
-                 output: str = "numpy", device: int = 0, spawn_mode: str = "device", stream=None, **kwargs):
+                 output: str = "numpy", device: int = 0, spawn_mode: str = "device", stream=None, max_plan_bytes: int = 1 << 30,
+                 **kwargs):
         mode = str(getattr(autoreset_mode, "value", autoreset_mode)).lower().replace("_", "")
         if mode not in ("nextstep", "samestep", "disabled"):
             raise ValueError("autoreset_mode must be one of ('NextStep', 'SameStep', 'Disabled')")
@@ -494,7 +634,8 @@ class ParkingVectorEnv(_VecBase):
         elif stream is not None:
             raise ValueError("stream= needs output='torch'")
         cls = REGISTRY[env.split("/", 1)[-1]][1] if isinstance(env, str) else env
-        self.env = cls(config, num_envs=num_envs, device=device, spawn_mode=spawn_mode, autoreset=mode == "nextstep", stream=stream)
+        self.env = cls(config, num_envs=num_envs, device=device, spawn_mode=spawn_mode, autoreset=mode == "nextstep", stream=stream,
+                       max_plan_bytes=max_plan_bytes)
         self.num_envs = self.env.num_envs
         self.single_observation_space, self.single_action_space = self.env.single_observation_space, self.env.single_action_space
         if _gym is not None:
@@ -534,6 +675,85 @@ class ParkingVectorEnv(_VecBase):
         f = d["flags"]
         info = {"is_success": (f & S_SUCCESS) != 0, "crashed": (f & S_CRASHED) != 0}
         return obs_dict(d["obs"]), d["reward"], (f & S_TERMINATED) != 0, (f & S_TRUNCATED) != 0, info
+
+    def _on_stream(self, enqueue, inputs=()):
+        """Run ``enqueue()`` on the handle's stream, ordered against the current stream the way ``step`` is."""
+        cur = self._torch.cuda.current_stream()
+        same = cur.cuda_stream == self._tstream.cuda_stream
+        if not same:
+            self._tstream.wait_stream(cur)
+        enqueue()
+        if not same:
+            cur.wait_stream(self._tstream)
+            for x in inputs:
+                x.record_stream(self._tstream)
+
+    def score_sequences(self, actions, gamma: float = 1.0, return_details: bool = False):
+        """``BatchedParkingEnv.score_sequences``.  ``output="torch"``: ``actions`` may be a device tensor (not validated: a non-finite
+        pair keeps the stored controls), the returns and the details are device tensors, one launch and no host round trip."""
+        if self.output != "torch":
+            return self.env.score_sequences(actions, gamma, return_details)
+        t, E, env = self._torch, self.num_envs, self.env
+        if self._dev is None:
+            raise RuntimeError("score_sequences() before reset()")
+        dev = self._dev["obs"].device
+        a = actions if isinstance(actions, t.Tensor) else t.from_numpy(env._sequences(actions))
+        a = a.to(device=dev, dtype=t.float32)
+        a = (a.unsqueeze(0).expand(E, *a.shape) if a.dim() == 3 else a).contiguous()
+        if a.dim() != 4 or a.shape[0] != E or a.shape[3] != 2:
+            raise ValueError(f"action sequences must have shape [B, K, 2] or [{E}, B, K, 2]; got {tuple(a.shape)}")
+        B, K = int(a.shape[1]), int(a.shape[2])
+        park_cem_params(B, 1, 1, K, gamma, 0.0, 0.0, 1.0, 0)
+        env._plan_fits()
+        ret = t.empty((E, B), dtype=t.float64, device=dev)
+        sr = t.empty((E, B, K), dtype=t.float64, device=dev) if return_details else None
+        sf = t.empty((E, B, K), dtype=t.uint8, device=dev) if return_details else None
+        self._on_stream(lambda: env._engine.score_device(B, K, gamma, a.data_ptr(), ret.data_ptr(), sr.data_ptr() if return_details else None,
+                                                         sf.data_ptr() if return_details else None), [a])
+        if not return_details:
+            return ret
+        return ret, {"reward": sr, "terminated": (sf & S_TERMINATED) != 0, "truncated": (sf & S_TRUNCATED) != 0,
+                     "is_success": (sf & S_SUCCESS) != 0, "crashed": (sf & S_CRASHED) != 0}
+
+    def plan_cem(self, population: int = 64, elites: int = 8, iterations: int = 3, horizon: int = 8, gamma: float = 0.9,
+                 init_std: float = 0.5, min_std: float = 0.05, alpha: float = 1.0, seed: int | None = None, init_mean=None,
+                 return_details: bool = False, debug: bool = False):
+        """``BatchedParkingEnv.plan_cem``.  ``output="torch"``: the device tensor the kernel wrote (and, with ``return_details``,
+        device tensors of the details; valid until the next call of that horizon), ordered on the current stream like ``step`` --
+        one ``hwy_park_cem_plan_device`` call, and ``env.step(env.plan_cem())`` never leaves the GPU.  ``init_mean``: a float64
+        array or device tensor [K, 2] or [E, K, 2]; a device tensor is not validated."""
+        if self.output != "torch":
+            return self.env.plan_cem(population, elites, iterations, horizon, gamma, init_std, min_std, alpha, seed, init_mean,
+                                     return_details=return_details, debug=debug)
+        t, E, env = self._torch, self.num_envs, self.env
+        cem = env._cem_setup(population, elites, iterations, horizon, gamma, init_std, min_std, alpha, seed)
+        if self._dev is None:
+            raise RuntimeError("plan_cem() before reset()")
+        K, dev = cem.horizon, self._dev["obs"].device
+        if ("cem", K) not in self._dev:
+            self._dev["cem", K] = {"action": t.empty((E, 2), dtype=t.float32, device=dev), "best_return": t.empty(E, dtype=t.float64, device=dev),
+                                   "mean": t.empty((E, K, 2), dtype=t.float64, device=dev), "std": t.empty((E, K, 2), dtype=t.float64, device=dev),
+                                   "best_sequence": t.empty((E, K, 2), dtype=t.float32, device=dev)}
+        d, dbg = self._dev["cem", K], {}
+        if debug:  # (allocated per call: a test's door, not the hot path)
+            shape = (cem.iterations, E, cem.population, K, 2)
+            dbg = {"noise": t.empty(shape, dtype=t.float64, device=dev), "samples": t.empty(shape, dtype=t.float32, device=dev),
+                   "returns": t.empty(shape[:3], dtype=t.float64, device=dev),
+                   "elites": t.empty((cem.iterations, E, cem.elites), dtype=t.int32, device=dev)}
+        im = None
+        if init_mean is not None:
+            if isinstance(init_mean, t.Tensor):
+                im = init_mean.to(device=dev, dtype=t.float64)
+                im = (im.unsqueeze(0).expand(E, K, 2) if im.dim() == 2 else im).reshape(E, K, 2).contiguous()
+            else:
+                im = t.from_numpy(env._cem_init_mean(init_mean, K)).to(dev)
+        self._on_stream(lambda: env._engine.cem_plan_device(cem, d["action"].data_ptr(), None if im is None else im.data_ptr(),
+                                                            *(d[k].data_ptr() for k in ("best_return", "mean", "std", "best_sequence")),
+                                                            *(dbg[k].data_ptr() for k in ("noise", "samples", "returns", "elites") if debug)),
+                        ([im] if im is not None else []) + list(dbg.values()))
+        if not return_details:
+            return d["action"]
+        return d["action"], dict({k: d[k] for k in ("best_return", "best_sequence", "mean", "std")}, **dbg)
 
     def step_async(self, actions):
         self._pending = actions

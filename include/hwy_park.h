@@ -1,7 +1,9 @@
 /* hwy_park.h -- C-ABI of the parking scenario (the reference's ParkingEnv, envs/parking_env.py): goal-conditioned continuous
  * control, E environments of ONE moving rectangle (the ContinuousAction ego), up to 26 resting ones and four walls, advanced by
  * a kernel of its own (csrc/hwy_park.h: one THREAD per environment).  A door next to the engine of hwy_engine.h: an opaque handle
- * of its own, exported from the same shared library; hwy_config and the engine's ABI version are not involved.
+ * of its own, exported from the same shared library; hwy_config and the engine's ABI version are not involved.  Sampling MPC on it
+ * (hwy_park_cem_plan, hwy_park_score: csrc/hwy_park_cem.h, one WAVEFRONT per environment, a candidate per lane) takes the engine's
+ * hwy_cem_params; nothing else of hwy_engine.h is used.
  *
  * Scope (hwy_park_create returns HWY_PARK_ERR_INVALID_ARG outside it, before anything reaches the device): one controlled vehicle,
  * vehicles_count 0 .. 26, walls or none, 1 .. 15 frames per policy step, the six default features in their default order, a
@@ -23,6 +25,8 @@
 
 #include <stddef.h>
 #include <stdint.h>
+
+#include "hwy_engine.h" /* hwy_cem_params */
 
 #ifdef __cplusplus
 extern "C" {
@@ -90,6 +94,40 @@ int hwy_park_observe(hwy_park *p, float *obs);
 int hwy_park_goal_reward_device(hwy_park *p, int64_t m, const double *d_achieved, const double *d_desired, double *d_out);
 int hwy_park_goal_reward(hwy_park *p, int64_t m, const double *achieved, const double *desired, double *out);
 int hwy_park_sync(hwy_park *p);
+
+/* ---- sampling MPC (csrc/hwy_park_cem.h): a cross-entropy-method search of every environment in ONE launch --------------------
+ * The parameters are hwy_engine.h's hwy_cem_params under parking's own, tighter caps: population 1 .. HWY_PARK_CEM_MAX_POP, elites
+ * 1 .. population, horizon 1 .. HWY_PARK_CEM_MAX_HORIZON, population * horizon <= HWY_PARK_CEM_MAX_SAMPLES, iterations 1 ..
+ * HWY_PARK_CEM_MAX_ITERATIONS, gamma finite, init_std and min_std finite and >= 0, alpha in [0, 1]; HWY_PARK_ERR_INVALID_ARG with a
+ * reason in hwy_park_last_error otherwise.  The environments of the handle are the parents: they are read, never written; the
+ * handle's autoreset setting is not read, an environment that has ended is stepped as it is.  Candidates keep the bodies they
+ * strike in a block of the handle, f64 [4][26][64 E] (53 248 bytes per environment), allocated by the first call.
+ *
+ * hwy_park_cem_plan_device: DEVICE pointers, enqueued on the handle's stream, no host round trip.  d_init_mean f64 [E][K][2] or NULL
+ * (zeros; not validated here).  d_action f32 [E][2]: step 0 of the best sequence.  Optional (NULL: not written): d_best_return f64
+ * [E], d_mean / d_std f64 [E][K][2], d_best_sequence f32 [E][K][2], d_noise f64 and d_samples f32 [I][E][B][K][2], d_returns f64
+ * [I][E][B], d_elites i32 [I][E][M] (every iteration's elite branches, ascending).
+ * hwy_park_cem_plan: the same with HOST pointers; stages, HWY_PARK_ERR_ACTION for a non-finite init_mean before anything runs,
+ * synchronises.
+ * hwy_park_score_device: the discounted returns d_ret f64 [E][B] of B = branches given sequences of K = k_steps action pairs,
+ * d_actions f32 [E][B][K][2], each stepped from its environment's current state; an episode that ends within a sequence is
+ * absorbing.  Optional d_step_reward f64 [E][B][K] and d_step_flags u8 [E][B][K] (HWY_PARK_S_*) of every step, as an advance of K
+ * steps without autoreset gives them.  A non-finite pair keeps the stored controls.  The caps are the search's (population =
+ * branches, horizon = k_steps).  hwy_park_score: HOST pointers; HWY_PARK_ERR_ACTION for non-finite actions before anything runs. */
+#define HWY_PARK_CEM_MAX_POP 256
+#define HWY_PARK_CEM_MAX_HORIZON 32
+#define HWY_PARK_CEM_MAX_SAMPLES 4096  /* population * horizon: the sample table in LDS, 32 KB */
+#define HWY_PARK_CEM_MAX_ITERATIONS 16
+int hwy_park_cem_plan_device(hwy_park *p, const hwy_cem_params *cem, const double *d_init_mean, float *d_action, double *d_best_return,
+                             double *d_mean, double *d_std, float *d_best_sequence, double *d_noise, float *d_samples,
+                             double *d_returns, int32_t *d_elites);
+int hwy_park_cem_plan(hwy_park *p, const hwy_cem_params *cem, const double *init_mean, float *action, double *best_return,
+                      double *mean, double *stddev, float *best_sequence, double *noise, float *samples, double *returns,
+                      int32_t *elites);
+int hwy_park_score_device(hwy_park *p, int32_t branches, int32_t k_steps, double gamma, const float *d_actions, double *d_ret,
+                          double *d_step_reward, uint8_t *d_step_flags);
+int hwy_park_score(hwy_park *p, int32_t branches, int32_t k_steps, double gamma, const float *actions, double *ret,
+                   double *step_reward, uint8_t *step_flags);
 
 #ifdef __cplusplus
 }

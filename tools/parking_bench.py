@@ -4,6 +4,7 @@
 they imply.  Needs a GPU (there is no fallback).  One JSON line per shape; ``--out`` also writes them to a file.
 
     python tools/parking_bench.py [--envs 4096 65536] [--vehicles 0 10] [--k 1 16] [--launches 200] [--repeats 5] [--out FILE]
+    python tools/parking_bench.py --plan [--plan-shape 4096 64 8 3] [--plan-launches 200] [--repeats 5] [--out FILE]   (bench_plan)
 
 Method: device tensors in and out (``hwy_park_advance_device``: no host round trip), a device reset, ``--warmup`` launches, then
 ``--repeats`` windows of ``--launches`` back-to-back launches, each window closed by a stream synchronise and timed by the host
@@ -31,8 +32,82 @@ def launch_bytes(E: int, k_steps: int) -> int:
     return E * (2 * (9 * 8 + 8 * 4) + k_steps * 8 + 18 * 4 + 8 + 1)
 
 
+def bench_plan(args) -> list:
+    """``--plan``: one CEM search of every environment at ``parking-parked-v0`` (E, B, K, I = ``--plan-shape``), two ways.
+    ``plan_cem``: ``hwy_park_cem_plan_device`` (csrc/hwy_park_cem.h, one launch per search) into device tensors, ``--warmup``
+    searches, then ``--repeats`` windows of ``--plan-launches`` back-to-back searches, each closed by a stream synchronise.
+    ``doors``: the same search built from ``get_state`` / ``set_state`` / ``rollout``: per iteration the parent state tiled into a
+    second engine of E * B environments, host sampling (NumPy normals around the mean), one K-step rollout, the fold and the refit on
+    the host; one warm-up search, then ``--repeats`` searches timed one by one by the host clock (every call synchronises)."""
+    import numpy as np
+    import torch
+    from highwayenv_amd import build, parking
+    E, B, K, I = args.plan_shape
+    M, gamma = 8, 0.9
+    res = build.kernel_resources()["hwy::hwy_park_cem_kernel<true>"]
+    cfg = dict(parking.parking_default_config(), vehicles_count=10)
+    eng = parking.ParkEngine(parking.make_park_config(cfg, E, base_seed=1))
+    eng.reset()
+    cem = parking.park_cem_params(B, M, I, K, gamma, 0.5, 0.05, 1.0, 7)
+    action = torch.empty((E, 2), dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    for _ in range(args.warmup):
+        eng.cem_plan_device(cem, action.data_ptr())
+    eng.sync()
+    windows = []
+    for _ in range(args.repeats):
+        t0 = time.perf_counter()
+        for _ in range(args.plan_launches):
+            eng.cem_plan_device(cem, action.data_ptr())
+        eng.sync()
+        windows.append((time.perf_counter() - t0) / args.plan_launches)
+    windows.sort()
+    lines = [{"what": "plan_cem", "envs": E, "population": B, "horizon": K, "iterations": I, "vehicles_count": 10,
+              "ms_per_search": windows[len(windows) // 2] * 1e3, "ms_per_search_min": windows[0] * 1e3, "ms_per_search_max": windows[-1] * 1e3,
+              "env_steps_per_s": E * B * K * I / windows[len(windows) // 2], "vgpr": res["vgpr"], "vgpr_spill": res["vgpr_spill"],
+              "scratch": res["scratch"], "lds_static": res["lds"], "lds_dynamic": 8 * B * K}]
+
+    work = parking.ParkEngine(parking.make_park_config(cfg, E * B))
+    rng = np.random.default_rng(7)
+
+    def doors_search():
+        parent = eng.get_state()
+        mean, std = np.zeros((E, K, 2)), np.full((E, K, 2), 0.5)
+        for _ in range(I):
+            work.set_state({k: np.repeat(v, B, axis=0) for k, v in parent.items()})
+            z = rng.standard_normal((E, B, K, 2))
+            z[:, 0] = 0.0
+            x = np.clip(mean[:, None] + std[:, None] * z, -1.0, 1.0).astype(np.float32)
+            _, _, _, sr, sf = work.advance(np.ascontiguousarray(x.reshape(E * B, K, 2).transpose(1, 0, 2)), per_step=True)
+            ended = (sf & (parking.S_TERMINATED | parking.S_TRUNCATED)) != 0
+            alive = np.vstack([np.ones((1, E * B), bool), ~np.logical_or.accumulate(ended, axis=0)[:-1]])
+            ret = ((gamma ** np.arange(K))[:, None] * sr * alive).sum(0).reshape(E, B)
+            elite = np.take_along_axis(x, np.argsort(-ret, axis=1, kind="stable")[:, :M, None, None], axis=1).astype(np.float64)
+            mean, std = elite.mean(1), np.maximum(0.05, elite.std(1))
+        return mean
+
+    doors_search()
+    times = []
+    for _ in range(args.repeats):
+        t0 = time.perf_counter()
+        doors_search()
+        times.append(time.perf_counter() - t0)
+    times.sort()
+    lines.append({"what": "doors", "envs": E, "population": B, "horizon": K, "iterations": I, "vehicles_count": 10,
+                  "ms_per_search": times[len(times) // 2] * 1e3, "ms_per_search_min": times[0] * 1e3, "ms_per_search_max": times[-1] * 1e3,
+                  "env_steps_per_s": E * B * K * I / times[len(times) // 2]})
+    work.close()
+    eng.close()
+    for line in lines:
+        print(json.dumps(line), flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--plan", action="store_true", help="time a CEM search (plan_cem against the same search through the doors) instead")
+    ap.add_argument("--plan-shape", type=int, nargs=4, default=[4096, 64, 8, 3], metavar=("E", "B", "K", "I"))
+    ap.add_argument("--plan-launches", type=int, default=200)
     ap.add_argument("--envs", type=int, nargs="+", default=[4096, 65536])
     ap.add_argument("--vehicles", type=int, nargs="+", default=[0, 10])
     ap.add_argument("--k", type=int, nargs="+", default=[1, 16])
@@ -46,8 +121,8 @@ def main():
         raise SystemExit("parking_bench needs a GPU: nothing is measured without one")
     from highwayenv_amd import build, parking
     res = build.kernel_resources()["hwy::hwy_park_advance_kernel<256>"]
-    lines = []
-    for E in args.envs:
+    lines = bench_plan(args) if args.plan else []
+    for E in [] if args.plan else args.envs:
         for vc in args.vehicles:
             cfg = dict(parking.parking_default_config(), vehicles_count=vc)
             eng = parking.ParkEngine(parking.make_park_config(cfg, E, autoreset=True, base_seed=1))
