@@ -10,9 +10,11 @@
 
 #include "hwy_park.h"
 #include "hwy_park_cem.h"
+#include "hwy_park_mppi.h"
 
 namespace hwy {
 hipError_t launch_park_cem(const ParkCemParams &q, bool sample, hipStream_t stream);
+hipError_t launch_park_mppi(const ParkMppiParams &q, hipStream_t stream);
 hipError_t launch_park_advance(const ParkParams &p, hipStream_t stream);
 hipError_t launch_park_reset(const ParkParams &p, bool reset, hipStream_t stream);
 hipError_t launch_park_goal_reward(const ParkGoalParams &g, hipStream_t stream);
@@ -415,6 +417,62 @@ extern "C" int hwy_park_score(hwy_park *p, int32_t branches, int32_t k_steps, do
   PARK_HIP(p, hipMemcpyAsync(ret, p->d_stage + o_ret, rows * 8, hipMemcpyDeviceToHost, p->stream));
   if (step_reward) PARK_HIP(p, hipMemcpyAsync(step_reward, p->d_stage + o_sr, steps * 8, hipMemcpyDeviceToHost, p->stream));
   if (step_flags) PARK_HIP(p, hipMemcpyAsync(step_flags, p->d_stage + o_sf, steps, hipMemcpyDeviceToHost, p->stream));
+  PARK_HIP(p, hipStreamSynchronize(p->stream));
+  return HWY_PARK_OK;
+}
+
+// ---- MPPI (hwy_park_mppi.h): one launch per search.  The parameters are checked before the handle, so a refusal needs no device ---------
+extern "C" int hwy_park_mppi_plan_device(hwy_park *p, const hwy_park_mppi_params *mppi, const double *d_init_mean, float *d_action,
+                                         double *d_best_return, double *d_mean, double *d_weights_ess, double *d_noise, float *d_samples,
+                                         double *d_returns, double *d_weights, double *d_mean_history) {
+  const char *why = "";
+  if (int rc = hwy::park_mppi_validate(mppi, &why)) return park_fail(p, rc, std::string("hwy_park_mppi_plan: ") + why);
+  if (!p) return park_fail(nullptr, HWY_PARK_ERR_INVALID_ARG, "hwy_park_mppi_plan: the handle is NULL");
+  if (!d_action) return park_fail(p, HWY_PARK_ERR_INVALID_ARG, "hwy_park_mppi_plan: action must be non-NULL");
+  PARK_HIP(p, hipSetDevice(p->device));
+  if (int rc = plan_block(p)) return rc;
+  hwy::ParkMppiParams q;
+  memset(&q, 0, sizeof q);
+  q.park = params_of(p);
+  q.planes = p->d_plan;
+  q.init_mean = d_init_mean; q.action = d_action; q.best_return = d_best_return; q.mean = d_mean; q.weights_ess = d_weights_ess;
+  q.noise = d_noise; q.samples = d_samples; q.returns = d_returns; q.weights = d_weights; q.mean_history = d_mean_history;
+  q.gamma = mppi->gamma; q.noise_std = mppi->noise_std; q.temperature = mppi->temperature; q.beta = mppi->beta; q.beta_c = mppi->beta_c;
+  q.alpha = mppi->alpha; q.seed = mppi->seed;
+  q.B = mppi->population; q.K = mppi->horizon; q.I = mppi->iterations;
+  PARK_HIP(p, hwy::launch_park_mppi(q, p->stream));
+  return HWY_PARK_OK;
+}
+
+extern "C" int hwy_park_mppi_plan(hwy_park *p, const hwy_park_mppi_params *mppi, const double *init_mean, float *action, double *best_return,
+                                  double *mean, double *weights_ess, double *noise, float *samples, double *returns, double *weights,
+                                  double *mean_history) {
+  const char *why = "";
+  if (int rc = hwy::park_mppi_validate(mppi, &why)) return park_fail(p, rc, std::string("hwy_park_mppi_plan: ") + why);
+  if (!p) return park_fail(nullptr, HWY_PARK_ERR_INVALID_ARG, "hwy_park_mppi_plan: the handle is NULL");
+  if (!action) return park_fail(p, HWY_PARK_ERR_INVALID_ARG, "hwy_park_mppi_plan: action must be non-NULL");
+  const size_t E = (size_t)p->cfg.num_envs, cols = E * mppi->horizon * 2, I = (size_t)mppi->iterations;
+  const size_t draws = I * E * mppi->population * mppi->horizon * 2, rets = I * E * mppi->population, hist = (I + 1) * cols;
+  if (init_mean && !hwy::cem_all_finite(init_mean, cols)) return park_fail(p, HWY_PARK_ERR_ACTION, "hwy_park_mppi_plan: non-finite init_mean");
+  PARK_HIP(p, hipSetDevice(p->device));
+  ParkStage st;
+  const size_t o_init = st.take(cols * 8, init_mean), o_best = st.take(E * 8, best_return), o_mean = st.take(cols * 8, mean);
+  const size_t o_ess = st.take(E * 8, weights_ess), o_noise = st.take(draws * 8, noise), o_rets = st.take(rets * 8, returns);
+  const size_t o_w = st.take(rets * 8, weights), o_hist = st.take(hist * 8, mean_history), o_action = st.take(E * 2 * 4, true);
+  const size_t o_samples = st.take(draws * 4, samples);
+  if (int rc = stage_block(p, st.bytes)) return rc;
+  if (init_mean) PARK_HIP(p, hipMemcpyAsync(p->d_stage + o_init, init_mean, cols * 8, hipMemcpyHostToDevice, p->stream));
+  if (int rc = hwy_park_mppi_plan_device(p, mppi, staged<double>(p, o_init), staged<float>(p, o_action), staged<double>(p, o_best),
+                                         staged<double>(p, o_mean), staged<double>(p, o_ess), staged<double>(p, o_noise),
+                                         staged<float>(p, o_samples), staged<double>(p, o_rets), staged<double>(p, o_w),
+                                         staged<double>(p, o_hist)))
+    return rc;
+  const struct { void *dst; size_t off, bytes; } back[] = {
+      {action, o_action, E * 2 * 4}, {best_return, o_best, E * 8}, {mean, o_mean, cols * 8}, {weights_ess, o_ess, E * 8},
+      {noise, o_noise, draws * 8}, {samples, o_samples, draws * 4}, {returns, o_rets, rets * 8}, {weights, o_w, rets * 8},
+      {mean_history, o_hist, hist * 8}};
+  for (const auto &b : back)
+    if (b.dst) PARK_HIP(p, hipMemcpyAsync(b.dst, p->d_stage + b.off, b.bytes, hipMemcpyDeviceToHost, p->stream));
   PARK_HIP(p, hipStreamSynchronize(p->stream));
   return HWY_PARK_OK;
 }

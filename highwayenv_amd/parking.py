@@ -5,7 +5,8 @@ E environments of one ``ContinuousAction`` ego, up to 26 parked vehicles and fou
 
 * ``BatchedParkingEnv(config, num_envs)``: ``reset`` / ``step(actions)`` / ``rollout(actions[K])`` / ``compute_reward`` /
   ``get_state`` / ``set_state`` / ``plan_cem`` / ``score_sequences`` (sampling MPC, ``csrc/hwy_park_cem.h``: the whole search of
-  every environment in one launch, a wavefront per environment and a candidate per lane); observations are the reference's dict of ``observation`` / ``achieved_goal`` / ``desired_goal``,
+  every environment in one launch, a wavefront per environment and a candidate per lane) / ``plan_mppi`` (the MPPI planner of
+  ``csrc/hwy_park_mppi.h``, built the same way); observations are the reference's dict of ``observation`` / ``achieved_goal`` / ``desired_goal``,
   float32 ``[E, 6]`` each.
 * ``ParkingEnv``, ``ParkingEnvActionRepeat``, ``ParkingEnvParkedVehicles``: single-environment drop-ins with ``info["is_success"]``.
 * ``REGISTRY`` / ``register_envs``: the ids ``parking-v0``, ``parking-ActionRepeat-v0`` and ``parking-parked-v0``.  They live here
@@ -41,7 +42,7 @@ FEATURES = ["x", "y", "vx", "vy", "cos_h", "sin_h"]
 EXPORTS = ["hwy_park_create", "hwy_park_destroy", "hwy_park_last_error", "hwy_park_reset", "hwy_park_set_autoreset",
            "hwy_park_set_state", "hwy_park_get_state", "hwy_park_advance", "hwy_park_advance_device", "hwy_park_observe",
            "hwy_park_goal_reward_device", "hwy_park_goal_reward", "hwy_park_sync", "hwy_park_cem_plan_device", "hwy_park_cem_plan",
-           "hwy_park_score_device", "hwy_park_score"]
+           "hwy_park_score_device", "hwy_park_score", "hwy_park_mppi_plan_device", "hwy_park_mppi_plan"]
 CEM_MAX_POP, CEM_MAX_HORIZON, CEM_MAX_SAMPLES, CEM_MAX_ITERATIONS = 256, 32, 4096, 16  # include/hwy_park.h: HWY_PARK_CEM_*
 PLAN_BYTES_PER_ENV = 8 * 4 * MAX_PARKED * 64  # the candidates' struck bodies, f64 [4][26][64] per environment
 
@@ -125,6 +126,43 @@ def park_cem_params(population, elites, iterations, horizon, gamma, init_std, mi
     return cem
 
 
+class HwyParkMppiParams(C.Structure):
+    """ctypes mirror of ``hwy_park_mppi_params`` (include/hwy_park.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("population", C.c_int32), ("iterations", C.c_int32), ("horizon", C.c_int32),
+                ("gamma", C.c_double), ("noise_std", C.c_double), ("temperature", C.c_double), ("beta", C.c_double),
+                ("beta_c", C.c_double), ("alpha", C.c_double), ("seed", C.c_uint64)]
+
+
+def park_mppi_params(population, iterations, horizon, gamma, noise_std, temperature, beta, alpha, seed) -> HwyParkMppiParams:
+    """``hwy_park_mppi_params`` of an MPPI search on parking, ``beta_c = sqrt(1 - beta * beta)`` in float64 included.  ValueError for
+    what ``hwy_park_mppi_plan`` rejects as HWY_PARK_ERR_INVALID_ARG."""
+    B, I, K = int(population), int(iterations), int(horizon)
+    if not 1 <= B <= CEM_MAX_POP:
+        raise ValueError(f"parking: population ({B}) must be in [1, {CEM_MAX_POP}]")
+    if not 1 <= K <= CEM_MAX_HORIZON:
+        raise ValueError(f"parking: horizon ({K}) must be in [1, {CEM_MAX_HORIZON}]")
+    if B * K > CEM_MAX_SAMPLES:
+        raise ValueError(f"parking: population * horizon ({B * K}) must be at most {CEM_MAX_SAMPLES}")
+    if not 1 <= I <= CEM_MAX_ITERATIONS:
+        raise ValueError(f"parking: iterations ({I}) must be in [1, {CEM_MAX_ITERATIONS}]")
+    if not np.isfinite(gamma):
+        raise ValueError("gamma must be finite")
+    if not (np.isfinite(noise_std) and noise_std >= 0):
+        raise ValueError("noise_std must be finite and >= 0")
+    if not (np.isfinite(temperature) and temperature > 0):
+        raise ValueError("temperature must be finite and > 0")
+    if not 0.0 <= beta < 1.0:
+        raise ValueError("beta must be in [0, 1)")
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError("alpha must be in [0, 1]")
+    p = HwyParkMppiParams()
+    p.struct_size, p.population, p.iterations, p.horizon = C.sizeof(HwyParkMppiParams), B, I, K
+    p.gamma, p.noise_std, p.temperature, p.alpha = float(gamma), float(noise_std), float(temperature), float(alpha)
+    p.beta, p.beta_c = float(beta), float(np.sqrt(np.float64(1.0) - np.float64(beta) * np.float64(beta)))
+    p.seed = int(seed) & (2 ** 64 - 1)
+    return p
+
+
 _park_lib = None
 
 
@@ -146,6 +184,7 @@ def load():
         lib.hwy_park_goal_reward.argtypes = lib.hwy_park_goal_reward_device.argtypes = [vp, C.c_int64, vp, vp, vp]
         lib.hwy_park_sync.argtypes = [vp]
         lib.hwy_park_cem_plan.argtypes = lib.hwy_park_cem_plan_device.argtypes = [vp] * 12
+        lib.hwy_park_mppi_plan.argtypes = lib.hwy_park_mppi_plan_device.argtypes = [vp] * 12
         lib.hwy_park_score.argtypes = lib.hwy_park_score_device.argtypes = [vp, i32, i32, C.c_double] + [vp] * 4
         _park_lib = lib
     return _park_lib
@@ -268,6 +307,23 @@ class ParkEngine:
                         d_noise=None, d_samples=None, d_returns=None, d_elites=None):
         self._check(self.lib.hwy_park_cem_plan_device(self.h, C.addressof(cem), d_init_mean, d_action, d_best_return, d_mean, d_std,
                                                       d_best_sequence, d_noise, d_samples, d_returns, d_elites))
+
+    def mppi_plan(self, mppi, init_mean=None, debug: bool = False) -> dict:
+        """One MPPI search per environment (``hwy_park_mppi_plan``): ``action`` f32 [E, 2], ``best_return``, ``mean``, ``weights_ess``,
+        and with ``debug`` every iteration's ``noise``, ``samples``, ``returns``, ``weights`` and the ``mean_history``."""
+        E, B, K, I = self.E, mppi.population, mppi.horizon, mppi.iterations
+        out = {"action": np.empty((E, 2), np.float32), "best_return": np.empty(E), "mean": np.empty((E, K, 2)), "weights_ess": np.empty(E)}
+        dbg = {"noise": np.empty((I, E, B, K, 2)), "samples": np.empty((I, E, B, K, 2), np.float32), "returns": np.empty((I, E, B)),
+               "weights": np.empty((I, E, B)), "mean_history": np.empty((I + 1, E, K, 2))} if debug else {}
+        im = None if init_mean is None else np.ascontiguousarray(init_mean, np.float64)
+        self._check(self.lib.hwy_park_mppi_plan(self.h, C.addressof(mppi), _ptr(im), *(_ptr(out[k]) for k in ("action", "best_return", "mean", "weights_ess")),
+                                                *(_ptr(dbg.get(k)) for k in ("noise", "samples", "returns", "weights", "mean_history"))))
+        return dict(out, **dbg)
+
+    def mppi_plan_device(self, mppi, d_action, d_init_mean=None, d_best_return=None, d_mean=None, d_weights_ess=None, d_noise=None,
+                         d_samples=None, d_returns=None, d_weights=None, d_mean_history=None):
+        self._check(self.lib.hwy_park_mppi_plan_device(self.h, C.addressof(mppi), d_init_mean, d_action, d_best_return, d_mean, d_weights_ess,
+                                                       d_noise, d_samples, d_returns, d_weights, d_mean_history))
 
 
 # ---- the lot and the host spawn (ParkingEnv._create_road / _create_vehicles on NumPy's generator) ----------------------------------
@@ -458,12 +514,21 @@ class BatchedParkingEnv:
 
     def _cem_setup(self, population, elites, iterations, horizon, gamma, init_std, min_std, alpha, seed):
         """The checks of ``plan_cem`` -- all before the engine is created -- and its ``hwy_cem_params``."""
+        cem = park_cem_params(population, elites, iterations, horizon, gamma, init_std, min_std, alpha, self._plan_seed(seed))
+        self._plan_fits()
+        return cem
+
+    def _plan_seed(self, seed):
         if seed is None:  # successive decisions draw different noise; an explicit seed is used as given
             seed = int(np.random.SeedSequence((self._plan_entropy, self._steps, self._cem_decisions)).generate_state(1, np.uint64)[0])
             self._cem_decisions += 1
-        cem = park_cem_params(population, elites, iterations, horizon, gamma, init_std, min_std, alpha, seed)
+        return seed
+
+    def _mppi_setup(self, population, iterations, horizon, gamma, noise_std, temperature, beta, alpha, seed):
+        """The checks of ``plan_mppi`` -- all before the engine is created -- and its ``hwy_park_mppi_params``."""
+        mppi = park_mppi_params(population, iterations, horizon, gamma, noise_std, temperature, beta, alpha, self._plan_seed(seed))
         self._plan_fits()
-        return cem
+        return mppi
 
     def _cem_init_mean(self, init_mean, K: int):
         if init_mean is None:
@@ -509,6 +574,29 @@ class BatchedParkingEnv:
         keys = ("best_return", "best_sequence", "mean", "std") + (("noise", "samples", "returns", "elites") if debug else ())
         return out["action"], {k: out[k] for k in keys}
 
+    MPPI_DETAILS, MPPI_DEBUG = ("best_return", "mean", "weights_ess"), ("noise", "samples", "returns", "weights", "mean_history")
+
+    def plan_mppi(self, population: int = 64, iterations: int = 3, horizon: int = 8, gamma: float = 0.9, noise_std: float = 0.5,
+                  temperature: float = 0.1, beta: float = 0.0, alpha: float = 1.0, seed: int | None = None, init_mean=None,
+                  return_details: bool = False, debug: bool = False):
+        """Sampling MPC by MPPI (model-predictive path integral control): the first action float32 [E, 2] of the plan, the whole
+        search of every environment in ONE launch (``hwy_park_mppi_plan``; DESIGN.md "MPPI on parking").  Every iteration draws
+        ``population`` sequences ``clip(mean + noise_std * n, -1, 1)`` around the mean f64 [K, 2] (``init_mean`` or zeros), scores
+        them with the true simulator and moves the mean to ``alpha`` times their average under the weights
+        ``exp((return - best return) / temperature)`` plus ``1 - alpha`` times itself; the action is ``clip(mean[0], -1, 1)``.
+        ``beta`` in [0, 1) colours the noise along the horizon, ``n[k] = beta n[k-1] + sqrt(1 - beta^2) z[k]`` (0: white); the white
+        ``z`` and the caps are ``plan_cem``'s.  The default ``temperature`` of 0.1 is a guess: nobody has measured it.  Tune it by
+        ``weights_ess``, the effective number of candidates the last update averaged.  ``seed=None``: ``plan_cem``'s rule.  This
+        environment is left exactly as it was.  ``return_details``: also ``best_return`` f64 [E] (the highest return any candidate
+        reached), ``mean`` f64 [E, K, 2], ``weights_ess`` f64 [E]; with ``debug`` also ``noise`` f64 / ``samples`` f32 [I, E, B, K, 2],
+        ``returns`` / ``weights`` f64 [I, E, B] and ``mean_history`` f64 [I + 1, E, K, 2]."""
+        mppi = self._mppi_setup(population, iterations, horizon, gamma, noise_std, temperature, beta, alpha, seed)
+        im = self._cem_init_mean(init_mean, mppi.horizon)
+        out = self._ensure_engine().mppi_plan(mppi, im, debug=debug)
+        if not return_details:
+            return out["action"]
+        return out["action"], {k: out[k] for k in self.MPPI_DETAILS + (self.MPPI_DEBUG if debug else ())}
+
     def get_state(self) -> dict:
         return self._ensure_engine().get_state()
 
@@ -539,6 +627,12 @@ class _SingleParkingMixin:
         if not isinstance(out, tuple):
             return out[0]
         return out[0][0], {k: (v[:, 0] if k in ("noise", "samples", "returns", "elites") else v[0]) for k, v in out[1].items()}
+
+    def plan_mppi(self, *args, **kwargs):
+        out = super().plan_mppi(*args, **kwargs)
+        if not isinstance(out, tuple):
+            return out[0]
+        return out[0][0], {k: (v[:, 0] if k in self.MPPI_DEBUG else v[0]) for k, v in out[1].items()}
 
     @staticmethod
     def _one(obs):
@@ -754,6 +848,45 @@ class ParkingVectorEnv(_VecBase):
         if not return_details:
             return d["action"]
         return d["action"], dict({k: d[k] for k in ("best_return", "best_sequence", "mean", "std")}, **dbg)
+
+    def plan_mppi(self, population: int = 64, iterations: int = 3, horizon: int = 8, gamma: float = 0.9, noise_std: float = 0.5,
+                  temperature: float = 0.1, beta: float = 0.0, alpha: float = 1.0, seed: int | None = None, init_mean=None,
+                  return_details: bool = False, debug: bool = False):
+        """``BatchedParkingEnv.plan_mppi`` (the default ``temperature`` is an untuned guess).  ``output="torch"``: the device tensor the
+        kernel wrote (and, with ``return_details``, device tensors of the details; valid until the next call of that horizon),
+        ordered on the current stream like ``step`` -- one ``hwy_park_mppi_plan_device`` call, and ``env.step(env.plan_mppi())``
+        never leaves the GPU.  ``init_mean``: a float64 array or device tensor [K, 2] or [E, K, 2]; a device tensor is not validated."""
+        if self.output != "torch":
+            return self.env.plan_mppi(population, iterations, horizon, gamma, noise_std, temperature, beta, alpha, seed, init_mean,
+                                      return_details=return_details, debug=debug)
+        t, E, env = self._torch, self.num_envs, self.env
+        mppi = env._mppi_setup(population, iterations, horizon, gamma, noise_std, temperature, beta, alpha, seed)
+        if self._dev is None:
+            raise RuntimeError("plan_mppi() before reset()")
+        K, dev = mppi.horizon, self._dev["obs"].device
+        if ("mppi", K) not in self._dev:
+            self._dev["mppi", K] = {"action": t.empty((E, 2), dtype=t.float32, device=dev), "best_return": t.empty(E, dtype=t.float64, device=dev),
+                                    "mean": t.empty((E, K, 2), dtype=t.float64, device=dev), "weights_ess": t.empty(E, dtype=t.float64, device=dev)}
+        d, dbg = self._dev["mppi", K], {}
+        if debug:  # (allocated per call: a test's door, not the hot path)
+            shape = (mppi.iterations, E, mppi.population, K, 2)
+            dbg = {"noise": t.empty(shape, dtype=t.float64, device=dev), "samples": t.empty(shape, dtype=t.float32, device=dev),
+                   "returns": t.empty(shape[:3], dtype=t.float64, device=dev), "weights": t.empty(shape[:3], dtype=t.float64, device=dev),
+                   "mean_history": t.empty((mppi.iterations + 1, E, K, 2), dtype=t.float64, device=dev)}
+        im = None
+        if init_mean is not None:
+            if isinstance(init_mean, t.Tensor):
+                im = init_mean.to(device=dev, dtype=t.float64)
+                im = (im.unsqueeze(0).expand(E, K, 2) if im.dim() == 2 else im).reshape(E, K, 2).contiguous()
+            else:
+                im = t.from_numpy(env._cem_init_mean(init_mean, K)).to(dev)
+        self._on_stream(lambda: env._engine.mppi_plan_device(mppi, d["action"].data_ptr(), None if im is None else im.data_ptr(),
+                                                             *(d[k].data_ptr() for k in env.MPPI_DETAILS),
+                                                             *(dbg[k].data_ptr() for k in env.MPPI_DEBUG if debug)),
+                        ([im] if im is not None else []) + list(dbg.values()))
+        if not return_details:
+            return d["action"]
+        return d["action"], dict({k: d[k] for k in env.MPPI_DETAILS}, **dbg)
 
     def step_async(self, actions):
         self._pending = actions

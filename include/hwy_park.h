@@ -129,6 +129,39 @@ int hwy_park_score_device(hwy_park *p, int32_t branches, int32_t k_steps, double
 int hwy_park_score(hwy_park *p, int32_t branches, int32_t k_steps, double gamma, const float *actions, double *ret,
                    double *step_reward, uint8_t *step_flags);
 
+/* ---- MPPI (csrc/hwy_park_mppi.h): a model-predictive path integral search of every environment in ONE launch ------------------
+ * A second planner on the same simulator, white noise, caps and struck-body block as the CEM search.  Per environment, with a mean
+ * u f64 [K][2] (d_init_mean or zeros): every iteration draws B candidates x = (float)clip(u + noise_std * n, -1, 1), where n is the
+ * CEM search's white noise z coloured per axis by n[0] = z[0], n[k] = beta * n[k-1] + beta_c * z[k] (candidate 0: n = 0), rolls
+ * each out to its discounted return g, weighs it w = exp((g - max g) / temperature) and moves the mean to
+ * u = alpha * (sum w x / sum w) + (1 - alpha) * u.  The action is (float)clip(u[0], -1, 1) after the last iteration.
+ * population, horizon, their product and iterations under the HWY_PARK_CEM_MAX_* caps, gamma finite, noise_std finite and >= 0,
+ * temperature finite and > 0, 0 <= beta < 1, beta_c = sqrt(1 - beta * beta) computed by the caller in double, alpha in [0, 1];
+ * HWY_PARK_ERR_INVALID_ARG with a reason in hwy_park_last_error otherwise (checked before the handle: hwy_park_last_error(NULL)
+ * holds the reason when p is NULL).
+ *
+ * hwy_park_mppi_plan_device: DEVICE pointers, enqueued on the handle's stream, no host round trip.  d_action f32 [E][2].  Optional
+ * (NULL: not written): d_best_return f64 [E] (the highest return any candidate of the search reached), d_mean f64 [E][K][2],
+ * d_weights_ess f64 [E] (the effective sample size (sum w)^2 / sum w^2 of the last iteration), d_noise f64 (the coloured n) and
+ * d_samples f32 [I][E][B][K][2], d_returns and d_weights f64 [I][E][B], d_mean_history f64 [I + 1][E][K][2] (the mean before
+ * iteration 0 and after every iteration).
+ * hwy_park_mppi_plan: the same with HOST pointers; stages, HWY_PARK_ERR_ACTION for a non-finite init_mean before anything runs,
+ * synchronises. */
+typedef struct hwy_park_mppi_params {
+  int32_t struct_size;   /* sizeof(hwy_park_mppi_params) */
+  int32_t population, iterations, horizon;
+  double gamma, noise_std, temperature;
+  double beta, beta_c;   /* beta_c = sqrt(1 - beta * beta) */
+  double alpha;
+  uint64_t seed;
+} hwy_park_mppi_params;
+int hwy_park_mppi_plan_device(hwy_park *p, const hwy_park_mppi_params *mppi, const double *d_init_mean, float *d_action,
+                              double *d_best_return, double *d_mean, double *d_weights_ess, double *d_noise, float *d_samples,
+                              double *d_returns, double *d_weights, double *d_mean_history);
+int hwy_park_mppi_plan(hwy_park *p, const hwy_park_mppi_params *mppi, const double *init_mean, float *action, double *best_return,
+                       double *mean, double *weights_ess, double *noise, float *samples, double *returns, double *weights,
+                       double *mean_history);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,9 +33,11 @@ def launch_bytes(E: int, k_steps: int) -> int:
 
 
 def bench_plan(args) -> list:
-    """``--plan``: one CEM search of every environment at ``parking-parked-v0`` (E, B, K, I = ``--plan-shape``), two ways.
+    """``--plan``: one search of every environment at ``parking-parked-v0`` (E, B, K, I = ``--plan-shape``), three ways.
     ``plan_cem``: ``hwy_park_cem_plan_device`` (csrc/hwy_park_cem.h, one launch per search) into device tensors, ``--warmup``
     searches, then ``--repeats`` windows of ``--plan-launches`` back-to-back searches, each closed by a stream synchronise.
+    ``plan_mppi``: ``hwy_park_mppi_plan_device`` (csrc/hwy_park_mppi.h) from the same parents with the same seed, temperature 0.1,
+    timed the same way; its windows alternate with ``plan_cem``'s, so that the two share whatever else the machine is doing.
     ``doors``: the same search built from ``get_state`` / ``set_state`` / ``rollout``: per iteration the parent state tiled into a
     second engine of E * B environments, host sampling (NumPy normals around the mean), one K-step rollout, the fold and the refit on
     the host; one warm-up search, then ``--repeats`` searches timed one by one by the host clock (every call synchronises)."""
@@ -44,28 +46,37 @@ def bench_plan(args) -> list:
     from highwayenv_amd import build, parking
     E, B, K, I = args.plan_shape
     M, gamma = 8, 0.9
-    res = build.kernel_resources()["hwy::hwy_park_cem_kernel<true>"]
+    kernels = build.kernel_resources()
     cfg = dict(parking.parking_default_config(), vehicles_count=10)
     eng = parking.ParkEngine(parking.make_park_config(cfg, E, base_seed=1))
     eng.reset()
     cem = parking.park_cem_params(B, M, I, K, gamma, 0.5, 0.05, 1.0, 7)
+    mppi = parking.park_mppi_params(B, I, K, gamma, 0.5, 0.1, args.mppi_beta, 1.0, 7)
     action = torch.empty((E, 2), dtype=torch.float32, device="cuda")
     torch.cuda.synchronize()
-    for _ in range(args.warmup):
-        eng.cem_plan_device(cem, action.data_ptr())
+    # the two planners side by side: same parents, same white noise, their windows alternated within one run
+    legs = {"plan_cem": (lambda: eng.cem_plan_device(cem, action.data_ptr()), "hwy::hwy_park_cem_kernel<true>"),
+            "plan_mppi": (lambda: eng.mppi_plan_device(mppi, action.data_ptr()), "hwy::hwy_park_mppi_kernel<false>")}
+    for search, _ in legs.values():
+        for _ in range(args.warmup):
+            search()
     eng.sync()
-    windows = []
+    windows = {what: [] for what in legs}
     for _ in range(args.repeats):
-        t0 = time.perf_counter()
-        for _ in range(args.plan_launches):
-            eng.cem_plan_device(cem, action.data_ptr())
-        eng.sync()
-        windows.append((time.perf_counter() - t0) / args.plan_launches)
-    windows.sort()
-    lines = [{"what": "plan_cem", "envs": E, "population": B, "horizon": K, "iterations": I, "vehicles_count": 10,
-              "ms_per_search": windows[len(windows) // 2] * 1e3, "ms_per_search_min": windows[0] * 1e3, "ms_per_search_max": windows[-1] * 1e3,
-              "env_steps_per_s": E * B * K * I / windows[len(windows) // 2], "vgpr": res["vgpr"], "vgpr_spill": res["vgpr_spill"],
-              "scratch": res["scratch"], "lds_static": res["lds"], "lds_dynamic": 8 * B * K}]
+        for what, (search, _) in legs.items():
+            t0 = time.perf_counter()
+            for _ in range(args.plan_launches):
+                search()
+            eng.sync()
+            windows[what].append((time.perf_counter() - t0) / args.plan_launches)
+    lines = []
+    for what, (_, kernel) in legs.items():
+        w, res = sorted(windows[what]), kernels[kernel]
+        lines.append({"what": what, "envs": E, "population": B, "horizon": K, "iterations": I, "vehicles_count": 10,
+                      "ms_per_search": w[len(w) // 2] * 1e3, "ms_per_search_min": w[0] * 1e3, "ms_per_search_max": w[-1] * 1e3,
+                      "env_steps_per_s": E * B * K * I / w[len(w) // 2], "vgpr": res["vgpr"], "vgpr_spill": res["vgpr_spill"],
+                      "scratch": res["scratch"], "lds_static": res["lds"], "lds_dynamic": 8 * B * K})
+    lines[1]["beta"] = args.mppi_beta
 
     work = parking.ParkEngine(parking.make_park_config(cfg, E * B))
     rng = np.random.default_rng(7)
@@ -105,9 +116,10 @@ def bench_plan(args) -> list:
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--plan", action="store_true", help="time a CEM search (plan_cem against the same search through the doors) instead")
+    ap.add_argument("--plan", action="store_true", help="time a search instead (plan_cem beside plan_mppi, and the CEM search through the doors)")
     ap.add_argument("--plan-shape", type=int, nargs=4, default=[4096, 64, 8, 3], metavar=("E", "B", "K", "I"))
     ap.add_argument("--plan-launches", type=int, default=200)
+    ap.add_argument("--mppi-beta", type=float, default=0.0, help="the noise colouring of the plan_mppi leg")
     ap.add_argument("--envs", type=int, nargs="+", default=[4096, 65536])
     ap.add_argument("--vehicles", type=int, nargs="+", default=[0, 10])
     ap.add_argument("--k", type=int, nargs="+", default=[1, 16])
